@@ -19,9 +19,23 @@ and a prompt's scores do not depend on its batch). Inputs (history ids, labels, 
 HBM before the timed region. One process per GPU over RCCL; users are sharded, weights replicated; the only
 collective is the final all-reduce of the int64 rank histograms (inside the timed region).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
+Rank 0 prints ONE JSON line: metric, value (users/s), unit, higher_is_better, dtype, ms_per_step (wall time of one timed
+step), the run's config and the retrieve / rerank metrics the timed steps computed. A plain run does nothing else: it sets
+up, warms up, times the steps, writes --dump-outputs and prints the line.
+
+  --dump-outputs DIR  after the timed steps, rank 0 writes what its last timed step returned to the caller, as float64 .npy:
+                      top50_ids.npy [B, 50] (retriever top-50 item ids), reranked_top20_ids.npy [B, 20] (reranked
+                      candidate ids), retrieve_metrics.npy / rerank_metrics.npy (TwoStagePipeline.finish()'s dicts, values in
+                      the dicts' own key order: k descending, Recall / MRR / NDCG per k) and users_counted.npy [1]. Inputs
+                      are seeded: the same arguments give the same inputs on every run.
+
+--full adds every side measurement and check, each of which can still be switched off by its --no-* option:
   roofline     -- the dominant kernel (256x256x64 bf16 MFMA GEMM): algorithmic FLOPs per launch over its measured
-                  duration (HIP events recorded by the library on the launch stream)
+                  duration (HIP events recorded by the library on the launch stream during the timed steps), with the
+                  attention / stage-1 figures of the same events, the stage-1-only rate, the device placement census and
+                  the planted-label expectation of the retrieve metrics
+  other shapes -- the ML-100k shape, the online single-user path, the LoRA step and the retriever's training step
+                  (N = 1, 32 layers only)
   cpu_baseline -- the CPU oracle (a port of the reference algorithm) timed on the host cores on a bounded sample
                   of the same workload (N = 1 only)
   parity       -- GPU vs that oracle on the same sample, outside the timed region (N = 1 only)
@@ -68,14 +82,20 @@ def parse():
     ap.add_argument("--fold-norms", action="store_true", help="A/B only: RMSNorm folded into the QKV and gate/up GEMMs "
                     "(LlamaRanker.set_fold_norms; not the default because it leaves the reference's rounding points)")
     ap.add_argument("--layers", type=int, default=32, help="Llama layers (32 = Llama-2-7b; other values are for profiling only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle leg (and the parity block that reuses it)")
-    ap.add_argument("--no-other-shapes", action="store_true", help="skip the short ML-100k-shape and LoRA-step side measurements")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events")
-    ap.add_argument("--no-item-roofline", action="store_true", help="skip the Synth-1M item-GEMM roofline side field (N = 1)")
+    ap.add_argument("--full", action="store_true", help="also take the side measurements and checks (rooflines, per-kernel "
+                    "HIP events, stage-1-only rate, placement, planted-label expectation, other shapes, CPU baseline, parity)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle leg (and the parity block that reuses it)")
+    ap.add_argument("--no-other-shapes", action="store_true", help="--full: skip the short ML-100k-shape and LoRA-step side measurements")
+    ap.add_argument("--no-profile", action="store_true", help="--full: do not record per-kernel HIP events")
+    ap.add_argument("--no-item-roofline", action="store_true", help="--full: skip the Synth-1M item-GEMM roofline side field (N = 1)")
     ap.add_argument("--dist-backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo only to "
                     "rehearse several ranks on one GPU)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -395,6 +415,26 @@ def metrics_of_ranks(pos, ks, denom=None):
     return out
 
 
+DUMP_LIMIT_BYTES = 60 << 20   # the two id arrays; with the metric files and .npy headers the dump stays under 64 MB
+
+
+def dump_outputs(path, last, retr, rer, total_users):
+    """--dump-outputs: the last timed step's (top-50 ids, reranked top-20 ids) and finish()'s metrics as float64 .npy files
+    (item ids are exact in float64). Rows beyond DUMP_LIMIT_BYTES are cut to a fixed, seeded, sorted sample of users."""
+    top, reranked = (np.asarray(a, dtype=np.float64) for a in last)
+    rows = top.shape[0]
+    cap = DUMP_LIMIT_BYTES // ((top.shape[1] + reranked.shape[1]) * 8)
+    if rows > cap:
+        keep = np.sort(np.random.default_rng(0).choice(rows, size=cap, replace=False))
+        top, reranked = top[keep], reranked[keep]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "top50_ids.npy"), top)
+    np.save(os.path.join(path, "reranked_top20_ids.npy"), reranked)
+    np.save(os.path.join(path, "retrieve_metrics.npy"), np.array(list(retr.values()), dtype=np.float64))
+    np.save(os.path.join(path, "rerank_metrics.npy"), np.array(list(rer.values()), dtype=np.float64))
+    np.save(os.path.join(path, "users_counted.npy"), np.array([total_users], dtype=np.float64))
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -456,32 +496,38 @@ def main():
     pipe.reset()
     torch.cuda.synchronize()
 
+    profile = args.full and not args.no_profile
     lib = _lib.lib()
-    if not args.no_profile:
+    if profile:
         _lib.check(lib.lr_profile_start(args.steps * (args.layers * 8 + 24)), "lr_profile_start")
     D.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        run(steps[i % nb])
+        last = run(steps[i % nb])
     retr, rer, total_users = pipe.finish()
     torch.cuda.synchronize()
     D.barrier()
     elapsed = time.perf_counter() - t0
-    lib.lr_profile_stop()
+    if profile:
+        lib.lr_profile_stop()
     elapsed = D.all_reduce_max_float(elapsed, device=dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [t.cpu().numpy() for t in last], retr, rer, total_users)
 
     users_rank = sum(steps[i % nb]["users"] for i in range(args.steps))
-    # what the planted labels make the retrieve metrics: float64 on the host from the planted ranks of the timed steps'
-    # users, summed over ranks (outside the timed region)
-    first = np.concatenate([[0], np.cumsum([s["users"] for s in steps])])
-    timed_ranks = np.concatenate([planted_ranks[first[i % nb]: first[i % nb + 1]] for i in range(args.steps)])
-    exp_keys = ["Recall@10", "MRR@10", "NDCG@10", "NDCG@50"]
-    exp_local = metrics_of_ranks(timed_ranks, [10, 50], denom=1)
-    exp_t = torch.tensor([exp_local[k] for k in exp_keys], dtype=torch.float64, device=dev)
-    if world > 1:
-        torch.distributed.all_reduce(exp_t)
-    expected = {k: float(v) / max(1, total_users) for k, v in zip(exp_keys, exp_t.tolist())}
+    expected = None
+    if args.full:
+        # what the planted labels make the retrieve metrics: float64 on the host from the planted ranks of the timed steps'
+        # users, summed over ranks (outside the timed region)
+        first = np.concatenate([[0], np.cumsum([s["users"] for s in steps])])
+        timed_ranks = np.concatenate([planted_ranks[first[i % nb]: first[i % nb + 1]] for i in range(args.steps)])
+        exp_keys = ["Recall@10", "MRR@10", "NDCG@10", "NDCG@50"]
+        exp_local = metrics_of_ranks(timed_ranks, [10, 50], denom=1)
+        exp_t = torch.tensor([exp_local[k] for k in exp_keys], dtype=torch.float64, device=dev)
+        if world > 1:
+            torch.distributed.all_reduce(exp_t)
+        expected = {k: float(v) / max(1, total_users) for k, v in zip(exp_keys, exp_t.tolist())}
     tok_rank = sum(int(steps[i % nb]["cu"][-1]) for i in range(args.steps))
     # rows the prefill executes: the shared prefix once per step instead of once per prompt
     rows_rank = sum(int(steps[i % nb]["cu"][-1]) - (steps[i % nb]["users"] - 1) * steps[i % nb]["prefix"] for i in range(args.steps))
@@ -495,7 +541,7 @@ def main():
 
     roofline = None
     extra = {}
-    if not args.no_profile:
+    if profile:
         g_ms, g_fl, g_n = collect(0)
         a_ms, a_fl, a_n = collect(2)
         e_ms, _, e_n = collect(4)
@@ -520,20 +566,21 @@ def main():
                  "stage1_ms_per_step": (e_ms + k_ms) / max(1, args.steps),
                  "item_topk_tflops_f32": (k_fl / (k_ms * 1e-3) / 1e12) if k_n else None}
 
-    # stage-1-only throughput over this rank's resident users (one call; reported, not the metric)
-    all_hist = torch.from_numpy(hist).to(dev)
-    retriever.retrieve_topk(all_hist, 50, True)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    retriever.retrieve_topk(all_hist, 50, True)
-    torch.cuda.synchronize()
-    stage1_users_per_s = len(hist) / (time.perf_counter() - t1)
+    if args.full:
+        # stage-1-only throughput over this rank's resident users (one call; reported, not the metric)
+        all_hist = torch.from_numpy(hist).to(dev)
+        retriever.retrieve_topk(all_hist, 50, True)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        retriever.retrieve_topk(all_hist, 50, True)
+        torch.cuda.synchronize()
+        stage1_users_per_s = len(hist) / (time.perf_counter() - t1)
 
-    # placement: every rank on its own device, nothing allocated elsewhere (summed over the ranks)
-    own, elsewhere = D.device_placement(local)
-    place = torch.tensor([own, elsewhere], dtype=torch.int64, device=dev)
-    D.all_reduce_sum_(place)
-    place = [int(v) for v in place.tolist()]
+        # placement: every rank on its own device, nothing allocated elsewhere (summed over the ranks)
+        own, elsewhere = D.device_placement(local)
+        place = torch.tensor([own, elsewhere], dtype=torch.int64, device=dev)
+        D.all_reduce_sum_(place)
+        place = [int(v) for v in place.tolist()]
 
     if rank == 0:
         # algorithmic prefill work of the timed region (T * 1.2952e10 + T^2 * 2.62e5 per user), whatever
@@ -544,7 +591,6 @@ def main():
             "metric": "users/sec through retrieve+rerank", "value": users / elapsed, "unit": "users/s",
             "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup,
             "peak_device_mem_gb_rank0": torch.cuda.max_memory_allocated(dev) / 1e9,
-            "placement": {"ranks_on_their_own_device": place[0], "torch_bytes_on_other_devices": place[1], "share_gpu": bool(args.share_gpu)},
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "config": {"workload": (f"{args.workload} two-stage: LRURec(V={w['V']}, L={w['L']}, D=64, 2 blocks) top-50 with "
@@ -556,22 +602,25 @@ def main():
                        "users_per_step": users_rank / args.steps, "mean_prompt_tokens_per_step": tok_rank / args.steps,
                        "mean_rows_per_step": rows_rank / args.steps,
                        "rmsnorm_folded_into_gemm": bool(args.fold_norms), "llama_layers": args.layers, "parallelism": f"dp{world}", "collective_backend": args.dist_backend or "nccl"},
-            "roofline": roofline, "stage1_only_users_per_s": stage1_users_per_s,
             "prefill_algorithmic_tflops_per_gpu": alg_flops / elapsed / 1e12,
             "metrics": {"retrieve_NDCG@10": retr["NDCG@10"], "rerank_overall_NDCG@10": rer["NDCG@10"],
                         "retrieve_Recall@10": retr["Recall@10"], "retrieve_MRR@10": retr["MRR@10"],
                         "rerank_overall_Recall@10": rer["Recall@10"], "users_counted": total_users,
                         "labels": (f"planted outside the timed region: user j's label = the retriever's rank-(j mod "
-                                   f"{PLANT_PERIOD}) item, none for ranks >= 50 (bench.py plant_labels)"),
-                        "expected_retrieve": expected,
-                        "retrieve_matches_expected": bool(all(abs(retr[k] - v) <= 1e-9 for k, v in expected.items()))},
+                                   f"{PLANT_PERIOD}) item, none for ranks >= 50 (bench.py plant_labels)")},
         }
-        out.update(extra)
-        if world == 1 and not args.no_other_shapes and args.layers == LLAMA2_7B["num_hidden_layers"]:
+        if args.full:
+            out["placement"] = {"ranks_on_their_own_device": place[0], "torch_bytes_on_other_devices": place[1],
+                                "share_gpu": bool(args.share_gpu)}
+            out["roofline"], out["stage1_only_users_per_s"] = roofline, stage1_users_per_s
+            out["metrics"]["expected_retrieve"] = expected
+            out["metrics"]["retrieve_matches_expected"] = bool(all(abs(retr[k] - v) <= 1e-9 for k, v in expected.items()))
+            out.update(extra)
+        if args.full and world == 1 and not args.no_other_shapes and args.layers == LLAMA2_7B["num_hidden_layers"]:
             out.update(side_measurements(args, ranker, label_ids, dev, steps, shared))
-        if world == 1 and not args.no_item_roofline:
+        if args.full and world == 1 and not args.no_item_roofline:
             out.update(item_gemm_roofline(dev))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             n1 = min(len(hist), 512)
             out["cpu_baseline"], out["parity"] = cpu_baseline_and_parity(args.workload, hist[:n1], labels[:n1], T[:4], lru_sd,
                                                                          retriever, dev)

@@ -1,5 +1,6 @@
 """bench.py's one JSON line, end to end on the GPU at a 2-layer depth: every field the driver reads is present and
-sane, the roofline and CPU-baseline objects are filled, and the line's own parity block is green."""
+sane; with --full the roofline and CPU-baseline objects are filled and the line's own parity block is green, without it
+the line carries the headline alone and --dump-outputs writes the last timed step's outputs."""
 import json
 import os
 import subprocess
@@ -12,7 +13,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--layers", "2", "--no-other-shapes"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--layers", "2", "--no-other-shapes",
+           "--full"]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=900)   # a child process: never exec-replace
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -62,7 +64,7 @@ def test_bench_two_ranks_on_one_card_over_gloo():
     cuda:0 over gloo (--share-gpu --dist-backend gloo): n_gpus, the all-reduced rank census, both ranks' users in the
     all-reduced histogram and the planted-label metrics are checked. The driver's 8-GPU run is the same code with nccl."""
     r = _run_bench(["--gpus", "2", "--share-gpu", "--dist-backend", "gloo", "--layers", "2", "--steps", "2", "--warmup", "1",
-                    "--no-other-shapes"])
+                    "--no-other-shapes", "--full"])
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -86,7 +88,7 @@ def test_bench_four_ranks_on_one_card_over_gloo():
     itself is the driver's to run; everything rank-count-dependent -- the port/rank plumbing of spawn_ranks, N random inits,
     the census, the all-reduced histogram -- is the same code at 4. Rank 0's peak device memory rides in the line."""
     r = _run_bench(["--gpus", "4", "--share-gpu", "--dist-backend", "gloo", "--layers", "1", "--steps", "1", "--warmup", "0",
-                    "--no-other-shapes"])
+                    "--no-other-shapes", "--full"])
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -115,10 +117,10 @@ def test_bench_refuses_more_ranks_than_gpus():
 
 @pytest.mark.gpu
 def test_bench_side_fields_carry_the_training_steps():
-    """The default run's side measurements (never part of `value`): the other BASELINE shape through the same pipeline, the
+    """The --full run's side measurements (never part of `value`): the other BASELINE shape through the same pipeline, the
     ranker's LoRA step and the retriever's training step. bench.py takes them at full depth only (32 layers), so this is the
-    default run with two timed steps and without the CPU and Synth-1M legs."""
-    r = _run_bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-item-roofline"])
+    full-depth --full run with two timed steps and without the CPU and Synth-1M legs."""
+    r = _run_bench(["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-item-roofline"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     rt = d["retriever_train_shape"]
@@ -133,3 +135,47 @@ def test_bench_side_fields_carry_the_training_steps():
     assert on["users"] == 1 and on["prompt_tokens"] == 460 and on["layers"] == 32
     assert abs(on["ms_total"] - (on["ms_retrieve"] + on["ms_prefill"])) < 1e-6
     assert 0.0 < on["compute_floor_ms"] < on["ms_prefill"] < 50.0 and 0.0 < on["ms_retrieve"] < 10.0
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line without the side measurements, times exactly --steps steps, and
+    --dump-outputs writes what the last timed step returned: float64 item ids and finish()'s metrics, under 64 MB. Two runs
+    with the same arguments see the same seeded inputs and write the same arrays."""
+    import numpy as np
+
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = _run_bench(["--steps", "3", "--warmup", "1", "--layers", "2", "--dump-outputs", str(out)], timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["unit"] == "users/s" and d["higher_is_better"] is True and d["dtype"] == "bf16" and d["steps"] == 3
+        assert d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 * d["steps"] - d["metrics"]["users_counted"]) < 1e-6 * d["value"]
+        for k in ("roofline", "cpu_baseline", "parity", "roofline_item_gemm", "placement", "stage1_only_users_per_s",
+                  "online_shape", "lora_train_shape"):
+            assert k not in d, k
+        files = sorted(os.listdir(out))
+        assert files == sorted(["top50_ids.npy", "reranked_top20_ids.npy", "retrieve_metrics.npy", "rerank_metrics.npy",
+                                "users_counted.npy"]), files
+        assert sum(os.path.getsize(out / f) for f in files) < 64e6
+        a = {f[:-4]: np.load(out / f) for f in files}
+        assert all(v.dtype == np.float64 for v in a.values())
+        top, rer = a["top50_ids"], a["reranked_top20_ids"]
+        assert top.ndim == 2 and top.shape[1] == 50 and rer.shape == (top.shape[0], 20) and top.shape[0] > 0
+        assert (top >= 1).all() and (top == np.round(top)).all()
+        assert all(sorted(rer[i]) == sorted(top[i, :20]) for i in range(top.shape[0]))   # the reranked candidates
+        assert a["users_counted"][0] == d["metrics"]["users_counted"]
+        # finish()'s dicts in their own order (k descending; Recall, MRR, NDCG): NDCG@10 is entry 8 of k = 50, 20, 10, 5, 1
+        assert a["retrieve_metrics"].shape == (15,) and a["rerank_metrics"].shape == (9,)
+        assert a["retrieve_metrics"][8] == d["metrics"]["retrieve_NDCG@10"]
+        assert a["rerank_metrics"][2] == d["metrics"]["rerank_overall_NDCG@10"]
+        assert d["metrics"]["retrieve_NDCG@10"] > 0
+        dumps.append(a)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k

@@ -17,7 +17,7 @@ for i in 1 2; do
     [ $which = old ] && lib=$L/libllamarec_old.so
     echo "== $which $i"
     LLAMAREC_LIB=$lib timeout -k 10 200 python tools/bench_gemm.py 4 ${AB_M:-32768} 2>&1 | grep "TF/s"
-    LLAMAREC_LIB=$lib timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-other-shapes > $OUT/${which}_$i.json 2>$OUT/${which}_$i.err || { echo "bench failed"; tail -3 $OUT/${which}_$i.err; exit 1; }
+    LLAMAREC_LIB=$lib timeout -k 10 200 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-other-shapes > $OUT/${which}_$i.json 2>$OUT/${which}_$i.err || { echo "bench failed"; tail -3 $OUT/${which}_$i.err; exit 1; }
     python - $OUT/${which}_$i.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d["roofline"]

@@ -3,7 +3,7 @@
 # layers 1.. skipped (timing-only experiment library: what the step would take if the row sums came for free from the o / down
 # residual epilogues). Two interleaved rounds.
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; mkdir -p gpurun_out/foldab
-B="python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-other-shapes --no-item-roofline"
+B="python bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-other-shapes --no-item-roofline"
 for round in 1 2; do
   timeout -k 10 400 $B > gpurun_out/foldab/a$round.log 2>&1 || exit 1
   echo "round $round default done"
