@@ -213,11 +213,33 @@ typedef struct lr_llama lr_llama_t;
 int lr_llama_create(const LrLlamaConfig* cfg, const LrLlamaWeightsDesc* w, lr_llama_t** out);
 void lr_llama_destroy(lr_llama_t* h);
 
+/* Backbone arithmetic of a family that shares Llama's layer structure (rotate-half RoPE, gated MLP, RMSNorm, GQA/MQA)
+ * but rounds differently. All zeros except embed_scale = 1 is Llama (lr_llama_create). Gemma v1 (the reference's
+ * GemmaForCausalLMPatched, model/llm.py:354-456, over HF GemmaModel) is {1, 1, bf16(sqrt(hidden_size))}:
+ *   norm_style 1: RMSNorm = bf16(x * rstd * (1 + w)), all in fp32 (HF GemmaRMSNorm; Llama: bf16(w * bf16(x * rstd)))
+ *   mlp_act 1   : gated MLP with tanh-approximate GELU (gelu_pytorch_tanh) instead of SiLU, same bf16 rounding points
+ *   embed_scale : embedding rows multiplied by it, bf16(bf16(e) * embed_scale) (HF casts the scale to the weight dtype:
+ *                 45.25 for hidden 2048)
+ * A Gemma handle scores (prefill, verbalizer, last logits); it has no folded norms and no LoRA fine-tuning
+ * (lr_llama_set_folded_norms and lr_llama_lora_create return LR_EUNSUPPORTED). The tied lm_head is passed as
+ * LrLlamaWeightsDesc.lm_head = embed (unscaled). */
+typedef struct LrLlamaArch {
+  int32_t norm_style;    /* 0 = Llama, 1 = Gemma */
+  int32_t mlp_act;       /* 0 = SiLU, 1 = GELU (tanh approximation) */
+  float embed_scale;     /* 1 = none */
+  int32_t reserved[5];   /* must be zero */
+} LrLlamaArch;
+
+/* lr_llama_create with an explicit arch (NULL = Llama). lr_llama_create(c, w, out) == lr_llama_create_ex(c, NULL, w, out). */
+int lr_llama_create_ex(const LrLlamaConfig* cfg, const LrLlamaArch* arch, const LrLlamaWeightsDesc* w, lr_llama_t** out);
+
 /* Kernel selection: 0 = auto (default), 1 = generic kernels (any shape; the in-library cross-check of the fast
  * ones), attention 2 = head_dim-128 MFMA flash attention (K/V by LDS-DMA, 128 query rows per workgroup),
  * attention 3 = head_dim-128 flash attention on 256-row tiles, one wave per SIMD, persistent workgroups (shared prefix of at
  * most 64 tokens, falls back to 2 otherwise; ahead of 2 on long prompts -- thousands of tokens -- and behind it on this
  * path's 460 .. 1 125-token prompts, so auto keeps 2),
+ * attention 4 = head_dim-256 MFMA flash attention (Gemma; 8 waves x 16 query rows per workgroup, K/V by LDS-DMA, no
+ * shared prefix); auto takes it in the prefill for head_dim 256, and any other head_dim is LR_EUNSUPPORTED,
  * gemm 4 = the ping-pong pipelined 256x256x64 MFMA GEMM (an error if a shape does not fit).
  * gemm 5 = LATENCY MODE for the online single-user path (demo/inference.py:56-76):
  * variant 4 plus split-K wherever the output tiles alone would leave most CUs idle (a 460-token prompt
@@ -323,7 +345,8 @@ int lr_gemm_bf16_nt_ws(const uint16_t* A, const uint16_t* B, uint16_t* C, int32_
  *   epilogue 0 store | 1 residual: C = bf16(bf16(acc) + R), R bf16 [M][N], may alias C | 2 SwiGLU over gate/up rows
  *   interleaved in groups of 16 (lr_llama_pack_gate_up), C is [M][N/2] | 3 rotary embedding on columns
  *   [0, rot_cols) of pair-interleaved q/k rows (lr_llama_pack_qkv), tok_pos int32 [M] (every entry < rope_positions),
- *   rope_cs / rope_positions = the buffer lr_rope_table filled and its max_positions.
+ *   rope_cs / rope_positions = the buffer lr_rope_table filled and its max_positions | 5 GeGLU: as 2 with the tanh-approximate
+ *   GELU (Gemma) in place of SiLU.
  * These are the epilogues of HF LlamaAttention / LlamaMLP around the Linears of model/llm.py:89-100 (reference). */
 int lr_gemm_bf16_nt_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const uint16_t* R, int32_t M, int32_t N,
                         int32_t K, int32_t epilogue, int32_t variant, const int32_t* tok_pos, const float* rope_cs,
@@ -337,6 +360,11 @@ int lr_gemm_bf16_nt_residual_rmsnorm(const uint16_t* A, const uint16_t* B, uint1
                                      int32_t N, int32_t K, int32_t variant, const uint16_t* norm_w, uint16_t* norm_out,
                                      float eps, int32_t fuse, int32_t* was_fused, void* workspace, size_t workspace_bytes,
                                      void* hip_stream);
+/* The same with the norm of an LrLlamaArch: norm_style 1 = Gemma, norm_out = bf16(C * rsqrt(mean(C^2) + eps) * (1 + norm_w)). */
+int lr_gemm_bf16_nt_residual_rmsnorm_ex(const uint16_t* A, const uint16_t* B, uint16_t* C, const uint16_t* R, int32_t M,
+                                        int32_t N, int32_t K, int32_t variant, const uint16_t* norm_w, uint16_t* norm_out,
+                                        float eps, int32_t norm_style, int32_t fuse, int32_t* was_fused, void* workspace,
+                                        size_t workspace_bytes, void* hip_stream);
 /* cs: DEVICE buffer of lr_rope_table_bytes(max_positions, head_dim) bytes: fp32 [max_positions][head_dim/2][2] = (cos, sin)
  * of position * theta^(-2i/head_dim), rounded to bf16 values (HF LlamaRotaryEmbedding casts cos/sin to the activations'
  * dtype), followed by the same values packed as bf16 pairs, uint32 [max_positions][head_dim/2] = cos | sin << 16. */
@@ -345,7 +373,8 @@ int lr_rope_table(float* cs, int32_t max_positions, int32_t head_dim, float thet
 
 /* Stand-alone varlen causal attention (exposed for parity tests):
  * qkv: DEVICE bf16 [total][(nh+2*nkv)*hd] (RoPE already applied; any consistent permutation of the
- * dims inside q and k heads), out: bf16 [total][nh*hd]. */
+ * dims inside q and k heads), out: bf16 [total][nh*hd]. variant 0 = auto (2 at head_dim 128, else 1), 1 generic,
+ * 2 = head_dim-128 MFMA, 4 = head_dim-256 MFMA. */
 int lr_attention_varlen(const uint16_t* qkv, uint16_t* out, const int32_t* cu_seqlens,
                         const int32_t* cu_seqlens_host, int32_t B, int32_t num_heads,
                         int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* hip_stream);

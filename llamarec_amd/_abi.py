@@ -58,6 +58,15 @@ class LrLlamaConfig(C.Structure):
     ]
 
 
+class LrLlamaArch(C.Structure):
+    _fields_ = [
+        ("norm_style", C.c_int32),
+        ("mlp_act", C.c_int32),
+        ("embed_scale", C.c_float),
+        ("reserved", C.c_int32 * 5),
+    ]
+
+
 class LrLlamaLayerWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("input_norm", "wqkv", "wo", "post_norm", "wgu", "wdown")]
 

@@ -50,6 +50,9 @@ PROTOTYPES = {
     "lr_gemm_bf16_nt_residual_rmsnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
                                                    C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lr_gemm_bf16_nt_residual_rmsnorm_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
+                                                      C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]),
     "lr_rope_table_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lr_rope_table": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "lr_metrics_from_histogram": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -68,6 +71,8 @@ PROTOTYPES = {
     "lr_lru_train_param_range": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "lr_llama_create": (C.c_int, [C.POINTER(A.LrLlamaConfig), C.POINTER(A.LrLlamaWeightsDesc),
                                   C.POINTER(C.c_void_p)]),
+    "lr_llama_create_ex": (C.c_int, [C.POINTER(A.LrLlamaConfig), C.POINTER(A.LrLlamaArch), C.POINTER(A.LrLlamaWeightsDesc),
+                                     C.POINTER(C.c_void_p)]),
     "lr_llama_destroy": (None, [C.c_void_p]),
     "lr_llama_set_variants": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "lr_llama_set_last_layer_pruning": (C.c_int, [C.c_void_p, C.c_int32]),

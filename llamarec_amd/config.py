@@ -12,6 +12,20 @@ from .prompt import DEFAULT_INPUT_TEMPLATE, DEFAULT_SYSTEM_TEMPLATE
 EXPERIMENT_ROOT = "experiments"   # config.py:5-9
 STATE_DICT_KEY = "model_state_dict"
 RAW_DATASET_ROOT_FOLDER = "data"
+# --llm -> base model / tokenizer of the reference's set_template (config.py:29-55). The ranker's kernels serve the llama
+# (llama2, llama3, mistral) and gemma families (llm.model_family); the other names parse like the reference's and are
+# refused when their checkpoint is loaded.
+LLM_CHOICES = ["llama2", "llama3", "phi3", "gemma", "mistral", "gemma2", "qwen2"]
+LLM_BASE_MODELS = {
+    "phi3": "microsoft/Phi-3-mini-4k-instruct",
+    "llama2": "meta-llama/Llama-2-7b-hf",
+    "llama3": "meta-llama/Meta-Llama-3-8B",
+    "gemma": "google/gemma-2b",
+    "mistral": "mistralai/Mistral-7B-v0.3",
+    "gemma2": "google/gemma-2-9b",
+    "qwen2": "Qwen/Qwen2-0.5B",
+}
+DEFAULT_LLM_BASE = "meta-llama/Llama-2-7b-hf"
 
 
 def build_parser():
@@ -30,8 +44,9 @@ def build_parser():
     p.add_argument("--bert_max_len", type=int, default=None)
     p.add_argument("--bert_hidden_units", type=int, default=64)
     p.add_argument("--bert_num_blocks", type=int, default=None)
-    p.add_argument("--llm_base_model", type=str, default="meta-llama/Llama-2-7b-hf")
-    p.add_argument("--llm_base_tokenizer", type=str, default="meta-llama/Llama-2-7b-hf")
+    p.add_argument("--llm", type=str, default=None, choices=LLM_CHOICES)   # config.py:223-228
+    p.add_argument("--llm_base_model", type=str, default=DEFAULT_LLM_BASE)
+    p.add_argument("--llm_base_tokenizer", type=str, default=DEFAULT_LLM_BASE)
     p.add_argument("--llm_max_title_len", type=int, default=32)
     p.add_argument("--llm_max_text_len", type=int, default=1536)
     p.add_argument("--llm_max_history", type=int, default=20)
@@ -102,8 +117,15 @@ def set_template(args):
         args.bert_max_len = 200 if ml else 50
     if args.bert_num_blocks is None:
         args.bert_num_blocks = 2
+    llm = getattr(args, "llm", None)
+    if llm is not None:                                    # config.py:29-55 (an explicitly given local path is kept)
+        if args.llm_base_model == DEFAULT_LLM_BASE:
+            args.llm_base_model = LLM_BASE_MODELS[llm]
+        if args.llm_base_tokenizer == DEFAULT_LLM_BASE:
+            args.llm_base_tokenizer = LLM_BASE_MODELS[llm]
+    llm_div = {"llama3": 2, "gemma": 4}.get(llm, 1)       # config.py:90-102: llama3 halves the batches, gemma quarters them
     if args.train_batch_size is None:                      # config.py:90-107
-        args.train_batch_size = (32 if ml else 16) if args.model_code == "llm" else (16 if ml else 64)
+        args.train_batch_size = (32 if ml else 16) // llm_div if args.model_code == "llm" else (16 if ml else 64)
     if args.lr is None:                                    # config.py:121-124
         args.lr = 1e-3
     if args.weight_decay is None:
@@ -132,9 +154,9 @@ def set_template(args):
         args.rerank_best_metric = "NDCG@10"
     if args.model_code == "llm":
         if args.lora_micro_batch_size is None:             # config.py:90-97
-            args.lora_micro_batch_size = 8 if args.dataset_code == "beauty" else 16
+            args.lora_micro_batch_size = (8 if args.dataset_code == "beauty" else 16) // llm_div
         if args.test_batch_size is None:
-            args.test_batch_size = 32 if ml else 16
+            args.test_batch_size = (32 if ml else 16) // llm_div
         if args.val_batch_size is None:
             args.val_batch_size = args.test_batch_size
     else:

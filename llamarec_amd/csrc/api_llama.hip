@@ -9,8 +9,17 @@
 
 typedef unsigned short u16;
 
-extern "C" int lr_llama_create(const LrLlamaConfig* cfg, const LrLlamaWeightsDesc* w, lr_llama_t** out) {
+extern "C" int lr_llama_create_ex(const LrLlamaConfig* cfg, const LrLlamaArch* arch, const LrLlamaWeightsDesc* w,
+                                  lr_llama_t** out) {
   if (!cfg || !w || !out || !w->layers) LR_FAIL(LR_EINVAL, "lr_llama_create: null argument");
+  const LrLlamaArch llama_arch = {0, 0, 1.0f, {0, 0, 0, 0, 0}};
+  if (!arch) arch = &llama_arch;
+  if (arch->norm_style < 0 || arch->norm_style > 1 || arch->mlp_act < 0 || arch->mlp_act > 1 ||
+      !(arch->embed_scale > 0.f) || arch->embed_scale != arch->embed_scale)
+    LR_FAIL(LR_EINVAL, "lr_llama_create_ex: arch norm_style=%d mlp_act=%d embed_scale=%g", arch->norm_style, arch->mlp_act,
+            (double)arch->embed_scale);
+  for (int i = 0; i < 5; ++i)
+    if (arch->reserved[i]) LR_FAIL(LR_EINVAL, "lr_llama_create_ex: arch reserved word %d is not zero", i);
   if (cfg->num_layers < 1 || cfg->num_heads < 1 || cfg->num_kv_heads < 1 || cfg->vocab_size < 1)
     LR_FAIL(LR_EINVAL, "lr_llama_create: bad config");
   if (cfg->hidden_size % 8 != 0 || cfg->intermediate_size % 16 != 0)
@@ -29,6 +38,7 @@ extern "C" int lr_llama_create(const LrLlamaConfig* cfg, const LrLlamaWeightsDes
   lr_llama* h = (lr_llama*)calloc(1, sizeof(lr_llama));
   if (!h) LR_FAIL(LR_EINVAL, "lr_llama_create: out of host memory");
   h->cfg = *cfg;
+  h->arch = *arch;
   h->embed = w->embed;
   h->final_norm = w->final_norm;
   h->lm_head = w->lm_head;
@@ -40,10 +50,14 @@ extern "C" int lr_llama_create(const LrLlamaConfig* cfg, const LrLlamaWeightsDes
   return LR_OK;
 }
 
+extern "C" int lr_llama_create(const LrLlamaConfig* cfg, const LrLlamaWeightsDesc* w, lr_llama_t** out) {
+  return lr_llama_create_ex(cfg, nullptr, w, out);
+}
+
 extern "C" int lr_llama_set_variants(lr_llama_t* h, int32_t gemm_variant, int32_t attention_variant) {
   if (!h || (gemm_variant != 0 && gemm_variant != 1 && gemm_variant != 4 && gemm_variant != 5) || attention_variant < 0 ||
-      attention_variant > 3)
-    LR_FAIL(LR_EINVAL, "lr_llama_set_variants: gemm in {0, 1, 4, 5}, attention in {0, 1, 2, 3}");
+      attention_variant > 4)
+    LR_FAIL(LR_EINVAL, "lr_llama_set_variants: gemm in {0, 1, 4, 5}, attention in {0, 1, 2, 3, 4}");
   h->gemm_variant = gemm_variant;
   h->attn_variant = attention_variant;
   return LR_OK;
@@ -72,6 +86,8 @@ extern "C" int lr_fold_norm_bf16(const uint16_t* w, const uint16_t* norm_w, int3
 extern "C" int lr_llama_set_folded_norms(lr_llama_t* h, const uint16_t* const* wqkv_folded,
                                          const uint16_t* const* wgu_folded) {
   if (!h) LR_FAIL(LR_EINVAL, "lr_llama_set_folded_norms: null handle");
+  if (h->arch.norm_style != 0 && (wqkv_folded || wgu_folded))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: a Gemma norm (1 + w) cannot be folded into bf16 weights at HF's rounding");
   free(h->wqkv_folded);
   free(h->wgu_folded);
   h->wqkv_folded = h->wgu_folded = nullptr;
@@ -190,6 +206,8 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
   const int d = c.hidden_size, f = c.intermediate_size, nh = c.num_heads, nkv = c.num_kv_heads,
             hd = c.head_dim;
   const int qkv_w = (nh + 2 * nkv) * hd;
+  const int ns = h->arch.norm_style;                               // 0 Llama, 1 Gemma RMSNorm
+  const int epi_mlp = h->arch.mlp_act == 1 ? LR_EPI_GEGLU : LR_EPI_SWIGLU;
   int rc;
 #define RUN(x)              \
   do {                      \
@@ -204,9 +222,13 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
   const bool attn256 = h->attn_variant == 3 && lr_attention256_takes(hd, P);
   if (h->attn_variant == 3 && !attn256 && hd != 128)
     LR_FAIL(LR_EUNSUPPORTED, "llama prefill: attention variant 3 needs head_dim 128 (got %d)", hd);
-  const int attn_var = attn256 ? 3 : (h->attn_variant == 3 ? 2 : h->attn_variant);
+  if (h->attn_variant == 4 && hd != 256)
+    LR_FAIL(LR_EUNSUPPORTED, "llama prefill: attention variant 4 needs head_dim 256 (got %d)", hd);
+  // 4 = head_dim-256 MFMA kernel (llama_attn_hd256.hip): auto takes it at head_dim 256 (P is 0 there)
+  const bool attn_hd256 = hd == 256 && (h->attn_variant == 0 || h->attn_variant == 4);
+  const int attn_var = attn256 ? 3 : attn_hd256 ? 4 : (h->attn_variant == 3 ? 2 : h->attn_variant);
   if (attn256) RUN(lr_launch_attn256_items(ws.seg_start, S, n, nh, P, ws.attn_items, ws.attn_items_bytes, st));
-  RUN(lr_launch_embed(ids, ws.tok_src, h->embed, c.vocab_size, d, ws.x, n, st));
+  RUN(lr_launch_embed(ids, ws.tok_src, h->embed, c.vocab_size, d, ws.x, n, st, h->arch.embed_scale));
   bool input_normed = false;   // ws.xn already holds RMSNorm(ws.x) with this layer's input_norm
 #ifdef LR_EXPERIMENTS   // timing-only arm (never in the product library): the row statistics of layer 0 serve every layer
   static const bool exp_rstd_once = getenv("LR_EXP_RSTD_ONCE") && getenv("LR_EXP_RSTD_ONCE")[0] == '1';
@@ -228,7 +250,7 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
     if (last_q_only) {
       const int q_w = nh * hd, kv_w = 2 * nkv * hd;
       const int pv = (h->gemm_variant == 5 || (h->gemm_variant == 0 && B <= 256)) ? 5 : 1;
-      if (!input_normed) RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st));
+      if (!input_normed) RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st, ns));
       RUN(lr_launch_gemm(ws.xn, w.wqkv + (size_t)q_w * d, ws.qkv, nullptr, n, kv_w, d, LR_EPI_ROPE, h->gemm_variant, st,
                          ws.tok_pos, ws.rope, hd, nkv * hd, ws.splitk, LR_SPLITK_WS_BYTES, nullptr, ws.rope16));
       RUN(lr_launch_gather_rows(ws.xn, ws.last_rows, B, d, ws.xn_last, st));
@@ -240,7 +262,7 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
       RUN(lr_launch_gemm(ws.x, h->wqkv_folded[l], ws.qkv, nullptr, n, qkv_w, d, LR_EPI_ROPE, h->gemm_variant, st, ws.tok_pos,
                          ws.rope, hd, (nh + nkv) * hd, ws.splitk, LR_SPLITK_WS_BYTES, ws.rstd, ws.rope16));
     } else {
-      if (!input_normed) RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st));
+      if (!input_normed) RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st, ns));
       RUN(lr_launch_gemm(ws.xn, w.wqkv, ws.qkv, nullptr, n, qkv_w, d, LR_EPI_ROPE, h->gemm_variant, st, ws.tok_pos,
                          ws.rope, hd, (nh + nkv) * hd, ws.splitk, LR_SPLITK_WS_BYTES, nullptr, ws.rope16));
     }
@@ -249,9 +271,9 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
       // last layer needs K/V for every token but attention output, o_proj, and the MLP for B rows only.
       if (last_q_only) {
         // ws.att_last already holds the attention rows of the last tokens
-      } else if (hd == 128 && h->attn_variant != 1) {
+      } else if ((hd == 128 && h->attn_variant != 1) || attn_var == 4) {
         // the MFMA kernel over ALL rows (188 us for 14.8 k tokens, 16 us for one prompt) beats the scalar kernel over the
-        // B last rows (459 / 295 us): attend everything, keep the last rows
+        // B last rows (459 / 295 us): attend everything, keep the last rows (head_dim 256 likewise, on variant 4)
         if (attn256)
           RUN(lr_launch_attention256(ws.qkv, ws.att, ws.seg_start, seg_host, S, n, nh, nkv, hd, nullptr, ws.attn_items, st, P));
         else
@@ -270,9 +292,9 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
       const int pv = (h->gemm_variant == 5 || (h->gemm_variant == 0 && B <= 256)) ? 5 : 1;
       bool normed = false;   // a split-K product's reduce pass also writes the RMSNorm that follows (same bits)
       RUN(lr_launch_gemm(ws.att_last, w.wo, ws.x_last, ws.x_last, B, d, nh * hd, LR_EPI_RESIDUAL, pv, st, nullptr, nullptr,
-                         0, 0, ws.splitk, LR_SPLITK_WS_BYTES, nullptr, nullptr, w.post_norm, ws.xn_last, c.rms_eps, &normed));
-      if (!normed) RUN(lr_launch_rmsnorm(ws.x_last, w.post_norm, ws.xn_last, B, d, c.rms_eps, nullptr, st));
-      RUN(lr_launch_gemm(ws.xn_last, w.wgu, ws.h_last, nullptr, B, 2 * f, d, LR_EPI_SWIGLU, pv, st, nullptr, nullptr, 0, 0,
+                         0, 0, ws.splitk, LR_SPLITK_WS_BYTES, nullptr, nullptr, w.post_norm, ws.xn_last, c.rms_eps, &normed, ns));
+      if (!normed) RUN(lr_launch_rmsnorm(ws.x_last, w.post_norm, ws.xn_last, B, d, c.rms_eps, nullptr, st, ns));
+      RUN(lr_launch_gemm(ws.xn_last, w.wgu, ws.h_last, nullptr, B, 2 * f, d, epi_mlp, pv, st, nullptr, nullptr, 0, 0,
                          ws.splitk, LR_SPLITK_WS_BYTES));
       RUN(lr_launch_gemm(ws.h_last, w.wdown, ws.x_last, ws.x_last, B, d, f, LR_EPI_RESIDUAL, pv, st, nullptr, nullptr, 0, 0,
                          ws.splitk, LR_SPLITK_WS_BYTES));
@@ -287,21 +309,21 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
     bool post_normed = false;
     RUN(lr_launch_gemm(ws.att, w.wo, ws.x, ws.x, n, d, nh * hd, LR_EPI_RESIDUAL, h->gemm_variant, st, nullptr, nullptr, 0,
                        0, ws.splitk, LR_SPLITK_WS_BYTES, nullptr, nullptr, folded ? nullptr : w.post_norm, ws.xn, c.rms_eps,
-                       &post_normed));
+                       &post_normed, ns));
     if (folded) {
       if (!EXP_SKIP_SWEEP) RUN(lr_launch_rms_rstd(ws.x, ws.rstd, n, d, c.rms_eps, st));
       RUN(lr_launch_gemm(ws.x, h->wgu_folded[l], ws.hmid, nullptr, n, 2 * f, d, LR_EPI_SWIGLU, h->gemm_variant, st, nullptr,
                          nullptr, 0, 0, ws.splitk, LR_SPLITK_WS_BYTES, ws.rstd));
     } else {
-      if (!post_normed) RUN(lr_launch_rmsnorm(ws.x, w.post_norm, ws.xn, n, d, c.rms_eps, nullptr, st));
-      RUN(lr_launch_gemm(ws.xn, w.wgu, ws.hmid, nullptr, n, 2 * f, d, LR_EPI_SWIGLU, h->gemm_variant, st, nullptr, nullptr,
+      if (!post_normed) RUN(lr_launch_rmsnorm(ws.x, w.post_norm, ws.xn, n, d, c.rms_eps, nullptr, st, ns));
+      RUN(lr_launch_gemm(ws.xn, w.wgu, ws.hmid, nullptr, n, 2 * f, d, epi_mlp, h->gemm_variant, st, nullptr, nullptr,
                          0, 0, ws.splitk, LR_SPLITK_WS_BYTES));
     }
     // down_proj; its reduce pass (latency mode) also writes the NEXT layer's input RMSNorm when that layer reads ws.xn
     const bool next_reads_xn = l + 1 < c.num_layers && !folded;
     RUN(lr_launch_gemm(ws.hmid, w.wdown, ws.x, ws.x, n, d, f, LR_EPI_RESIDUAL, h->gemm_variant, st, nullptr, nullptr, 0, 0,
                        ws.splitk, LR_SPLITK_WS_BYTES, nullptr, nullptr, next_reads_xn ? h->layers[l + 1].input_norm : nullptr,
-                       ws.xn, c.rms_eps, &input_normed));
+                       ws.xn, c.rms_eps, &input_normed, ns));
   }
 #undef RUN
 #undef EXP_SKIP_SWEEP
@@ -316,7 +338,8 @@ static int prefill_head(lr_llama_t* h, const int32_t* packed_ids, const int32_t*
   int rc = run_body(h, packed_ids, cu_seqlens, cu_seqlens_host, B, prefix_len, workspace, workspace_bytes, st, &ws);
   if (rc) return rc;
   return lr_launch_head(ws.compact ? ws.x_last : ws.x, ws.compact ? nullptr : ws.last_rows, h->final_norm, h->lm_head,
-                        class_ids, B, C, h->cfg.hidden_size, h->cfg.rms_eps, out, h->cfg.vocab_size, st, ws.prefix_bad);
+                        class_ids, B, C, h->cfg.hidden_size, h->cfg.rms_eps, out, h->cfg.vocab_size, st, ws.prefix_bad,
+                        h->arch.norm_style);
 }
 
 extern "C" int lr_llama_prefill_verbalize(lr_llama_t* h, const int32_t* packed_ids, const int32_t* cu_seqlens,
@@ -414,7 +437,8 @@ extern "C" int lr_gemm_bf16_nt_epi(const uint16_t* A, const uint16_t* B, uint16_
                                    const float* rope_cs, int32_t rope_positions, int32_t head_dim, int32_t rot_cols,
                                    void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (!A || !B || !C) LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt_epi: null pointer");
-  if (epilogue < LR_EPI_STORE || epilogue > LR_EPI_ROPE) LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt_epi: epilogue %d", epilogue);
+  if (epilogue < LR_EPI_STORE || epilogue > LR_EPI_GEGLU || epilogue == LR_EPI_PARTIAL)
+    LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt_epi: epilogue %d", epilogue);
   // the packed half of lr_rope_table's buffer sits behind the fp32 half
   const unsigned* cs16 = (rope_cs && rope_positions > 0 && head_dim >= 2)
                              ? reinterpret_cast<const unsigned*>(rope_cs + (size_t)rope_positions * head_dim) : nullptr;
@@ -422,19 +446,29 @@ extern "C" int lr_gemm_bf16_nt_epi(const uint16_t* A, const uint16_t* B, uint16_
                         rot_cols, (float*)workspace, workspace_bytes, nullptr, cs16);
 }
 
+extern "C" int lr_gemm_bf16_nt_residual_rmsnorm_ex(const uint16_t* A, const uint16_t* B, uint16_t* C, const uint16_t* R,
+                                                   int32_t M, int32_t N, int32_t K, int32_t variant, const uint16_t* norm_w,
+                                                   uint16_t* norm_out, float eps, int32_t norm_style, int32_t fuse,
+                                                   int32_t* was_fused, void* workspace, size_t workspace_bytes,
+                                                   void* hip_stream) {
+  if (!A || !B || !C || !R || !norm_w || !norm_out) LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt_residual_rmsnorm: null pointer");
+  if (norm_style != 0 && norm_style != 1) LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt_residual_rmsnorm_ex: norm_style %d", norm_style);
+  hipStream_t st = (hipStream_t)hip_stream;
+  bool done = false;
+  int rc = lr_launch_gemm(A, B, C, R, M, N, K, LR_EPI_RESIDUAL, variant, st, nullptr, nullptr, 0, 0, (float*)workspace,
+                          workspace_bytes, nullptr, nullptr, fuse ? norm_w : nullptr, norm_out, eps, &done, norm_style);
+  if (rc) return rc;
+  if (was_fused) *was_fused = done ? 1 : 0;
+  if (done) return LR_OK;
+  return lr_launch_rmsnorm(C, norm_w, norm_out, M, N, eps, nullptr, st, norm_style);
+}
+
 extern "C" int lr_gemm_bf16_nt_residual_rmsnorm(const uint16_t* A, const uint16_t* B, uint16_t* C, const uint16_t* R,
                                                 int32_t M, int32_t N, int32_t K, int32_t variant, const uint16_t* norm_w,
                                                 uint16_t* norm_out, float eps, int32_t fuse, int32_t* was_fused,
                                                 void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (!A || !B || !C || !R || !norm_w || !norm_out) LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt_residual_rmsnorm: null pointer");
-  hipStream_t st = (hipStream_t)hip_stream;
-  bool done = false;
-  int rc = lr_launch_gemm(A, B, C, R, M, N, K, LR_EPI_RESIDUAL, variant, st, nullptr, nullptr, 0, 0, (float*)workspace,
-                          workspace_bytes, nullptr, nullptr, fuse ? norm_w : nullptr, norm_out, eps, &done);
-  if (rc) return rc;
-  if (was_fused) *was_fused = done ? 1 : 0;
-  if (done) return LR_OK;
-  return lr_launch_rmsnorm(C, norm_w, norm_out, M, N, eps, nullptr, st);
+  return lr_gemm_bf16_nt_residual_rmsnorm_ex(A, B, C, R, M, N, K, variant, norm_w, norm_out, eps, 0, fuse, was_fused,
+                                             workspace, workspace_bytes, hip_stream);
 }
 
 extern "C" size_t lr_rope_table_bytes(int32_t max_positions, int32_t head_dim) {

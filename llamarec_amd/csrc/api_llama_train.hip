@@ -95,6 +95,8 @@ extern "C" int lr_llama_lora_create(lr_llama_t* base, const LrLlamaWeightsTDesc*
                                     void* state, size_t state_bytes, void* hip_stream, lr_llama_lora_t** out) {
   int rc = check_cfg(base, cfg, "lr_llama_lora_create");
   if (rc) return rc;
+  if (base->arch.norm_style != 0 || base->arch.mlp_act != 0 || base->arch.embed_scale != 1.0f)
+    LR_FAIL(LR_EUNSUPPORTED, "lr_llama_lora_create: fine-tuning needs a Llama base (no GeGLU / Gemma-norm backward)");
   if (!wt || !wt->layers || !wt->lm_head_t || !state || !out) LR_FAIL(LR_EINVAL, "lr_llama_lora_create: null argument");
   const LrLlamaConfig& c = base->cfg;
   for (int l = 0; l < c.num_layers; ++l) {

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "llama_kernels.h"
+#include "lr_attn_util.h"
 #include "lr_profile.h"
 
 typedef unsigned short u16;
@@ -116,78 +117,6 @@ __global__ __launch_bounds__(256) void attn_generic_kernel(const u16* qkv, u16* 
 
 __device__ __forceinline__ int v_off(int row, int ch) {  // dual-use swizzle, 256-byte rows
   return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-
-// LDS-DMA through a buffer descriptor as INLINE ASM. With the builtin (__builtin_amdgcn_raw_ptr_buffer_load_lds) hipcc
-// knows an LDS write is pending on the vector-memory counter and -- unable to prove that a ds_read_b64_tr_b16 (the V^T
-// fragment reads) touches another stage buffer -- puts `s_waitcnt vmcnt(0)` in front of the first transposed read of every
-// key block: each wave then sat out the landing of the NEXT block's tiles in the middle of the current block (found in
-// round 3 in the .s of the product kernel; it is also why requesting the V fragments earlier was slower). The asm form is
-// invisible to that pass; the one wait that is needed stands in front of the block's barrier, written by hand.
-// (M0 is a reserved register to hipcc: it cannot be named as a clobber, and nothing else in these kernels uses it --
-// gfx9+ LDS instructions do not read M0.)
-typedef int fa_int4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ fa_int4 fa_make_rsrc(const void* base, int num_records) {
-  const unsigned long long b = reinterpret_cast<unsigned long long>(base);
-  fa_int4 r;
-  r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-  r[1] = __builtin_amdgcn_readfirstlane((int)((b >> 32) & 0xffffu));   // stride 0
-  r[2] = __builtin_amdgcn_readfirstlane(num_records);
-  r[3] = 0x00020000;
-  return r;
-}
-__device__ __forceinline__ void fa_glds16(const void* gsrc, const void* lds_wave_base) {   // per-lane source address
-  const unsigned m0v = (unsigned)(size_t)((__attribute__((address_space(3))) const char*)lds_wave_base);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(m0v), "v"(gsrc) : "memory");
-}
-__device__ __forceinline__ void fa_dma16(fa_int4 rsrc, const void* lds_wave_base, unsigned voff) {
-  const unsigned m0v = (unsigned)(size_t)((__attribute__((address_space(3))) const char*)lds_wave_base);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(m0v), "v"(voff), "s"(rsrc)
-               : "memory");
-}
-
-// x[lane] (op) x[lane ^ 16] and x[lane] (op) x[lane ^ 32] without the LDS crossbar: gfx950's row / half swaps
-// (v_permlane16_swap, v_permlane32_swap) hand both partners to every lane at VALU speed; __shfl_xor compiles
-// to ds_bpermute_b32 (~100+ cycles of dependent latency, four of them on every key block's critical path).
-// hipcc pitfall: __builtin_bit_cast(float, r[1]) on the builtin's 2-vector result reads element 0 (the cast
-// takes the vector's address) -- copy the elements into scalars first.
-__device__ __forceinline__ void fa_swap16(float v, float& a, float& b) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  const unsigned r0 = r[0], r1 = r[1];
-  a = __builtin_bit_cast(float, r0);
-  b = __builtin_bit_cast(float, r1);
-}
-__device__ __forceinline__ void fa_swap32(float v, float& a, float& b) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  const unsigned r0 = r[0], r1 = r[1];
-  a = __builtin_bit_cast(float, r0);
-  b = __builtin_bit_cast(float, r1);
-}
-// v_max3_f32 on raw MFMA outputs: fmaxf() makes hipcc canonicalise every input first (a v_max_f32 x, x per score);
-// the scores are finite or -inf here, where max is exact whatever the association
-__device__ __forceinline__ float fa_max3(float a, float b, float c) {
-  float r;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-__device__ __forceinline__ float fa_max2(float a, float b) {
-  float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ float fa_max_xor16_32(float v) {
-  float a, b;
-  fa_swap16(v, a, b);
-  fa_swap32(fa_max2(a, b), a, b);
-  return fa_max2(a, b);
-}
-__device__ __forceinline__ float fa_sum_xor16_32(float v) {
-  float a, b;
-  fa_swap16(v, a, b);
-  fa_swap32(a + b, a, b);
-  return a + b;
 }
 
 #define FA_TILE_BYTES (FA_KB * 256)        // one K or V tile: 64 keys x 128 dims bf16
@@ -619,6 +548,8 @@ int lr_launch_attention(const u16* qkv, u16* out, const int32_t* cu, const int32
   if (n_tok <= 0 || B <= 0) return LR_OK;
   if (nh % nkv != 0) LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
   if (variant == 0) variant = (hd == 128) ? 2 : 1;
+  if (variant == 4 && prefix_len == 0 && !scratch)   // head_dim 256 (llama_attn_hd256.hip): no prefix, no lse
+    return lr_launch_attention_hd256(qkv, out, cu, cu_host, B, n_tok, nh, nkv, hd, st);
   if (prefix_len < 0 || (prefix_len > 0 && (variant != 2 || cu_host[1] - cu_host[0] != prefix_len)))
     LR_FAIL(LR_EINVAL, "attention: shared prefix of %d tokens needs the head_dim-128 MFMA kernel and segment 0 = the prefix",
             prefix_len);
@@ -667,8 +598,8 @@ int lr_launch_attention(const u16* qkv, u16* out, const int32_t* cu, const int32
                        n_tok, nh, nkv, hd, (const int32_t*)nullptr, lse);
     LR_CHECK_LAUNCH("attn_generic_kernel");
   } else {
-    LR_FAIL(LR_EINVAL, "attention: unknown variant %d here (0 auto, 1 generic, 2 = head_dim-128 MFMA; 3 needs a workspace: "
-            "lr_attention_varlen_ws)", variant);
+    LR_FAIL(LR_EINVAL, "attention: unknown variant %d here (0 auto, 1 generic, 2 = head_dim-128 MFMA, 4 = head_dim-256 MFMA "
+            "without shared prefix or lse; 3 needs a workspace: lr_attention_varlen_ws)", variant);
   }
   return LR_OK;
 }

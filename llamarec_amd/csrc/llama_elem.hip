@@ -70,22 +70,35 @@ __global__ void token_meta_kernel(const int32_t* cu, int B, int P, int32_t* seg_
 }
 
 // ---- embedding gather ------------------------------------------------------------------------
+// SCALE (Gemma): every value bf16(e * scale), the scale already a bf16 value
+template <bool SCALE>
 __global__ __launch_bounds__(256) void embed_kernel(const int32_t* ids, const int32_t* tok_src, const u16* table,
-                                                    int vocab, int d, u16* out) {
+                                                    int vocab, int d, u16* out, float scale) {
   const int tok = blockIdx.x;
   int id = ids[tok_src ? tok_src[tok] : tok];
   if (id < 0 || id >= vocab) id = 0;
   const u16x8* src = reinterpret_cast<const u16x8*>(table + (size_t)id * d);
   u16x8* dst = reinterpret_cast<u16x8*>(out + (size_t)tok * d);
-  for (int i = threadIdx.x; i < d / 8; i += 256) dst[i] = src[i];
+  for (int i = threadIdx.x; i < d / 8; i += 256) {
+    if (SCALE) {
+      const u16x8 e = src[i];
+      u16x8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = f2bf(bf2f(e[j]) * scale);
+      dst[i] = o;
+    } else {
+      dst[i] = src[i];
+    }
+  }
 }
 
 // ---- RMSNorm: out = bf16( w * bf16( x * rsqrt(mean(x^2) + eps) ) ) --------------------------
 // One workgroup per row. Rows of up to 8192 features stay in registers between the square sum and the scaling (each
 // thread keeps its <= 4 pieces of 8, and requests the matching weights with them): the kernel is a chain of memory
 // latencies per row, not bandwidth, and re-reading the row after the reduction added one more link. Same arithmetic,
-// same order, as the two-pass form that longer rows still take.
+// same order, as the two-pass form that longer rows still take. NS = norm style (rms_apply: 0 Llama, 1 Gemma).
 #define RMS_KEEP 4
+template <int NS>
 __global__ __launch_bounds__(256) void rmsnorm_kernel(const u16* x, const u16* w, u16* out, int d,
                                                       float eps, const int32_t* row_map) {
   __shared__ float red[4];
@@ -135,7 +148,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const u16* x, const u16* w
       if (i < nv) {
         u16x8 o;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = f2bf(bf2f(wb[k][j]) * bf2f(f2bf(bf2f(vb[k][j]) * rstd)));
+        for (int j = 0; j < 8; ++j) o[j] = rms_apply<NS>(wb[k][j], vb[k][j], rstd);
         orow[i] = o;
       }
     }
@@ -143,7 +156,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const u16* x, const u16* w
     for (int i = threadIdx.x; i < nv; i += 256) {
       u16x8 v = xr[i], wv = wr[i], o;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = f2bf(bf2f(wv[j]) * bf2f(f2bf(bf2f(v[j]) * rstd)));
+      for (int j = 0; j < 8; ++j) o[j] = rms_apply<NS>(wv[j], v[j], rstd);
       orow[i] = o;
     }
   }
@@ -156,6 +169,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const u16* x, const u16* w
 // columns, exactly rmsnorm_kernel's assignment, so the square sum is formed from the same values in the same order and the
 // two outputs (residual row C, normalised row `out`) carry the same bits as the two-launch form (planes summed in split
 // order, then bf16(bf16(sum) + residual) as in the GEMM's residual epilogue).
+template <int NS>
 __global__ __launch_bounds__(256) void reduce_residual_rmsnorm_kernel(const float* __restrict__ part, int S, size_t plane,
                                                                       u16* C, const u16* R, int N, const u16* w, u16* out,
                                                                       float eps) {
@@ -204,7 +218,7 @@ __global__ __launch_bounds__(256) void reduce_residual_rmsnorm_kernel(const floa
     if (i < nv) {
       u16x8 o;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = f2bf(bf2f(wb[k][j]) * bf2f(f2bf(bf2f(vb[k][j]) * rstd)));
+      for (int j = 0; j < 8; ++j) o[j] = rms_apply<NS>(wb[k][j], vb[k][j], rstd);
       reinterpret_cast<u16x8*>(out + (size_t)row * N)[i] = o;
     }
   }
@@ -212,10 +226,14 @@ __global__ __launch_bounds__(256) void reduce_residual_rmsnorm_kernel(const floa
 // false: the row is too long to keep in registers (the caller then runs the two launches)
 bool lr_reduce_residual_rmsnorm_fits(int N) { return N % 8 == 0 && N / 8 <= 256 * RMS_KEEP; }
 int lr_launch_reduce_residual_rmsnorm(const float* part, int S, u16* C, const u16* R, int M, int N, const u16* norm_w,
-                                      u16* norm_out, float eps, hipStream_t st) {
+                                      u16* norm_out, float eps, hipStream_t st, int norm_style) {
   if (!lr_reduce_residual_rmsnorm_fits(N)) LR_FAIL(LR_EUNSUPPORTED, "fused reduce + RMSNorm: %d columns", N);
-  hipLaunchKernelGGL(reduce_residual_rmsnorm_kernel, dim3(M), dim3(256), 0, st, part, S, (size_t)M * N, C, R, N, norm_w,
-                     norm_out, eps);
+  if (norm_style == 1)
+    hipLaunchKernelGGL(reduce_residual_rmsnorm_kernel<1>, dim3(M), dim3(256), 0, st, part, S, (size_t)M * N, C, R, N, norm_w,
+                       norm_out, eps);
+  else
+    hipLaunchKernelGGL(reduce_residual_rmsnorm_kernel<0>, dim3(M), dim3(256), 0, st, part, S, (size_t)M * N, C, R, N, norm_w,
+                       norm_out, eps);
   LR_CHECK_LAUNCH("reduce_residual_rmsnorm_kernel");
   return LR_OK;
 }
@@ -288,6 +306,7 @@ __global__ void rope_table_kernel(float* cs /*[T][hd/2][2]*/, unsigned* cs16 /*[
 
 // ---- final RMSNorm on each prompt's last token + dot with selected lm_head rows -------------
 // grid (B, ceil(C/32)); out[b][c] = float(bf16(sum_k xn[k] * W[row_c][k])), row_c = ids ? ids[c] : c
+template <int NS>
 __global__ __launch_bounds__(256) void head_kernel(const u16* x, const int32_t* rows, const u16* norm_w,
                                                    const u16* lm_head, const int32_t* class_ids, int C,
                                                    int d, float eps, float* out, int vocab, const int32_t* poison) {
@@ -312,7 +331,7 @@ __global__ __launch_bounds__(256) void head_kernel(const u16* x, const int32_t* 
   ss = block_sum_256(ss, red);
   const float rstd = 1.0f / sqrtf(ss / (float)d + eps);
   for (int i = threadIdx.x; i < d; i += 256)
-    xn[i] = f2bf(bf2f(norm_w[i]) * bf2f(f2bf(bf2f(xr[i]) * rstd)));
+    xn[i] = rms_apply<NS>(norm_w[i], xr[i], rstd);
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int cc = wave; cc < 32; cc += 4) {
@@ -364,15 +383,21 @@ int lr_launch_token_meta(const int32_t* cu, int B, int prefix_len, int32_t* seg_
 }
 
 int lr_launch_embed(const int32_t* ids, const int32_t* tok_src, const u16* table, int vocab, int d, u16* out, int n,
-                    hipStream_t st) {
-  hipLaunchKernelGGL(embed_kernel, dim3(n), dim3(256), 0, st, ids, tok_src, table, vocab, d, out);
+                    hipStream_t st, float scale) {
+  if (scale != 1.0f)
+    hipLaunchKernelGGL(embed_kernel<true>, dim3(n), dim3(256), 0, st, ids, tok_src, table, vocab, d, out, scale);
+  else
+    hipLaunchKernelGGL(embed_kernel<false>, dim3(n), dim3(256), 0, st, ids, tok_src, table, vocab, d, out, scale);
   LR_CHECK_LAUNCH("embed_kernel");
   return LR_OK;
 }
 
 int lr_launch_rmsnorm(const u16* x, const u16* w, u16* out, int rows, int d, float eps,
-                      const int32_t* row_map, hipStream_t st) {
-  hipLaunchKernelGGL(rmsnorm_kernel, dim3(rows), dim3(256), 0, st, x, w, out, d, eps, row_map);
+                      const int32_t* row_map, hipStream_t st, int norm_style) {
+  if (norm_style == 1)
+    hipLaunchKernelGGL(rmsnorm_kernel<1>, dim3(rows), dim3(256), 0, st, x, w, out, d, eps, row_map);
+  else
+    hipLaunchKernelGGL(rmsnorm_kernel<0>, dim3(rows), dim3(256), 0, st, x, w, out, d, eps, row_map);
   LR_CHECK_LAUNCH("rmsnorm_kernel");
   return LR_OK;
 }
@@ -386,10 +411,14 @@ int lr_launch_rope_table(float* cs, int T, int hd, float theta, hipStream_t st, 
 
 int lr_launch_head(const u16* x, const int32_t* rows, const u16* norm_w, const u16* lm_head,
                    const int32_t* class_ids, int B, int C, int d, float eps, float* out, int vocab,
-                   hipStream_t st, const int32_t* poison) {
+                   hipStream_t st, const int32_t* poison, int norm_style) {
   dim3 grid(B, (C + 31) / 32);
-  hipLaunchKernelGGL(head_kernel, grid, dim3(256), (size_t)d * sizeof(u16), st, x, rows, norm_w, lm_head,
-                     class_ids, C, d, eps, out, vocab, poison);
+  if (norm_style == 1)
+    hipLaunchKernelGGL(head_kernel<1>, grid, dim3(256), (size_t)d * sizeof(u16), st, x, rows, norm_w, lm_head,
+                       class_ids, C, d, eps, out, vocab, poison);
+  else
+    hipLaunchKernelGGL(head_kernel<0>, grid, dim3(256), (size_t)d * sizeof(u16), st, x, rows, norm_w, lm_head,
+                       class_ids, C, d, eps, out, vocab, poison);
   LR_CHECK_LAUNCH("head_kernel");
   return LR_OK;
 }

@@ -61,7 +61,7 @@ template <int EPI, int FOLD = -1>
 __device__ __forceinline__ u16x4 epi_value4(floatx4 v, floatx4 up, u16x4 r, const RopeArgs& rope, int row, int col,
                                             const float* pre_rs, const int* pre_pos, const float4* pre_cs = nullptr) {
   u16x4 o;
-  if ((EPI == LR_EPI_ROPE || EPI == LR_EPI_SWIGLU) && (FOLD == 1 || (FOLD == -1 && rope.row_scale))) {
+  if ((EPI == LR_EPI_ROPE || LR_EPI_IS_GATED(EPI)) && (FOLD == 1 || (FOLD == -1 && rope.row_scale))) {
     const float rs = pre_rs ? *pre_rs : rope.row_scale[row];
     v *= rs;
     up *= rs;
@@ -96,7 +96,8 @@ __device__ __forceinline__ u16x4 epi_value4(floatx4 v, floatx4 up, u16x4 r, cons
     for (int j = 0; j < 4; ++j) o[j] = f2bf(bf2f(f2bf(v[j])) + bf2f(r[j]));
   } else {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = swiglu_bf16(bf2f(f2bf(v[j])), bf2f(f2bf(up[j])));
+    for (int j = 0; j < 4; ++j)
+      o[j] = EPI == LR_EPI_GEGLU ? geglu_bf16(bf2f(f2bf(v[j])), bf2f(f2bf(up[j]))) : swiglu_bf16(bf2f(f2bf(v[j])), bf2f(f2bf(up[j])));
   }
   return o;
 }
@@ -191,14 +192,15 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(const u16* __restrict
             if (col + j < N) C[(size_t)row * N + col + j] = f2bf(acc[mt][nt][j] * (rope.row_scale ? rope.row_scale[row] : 1.0f));
         }
       }
-    } else if (EPI == LR_EPI_SWIGLU) {
+    } else if (LR_EPI_IS_GATED(EPI)) {
       int ocol = (n0 + wn * 32) / 2 + (lane >> 4) * 4;
       const float rs = rope.row_scale ? rope.row_scale[row] : 1.0f;
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (n0 + wn * 32 + 16 + (lane >> 4) * 4 + j < N)
           C[(size_t)row * (N / 2) + ocol + j] =
-              swiglu_bf16(bf2f(f2bf(acc[mt][0][j] * rs)), bf2f(f2bf(acc[mt][1][j] * rs)));
+              EPI == LR_EPI_GEGLU ? geglu_bf16(bf2f(f2bf(acc[mt][0][j] * rs)), bf2f(f2bf(acc[mt][1][j] * rs)))
+                                  : swiglu_bf16(bf2f(f2bf(acc[mt][0][j] * rs)), bf2f(f2bf(acc[mt][1][j] * rs)));
     } else {
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt)
@@ -446,7 +448,7 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
   // Folded RMSNorm: the tile's 256 row scales go to LDS (behind the two stage buffers) in front of the K loop, one per thread
   // of the first four waves; the epilogue reads its eight from there. Fetched in the epilogue they were a dependent global load
   // that nothing hides at one workgroup per CU (round 3: GEMMs 1 370 -> 1 347 TF/s).
-  constexpr bool has_rs = FOLD && (EPI == LR_EPI_ROPE || EPI == LR_EPI_SWIGLU);
+  constexpr bool has_rs = FOLD && (EPI == LR_EPI_ROPE || LR_EPI_IS_GATED(EPI));
   float* const rs_lds = reinterpret_cast<float*>(smem + 2 * G2_STAGE_BYTES);
   if (has_rs && tid < 256) rs_lds[tid] = rope.row_scale[min(m0 + tid, M - 1)];   // (visible behind the K loop's barriers)
   // ---- prologue: all of tile 0, then R0B, R0A, R1 of tile 1 (steady-state issue order)
@@ -490,7 +492,7 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
   // second: 16-byte stores (and residual loads: the swap is its own inverse, so the 16 bytes read at the store position
   // swap back into each lane's own columns). Partners share lane & 15, i.e. the row: the row guard never splits a pair.
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const int ldc = (EPI == LR_EPI_SWIGLU) ? (N >> 1) : N;
+  const int ldc = (LR_EPI_IS_GATED(EPI)) ? (N >> 1) : N;
   const int quad = lane >> 4;
   // Residual: all 16 reads of the lane are requested before the first store. Written load -> use -> store per pair, hipcc
   // keeps that order (R may alias C) and every read then waits, behind vmcnt(0), for the previous pair's store as well.
@@ -603,7 +605,7 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
         for (int nt = 0; nt < 4; ++nt)
           epi_store4<EPI>(acc[mt][nt], acc[mt][nt], C, R, (size_t)row * ldc + n0 + wn * 64 + nt * 16 + quad * 4);
       }
-    } else if (EPI == LR_EPI_SWIGLU) {
+    } else if (LR_EPI_IS_GATED(EPI)) {
       const int cbase = (n0 + wn * 64) >> 1;   // 32 output columns: tiles t = 0, 1 of 16
       unsigned a[2], b[2];
       {
@@ -672,7 +674,7 @@ template <int EPI>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int S, u16* C,
                                                             const u16* R, int M, int N, RopeArgs rope) {
   const size_t plane = (size_t)M * N;
-  if (EPI == LR_EPI_SWIGLU) {
+  if (LR_EPI_IS_GATED(EPI)) {
     // output column c of N/2: gate column (c/16)*32 + c%16, up column 16 further (16-row interleave of wgu)
     const int n_out = N >> 1;
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
@@ -732,7 +734,7 @@ static int gemm256_prepare() {
 template <int EPI>
 static int launch_splitk(const u16* A, const u16* B, u16* C, const u16* R, int M, int N, int K, int S, RopeArgs rope,
                          float* ws, hipStream_t st, const u16* then_norm_w = nullptr, u16* then_norm_out = nullptr,
-                         float then_norm_eps = 0.f, bool* then_norm_done = nullptr) {
+                         float then_norm_eps = 0.f, bool* then_norm_done = nullptr, int then_norm_style = 0) {
   LrProfScope prof(LR_PROF_GEMM256, 2.0 * M * (double)N * K, st, LR_PROF_GEMM_TAG(EPI, N, K));
   if (int rc = gemm256_prepare<LR_EPI_PARTIAL>()) return rc;
   const int nwg = ((M + 255) / 256) * (N / 256);
@@ -741,9 +743,9 @@ static int launch_splitk(const u16* A, const u16* B, u16* C, const u16* R, int M
   LR_CHECK_LAUNCH("gemm256rb_kernel<partial>");
   if (EPI == LR_EPI_RESIDUAL && then_norm_w && then_norm_out && then_norm_done && lr_reduce_residual_rmsnorm_fits(N)) {
     *then_norm_done = true;   // the reduce pass also writes RMSNorm(C) for the next projection
-    return lr_launch_reduce_residual_rmsnorm(ws, S, C, R, M, N, then_norm_w, then_norm_out, then_norm_eps, st);
+    return lr_launch_reduce_residual_rmsnorm(ws, S, C, R, M, N, then_norm_w, then_norm_out, then_norm_eps, st, then_norm_style);
   }
-  const size_t quads = (EPI == LR_EPI_SWIGLU ? (size_t)M * (N >> 1) : (size_t)M * N) / 4;
+  const size_t quads = (LR_EPI_IS_GATED(EPI) ? (size_t)M * (N >> 1) : (size_t)M * N) / 4;
   hipLaunchKernelGGL(splitk_reduce_kernel<EPI>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, ws, S, C, R, M,
                      N, rope);
   LR_CHECK_LAUNCH("splitk_reduce_kernel");
@@ -808,7 +810,7 @@ int lr_launch_gemm(const u16* A, const u16* B, u16* C, const u16* R, int M, int 
                    int variant, hipStream_t st, const int32_t* tok_pos, const float* rope_cs, int head_dim,
                    int rot_cols, float* splitk_ws, size_t splitk_ws_bytes, const float* row_scale,
                    const unsigned* rope_cs16, const u16* then_norm_w, u16* then_norm_out, float then_norm_eps,
-                   bool* then_norm_done) {
+                   bool* then_norm_done, int then_norm_style) {
   if (then_norm_done) *then_norm_done = false;
   if (M <= 0) return LR_OK;
   if (N <= 0 || K <= 0) LR_FAIL(LR_EINVAL, "gemm: N=%d K=%d", N, K);
@@ -819,7 +821,7 @@ int lr_launch_gemm(const u16* A, const u16* B, u16* C, const u16* R, int M, int 
     LR_FAIL(LR_EINVAL, "gemm: unknown variant %d (0 auto, 1 generic, 4 = 256x256x64 MFMA tile, 5 = 4 + split-K)", variant);
   if (variant == 4 && !fast_ok)
     LR_FAIL(LR_EUNSUPPORTED, "gemm variant 4 needs N%%256==0 and K%%64==0 (N=%d K=%d)", N, K);
-  if (epi == LR_EPI_SWIGLU && (N % 32 != 0)) LR_FAIL(LR_EINVAL, "swiglu epilogue needs N%%32==0 (N=%d)", N);
+  if (LR_EPI_IS_GATED(epi) && (N % 32 != 0)) LR_FAIL(LR_EINVAL, "gated-MLP epilogue needs N%%32==0 (N=%d)", N);
   if (epi == LR_EPI_RESIDUAL && !R) LR_FAIL(LR_EINVAL, "residual epilogue without residual pointer");
   RopeArgs rope{tok_pos, rope_cs, head_dim, rot_cols, row_scale, rope_cs16};
   if (row_scale && epi != LR_EPI_ROPE && epi != LR_EPI_SWIGLU)
@@ -838,8 +840,9 @@ int lr_launch_gemm(const u16* A, const u16* B, u16* C, const u16* R, int M, int 
         case LR_EPI_STORE: return launch_splitk<LR_EPI_STORE>(A, B, C, R, M, N, K, S, rope, splitk_ws, st);
         case LR_EPI_RESIDUAL:
           return launch_splitk<LR_EPI_RESIDUAL>(A, B, C, R, M, N, K, S, rope, splitk_ws, st, then_norm_w, then_norm_out,
-                                                then_norm_eps, then_norm_done);
+                                                then_norm_eps, then_norm_done, then_norm_style);
         case LR_EPI_SWIGLU: return launch_splitk<LR_EPI_SWIGLU>(A, B, C, R, M, N, K, S, rope, splitk_ws, st);
+        case LR_EPI_GEGLU: return launch_splitk<LR_EPI_GEGLU>(A, B, C, R, M, N, K, S, rope, splitk_ws, st);
         case LR_EPI_ROPE: return launch_splitk<LR_EPI_ROPE>(A, B, C, R, M, N, K, S, rope, splitk_ws, st);
       }
       LR_FAIL(LR_EINVAL, "gemm: unknown epilogue %d", epi);
@@ -850,6 +853,7 @@ int lr_launch_gemm(const u16* A, const u16* B, u16* C, const u16* R, int M, int 
     case LR_EPI_STORE: return launch_epi<LR_EPI_STORE>(A, B, C, R, M, N, K, variant, rope, st);
     case LR_EPI_RESIDUAL: return launch_epi<LR_EPI_RESIDUAL>(A, B, C, R, M, N, K, variant, rope, st);
     case LR_EPI_SWIGLU: return launch_epi<LR_EPI_SWIGLU>(A, B, C, R, M, N, K, variant, rope, st);
+    case LR_EPI_GEGLU: return launch_epi<LR_EPI_GEGLU>(A, B, C, R, M, N, K, variant, rope, st);
     case LR_EPI_ROPE: return launch_epi<LR_EPI_ROPE>(A, B, C, R, M, N, K, variant, rope, st);
   }
   LR_FAIL(LR_EINVAL, "gemm: unknown epilogue %d", epi);

@@ -20,12 +20,29 @@ __device__ __forceinline__ unsigned short swiglu_bf16(float g, float u) {
   return f2bf(s * u);
 }
 
+// Gemma's MLP: down_proj(gelu_pytorch_tanh(gate) * up) at swiglu_bf16's rounding points: bf16(gate) in, the activation
+// rounded to bf16, the product rounded to bf16. gelu(g) = 0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3))), fp32 (torch's
+// bf16 GELU computes in fp32 and rounds once).
+__device__ __forceinline__ unsigned short geglu_bf16(float g, float u) {
+  const float t = tanhf(0.7978845608028654f * (g + 0.044715f * g * g * g));
+  float s = bf2f(f2bf(0.5f * g * (1.0f + t)));
+  return f2bf(s * u);
+}
+// RMSNorm of one value: Llama (style 0) bf16(w * bf16(x * rstd)); Gemma (style 1) bf16(x * rstd * (1 + w)) in fp32
+template <int NS>
+__device__ __forceinline__ unsigned short rms_apply(unsigned short w, unsigned short x, float rstd) {
+  if (NS == 0) return f2bf(bf2f(w) * bf2f(f2bf(bf2f(x) * rstd)));
+  return f2bf(bf2f(x) * rstd * (1.0f + bf2f(w)));
+}
+
 // epilogue modes of the GEMMs
 #define LR_EPI_STORE 0     // C = bf16(acc)
 #define LR_EPI_RESIDUAL 1  // C = bf16( bf16(acc) + R )      (R may alias C)
 #define LR_EPI_SWIGLU 2    // C[M][N/2] = swiglu over interleaved gate/up 16-column groups
 #define LR_EPI_ROPE 3      // C = bf16(acc) with rotary embedding on the pair-interleaved q/k columns
 #define LR_EPI_PARTIAL 4   // internal (split-K): fp32 partial sums to the workspace, real epilogue in the reduce pass
+#define LR_EPI_GEGLU 5     // as LR_EPI_SWIGLU with the tanh-approximate GELU (Gemma)
+#define LR_EPI_IS_GATED(e) ((e) == LR_EPI_SWIGLU || (e) == LR_EPI_GEGLU)
 #define LR_SPLITK_WS_BYTES ((size_t)64 << 20)  // splits x tiles <= 256 tiles of 256 x 256 fp32
 
 // packed-layout metadata (llama_elem.hip): prefix_len = P > 0 lays the batch out as [P shared prefix rows][rest of
@@ -41,16 +58,19 @@ int lr_launch_gather_rows(const unsigned short* x, const int32_t* rows, int n_ro
 int lr_launch_attention_rows(const unsigned short* qkv, unsigned short* out, const int32_t* cu, int B,
                              const int32_t* q_rows, int n_rows, int nh, int nkv, int hd, hipStream_t st);
 int lr_launch_embed(const int32_t* ids, const int32_t* tok_src /*nullptr: identity*/, const unsigned short* table,
-                    int vocab, int d, unsigned short* out, int n, hipStream_t st);
+                    int vocab, int d, unsigned short* out, int n, hipStream_t st,
+                    float scale = 1.0f /* != 1: rows bf16(e * scale) (Gemma's embedding scale) */);
+// norm_style (here and below): 0 = Llama's RMSNorm, 1 = Gemma's (rms_apply)
 int lr_launch_rmsnorm(const unsigned short* x, const unsigned short* w, unsigned short* out, int rows, int d,
-                      float eps, const int32_t* row_map, hipStream_t st);
+                      float eps, const int32_t* row_map, hipStream_t st, int norm_style = 0);
 int lr_launch_rope_table(float* cs, int T, int hd, float theta, hipStream_t st,
                          unsigned* cs16 = nullptr /* [T][hd/2] (cos | sin << 16) as bf16 pairs, optional */);
 int lr_launch_head(const unsigned short* x, const int32_t* rows /*[B]; nullptr: x holds one row per prompt*/,
                    const unsigned short* norm_w,
                    const unsigned short* lm_head, const int32_t* class_ids, int B, int C, int d, float eps,
                    float* out, int vocab, hipStream_t st,
-                   const int32_t* poison = nullptr /* device word: non-zero -> every score of the call is NaN */);
+                   const int32_t* poison = nullptr /* device word: non-zero -> every score of the call is NaN */,
+                   int norm_style = 0);
 
 // C[M][N] (+epilogue) = A[M][K] * B[N][K]^T. variant: 0 auto, 1 generic, 4 = 256x256x64 MFMA tile,
 // 5 = variant 4 with split-K when the tiles alone would leave most CUs idle (needs splitk_ws).
@@ -65,18 +85,23 @@ int lr_launch_gemm(const unsigned short* A, const unsigned short* B, unsigned sh
                    float then_norm_eps = 0.f, bool* then_norm_done = nullptr /* residual epilogue only: the caller runs
                    RMSNorm(C) with this weight into then_norm_out next. If the product is split over K, its reduce pass
                    does that too (same bits) and *then_norm_done is set; otherwise it is left false and the caller launches
-                   lr_launch_rmsnorm itself */);
+                   lr_launch_rmsnorm itself */,
+                   int then_norm_style = 0);
 // split-K reduce (S fp32 planes of M x N) + residual + RMSNorm of the result in one pass (llama_elem.hip)
 bool lr_reduce_residual_rmsnorm_fits(int N);
 int lr_launch_reduce_residual_rmsnorm(const float* part, int S, unsigned short* C, const unsigned short* R, int M, int N,
-                                      const unsigned short* norm_w, unsigned short* norm_out, float eps, hipStream_t st);
+                                      const unsigned short* norm_w, unsigned short* norm_out, float eps, hipStream_t st,
+                                      int norm_style = 0);
 // rstd[m] = 1 / sqrt(mean(x[m][:]^2) + eps), fp32 (the statistic of HF's LlamaRMSNorm)
 int lr_launch_rms_rstd(const unsigned short* x, float* rstd, int rows, int d, float eps, hipStream_t st);
 // out[j][k] = bf16(w[j][k] * norm_w[k]): an RMSNorm weight folded into the following projection's [out][in] matrix
 int lr_launch_fold_norm(const unsigned short* w, const unsigned short* norm_w, unsigned short* out, size_t rows, int cols,
                         hipStream_t st);
 
-// varlen causal attention over packed qkv (RoPE applied). variant: 0 auto, 1 generic, 2 MFMA hd=128.
+// attention variant 4 (llama_attn_hd256.hip): head_dim-256 MFMA flash attention, cu / cu_host = prompt starts, no prefix
+int lr_launch_attention_hd256(const unsigned short* qkv, unsigned short* out, const int32_t* cu, const int32_t* cu_host, int B,
+                              int n_tok, int nh, int nkv, int hd, hipStream_t st);
+// varlen causal attention over packed qkv (RoPE applied). variant: 0 auto, 1 generic, 2 MFMA hd=128, 4 MFMA hd=256.
 // cu / cu_host = segment starts; prefix_len > 0: segment 0 is the prefix the other segments continue (MFMA kernel only)
 int lr_launch_attention_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
                              const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int hd,

@@ -146,13 +146,14 @@ int lr_launch_item_scores(const lr_lru* h, const float* q, const int64_t* ids, i
 // ---- stage-2 handle -------------------------------------------------------------------------
 struct lr_llama {
   LrLlamaConfig cfg;
+  LrLlamaArch arch;  // norm style, MLP activation, embedding scale (Llama: 0, 0, 1)
   const uint16_t* embed;
   const uint16_t* final_norm;
   const uint16_t* lm_head;
   LrLlamaLayerWeights* layers;  // host array
   int device;
   int gemm_variant;  // 0 auto, 1 generic, 4 256x256x64 MFMA tile, 5 = 4 + split-K (latency mode)
-  int attn_variant;  // 0 auto, 1 generic, 2 MFMA head_dim 128
+  int attn_variant;  // 0 auto, 1 generic, 2 MFMA head_dim 128, 3 256-row tiles, 4 MFMA head_dim 256
   int prune_last;    // last layer: attention output / o_proj / MLP only for each prompt's last token
   // folded RMSNorm (lr_llama_set_folded_norms): per layer wqkv * diag(input_norm) and wgu * diag(post_norm), or null
   const uint16_t** wqkv_folded;

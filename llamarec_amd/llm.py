@@ -24,6 +24,36 @@ from ._lib import check, lib, stream_ptr
 LLAMA2_7B = dict(vocab_size=32000, hidden_size=4096, intermediate_size=11008, num_hidden_layers=32,
                  num_attention_heads=32, num_key_value_heads=32, max_position_embeddings=4096,
                  rms_norm_eps=1e-5, rope_theta=10000.0)
+# google/gemma-2b and google/gemma-7b (config.json of the checkpoints; the reference's --llm gemma loads gemma-2b)
+GEMMA_2B = dict(model_type="gemma", vocab_size=256000, hidden_size=2048, intermediate_size=16384, num_hidden_layers=18,
+                num_attention_heads=8, num_key_value_heads=1, head_dim=256, max_position_embeddings=8192,
+                rms_norm_eps=1e-6, rope_theta=10000.0, hidden_activation="gelu_pytorch_tanh")
+GEMMA_7B = dict(GEMMA_2B, hidden_size=3072, intermediate_size=24576, num_hidden_layers=28, num_attention_heads=16,
+                num_key_value_heads=16)
+
+# model_type -> backbone family of the kernels (LrLlamaArch). Llama-2 / Llama-3 and Mistral share Llama's arithmetic.
+LLAMA_FAMILY = ("llama", "mistral")
+GEMMA_FAMILY = ("gemma",)
+SUPPORTED_MODEL_TYPES = LLAMA_FAMILY + GEMMA_FAMILY
+
+
+def model_family(config: dict) -> str:
+    """'llama' or 'gemma' for a HF config dict (a missing model_type means llama); anything else raises: the kernels
+    implement those two families' arithmetic only, and a checkpoint of another family would load (same tensor names)
+    and then score silently wrong."""
+    mt = config.get("model_type") or "llama"
+    if mt in LLAMA_FAMILY:
+        if config.get("rope_scaling") is not None:
+            raise NotImplementedError(f"model_type {mt!r} with rope_scaling={config['rope_scaling']!r}: the rotary tables "
+                                      "implement plain RoPE only")
+        return "llama"
+    if mt in GEMMA_FAMILY:
+        act = config.get("hidden_activation") or config.get("hidden_act") or "gelu_pytorch_tanh"
+        if act not in ("gelu_pytorch_tanh", "gelu"):
+            raise NotImplementedError(f"gemma with hidden_activation={act!r}: the kernels implement gelu_pytorch_tanh")
+        return "gemma"
+    raise NotImplementedError(f"model_type {mt!r} is not supported by the ranker's kernels; supported families: "
+                              f"{', '.join(SUPPORTED_MODEL_TYPES)}")
 
 
 @dataclass
@@ -106,7 +136,10 @@ class LlamaRanker:
         self.config = dict(config)
         self.device = torch.device(device)
         c = self.config
+        self.family = model_family(c)
         self.hd = c.get("head_dim") or c["hidden_size"] // c["num_attention_heads"]
+        # Mistral's sliding window: the kernels attend to the whole causal range, so a longer prompt is refused
+        self.max_prompt_len = c.get("sliding_window") if c.get("model_type") == "mistral" else None
         self._h = C.c_void_p()
         self._tensors = {}
         self._ws = None
@@ -195,16 +228,18 @@ class LlamaRanker:
             return (torch.randn(*shape, generator=g, device=dev, dtype=torch.float32) * std).to(torch.bfloat16)
 
         T = self._tensors
+        # unit norm scale: w = 1 for Llama, w = 0 for Gemma's (1 + w); Gemma's lm_head is the (tied) embedding
+        norm = torch.zeros if self.family == "gemma" else torch.ones
         T["embed"] = rnd(v, d)
-        T["final_norm"] = torch.ones(d, dtype=torch.bfloat16, device=dev)
-        T["lm_head"] = rnd(v, d)
+        T["final_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
+        T["lm_head"] = T["embed"] if self.family == "gemma" else rnd(v, d)
         for i in range(c["num_hidden_layers"]):
             T[f"{i}.wqkv"] = rnd((nh + 2 * nkv) * hd, d)
             T[f"{i}.wo"] = rnd(d, nh * hd)
             T[f"{i}.wgu"] = rnd(2 * f, d)  # already in the interleaved gate/up layout (random anyway)
             T[f"{i}.wdown"] = rnd(d, f)
-            T[f"{i}.input_norm"] = torch.ones(d, dtype=torch.bfloat16, device=dev)
-            T[f"{i}.post_norm"] = torch.ones(d, dtype=torch.bfloat16, device=dev)
+            T[f"{i}.input_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
+            T[f"{i}.post_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
         self._create()
         return self
 
@@ -212,10 +247,12 @@ class LlamaRanker:
     def from_pretrained(cls, path, device="cuda:0", adapter_path=None, load_in_4bit=False):
         """Local HF directory (config.json + *.safetensors), optionally a PEFT LoRA adapter directory
         (adapter_config.json + adapter_model.safetensors) merged at load. load_in_4bit: the reference's NF4 round trip
-        of the base Linears (see from_state_dict). No network access."""
+        of the base Linears (see from_state_dict). The family follows config.json's model_type (model_family).
+        No network access."""
         from safetensors import safe_open
 
         cfg = json.load(open(os.path.join(path, "config.json")))
+        model_family(cfg)   # refuse an unsupported checkpoint before reading gigabytes of it
         sd = {}
         for fn in sorted(os.listdir(path)):
             if fn.endswith(".safetensors"):
@@ -241,6 +278,14 @@ class LlamaRanker:
         u = up.to(torch.bfloat16).view(f // 16, 16, d)
         return torch.stack([g, u], dim=1).reshape(2 * f, d).contiguous()
 
+    def arch(self):
+        """The LrLlamaArch of this ranker's family (include/llamarec_mi355x.h)."""
+        if self.family == "gemma":
+            # HF GemmaModel: hidden * torch.tensor(hidden_size ** 0.5, dtype=bf16)
+            scale = float(torch.tensor(self.config["hidden_size"] ** 0.5, dtype=torch.bfloat16))
+            return A.LrLlamaArch(norm_style=1, mlp_act=1, embed_scale=scale)
+        return A.LrLlamaArch(norm_style=0, mlp_act=0, embed_scale=1.0)
+
     def _create(self):
         c, T = self.config, self._tensors
         cfg = A.LrLlamaConfig(
@@ -259,7 +304,7 @@ class LlamaRanker:
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             torch.cuda.synchronize()
-            check(lib().lr_llama_create(C.byref(cfg), C.byref(desc), C.byref(h)), "lr_llama_create")
+            check(lib().lr_llama_create_ex(C.byref(cfg), C.byref(self.arch()), C.byref(desc), C.byref(h)), "lr_llama_create_ex")
         self._h, self._layers_arr = h, arr
         if self.fold_norms:
             self.set_fold_norms(True)
@@ -270,6 +315,8 @@ class LlamaRanker:
         kept beside the originals (+66 % of the q/k/v/gate/up bytes; the originals serve LoRA fine-tuning and the
         pruned last layer). Opt-in: see the note at LlamaRanker.fold_norms."""
         T, L = self._tensors, self.config["num_hidden_layers"]
+        if enable and self.family == "gemma":
+            raise NotImplementedError("folded norms: Gemma's (1 + w) RMSNorm cannot be folded into bf16 weights at HF's rounding")
         if not enable:
             check(lib().lr_llama_set_folded_norms(self._h, None, None), "lr_llama_set_folded_norms")
             for i in range(L):
@@ -315,6 +362,11 @@ class LlamaRanker:
             pass
 
     # -- scoring -----------------------------------------------------------------------------
+    def _check_lengths(self, cu_host):
+        if self.max_prompt_len is not None and int(np.diff(cu_host).max()) > self.max_prompt_len:
+            raise NotImplementedError(f"a prompt of {int(np.diff(cu_host).max())} tokens exceeds Mistral's sliding window of "
+                                      f"{self.max_prompt_len}: the kernels attend to the whole causal range")
+
     def _workspace(self, n_tokens, n_seqs):
         need = lib().lr_llama_workspace_bytes(self._h, n_tokens, n_seqs)
         if self._ws is None or self._ws.numel() < need:
@@ -331,6 +383,7 @@ class LlamaRanker:
         (common_prefix_len on the host ids) that all prompts start with the same prefix_len tokens; they are then run
         once per batch (bit-identical scores, lr_llama_prefill_verbalize_prefix)."""
         B, Cn = len(cu_host) - 1, label_ids_dev.numel()
+        self._check_lengths(cu_host)
         if out is None:
             out = torch.empty((B, Cn), dtype=torch.float32, device=self.device)
         ws = self._workspace(int(cu_host[-1]), B)
@@ -353,6 +406,7 @@ class LlamaRanker:
     def last_logits(self, seqs):
         ids, cu, cu_host = self._packed(seqs)
         B = len(cu_host) - 1
+        self._check_lengths(cu_host)
         out = torch.empty((B, self.config["vocab_size"]), dtype=torch.float32, device=self.device)
         ws = self._workspace(int(cu_host[-1]), B)
         with torch.cuda.device(self.device):

@@ -86,6 +86,39 @@ def synth_llama_state(cfg: dict, seed: int, std: float = 0.02, norm_jitter: floa
     return sd
 
 
+def gemma_param_shapes(cfg: dict) -> list[tuple[str, tuple]]:
+    """HF GemmaForCausalLM parameter names and shapes: Llama's, with head_dim from the config (gemma-7b: 16 x 256 heads
+    on a 3072-wide residual) and no lm_head (tied to the embedding)."""
+    d, f, v = cfg["hidden_size"], cfg["intermediate_size"], cfg["vocab_size"]
+    nh, nkv = cfg["num_attention_heads"], cfg["num_key_value_heads"]
+    hd = cfg.get("head_dim") or d // nh
+    out = [("model.embed_tokens.weight", (v, d))]
+    for i in range(cfg["num_hidden_layers"]):
+        p = f"model.layers.{i}."
+        out += [
+            (p + "self_attn.q_proj.weight", (nh * hd, d)),
+            (p + "self_attn.k_proj.weight", (nkv * hd, d)),
+            (p + "self_attn.v_proj.weight", (nkv * hd, d)),
+            (p + "self_attn.o_proj.weight", (d, nh * hd)),
+            (p + "mlp.gate_proj.weight", (f, d)),
+            (p + "mlp.up_proj.weight", (f, d)),
+            (p + "mlp.down_proj.weight", (d, f)),
+            (p + "input_layernorm.weight", (d,)),
+            (p + "post_attention_layernorm.weight", (d,)),
+        ]
+    out += [("model.norm.weight", (d,))]
+    return out
+
+
+def synth_gemma_state(cfg: dict, seed: int, std: float = 0.02, norm_std: float = 0.3) -> dict:
+    """name -> float32 array for a Gemma config. Matrices ~ U(std); norm weights ~ U(norm_std) around 0 -- Gemma scales by
+    (1 + w), so non-zero w exercises that form (w = 0 would make it indistinguishable from Llama's w = 1). bf16 values."""
+    sd = {}
+    for i, (name, shape) in enumerate(gemma_param_shapes(cfg)):
+        sd[name] = bf16_round(hash_uniform(seed * 1000 + i, shape, norm_std if len(shape) == 1 else std))
+    return sd
+
+
 # ---------------------------------------------------------------------------------------------
 # Synthetic workloads of BASELINE.json's configs (BASELINE.md section 3 / SURVEY.md 8(d)).
 # V items, U users, L = bert_max_len, title-length range of the prompt model, rerank batch

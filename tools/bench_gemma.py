@@ -1,0 +1,131 @@
+"""Gemma ranker timings on one MI355X (prints a table and one JSON line):
+  1. attention: variant 4 (head_dim-256 MFMA) against the generic kernel at head_dim 256 and variant 2 at head_dim 128, on
+     16 x 600 and 16 x 1 125-token batches at (nh, nkv) = (8, 1) and (16, 16); TF/s of the causal work as
+     lr_launch_attention counts it (4 nh hd T (T + 1) / 2 per prompt), same process, median of the timed repeats.
+  2. a random-weight Gemma-2B prefill + verbalizer over a Beauty-sized token budget (prompts of 460 .. 1 125 tokens,
+     packing.TOKEN_BUDGET rows): ms per step and its kernel split from the library's LrProfScope records.
+Usage: python tools/bench_gemma.py [--reps 20] [--steps 5] [--layers 18]"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from llamarec_amd import _lib  # noqa: E402
+from llamarec_amd._lib import check, lib, stream_ptr  # noqa: E402
+
+KINDS = {0: "gemm 256-tile", 1: "gemm generic", 2: "attention MFMA", 3: "attention generic"}
+
+
+def time_attention(nh, nkv, hd, T, B, variant, reps):
+    n = B * T
+    g = torch.Generator(device="cuda").manual_seed(T + nh)
+    qkv = torch.randn(n, (nh + 2 * nkv) * hd, generator=g, device="cuda").to(torch.bfloat16)
+    out = torch.empty(n, nh * hd, dtype=torch.bfloat16, device="cuda")
+    cu = np.arange(0, n + 1, T, dtype=np.int32)
+    cud = torch.from_numpy(cu).cuda()
+
+    def run():
+        check(lib().lr_attention_varlen(qkv.data_ptr(), out.data_ptr(), cud.data_ptr(), cu.ctypes.data, B, nh, nkv, hd, variant,
+                                        stream_ptr()), "attention")
+
+    for _ in range(3):
+        run()
+    times = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run()
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1))
+    ms = float(np.median(times))
+    work = 4.0 * nh * hd * B * T * (T + 1) / 2
+    return ms, work / ms / 1e9
+
+
+def attention_table(reps):
+    rows = []
+    for nh, nkv in ((8, 1), (16, 16)):
+        for T in (600, 1125):
+            ms4, tf4 = time_attention(nh, nkv, 256, T, 16, 4, reps)
+            ms1, tf1 = time_attention(nh, nkv, 256, T, 16, 1, max(3, reps // 4))
+            ms2, tf2 = time_attention(nh, nkv, 128, T, 16, 2, reps)
+            rows.append(dict(nh=nh, nkv=nkv, T=T, B=16, v4_ms=ms4, v4_tflops=tf4, generic_ms=ms1, generic_tflops=tf1,
+                             v2_hd128_ms=ms2, v2_hd128_tflops=tf2, v4_over_generic=ms1 / ms4, v4_over_v2=tf4 / tf2))
+            print(f"attention nh={nh:2d} nkv={nkv:2d} 16 x {T:4d}: v4 hd256 {ms4:7.3f} ms {tf4:6.1f} TF/s | generic hd256 "
+                  f"{ms1:8.3f} ms {tf1:6.1f} TF/s | v2 hd128 {ms2:7.3f} ms {tf2:6.1f} TF/s | v4/generic {ms1 / ms4:5.1f}x "
+                  f"v4/v2 {tf4 / tf2:4.2f}", flush=True)
+    return rows
+
+
+def gemma2b_step(steps, layers):
+    from llamarec_amd.llm import GEMMA_2B, LlamaRanker, pack_prompts
+    from llamarec_amd.packing import TOKEN_BUDGET
+
+    cfg = dict(GEMMA_2B, num_hidden_layers=layers)
+    model = LlamaRanker.random_init(cfg, seed=1)
+    rng = np.random.default_rng(0)
+    seqs, total = [], 0
+    while True:
+        t = int(rng.integers(460, 1126))
+        if total + t > TOKEN_BUDGET:
+            break
+        seqs.append(np.concatenate([[2], rng.integers(3, cfg["vocab_size"], size=t - 1)]).astype(np.int32))
+        total += t
+    ids, cu = pack_prompts(seqs)
+    ids_d, cu_d = torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda()
+    lab = torch.arange(100, 120, dtype=torch.int32, device="cuda")
+    out = torch.empty(len(seqs), 20, dtype=torch.float32, device="cuda")
+    for _ in range(2):
+        model.prefill_verbalize_packed(ids_d, cu_d, cu, lab, out=out)
+    torch.cuda.synchronize()
+    L = lib()
+    check(L.lr_profile_start(steps * (layers * 10 + 32)), "lr_profile_start")
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        model.prefill_verbalize_packed(ids_d, cu_d, cu, lab, out=out)
+    e1.record()
+    torch.cuda.synchronize()
+    check(L.lr_profile_stop(), "lr_profile_stop")
+    step_ms = e0.elapsed_time(e1) / steps
+    split = {}
+    for kind, name in KINDS.items():
+        ms, work, n = C.c_double(), C.c_double(), C.c_int64()
+        L.lr_profile_collect(kind, C.byref(ms), C.byref(work), C.byref(n))
+        if n.value:
+            split[name] = dict(ms_per_step=ms.value / steps, tflops=work.value / max(ms.value, 1e-9) / 1e9,
+                               launches_per_step=n.value / steps)
+    assert torch.isfinite(out).all()
+    print(f"gemma-2b ({layers} layers, random weights) prefill + verbalizer: {len(seqs)} prompts, {total} tokens: "
+          f"{step_ms:.2f} ms per step", flush=True)
+    for name, v in split.items():
+        print(f"  {name:18s} {v['ms_per_step']:8.2f} ms/step {v['tflops']:7.1f} TF/s {v['launches_per_step']:6.1f} launches",
+              flush=True)
+    attn = sum(v["ms_per_step"] for k, v in split.items() if k.startswith("attention"))
+    return dict(prompts=len(seqs), tokens=total, layers=layers, step_ms=step_ms, kernels=split,
+                attention_share=attn / step_ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--layers", type=int, default=18)
+    args = ap.parse_args()
+    assert torch.cuda.is_available()
+    _lib.lib()
+    res = dict(attention=attention_table(args.reps), gemma2b=gemma2b_step(args.steps, args.layers))
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -18,6 +18,8 @@ import sys
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
+TRAIN_LLAMA_ONLY = ("LoRA fine-tuning needs a Llama-family base (the training step has no GeGLU, Gemma-norm or head_dim-256 "
+                    "attention backward): score a Gemma ranker with --eval_only [--llm_adapter_path <peft dir>]")
 
 
 def main(argv=None, export_root=None):
@@ -33,6 +35,8 @@ def main(argv=None, export_root=None):
     args = cfg.parse(argv, model_code="llm")
     if not args.llm_retrieved_path:
         raise SystemExit("--llm_retrieved_path experiments/lru/<dataset> is required")
+    if args.llm == "gemma" and not args.eval_only:
+        raise SystemExit(TRAIN_LLAMA_ONLY)
     export_root = export_root or args.export_root or os.path.join(
         cfg.EXPERIMENT_ROOT, args.llm_base_model.rstrip("/").split("/")[-1], args.dataset_code)
     retrieved = pickle.load(open(os.path.join(args.llm_retrieved_path, "retrieved.pkl"), "rb"))
@@ -47,7 +51,7 @@ def main(argv=None, export_root=None):
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
     if args.synthetic:
-        from llamarec_amd.synth import FakeTokenizer, synth_llama_state
+        from llamarec_amd.synth import FakeTokenizer, synth_gemma_state, synth_llama_state
 
         dataset = D.synthetic_dataset(num_users=300, num_items=1000, seed=args.seed)
         tokenizer = FakeTokenizer()
@@ -56,9 +60,14 @@ def main(argv=None, export_root=None):
                  rms_norm_eps=1e-5, rope_theta=10000.0)
         from llamarec_amd.llm import load_peft_adapter
 
-        model = LlamaRanker.from_state_dict(synth_llama_state(c, args.seed), c, device=device,
-                                            lora=load_peft_adapter(args.llm_adapter_path) if args.llm_adapter_path
-                                            else None, nf4=args.llm_load_in_4bit)
+        lora = load_peft_adapter(args.llm_adapter_path) if args.llm_adapter_path else None
+        if args.llm == "gemma":   # a tiny Gemma: head_dim 256, MQA, (1 + w) norms, GeGLU, scaled embedding
+            c = dict(c, model_type="gemma", num_key_value_heads=1, head_dim=256, rms_norm_eps=1e-6)
+            model = LlamaRanker.from_state_dict(synth_gemma_state(c, args.seed), c, device=device, lora=lora,
+                                                nf4=args.llm_load_in_4bit)
+        else:
+            model = LlamaRanker.from_state_dict(synth_llama_state(c, args.seed), c, device=device, lora=lora,
+                                                nf4=args.llm_load_in_4bit)
     else:
         from transformers import AutoTokenizer
 
@@ -72,6 +81,8 @@ def main(argv=None, export_root=None):
         tokenizer.clean_up_tokenization_spaces = True
         model = LlamaRanker.from_pretrained(args.llm_base_model, device=device, adapter_path=args.llm_adapter_path,
                                             load_in_4bit=args.llm_load_in_4bit)
+    if model.family != "llama" and not args.eval_only:
+        raise SystemExit(TRAIN_LLAMA_ONLY)
     ncls = args.llm_negative_sample_size + 1
     args.num_items = len(dataset["smap"])
     verbalizer = ManualVerbalizer(tokenizer=tokenizer, prefix="", post_log_softmax=False, classes=list(range(ncls)),
