@@ -374,7 +374,10 @@ int lr_rope_table(float* cs, int32_t max_positions, int32_t head_dim, float thet
 /* Stand-alone varlen causal attention (exposed for parity tests):
  * qkv: DEVICE bf16 [total][(nh+2*nkv)*hd] (RoPE already applied; any consistent permutation of the
  * dims inside q and k heads), out: bf16 [total][nh*hd]. variant 0 = auto (2 at head_dim 128, else 1), 1 generic,
- * 2 = head_dim-128 MFMA, 4 = head_dim-256 MFMA. */
+ * 2 = head_dim-128 MFMA, 4 = head_dim-256 MFMA.
+ * cu_seqlens_host (HOST int32 [B+1], the values of cu_seqlens): cu_seqlens_host[0] == 0 and strictly increasing, so that
+ * every segment holds at least one row. lr_attention_varlen, _ws, _lse and _bwd check this on the host and return LR_EINVAL
+ * before anything is launched (outputs untouched) when it does not hold. */
 int lr_attention_varlen(const uint16_t* qkv, uint16_t* out, const int32_t* cu_seqlens,
                         const int32_t* cu_seqlens_host, int32_t B, int32_t num_heads,
                         int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* hip_stream);

@@ -486,6 +486,7 @@ extern "C" int lr_attention_varlen(const uint16_t* qkv, uint16_t* out, const int
                                    const int32_t* cu_seqlens_host, int32_t B, int32_t num_heads,
                                    int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* hip_stream) {
   if (!qkv || !out || !cu_seqlens || !cu_seqlens_host || B < 1) LR_FAIL(LR_EINVAL, "lr_attention_varlen: bad argument");
+  if (int rc = lr_check_segments(cu_seqlens_host, B, "lr_attention_varlen")) return rc;
   return lr_launch_attention(qkv, out, cu_seqlens, cu_seqlens_host, nullptr, nullptr, B, cu_seqlens_host[B],
                              num_heads, num_kv_heads, head_dim, variant, nullptr, (hipStream_t)hip_stream);
 }
@@ -500,6 +501,7 @@ extern "C" int lr_attention_varlen_ws(const uint16_t* qkv, uint16_t* out, float*
                                       int32_t head_dim, int32_t variant, void* workspace, size_t workspace_bytes,
                                       void* hip_stream) {
   if (!qkv || !out || !cu_seqlens || !cu_seqlens_host || B < 1) LR_FAIL(LR_EINVAL, "lr_attention_varlen_ws: bad argument");
+  if (int rc = lr_check_segments(cu_seqlens_host, B, "lr_attention_varlen_ws")) return rc;
   hipStream_t st = (hipStream_t)hip_stream;
   const int n = cu_seqlens_host[B];
   if (variant == 3 || (variant == 0 && head_dim == 128 && workspace)) {

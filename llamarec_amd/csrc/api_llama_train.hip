@@ -486,6 +486,7 @@ extern "C" int lr_attention_varlen_lse(const uint16_t* qkv, uint16_t* out, float
                                        int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* hip_stream) {
   if (!qkv || !out || !lse || !cu_seqlens || !cu_seqlens_host || B < 1)
     LR_FAIL(LR_EINVAL, "lr_attention_varlen_lse: bad argument");
+  if (int rc = lr_check_segments(cu_seqlens_host, B, "lr_attention_varlen_lse")) return rc;
   return lr_launch_attention_lse(qkv, out, lse, cu_seqlens, cu_seqlens_host, B, cu_seqlens_host[B], num_heads,
                                  num_kv_heads, head_dim, variant, (hipStream_t)hip_stream);
 }
@@ -503,6 +504,7 @@ extern "C" int lr_attention_varlen_bwd(const uint16_t* qkv, const uint16_t* out,
                                        size_t scratch_bytes, void* hip_stream) {
   if (!qkv || !out || !d_out || !lse || !dqkv || !cu_seqlens || !cu_seqlens_host || !scratch || B < 1)
     LR_FAIL(LR_EINVAL, "lr_attention_varlen_bwd: bad argument");
+  if (int rc = lr_check_segments(cu_seqlens_host, B, "lr_attention_varlen_bwd")) return rc;
   const int n = cu_seqlens_host[B];
   if (scratch_bytes < lr_attention_bwd_scratch_bytes(n, num_heads, num_kv_heads, head_dim))
     LR_FAIL(LR_EWORKSPACE, "lr_attention_varlen_bwd: scratch too small");

@@ -653,6 +653,8 @@ __global__ __launch_bounds__(256) void attn_mfma256_kernel(const u16* __restrict
 int lr_launch_attention256(const u16* qkv, u16* out, const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh,
                            int nkv, int hd, float* lse, void* items_ws, hipStream_t st, int prefix_len) {
   if (n_tok <= 0 || S <= 0) return LR_OK;
+  if (int rc = lr_check_segments(cu_host, S, "attention (256-row tiles)")) return rc;
+  if (cu_host[S] != n_tok) LR_FAIL(LR_EINVAL, "attention (256-row tiles): segments cover %d rows, n_tok = %d", cu_host[S], n_tok);
   if (hd != 128 || nh % nkv != 0 || nh > 0xffff) LR_FAIL(LR_EUNSUPPORTED, "attention (256-row tiles): head_dim 128, nh %% nkv == 0 only");
   if (prefix_len < 0 || prefix_len > A2_KB || (prefix_len > 0 && cu_host[1] - cu_host[0] != prefix_len))
     LR_FAIL(LR_EINVAL, "attention (256-row tiles): shared prefix of %d tokens (<= 64, = segment 0)", prefix_len);

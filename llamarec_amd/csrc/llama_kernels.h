@@ -98,6 +98,18 @@ int lr_launch_rms_rstd(const unsigned short* x, float* rstd, int rows, int d, fl
 int lr_launch_fold_norm(const unsigned short* w, const unsigned short* norm_w, unsigned short* out, size_t rows, int cols,
                         hipStream_t st);
 
+// The segment rule of every attention entry point (include/llamarec_mi355x.h, cu_seqlens_host): cu_host[0] == 0 and
+// cu_host strictly increasing -- every segment holds at least one row. The kernels derive work items, tile counts and
+// buffer offsets from segment lengths, so an empty or negative segment must be refused here, before any launch.
+static inline int lr_check_segments(const int32_t* cu_host, int S, const char* who) {
+  if (!cu_host || S < 1) LR_FAIL(LR_EINVAL, "%s: %d segments", who, S);
+  if (cu_host[0] != 0) LR_FAIL(LR_EINVAL, "%s: cu_seqlens[0] = %d (must be 0)", who, cu_host[0]);
+  for (int b = 0; b < S; ++b)
+    if (cu_host[b + 1] <= cu_host[b])
+      LR_FAIL(LR_EINVAL, "%s: segment %d is empty or negative (cu_seqlens %d -> %d)", who, b, cu_host[b], cu_host[b + 1]);
+  return LR_OK;
+}
+
 // attention variant 4 (llama_attn_hd256.hip): head_dim-256 MFMA flash attention, cu / cu_host = prompt starts, no prefix
 int lr_launch_attention_hd256(const unsigned short* qkv, unsigned short* out, const int32_t* cu, const int32_t* cu_host, int B,
                               int n_tok, int nh, int nkv, int hd, hipStream_t st);

@@ -124,6 +124,12 @@ def test_geglu_epilogue_fast_equals_generic_bit_for_bit(M):
     gate, up = acc[:, :, 0].reshape(M, N // 2).bfloat16(), acc[:, :, 1].reshape(M, N // 2).bfloat16()
     want = (torch.nn.functional.gelu(gate, approximate="tanh") * up).float()
     assert ((ref.float() - want).abs() <= want.abs() * 2 ** -7 + 1e-6).float().mean() > 0.99
+    # ... and every element within the strict bound of the float64 reference (test_gpu_stage2_bounds.gated_ratio)
+    from tests.test_gpu_stage2_bounds import gated_ratio
+
+    A64, B64 = A.double().cpu().numpy(), B.double().cpu().numpy()
+    r = gated_ratio(5, A64 @ B64.T, np.abs(A64) @ np.abs(B64).T, K, ref.float().cpu().numpy())
+    assert r <= 1.0, r
     # the split-K reduce (latency mode) with the GeGLU epilogue: exact integer partial sums -> the generic kernel's bits
     Ai = (torch.arange(M * 4096, device="cuda").view(M, 4096) % 5 - 2).to(torch.bfloat16)
     Bi = ((torch.arange(N * 4096, device="cuda").view(N, 4096) * 3) % 7 - 3).to(torch.bfloat16) * 0.0625
