@@ -86,8 +86,9 @@ extern "C" int lr_fold_norm_bf16(const uint16_t* w, const uint16_t* norm_w, int3
 extern "C" int lr_llama_set_folded_norms(lr_llama_t* h, const uint16_t* const* wqkv_folded,
                                          const uint16_t* const* wgu_folded) {
   if (!h) LR_FAIL(LR_EINVAL, "lr_llama_set_folded_norms: null handle");
-  if (h->arch.norm_style != 0 && (wqkv_folded || wgu_folded))
-    LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: a Gemma norm (1 + w) cannot be folded into bf16 weights at HF's rounding");
+  if ((h->arch.norm_style != 0 || h->arch.mlp_act != 0) && (wqkv_folded || wgu_folded))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: Llama arch only (a Gemma norm (1 + w) cannot be folded into bf16 "
+            "weights at HF's rounding, and the GeGLU epilogue takes no row scale)");
   free(h->wqkv_folded);
   free(h->wgu_folded);
   h->wqkv_folded = h->wgu_folded = nullptr;
@@ -108,7 +109,7 @@ struct LlamaWs {
   float *rope, *rstd;
   u16 *x, *xn, *qkv, *att, *hmid;
   u16 *x_last, *xn_last, *att_last, *h_last, *q_last;  // compact [B][.] buffers of the pruned last layer
-  float* splitk;                              // fp32 partial planes of the split-K GEMMs (gemm variant 5)
+  LrGemmSplitK splitk;                        // fp32 partial planes of the split-K GEMMs (gemm variant 5)
   unsigned* rope16;                           // the rope table as packed bf16 (cos | sin << 16) pairs
   int32_t* prefix_bad;                        // device word: a prompt broke the shared-prefix promise (token_meta_kernel)
   void* attn_items;                           // work-item list of the 256-row attention kernel (llama_attn256.hip)
@@ -147,7 +148,7 @@ static LlamaWs carve(const LrLlamaConfig& c, int max_tokens, int max_seqs, char*
   w.att_last = (u16*)take(nb * (size_t)c.num_heads * c.head_dim * 2);
   w.h_last = (u16*)take(nb * c.intermediate_size * 2);
   w.q_last = (u16*)take(nb * (size_t)c.num_heads * c.head_dim * 2);
-  w.splitk = (float*)take(LR_SPLITK_WS_BYTES);
+  w.splitk = {.ws = (float*)take(LR_SPLITK_WS_BYTES), .bytes = LR_SPLITK_WS_BYTES};
   w.prefix_bad = (int32_t*)take(sizeof(int32_t));
   w.attn_items_bytes = lr_attn256_ws_bytes(max_tokens, (int)nb + 1, c.num_heads);
   w.attn_items = take(w.attn_items_bytes);
@@ -162,73 +163,82 @@ extern "C" size_t lr_llama_workspace_bytes(const lr_llama_t* h, int32_t max_toke
   return carve(h->cfg, max_tokens, max_seqs, nullptr).total;
 }
 
-// Runs the transformer body; leaves the residual stream (before the final norm) in ws.x (all internal rows) or,
-// after a pruned last layer, in ws.x_last (one row per prompt). prefix_len = P > 0: the first P tokens of every
-// prompt are the same (the caller's promise) and are run ONCE as segment 0 of the internal layout (llama_elem.hip,
-// token_meta_kernel); the other segments attend to its K/V rows. Every row then sees exactly the operands of the
-// unshared run, so the scores are bit-identical to prefix_len = 0.
-static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const int32_t* cu_host, int B, int P,
-                    void* workspace, size_t workspace_bytes, hipStream_t st, LlamaWs* out_ws) {
-  if (!h || !ids || !cu || !cu_host || !workspace) LR_FAIL(LR_EINVAL, "llama prefill: null argument");
-  if (B < 1) LR_FAIL(LR_EINVAL, "llama prefill: B=%d", B);
+// What run_body derives from a prompt batch before any launch: the internal layout, the carved workspace and seg_host, the
+// host copy of the segment starts (launch geometry of the attention kernels).
+// prefix_len = P > 0: the first P tokens of every prompt are the same (the caller's promise) and are run ONCE as segment 0
+// of the internal layout (llama_elem.hip, token_meta_kernel); the other segments attend to its K/V rows. Every row then sees
+// exactly the operands of the unshared run, so the scores are bit-identical to prefix_len = 0.
+struct PrefillPlan {
+  int P, n, S, maxT;              // shared prefix in effect, internal rows, segments, longest prompt
+  std::vector<int32_t> seg_host;  // [S + 1]
+  LlamaWs ws;
+};
+static int plan_batch(const lr_llama_t* h, const int32_t* cu_host, int B, int P, void* workspace, size_t workspace_bytes,
+                      PrefillPlan* out) {
   const LrLlamaConfig& c = h->cfg;
-  if (cu_host[0] != 0) LR_FAIL(LR_EINVAL, "llama prefill: cu_seqlens[0] must be 0");
-  int maxT = 0, minT = 0x7fffffff;
-  for (int b = 0; b < B; ++b) {
-    int t = cu_host[b + 1] - cu_host[b];
-    if (t < 1) LR_FAIL(LR_EINVAL, "llama prefill: prompt %d is empty", b);
-    if (t > maxT) maxT = t;
-    if (t < minT) minT = t;
-  }
-  if (maxT > c.max_positions)
-    LR_FAIL(LR_EINVAL, "llama prefill: prompt of %d tokens exceeds max_positions %d", maxT, c.max_positions);
+  int minT = 0;
+  LR_RUN(lr_check_segments(cu_host, B, "llama prefill", &minT, &out->maxT));
+  if (out->maxT > c.max_positions)
+    LR_FAIL(LR_EINVAL, "llama prefill: prompt of %d tokens exceeds max_positions %d", out->maxT, c.max_positions);
   if (P < 0 || (P > 0 && P >= minT))
     LR_FAIL(LR_EINVAL, "llama prefill: shared prefix of %d tokens, shortest prompt has %d (every prompt keeps >= 1 own token)",
             P, minT);
-  if (P > 0 && (c.head_dim != 128 || h->attn_variant == 1)) P = 0;  // only the MFMA attention kernels read a shared prefix
-  if (B == 1) P = 0;
+  if (B == 1 || !lr_attention_reads_prefix(h->attn_variant, c.head_dim)) P = 0;
   const int n_in = cu_host[B];
-  const int n = P > 0 ? n_in - (B - 1) * P : n_in;  // internal rows
-  const int S = P > 0 ? B + 1 : B;                   // segments
-  LlamaWs ws = carve(c, n_in, B, (char*)workspace);
-  if (ws.total > workspace_bytes)
-    LR_FAIL(LR_EWORKSPACE, "llama prefill: workspace needs %zu bytes for %d tokens, have %zu", ws.total, n_in,
+  out->ws = carve(c, n_in, B, (char*)workspace);
+  if (out->ws.total > workspace_bytes)
+    LR_FAIL(LR_EWORKSPACE, "llama prefill: workspace needs %zu bytes for %d tokens, have %zu", out->ws.total, n_in,
             workspace_bytes);
-  // host copy of the segment starts (launch geometry of the attention kernel)
-  std::vector<int32_t> seg_host_v((size_t)S + 1);
-  int32_t* seg_host = seg_host_v.data();
-  if (P > 0) {
-    seg_host[0] = 0;
-    for (int b = 0; b <= B; ++b) seg_host[b + 1] = P + cu_host[b] - b * P;
-  } else {
-    for (int b = 0; b <= B; ++b) seg_host[b] = cu_host[b];
-  }
-  const int d = c.hidden_size, f = c.intermediate_size, nh = c.num_heads, nkv = c.num_kv_heads,
-            hd = c.head_dim;
-  const int qkv_w = (nh + 2 * nkv) * hd;
+  out->P = P;
+  out->n = P > 0 ? n_in - (B - 1) * P : n_in;
+  out->S = P > 0 ? B + 1 : B;
+  out->seg_host.assign((size_t)out->S + 1, 0);   // P > 0: segment 0 = the prefix, then each prompt's own rows
+  for (int b = 0; b <= B; ++b) out->seg_host[b + (P > 0)] = P + cu_host[b] - b * P;
+  return LR_OK;
+}
+
+// B-row products (the pruned last layer): split-K over the 256-column tiles (weight streaming spread over 64-128 CUs
+// instead of N / 64 workgroups of the small-tile kernel: 23 rows x 4096 x 4096 took 134 us there). With B <= 256 rows there
+// is one row tile, so the split count depends on the weight's shape only and a prompt's arithmetic stays the same whatever
+// else is in the batch; more prompts than that take the small-tile kernel as before. (Shapes the 256-tile kernel does not
+// take fall back to it inside lr_launch_gemm.)
+static int b_row_gemm_variant(const lr_llama_t* h, int B) {
+  return (h->gemm_variant == 5 || (h->gemm_variant == 0 && B <= 256)) ? 5 : 1;
+}
+
+// Runs the transformer body; leaves the residual stream (before the final norm) in ws.x (all internal rows) or,
+// after a pruned last layer, in ws.x_last (one row per prompt).
+static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const int32_t* cu_host, int B, int prefix_len,
+                    void* workspace, size_t workspace_bytes, hipStream_t st, LlamaWs* out_ws) {
+  if (!h || !ids || !cu || !cu_host || !workspace) LR_FAIL(LR_EINVAL, "llama prefill: null argument");
+  PrefillPlan plan;
+  LR_RUN(plan_batch(h, cu_host, B, prefix_len, workspace, workspace_bytes, &plan));
+  const LrLlamaConfig& c = h->cfg;
+  const int P = plan.P, n = plan.n, S = plan.S;
+  LlamaWs& ws = plan.ws;
+  const int d = c.hidden_size, f = c.intermediate_size, nh = c.num_heads, nkv = c.num_kv_heads, hd = c.head_dim;
   const int ns = h->arch.norm_style;                               // 0 Llama, 1 Gemma RMSNorm
   const int epi_mlp = h->arch.mlp_act == 1 ? LR_EPI_GEGLU : LR_EPI_SWIGLU;
-  int rc;
-#define RUN(x)              \
-  do {                      \
-    rc = (x);               \
-    if (rc) return rc;      \
-  } while (0)
-  RUN(lr_launch_token_meta(cu, B, P, ws.seg_start, ws.tok_pos, ws.tok_src, ws.last_rows, st, ws.last_pos, ids,
-                           ws.prefix_bad));
-  RUN(lr_launch_rope_table(ws.rope, maxT, hd, c.rope_theta, st, ws.rope16));
-  // attention: 3 = 256-row tiles, one wave per SIMD (llama_attn256.hip), its item list built once per call. Auto keeps variant 2:
-  // on the prompts of this path (460 .. 1 125 tokens) the 128-row kernel with two workgroups per CU is still ahead
-  const bool attn256 = h->attn_variant == 3 && lr_attention256_takes(hd, P);
-  if (h->attn_variant == 3 && !attn256 && hd != 128)
-    LR_FAIL(LR_EUNSUPPORTED, "llama prefill: attention variant 3 needs head_dim 128 (got %d)", hd);
-  if (h->attn_variant == 4 && hd != 256)
-    LR_FAIL(LR_EUNSUPPORTED, "llama prefill: attention variant 4 needs head_dim 256 (got %d)", hd);
-  // 4 = head_dim-256 MFMA kernel (llama_attn_hd256.hip): auto takes it at head_dim 256 (P is 0 there)
-  const bool attn_hd256 = hd == 256 && (h->attn_variant == 0 || h->attn_variant == 4);
-  const int attn_var = attn256 ? 3 : attn_hd256 ? 4 : (h->attn_variant == 3 ? 2 : h->attn_variant);
-  if (attn256) RUN(lr_launch_attn256_items(ws.seg_start, S, n, nh, P, ws.attn_items, ws.attn_items_bytes, st));
-  RUN(lr_launch_embed(ids, ws.tok_src, h->embed, c.vocab_size, d, ws.x, n, st, h->arch.embed_scale));
+  const int gv = h->gemm_variant, pv = b_row_gemm_variant(h, B);
+  LrAttnKernel attn_kernel;
+  LR_RUN(lr_resolve_attention({.variant = h->attn_variant, .hd = hd, .prefix_len = P, .have_items_ws = true, .prefill = true},
+                              &attn_kernel));
+  // the MFMA kernels over ALL rows (188 us for 14.8 k tokens, 16 us for one prompt) beat the scalar kernel over the B last
+  // rows (459 / 295 us), so a pruned last layer attends everything and keeps the last rows
+  const bool attn_mfma = (hd == 128 && attn_kernel != LR_ATTN_GENERIC) || attn_kernel == LR_ATTN_HD256;
+  const LrAttnArgs attn = {.qkv = ws.qkv, .out = ws.att, .cu = ws.seg_start, .cu_host = plan.seg_host.data(), .S = S,
+                           .n_tok = n, .nh = nh, .nkv = nkv, .hd = hd, .prefix_len = P, .items_ws = ws.attn_items};
+  struct LayerRows { u16 *att, *x, *xn, *hmid; int M, gemm_variant; };   // what o_proj and the MLP run on
+  const LayerRows full = {ws.att, ws.x, ws.xn, ws.hmid, n, gv}, last = {ws.att_last, ws.x_last, ws.xn_last, ws.h_last, B, pv};
+  auto rope = [&](const int32_t* tok_pos, int rot_cols) {
+    return LrGemmRope{.tok_pos = tok_pos, .cs = ws.rope, .cs16 = ws.rope16, .head_dim = hd, .rot_cols = rot_cols};
+  };
+  LR_RUN(lr_launch_token_meta(cu, B, P, ws.seg_start, ws.tok_pos, ws.tok_src, ws.last_rows, st, ws.last_pos, ids,
+                              ws.prefix_bad));
+  LR_RUN(lr_launch_rope_table(ws.rope, plan.maxT, hd, c.rope_theta, st, ws.rope16));
+  if (attn_kernel == LR_ATTN_ROWS256)
+    LR_RUN(lr_launch_attn256_items(ws.seg_start, S, n, nh, P, ws.attn_items, ws.attn_items_bytes, st));
+  LR_RUN(lr_launch_embed(ids, ws.tok_src, h->embed, c.vocab_size, d, ws.x, n, st, h->arch.embed_scale));
   bool input_normed = false;   // ws.xn already holds RMSNorm(ws.x) with this layer's input_norm
 #ifdef LR_EXPERIMENTS   // timing-only arm (never in the product library): the row statistics of layer 0 serve every layer
   static const bool exp_rstd_once = getenv("LR_EXP_RSTD_ONCE") && getenv("LR_EXP_RSTD_ONCE")[0] == '1';
@@ -246,86 +256,57 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
     // needed for B rows only -- K and V for all of them. The projection runs on the K | V rows of wqkv (2/3 of the
     // product) for every row and on its Q rows for the B last rows; the attention kernel then evaluates ONE query row
     // per (prompt, head) over the prompt's keys instead of every tile.
-    const bool last_q_only = last_pruned && !folded && hd == 128 && h->attn_variant != 1 && h->gemm_variant != 1;
+    const bool last_q_only = last_pruned && !folded && hd == 128 && attn_mfma && gv != 1;
+    if (folded && !EXP_SKIP_SWEEP) LR_RUN(lr_launch_rms_rstd(ws.x, ws.rstd, n, d, c.rms_eps, st));
+    if (!folded && !input_normed) LR_RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st, ns));
+    const int q_w = nh * hd, kv_w = 2 * nkv * hd;
     if (last_q_only) {
-      const int q_w = nh * hd, kv_w = 2 * nkv * hd;
-      const int pv = (h->gemm_variant == 5 || (h->gemm_variant == 0 && B <= 256)) ? 5 : 1;
-      if (!input_normed) RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st, ns));
-      RUN(lr_launch_gemm(ws.xn, w.wqkv + (size_t)q_w * d, ws.qkv, nullptr, n, kv_w, d, LR_EPI_ROPE, h->gemm_variant, st,
-                         ws.tok_pos, ws.rope, hd, nkv * hd, ws.splitk, LR_SPLITK_WS_BYTES, nullptr, ws.rope16));
-      RUN(lr_launch_gather_rows(ws.xn, ws.last_rows, B, d, ws.xn_last, st));
-      RUN(lr_launch_gemm(ws.xn_last, w.wqkv, ws.q_last, nullptr, B, q_w, d, LR_EPI_ROPE, pv, st, ws.last_pos, ws.rope, hd,
-                         q_w, ws.splitk, LR_SPLITK_WS_BYTES, nullptr, ws.rope16));
-      RUN(lr_launch_attention_last(ws.qkv, ws.q_last, ws.att_last, ws.seg_start, seg_host, S, n, nh, nkv, hd, st, P));
-    } else if (folded) {
-      if (!EXP_SKIP_SWEEP) RUN(lr_launch_rms_rstd(ws.x, ws.rstd, n, d, c.rms_eps, st));
-      RUN(lr_launch_gemm(ws.x, h->wqkv_folded[l], ws.qkv, nullptr, n, qkv_w, d, LR_EPI_ROPE, h->gemm_variant, st, ws.tok_pos,
-                         ws.rope, hd, (nh + nkv) * hd, ws.splitk, LR_SPLITK_WS_BYTES, ws.rstd, ws.rope16));
+      LR_RUN(lr_launch_gemm({.A = ws.xn, .B = w.wqkv + (size_t)q_w * d, .C = ws.qkv, .M = n, .N = kv_w, .K = d,
+                             .epi = LR_EPI_ROPE, .variant = gv, .rope = rope(ws.tok_pos, kv_w / 2), .splitk = ws.splitk}, st));
+      LR_RUN(lr_launch_gather_rows(ws.xn, ws.last_rows, B, d, ws.xn_last, st));
+      LR_RUN(lr_launch_gemm({.A = ws.xn_last, .B = w.wqkv, .C = ws.q_last, .M = B, .N = q_w, .K = d, .epi = LR_EPI_ROPE,
+                             .variant = pv, .rope = rope(ws.last_pos, q_w), .splitk = ws.splitk}, st));
+      LR_RUN(lr_launch_attention_last(ws.qkv, ws.q_last, ws.att_last, attn.cu, attn.cu_host, S, n, nh, nkv, hd, st, P));
     } else {
-      if (!input_normed) RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st, ns));
-      RUN(lr_launch_gemm(ws.xn, w.wqkv, ws.qkv, nullptr, n, qkv_w, d, LR_EPI_ROPE, h->gemm_variant, st, ws.tok_pos,
-                         ws.rope, hd, (nh + nkv) * hd, ws.splitk, LR_SPLITK_WS_BYTES, nullptr, ws.rope16));
+      LR_RUN(lr_launch_gemm({.A = folded ? ws.x : ws.xn, .B = folded ? h->wqkv_folded[l] : w.wqkv, .C = ws.qkv, .M = n,
+                             .N = q_w + kv_w, .K = d, .epi = LR_EPI_ROPE, .variant = gv, .rope = rope(ws.tok_pos, q_w + kv_w / 2),
+                             .row_scale = folded ? ws.rstd : nullptr, .splitk = ws.splitk}, st));
     }
-    if (last_pruned) {
+    if (!last_pruned) {
+      LR_RUN(lr_launch_attention(attn, attn_kernel, st));
+    } else {
       // Only each prompt's LAST token is consumed after the final layer (model/llm.py:131), so the
       // last layer needs K/V for every token but attention output, o_proj, and the MLP for B rows only.
-      if (last_q_only) {
-        // ws.att_last already holds the attention rows of the last tokens
-      } else if ((hd == 128 && h->attn_variant != 1) || attn_var == 4) {
-        // the MFMA kernel over ALL rows (188 us for 14.8 k tokens, 16 us for one prompt) beats the scalar kernel over the
-        // B last rows (459 / 295 us): attend everything, keep the last rows (head_dim 256 likewise, on variant 4)
-        if (attn256)
-          RUN(lr_launch_attention256(ws.qkv, ws.att, ws.seg_start, seg_host, S, n, nh, nkv, hd, nullptr, ws.attn_items, st, P));
-        else
-          RUN(lr_launch_attention(ws.qkv, ws.att, ws.seg_start, seg_host, ws.tok_pos, nullptr, S, n, nh, nkv, hd,
-                                  attn_var, nullptr, st, P));
-        RUN(lr_launch_gather_rows(ws.att, ws.last_rows, B, nh * hd, ws.att_last, st));
-      } else {
-        RUN(lr_launch_attention_rows(ws.qkv, ws.att_last, cu, B, ws.last_rows, B, nh, nkv, hd, st));
+      // last_q_only: ws.att_last already holds the attention rows of the last tokens
+      if (!last_q_only && attn_mfma) {
+        LR_RUN(lr_launch_attention(attn, attn_kernel, st));
+        LR_RUN(lr_launch_gather_rows(ws.att, ws.last_rows, B, nh * hd, ws.att_last, st));
+      } else if (!last_q_only) {
+        LR_RUN(lr_launch_attention_rows(ws.qkv, ws.att_last, cu, B, ws.last_rows, B, nh, nkv, hd, st));
       }
-      RUN(lr_launch_gather_rows(ws.x, ws.last_rows, B, d, ws.x_last, st));
-      // B-row products: split-K over the 256-column tiles (weight streaming spread over 64-128 CUs instead of N / 64
-      // workgroups of the small-tile kernel: 23 rows x 4096 x 4096 took 134 us there). With B <= 256 rows there is one
-      // row tile, so the split count depends on the weight's shape only and a prompt's arithmetic stays the same whatever
-      // else is in the batch; more prompts than that take the small-tile kernel as before. (Shapes the 256-tile kernel
-      // does not take fall back to it inside lr_launch_gemm.)
-      const int pv = (h->gemm_variant == 5 || (h->gemm_variant == 0 && B <= 256)) ? 5 : 1;
-      bool normed = false;   // a split-K product's reduce pass also writes the RMSNorm that follows (same bits)
-      RUN(lr_launch_gemm(ws.att_last, w.wo, ws.x_last, ws.x_last, B, d, nh * hd, LR_EPI_RESIDUAL, pv, st, nullptr, nullptr,
-                         0, 0, ws.splitk, LR_SPLITK_WS_BYTES, nullptr, nullptr, w.post_norm, ws.xn_last, c.rms_eps, &normed, ns));
-      if (!normed) RUN(lr_launch_rmsnorm(ws.x_last, w.post_norm, ws.xn_last, B, d, c.rms_eps, nullptr, st, ns));
-      RUN(lr_launch_gemm(ws.xn_last, w.wgu, ws.h_last, nullptr, B, 2 * f, d, epi_mlp, pv, st, nullptr, nullptr, 0, 0,
-                         ws.splitk, LR_SPLITK_WS_BYTES));
-      RUN(lr_launch_gemm(ws.h_last, w.wdown, ws.x_last, ws.x_last, B, d, f, LR_EPI_RESIDUAL, pv, st, nullptr, nullptr, 0, 0,
-                         ws.splitk, LR_SPLITK_WS_BYTES));
-      ws.compact = true;
-      break;
+      LR_RUN(lr_launch_gather_rows(ws.x, ws.last_rows, B, d, ws.x_last, st));
+      ws.compact = true;   // and this was the last layer
     }
-    if (attn256)
-      RUN(lr_launch_attention256(ws.qkv, ws.att, ws.seg_start, seg_host, S, n, nh, nkv, hd, nullptr, ws.attn_items, st, P));
-    else
-      RUN(lr_launch_attention(ws.qkv, ws.att, ws.seg_start, seg_host, ws.tok_pos, nullptr, S, n, nh, nkv, hd, attn_var,
-                              nullptr, st, P));
-    bool post_normed = false;
-    RUN(lr_launch_gemm(ws.att, w.wo, ws.x, ws.x, n, d, nh * hd, LR_EPI_RESIDUAL, h->gemm_variant, st, nullptr, nullptr, 0,
-                       0, ws.splitk, LR_SPLITK_WS_BYTES, nullptr, nullptr, folded ? nullptr : w.post_norm, ws.xn, c.rms_eps,
-                       &post_normed, ns));
-    if (folded) {
-      if (!EXP_SKIP_SWEEP) RUN(lr_launch_rms_rstd(ws.x, ws.rstd, n, d, c.rms_eps, st));
-      RUN(lr_launch_gemm(ws.x, h->wgu_folded[l], ws.hmid, nullptr, n, 2 * f, d, LR_EPI_SWIGLU, h->gemm_variant, st, nullptr,
-                         nullptr, 0, 0, ws.splitk, LR_SPLITK_WS_BYTES, ws.rstd));
-    } else {
-      if (!post_normed) RUN(lr_launch_rmsnorm(ws.x, w.post_norm, ws.xn, n, d, c.rms_eps, nullptr, st, ns));
-      RUN(lr_launch_gemm(ws.xn, w.wgu, ws.hmid, nullptr, n, 2 * f, d, epi_mlp, h->gemm_variant, st, nullptr, nullptr,
-                         0, 0, ws.splitk, LR_SPLITK_WS_BYTES));
-    }
-    // down_proj; its reduce pass (latency mode) also writes the NEXT layer's input RMSNorm when that layer reads ws.xn
-    const bool next_reads_xn = l + 1 < c.num_layers && !folded;
-    RUN(lr_launch_gemm(ws.hmid, w.wdown, ws.x, ws.x, n, d, f, LR_EPI_RESIDUAL, h->gemm_variant, st, nullptr, nullptr, 0, 0,
-                       ws.splitk, LR_SPLITK_WS_BYTES, nullptr, nullptr, next_reads_xn ? h->layers[l + 1].input_norm : nullptr,
-                       ws.xn, c.rms_eps, &input_normed, ns));
+    // o_proj and the MLP: on every row, or -- pruned last layer -- on the B compact rows (b_row_gemm_variant, never folded)
+    const LayerRows& r = last_pruned ? last : full;
+    const bool fold_mlp = folded && !last_pruned;
+    bool post_normed = false;   // a split-K product's reduce pass also writes the RMSNorm that follows (same bits)
+    LR_RUN(lr_launch_gemm({.A = r.att, .B = w.wo, .C = r.x, .R = r.x, .M = r.M, .N = d, .K = nh * hd, .epi = LR_EPI_RESIDUAL,
+                           .variant = r.gemm_variant, .splitk = ws.splitk,
+                           .then_norm = {.w = fold_mlp ? nullptr : w.post_norm, .out = r.xn, .eps = c.rms_eps, .style = ns,
+                                         .done = &post_normed}}, st));
+    if (fold_mlp && !EXP_SKIP_SWEEP) LR_RUN(lr_launch_rms_rstd(r.x, ws.rstd, r.M, d, c.rms_eps, st));
+    if (!fold_mlp && !post_normed) LR_RUN(lr_launch_rmsnorm(r.x, w.post_norm, r.xn, r.M, d, c.rms_eps, nullptr, st, ns));
+    LR_RUN(lr_launch_gemm({.A = fold_mlp ? r.x : r.xn, .B = fold_mlp ? h->wgu_folded[l] : w.wgu, .C = r.hmid, .M = r.M,
+                           .N = 2 * f, .K = d, .epi = epi_mlp, .variant = r.gemm_variant,
+                           .row_scale = fold_mlp ? ws.rstd : nullptr, .splitk = ws.splitk}, st));
+    // down_proj; its reduce pass (latency mode) also writes the NEXT layer's input RMSNorm when there is one and it reads
+    // ws.xn (not folded)
+    LR_RUN(lr_launch_gemm({.A = r.hmid, .B = w.wdown, .C = r.x, .R = r.x, .M = r.M, .N = d, .K = f, .epi = LR_EPI_RESIDUAL,
+                           .variant = r.gemm_variant, .splitk = ws.splitk,
+                           .then_norm = {.w = l + 1 < c.num_layers && !folded ? h->layers[l + 1].input_norm : nullptr,
+                                         .out = r.xn, .eps = c.rms_eps, .style = ns, .done = &input_normed}}, st));
   }
-#undef RUN
 #undef EXP_SKIP_SWEEP
   *out_ws = ws;
   return LR_OK;
@@ -335,8 +316,7 @@ static int prefill_head(lr_llama_t* h, const int32_t* packed_ids, const int32_t*
                         int32_t B, int32_t prefix_len, const int32_t* class_ids, int32_t C, float* out, void* workspace,
                         size_t workspace_bytes, hipStream_t st) {
   LlamaWs ws;
-  int rc = run_body(h, packed_ids, cu_seqlens, cu_seqlens_host, B, prefix_len, workspace, workspace_bytes, st, &ws);
-  if (rc) return rc;
+  LR_RUN(run_body(h, packed_ids, cu_seqlens, cu_seqlens_host, B, prefix_len, workspace, workspace_bytes, st, &ws));
   return lr_launch_head(ws.compact ? ws.x_last : ws.x, ws.compact ? nullptr : ws.last_rows, h->final_norm, h->lm_head,
                         class_ids, B, C, h->cfg.hidden_size, h->cfg.rms_eps, out, h->cfg.vocab_size, st, ws.prefix_bad,
                         h->arch.norm_style);
@@ -421,15 +401,15 @@ extern "C" int lr_llama_pack_qkv(const uint16_t* q, const uint16_t* k, const uin
 extern "C" int lr_gemm_bf16_nt(const uint16_t* A, const uint16_t* B, uint16_t* C, int32_t M, int32_t N,
                                int32_t K, int32_t variant, void* hip_stream) {
   if (!A || !B || !C) LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt: null pointer");
-  return lr_launch_gemm(A, B, C, nullptr, M, N, K, LR_EPI_STORE, variant, (hipStream_t)hip_stream);
+  return lr_launch_gemm({.A = A, .B = B, .C = C, .M = M, .N = N, .K = K, .variant = variant}, (hipStream_t)hip_stream);
 }
 
 extern "C" int lr_gemm_bf16_nt_ws(const uint16_t* A, const uint16_t* B, uint16_t* C, int32_t M, int32_t N,
                                   int32_t K, int32_t variant, void* workspace, size_t workspace_bytes,
                                   void* hip_stream) {
   if (!A || !B || !C) LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt_ws: null pointer");
-  return lr_launch_gemm(A, B, C, nullptr, M, N, K, LR_EPI_STORE, variant, (hipStream_t)hip_stream, nullptr, nullptr, 0,
-                        0, (float*)workspace, workspace_bytes);
+  return lr_launch_gemm({.A = A, .B = B, .C = C, .M = M, .N = N, .K = K, .variant = variant,
+                         .splitk = {.ws = (float*)workspace, .bytes = workspace_bytes}}, (hipStream_t)hip_stream);
 }
 
 extern "C" int lr_gemm_bf16_nt_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const uint16_t* R, int32_t M,
@@ -442,8 +422,9 @@ extern "C" int lr_gemm_bf16_nt_epi(const uint16_t* A, const uint16_t* B, uint16_
   // the packed half of lr_rope_table's buffer sits behind the fp32 half
   const unsigned* cs16 = (rope_cs && rope_positions > 0 && head_dim >= 2)
                              ? reinterpret_cast<const unsigned*>(rope_cs + (size_t)rope_positions * head_dim) : nullptr;
-  return lr_launch_gemm(A, B, C, R, M, N, K, epilogue, variant, (hipStream_t)hip_stream, tok_pos, rope_cs, head_dim,
-                        rot_cols, (float*)workspace, workspace_bytes, nullptr, cs16);
+  return lr_launch_gemm({.A = A, .B = B, .C = C, .R = R, .M = M, .N = N, .K = K, .epi = epilogue, .variant = variant,
+                         .rope = {.tok_pos = tok_pos, .cs = rope_cs, .cs16 = cs16, .head_dim = head_dim, .rot_cols = rot_cols},
+                         .splitk = {.ws = (float*)workspace, .bytes = workspace_bytes}}, (hipStream_t)hip_stream);
 }
 
 extern "C" int lr_gemm_bf16_nt_residual_rmsnorm_ex(const uint16_t* A, const uint16_t* B, uint16_t* C, const uint16_t* R,
@@ -455,9 +436,10 @@ extern "C" int lr_gemm_bf16_nt_residual_rmsnorm_ex(const uint16_t* A, const uint
   if (norm_style != 0 && norm_style != 1) LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt_residual_rmsnorm_ex: norm_style %d", norm_style);
   hipStream_t st = (hipStream_t)hip_stream;
   bool done = false;
-  int rc = lr_launch_gemm(A, B, C, R, M, N, K, LR_EPI_RESIDUAL, variant, st, nullptr, nullptr, 0, 0, (float*)workspace,
-                          workspace_bytes, nullptr, nullptr, fuse ? norm_w : nullptr, norm_out, eps, &done, norm_style);
-  if (rc) return rc;
+  LR_RUN(lr_launch_gemm({.A = A, .B = B, .C = C, .R = R, .M = M, .N = N, .K = K, .epi = LR_EPI_RESIDUAL, .variant = variant,
+                         .splitk = {.ws = (float*)workspace, .bytes = workspace_bytes},
+                         .then_norm = {.w = fuse ? norm_w : nullptr, .out = norm_out, .eps = eps, .style = norm_style,
+                                       .done = &done}}, st));
   if (was_fused) *was_fused = done ? 1 : 0;
   if (done) return LR_OK;
   return lr_launch_rmsnorm(C, norm_w, norm_out, M, N, eps, nullptr, st, norm_style);
@@ -487,8 +469,11 @@ extern "C" int lr_attention_varlen(const uint16_t* qkv, uint16_t* out, const int
                                    int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* hip_stream) {
   if (!qkv || !out || !cu_seqlens || !cu_seqlens_host || B < 1) LR_FAIL(LR_EINVAL, "lr_attention_varlen: bad argument");
   if (int rc = lr_check_segments(cu_seqlens_host, B, "lr_attention_varlen")) return rc;
-  return lr_launch_attention(qkv, out, cu_seqlens, cu_seqlens_host, nullptr, nullptr, B, cu_seqlens_host[B],
-                             num_heads, num_kv_heads, head_dim, variant, nullptr, (hipStream_t)hip_stream);
+  LrAttnKernel kernel;
+  if (int rc = lr_resolve_attention({.variant = variant, .hd = head_dim}, &kernel)) return rc;
+  return lr_launch_attention({.qkv = qkv, .out = out, .cu = cu_seqlens, .cu_host = cu_seqlens_host, .S = B,
+                              .n_tok = cu_seqlens_host[B], .nh = num_heads, .nkv = num_kv_heads, .hd = head_dim},
+                             kernel, (hipStream_t)hip_stream);
 }
 
 extern "C" size_t lr_attention_workspace_bytes(int32_t total_tokens, int32_t B, int32_t num_heads) {
@@ -504,12 +489,13 @@ extern "C" int lr_attention_varlen_ws(const uint16_t* qkv, uint16_t* out, float*
   if (int rc = lr_check_segments(cu_seqlens_host, B, "lr_attention_varlen_ws")) return rc;
   hipStream_t st = (hipStream_t)hip_stream;
   const int n = cu_seqlens_host[B];
-  if (variant == 3 || (variant == 0 && head_dim == 128 && workspace)) {
-    if (head_dim != 128) LR_FAIL(LR_EUNSUPPORTED, "lr_attention_varlen_ws: variant 3 needs head_dim 128 (got %d)", head_dim);
+  LrAttnKernel kernel;
+  // a variant-3 request always reaches the item-list builder, which reports a missing or short workspace (LR_EWORKSPACE)
+  LR_RUN(lr_resolve_attention({.variant = variant, .hd = head_dim, .want_lse = lse != nullptr,
+                               .have_items_ws = workspace != nullptr || variant == 3}, &kernel));
+  if (kernel == LR_ATTN_ROWS256)
     if (int rc = lr_launch_attn256_items(cu_seqlens, B, n, num_heads, 0, workspace, workspace_bytes, st)) return rc;
-    return lr_launch_attention256(qkv, out, cu_seqlens, cu_seqlens_host, B, n, num_heads, num_kv_heads, head_dim, lse,
-                                  workspace, st, 0);
-  }
-  return lr_launch_attention(qkv, out, cu_seqlens, cu_seqlens_host, nullptr, nullptr, B, n, num_heads, num_kv_heads, head_dim,
-                             variant, lse, st);
+  return lr_launch_attention({.qkv = qkv, .out = out, .lse = lse, .cu = cu_seqlens, .cu_host = cu_seqlens_host, .S = B,
+                              .n_tok = n, .nh = num_heads, .nkv = num_kv_heads, .hd = head_dim, .items_ws = workspace},
+                             kernel, st);
 }

@@ -201,7 +201,7 @@ struct LoraLayerSave {
   float* lse;
 };
 struct LoraWs {
-  int32_t *tok_pos, *tok_seq, *last_rows;
+  int32_t *tok_pos, *last_rows;
   float* rope;
   u16 *x_final, *xn2, *hmid;              // forward transients (xn2/hmid alias backward transients)
   u16 *dx, *dh, *dxn, *datt, *dqkv, *dt;  // backward
@@ -226,7 +226,6 @@ static LoraWs carve(const LrLlamaConfig& c, int n_tok, int B, int m, int slots, 
   const size_t qcols = (size_t)c.num_heads * c.head_dim, kv = (size_t)c.num_kv_heads * c.head_dim;
   const size_t qw = qcols + 2 * kv;
   w.tok_pos = (int32_t*)(base + take(n * 4));
-  w.tok_seq = (int32_t*)(base + take(n * 4));
   w.last_rows = (int32_t*)(base + take((size_t)(B > 0 ? B : 1) * 4));
   w.rope = (float*)(base + take((size_t)c.max_positions * (c.head_dim / 2) * 2 * sizeof(float)));
   w.x_final = (u16*)(base + take(n * d * 2));
@@ -292,43 +291,28 @@ extern "C" size_t lr_llama_lora_eval_workspace_bytes(const lr_llama_lora_t* h, i
   return carve(h->base->cfg, max_tokens, max_seqs, 0, 1, false, nullptr).total;
 }
 
-#define RUN(x)         \
-  do {                 \
-    rc = (x);          \
-    if (rc) return rc; \
-  } while (0)
-
 static u16* work_of(const lr_llama_lora* h, int l) { return h->work + (size_t)l * h->work_per_layer; }
 
 // bf16 working copies of every layer's adapters from the fp32 masters
 static int prep_adapters(lr_llama_lora* h, hipStream_t st) {
   const LrLlamaConfig& c = h->base->cfg;
   const size_t r = h->cfg.r, d = c.hidden_size;
-  int rc;
   for (int l = 0; l < c.num_layers; ++l) {
     const float* p = h->params + (size_t)l * h->per_layer;
     u16* w = work_of(h, l);
-    RUN(lr_launch_prep_lora(p, p + r * d, p + r * d + r * h->qcols, p + 2 * r * d + r * h->qcols, (int)r, (int)d,
-                            h->qcols, h->vcols, c.head_dim, w, w + 2 * LT_RP * d, w + 2 * LT_RP * d + LT_RP * h->qcols,
-                            st));
+    LR_RUN(lr_launch_prep_lora(p, p + r * d, p + r * d + r * h->qcols, p + 2 * r * d + r * h->qcols, (int)r, (int)d,
+                               h->qcols, h->vcols, c.head_dim, w, w + 2 * LT_RP * d, w + 2 * LT_RP * d + LT_RP * h->qcols,
+                               st));
   }
   return LR_OK;
 }
 
 static int validate_batch(const lr_llama_lora* h, const int32_t* cu_host, int B, int* n_out, int* maxT_out) {
   const LrLlamaConfig& c = h->base->cfg;
-  if (B < 1) LR_FAIL(LR_EINVAL, "llama lora: B=%d", B);
-  if (cu_host[0] != 0) LR_FAIL(LR_EINVAL, "llama lora: cu_seqlens[0] must be 0");
-  int maxT = 0;
-  for (int b = 0; b < B; ++b) {
-    const int t = cu_host[b + 1] - cu_host[b];
-    if (t < 1) LR_FAIL(LR_EINVAL, "llama lora: prompt %d is empty", b);
-    if (t > maxT) maxT = t;
-  }
-  if (maxT > c.max_positions)
-    LR_FAIL(LR_EINVAL, "llama lora: prompt of %d tokens exceeds max_positions %d", maxT, c.max_positions);
+  if (int rc = lr_check_segments(cu_host, B, "llama lora", nullptr, maxT_out)) return rc;
+  if (*maxT_out > c.max_positions)
+    LR_FAIL(LR_EINVAL, "llama lora: prompt of %d tokens exceeds max_positions %d", *maxT_out, c.max_positions);
   *n_out = cu_host[B];
-  *maxT_out = maxT;
   return LR_OK;
 }
 
@@ -340,10 +324,11 @@ static int forward(lr_llama_lora* h, const int32_t* ids, const int32_t* cu, cons
   const int qw = (nh + 2 * nkv) * hd;
   const float scaling = h->cfg.alpha / (float)h->cfg.r;
   const int gv = h->base->gemm_variant == 5 ? 0 : h->base->gemm_variant;
-  int rc;
-  RUN(lr_launch_token_meta(cu, B, 0, nullptr, ws.tok_pos, nullptr, ws.last_rows, st));
-  RUN(lr_launch_rope_table(ws.rope, maxT, hd, c.rope_theta, st));
-  RUN(lr_launch_embed(ids, nullptr, h->base->embed, c.vocab_size, d, slot(ws, 0).x, n, st));
+  LrAttnKernel attn_kernel;  // the backward needs the statistics: lse wanted
+  LR_RUN(lr_resolve_attention({.variant = h->base->attn_variant, .hd = hd, .want_lse = true}, &attn_kernel));
+  LR_RUN(lr_launch_token_meta(cu, B, 0, nullptr, ws.tok_pos, nullptr, ws.last_rows, st));
+  LR_RUN(lr_launch_rope_table(ws.rope, maxT, hd, c.rope_theta, st));
+  LR_RUN(lr_launch_embed(ids, nullptr, h->base->embed, c.vocab_size, d, slot(ws, 0).x, n, st));
   for (int l = 0; l < c.num_layers; ++l) {
     const LrLlamaLayerWeights& w = h->base->layers[l];
     const LoraLayerSave s = slot(ws, save ? l : 0);
@@ -351,20 +336,23 @@ static int forward(lr_llama_lora* h, const int32_t* ids, const int32_t* cu, cons
     const u16* wk = work_of(h, l);
     const u16 *a_cat = wk, *bq_t = wk + 2 * LT_RP * (size_t)d, *bv_t = bq_t + LT_RP * (size_t)h->qcols;
     const uint32_t stream = lr_lora_drop_stream(h->cfg.seed, h->pass, (uint32_t)l);
-    RUN(lr_launch_rmsnorm(s.x, w.input_norm, s.xn, n, d, c.rms_eps, nullptr, st));
+    LR_RUN(lr_launch_rmsnorm(s.x, w.input_norm, s.xn, n, d, c.rms_eps, nullptr, st));
     hipStream_t sd;
-    RUN(fork_side(h, st, &sd));  // t = drop(xn) A^T next to the QKV GEMM: both only read xn
-    RUN(lr_launch_skinny(s.xn, d, n, d, a_cat, 2, s.t, 2 * LT_RP, 0, 1.0f, stream, drop_p, sd));
-    RUN(lr_launch_gemm(s.xn, w.wqkv, s.qkv, nullptr, n, qw, d, LR_EPI_STORE, gv, st));
-    RUN(join_side(h, st));
-    RUN(lr_launch_lora_rope_fwd(s.qkv, n, qw, h->qcols, h->kcols, hd, s.t, bq_t, bv_t, h->cfg.r, scaling, ws.tok_pos,
-                                ws.rope, st));
-    RUN(lr_launch_attention_lse(s.qkv, s.att, s.lse, cu, cu_host, B, n, nh, nkv, hd, h->base->attn_variant, st));
-    RUN(lr_launch_gemm(s.att, w.wo, s.xmid, s.x, n, d, nh * hd, LR_EPI_RESIDUAL, gv, st));
-    RUN(lr_launch_rmsnorm(s.xmid, w.post_norm, ws.xn2, n, d, c.rms_eps, nullptr, st));
-    RUN(lr_launch_gemm(ws.xn2, w.wgu, s.gu, nullptr, n, 2 * f, d, LR_EPI_STORE, gv, st));
-    RUN(lr_launch_swiglu_fwd(s.gu, ws.hmid, n, f, st));
-    RUN(lr_launch_gemm(ws.hmid, w.wdown, x_next, s.xmid, n, d, f, LR_EPI_RESIDUAL, gv, st));
+    LR_RUN(fork_side(h, st, &sd));  // t = drop(xn) A^T next to the QKV GEMM: both only read xn
+    LR_RUN(lr_launch_skinny(s.xn, d, n, d, a_cat, 2, s.t, 2 * LT_RP, 0, 1.0f, stream, drop_p, sd));
+    LR_RUN(lr_launch_gemm({.A = s.xn, .B = w.wqkv, .C = s.qkv, .M = n, .N = qw, .K = d, .variant = gv}, st));
+    LR_RUN(join_side(h, st));
+    LR_RUN(lr_launch_lora_rope_fwd(s.qkv, n, qw, h->qcols, h->kcols, hd, s.t, bq_t, bv_t, h->cfg.r, scaling, ws.tok_pos,
+                                   ws.rope, st));
+    LR_RUN(lr_launch_attention({.qkv = s.qkv, .out = s.att, .lse = s.lse, .cu = cu, .cu_host = cu_host, .S = B, .n_tok = n,
+                                .nh = nh, .nkv = nkv, .hd = hd}, attn_kernel, st));
+    LR_RUN(lr_launch_gemm({.A = s.att, .B = w.wo, .C = s.xmid, .R = s.x, .M = n, .N = d, .K = nh * hd, .epi = LR_EPI_RESIDUAL,
+                           .variant = gv}, st));
+    LR_RUN(lr_launch_rmsnorm(s.xmid, w.post_norm, ws.xn2, n, d, c.rms_eps, nullptr, st));
+    LR_RUN(lr_launch_gemm({.A = ws.xn2, .B = w.wgu, .C = s.gu, .M = n, .N = 2 * f, .K = d, .variant = gv}, st));
+    LR_RUN(lr_launch_swiglu_fwd(s.gu, ws.hmid, n, f, st));
+    LR_RUN(lr_launch_gemm({.A = ws.hmid, .B = w.wdown, .C = x_next, .R = s.xmid, .M = n, .N = d, .K = f, .epi = LR_EPI_RESIDUAL,
+                           .variant = gv}, st));
   }
   return LR_OK;
 }
@@ -378,8 +366,8 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
   if (m < 1) LR_FAIL(LR_EINVAL, "lr_llama_lora_loss_grad: no labelled rows (m=%d)", m);
   hipStream_t st = (hipStream_t)hip_stream;
   const LrLlamaConfig& c = h->base->cfg;
-  int n, maxT, rc;
-  RUN(validate_batch(h, cu_seqlens_host, B, &n, &maxT));
+  int n, maxT;
+  LR_RUN(validate_batch(h, cu_seqlens_host, B, &n, &maxT));
   if (m > n) LR_FAIL(LR_EINVAL, "lr_llama_lora_loss_grad: %d labelled rows for %d tokens", m, n);
   const LoraWs ws = carve(c, n, B, m, c.num_layers, true, (char*)workspace);
   if (ws.total > workspace_bytes)
@@ -392,19 +380,19 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
   h->pass += 1;
   if (!accumulate) LR_CHECK_HIP(hipMemsetAsync(h->grads, 0, h->n_params * sizeof(float), st));
   LR_CHECK_HIP(hipMemsetAsync(h->scratch, 0, 2 * sizeof(float), st));
-  RUN(prep_adapters(h, st));
-  RUN(forward(h, packed_ids, cu_seqlens, cu_seqlens_host, B, n, maxT, ws, true, drop_p, st));
+  LR_RUN(prep_adapters(h, st));
+  LR_RUN(forward(h, packed_ids, cu_seqlens, cu_seqlens_host, B, n, maxT, ws, true, drop_p, st));
 
   // ---- loss head on the labelled rows only (model/llm.py:113-126)
-  RUN(lr_launch_gather_rows(ws.x_final, loss_rows, m, d, ws.xg, st));
-  RUN(lr_launch_rmsnorm(ws.xg, h->base->final_norm, ws.hn, m, d, c.rms_eps, nullptr, st));
-  RUN(lr_launch_gemm(ws.hn, h->base->lm_head, ws.logits, nullptr, m, c.vocab_size, d, LR_EPI_STORE, gv, st));
-  RUN(lr_launch_ce_bf16(ws.logits, m, c.vocab_size, loss_targets, grad_scale / (float)m, h->scratch, st));
-  RUN(lr_launch_finish_loss(h->scratch, m, out, st));
-  RUN(lr_launch_gemm(ws.logits, h->lm_head_t, ws.dhn, nullptr, m, d, c.vocab_size, LR_EPI_STORE, gv, st));
+  LR_RUN(lr_launch_gather_rows(ws.x_final, loss_rows, m, d, ws.xg, st));
+  LR_RUN(lr_launch_rmsnorm(ws.xg, h->base->final_norm, ws.hn, m, d, c.rms_eps, nullptr, st));
+  LR_RUN(lr_launch_gemm({.A = ws.hn, .B = h->base->lm_head, .C = ws.logits, .M = m, .N = c.vocab_size, .K = d, .variant = gv}, st));
+  LR_RUN(lr_launch_ce_bf16(ws.logits, m, c.vocab_size, loss_targets, grad_scale / (float)m, h->scratch, st));
+  LR_RUN(lr_launch_finish_loss(h->scratch, m, out, st));
+  LR_RUN(lr_launch_gemm({.A = ws.logits, .B = h->lm_head_t, .C = ws.dhn, .M = m, .N = d, .K = c.vocab_size, .variant = gv}, st));
   LR_CHECK_HIP(hipMemsetAsync(ws.dx, 0, (size_t)n * d * 2, st));
-  RUN(lr_launch_rmsnorm_bwd(ws.dhn, ws.xg, h->base->final_norm, nullptr, ws.dx, m, d, c.rms_eps, loss_rows, nullptr,
-                            nullptr, 0, 0, 0.f, st));
+  LR_RUN(lr_launch_rmsnorm_bwd(ws.dhn, ws.xg, h->base->final_norm, nullptr, ws.dx, m, d, c.rms_eps, loss_rows, nullptr,
+                               nullptr, 0, 0, 0.f, st));
 
   // ---- backward through the layers; ws.dx = gradient of the residual stream
   for (int l = c.num_layers - 1; l >= 0; --l) {
@@ -417,31 +405,31 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
     float *daq = g, *dbq = g + (size_t)r * d, *dav = dbq + (size_t)r * h->qcols, *dbv = dav + (size_t)r * d;
     const uint32_t stream = lr_lora_drop_stream(h->cfg.seed, h->pass, (uint32_t)l);
     // MLP: x_out = xmid + down(silu(gate) * up)
-    RUN(lr_launch_gemm(ws.dx, wt.wdown_t, ws.dh, nullptr, n, f, d, LR_EPI_STORE, gv, st));
-    RUN(lr_launch_swiglu_bwd(s.gu, ws.dh, n, f, st));
-    RUN(lr_launch_gemm(s.gu, wt.wgu_t, ws.dxn, nullptr, n, d, 2 * f, LR_EPI_STORE, gv, st));
-    RUN(lr_launch_rmsnorm_bwd(ws.dxn, s.xmid, w.post_norm, ws.dx, ws.dx, n, d, c.rms_eps, nullptr, nullptr, nullptr, 0,
-                              0, 0.f, st));
+    LR_RUN(lr_launch_gemm({.A = ws.dx, .B = wt.wdown_t, .C = ws.dh, .M = n, .N = f, .K = d, .variant = gv}, st));
+    LR_RUN(lr_launch_swiglu_bwd(s.gu, ws.dh, n, f, st));
+    LR_RUN(lr_launch_gemm({.A = s.gu, .B = wt.wgu_t, .C = ws.dxn, .M = n, .N = d, .K = 2 * f, .variant = gv}, st));
+    LR_RUN(lr_launch_rmsnorm_bwd(ws.dxn, s.xmid, w.post_norm, ws.dx, ws.dx, n, d, c.rms_eps, nullptr, nullptr, nullptr, 0,
+                                 0, 0.f, st));
     // attention block: xmid = x + o_proj(attention(q, k, v))
-    RUN(lr_launch_gemm(ws.dx, wt.wo_t, ws.datt, nullptr, n, nh * hd, d, LR_EPI_STORE, gv, st));
+    LR_RUN(lr_launch_gemm({.A = ws.dx, .B = wt.wo_t, .C = ws.datt, .M = n, .N = nh * hd, .K = d, .variant = gv}, st));
     // ... down to the gradient of the UNROTATED q, k, v (the inverse rotation rides in the attention passes)
-    RUN(lr_launch_attention_bwd(s.qkv, s.att, ws.datt, s.lse, ws.dqkv, ws.dsum, ws.dkv32, cu_seqlens, cu_seqlens_host, B,
-                                n, nh, nkv, hd, h->base->attn_variant, st, ws.tok_pos, ws.rope));
+    LR_RUN(lr_launch_attention_bwd(s.qkv, s.att, ws.datt, s.lse, ws.dqkv, ws.dsum, ws.dkv32, cu_seqlens, cu_seqlens_host, B,
+                                   n, nh, nkv, hd, h->base->attn_variant, st, ws.tok_pos, ws.rope));
     // adapters (side stream, next to the qkv data-gradient GEMM; both only read dqkv):
     // d B, d t = scaling * (d q B_q | d v B_v), d A
     hipStream_t sd;
-    RUN(fork_side(h, st, &sd));
-    RUN(lr_launch_lora_db(ws.dqkv, n, qw, h->qcols, h->kcols, hd, s.t, r, scaling, dbq, dbv, sd));
-    RUN(lr_launch_skinny(ws.dqkv, qw, n, h->qcols, bq_t, 1, ws.dt, 2 * LT_RP, 0, scaling, 0, 0.f, sd));
-    RUN(lr_launch_skinny(ws.dqkv + h->qcols + h->kcols, qw, n, h->vcols, bv_t, 1, ws.dt, 2 * LT_RP, LT_RP, scaling, 0,
-                         0.f, sd));
-    RUN(lr_launch_lora_da(s.xn, n, d, ws.dt, r, stream, drop_p, daq, dav, sd));
+    LR_RUN(fork_side(h, st, &sd));
+    LR_RUN(lr_launch_lora_db(ws.dqkv, n, qw, h->qcols, h->kcols, hd, s.t, r, scaling, dbq, dbv, sd));
+    LR_RUN(lr_launch_skinny(ws.dqkv, qw, n, h->qcols, bq_t, 1, ws.dt, 2 * LT_RP, 0, scaling, 0, 0.f, sd));
+    LR_RUN(lr_launch_skinny(ws.dqkv + h->qcols + h->kcols, qw, n, h->vcols, bv_t, 1, ws.dt, 2 * LT_RP, LT_RP, scaling, 0,
+                            0.f, sd));
+    LR_RUN(lr_launch_lora_da(s.xn, n, d, ws.dt, r, stream, drop_p, daq, dav, sd));
     if (l > 0)  // below layer 0 only the frozen embedding is left: its input gradient has no reader
-      RUN(lr_launch_gemm(ws.dqkv, wt.wqkv_t, ws.dxn, nullptr, n, d, qw, LR_EPI_STORE, gv, st));
-    RUN(join_side(h, st));
+      LR_RUN(lr_launch_gemm({.A = ws.dqkv, .B = wt.wqkv_t, .C = ws.dxn, .M = n, .N = d, .K = qw, .variant = gv}, st));
+    LR_RUN(join_side(h, st));
     if (l > 0)
-      RUN(lr_launch_rmsnorm_bwd(ws.dxn, s.x, w.input_norm, ws.dx, ws.dx, n, d, c.rms_eps, nullptr, ws.dt, a_cat, r,
-                                stream, drop_p, st));
+      LR_RUN(lr_launch_rmsnorm_bwd(ws.dxn, s.x, w.input_norm, ws.dx, ws.dx, n, d, c.rms_eps, nullptr, ws.dt, a_cat, r,
+                                   stream, drop_p, st));
   }
   return LR_OK;
 }
@@ -464,14 +452,14 @@ extern "C" int lr_llama_lora_prefill_verbalize(lr_llama_lora_t* h, const int32_t
     LR_FAIL(LR_EINVAL, "lr_llama_lora_prefill_verbalize: bad argument");
   hipStream_t st = (hipStream_t)hip_stream;
   const LrLlamaConfig& c = h->base->cfg;
-  int n, maxT, rc;
-  RUN(validate_batch(h, cu_seqlens_host, B, &n, &maxT));
+  int n, maxT;
+  LR_RUN(validate_batch(h, cu_seqlens_host, B, &n, &maxT));
   const LoraWs ws = carve(c, n, B, 0, 1, false, (char*)workspace);
   if (ws.total > workspace_bytes)
     LR_FAIL(LR_EWORKSPACE, "lr_llama_lora_prefill_verbalize: workspace needs %zu bytes for %d tokens, have %zu",
             ws.total, n, workspace_bytes);
-  RUN(prep_adapters(h, st));
-  RUN(forward(h, packed_ids, cu_seqlens, cu_seqlens_host, B, n, maxT, ws, false, 0.f, st));
+  LR_RUN(prep_adapters(h, st));
+  LR_RUN(forward(h, packed_ids, cu_seqlens, cu_seqlens_host, B, n, maxT, ws, false, 0.f, st));
   return lr_launch_head(ws.x_final, ws.last_rows, h->base->final_norm, h->base->lm_head, label_token_ids, B, C,
                         c.hidden_size, c.rms_eps, out_scores, c.vocab_size, st);
 }
@@ -487,8 +475,11 @@ extern "C" int lr_attention_varlen_lse(const uint16_t* qkv, uint16_t* out, float
   if (!qkv || !out || !lse || !cu_seqlens || !cu_seqlens_host || B < 1)
     LR_FAIL(LR_EINVAL, "lr_attention_varlen_lse: bad argument");
   if (int rc = lr_check_segments(cu_seqlens_host, B, "lr_attention_varlen_lse")) return rc;
-  return lr_launch_attention_lse(qkv, out, lse, cu_seqlens, cu_seqlens_host, B, cu_seqlens_host[B], num_heads,
-                                 num_kv_heads, head_dim, variant, (hipStream_t)hip_stream);
+  LrAttnKernel kernel;
+  if (int rc = lr_resolve_attention({.variant = variant, .hd = head_dim, .want_lse = true}, &kernel)) return rc;
+  return lr_launch_attention({.qkv = qkv, .out = out, .lse = lse, .cu = cu_seqlens, .cu_host = cu_seqlens_host, .S = B,
+                              .n_tok = cu_seqlens_host[B], .nh = num_heads, .nkv = num_kv_heads, .hd = head_dim},
+                             kernel, (hipStream_t)hip_stream);
 }
 
 extern "C" size_t lr_attention_bwd_scratch_bytes(int32_t total, int32_t num_heads, int32_t num_kv_heads,

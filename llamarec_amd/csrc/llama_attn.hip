@@ -537,20 +537,44 @@ int lr_launch_attention_rows(const u16* qkv, u16* out, const int32_t* cu, int B,
 }
 
 // =============================================================================================
-// cu / cu_host: segment starts [S + 1] in packed rows. prefix_len = P > 0: segment 0 is the shared prefix (P rows)
-// and segments 1.. continue it (see the kernel); only the MFMA kernel implements that.
-int lr_launch_attention(const u16* qkv, u16* out, const int32_t* cu, const int32_t* cu_host,
-                        const int32_t* tok_pos, const int32_t* tok_seq, int B, int n_tok, int nh, int nkv,
-                        int hd, int variant, void* scratch, hipStream_t st, int prefix_len) {
-  float* lse = (float*)scratch;  // optional [n_tok][nh] log-sum-exp output
-  (void)tok_pos;
-  (void)tok_seq;
+// the table in llama_kernels.h
+int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
+  const int hd = r.hd;
+  switch (r.variant) {
+    case 0:
+      if (hd == 128) *kernel = (r.have_items_ws && !r.prefill) ? LR_ATTN_ROWS256 : LR_ATTN_MFMA128;
+      else *kernel = (hd == 256 && r.prefill) ? LR_ATTN_HD256 : LR_ATTN_GENERIC;
+      return LR_OK;
+    case 1: *kernel = LR_ATTN_GENERIC; return LR_OK;
+    case 2: *kernel = LR_ATTN_MFMA128; return LR_OK;
+    case 3:
+      if (!r.have_items_ws)
+        LR_FAIL(LR_EINVAL, "attention variant 3 (256-row tiles) is not available here: it takes an item workspace "
+                "(lr_attention_varlen_ws, the prefill)");
+      if (hd != 128) LR_FAIL(LR_EUNSUPPORTED, "attention variant 3 needs head_dim 128 (got %d)", hd);
+      *kernel = r.prefix_len <= 64 ? LR_ATTN_ROWS256 : LR_ATTN_MFMA128;
+      return LR_OK;
+    case 4:
+      if (r.want_lse) LR_FAIL(LR_EINVAL, "attention variant 4 (head_dim-256 MFMA) writes no lse");
+      if (r.prefill && hd != 256) LR_FAIL(LR_EUNSUPPORTED, "attention variant 4 needs head_dim 256 (got %d)", hd);
+      *kernel = LR_ATTN_HD256;
+      return LR_OK;
+  }
+  LR_FAIL(LR_EINVAL, "attention: unknown variant %d (0 auto, 1 generic, 2 = head_dim-128 MFMA, 3 = 256-row tiles, "
+          "4 = head_dim-256 MFMA)", r.variant);
+}
+
+int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st) {
+  const int32_t* cu_host = a.cu_host;
+  const int B = a.S, n_tok = a.n_tok, nh = a.nh, nkv = a.nkv, hd = a.hd, prefix_len = a.prefix_len;
   if (n_tok <= 0 || B <= 0) return LR_OK;
+  if (kernel == LR_ATTN_ROWS256) return lr_launch_attention256(a, st);
   if (nh % nkv != 0) LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
-  if (variant == 0) variant = (hd == 128) ? 2 : 1;
-  if (variant == 4 && prefix_len == 0 && !scratch)   // head_dim 256 (llama_attn_hd256.hip): no prefix, no lse
-    return lr_launch_attention_hd256(qkv, out, cu, cu_host, B, n_tok, nh, nkv, hd, st);
-  if (prefix_len < 0 || (prefix_len > 0 && (variant != 2 || cu_host[1] - cu_host[0] != prefix_len)))
+  if (kernel == LR_ATTN_HD256) {
+    if (prefix_len != 0 || a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-256 MFMA kernel takes no shared prefix, writes no lse");
+    return lr_launch_attention_hd256(a, st);
+  }
+  if (prefix_len < 0 || (prefix_len > 0 && (kernel != LR_ATTN_MFMA128 || cu_host[1] - cu_host[0] != prefix_len)))
     LR_FAIL(LR_EINVAL, "attention: shared prefix of %d tokens needs the head_dim-128 MFMA kernel and segment 0 = the prefix",
             prefix_len);
   double work = 0;  // causal QK^T + PV flops of the rows each segment owns
@@ -561,8 +585,8 @@ int lr_launch_attention(const u16* qkv, u16* out, const int32_t* cu, const int32
     work += 4.0 * nh * hd * (T * (T + 1) / 2 - P * (P + 1) / 2);
     maxT = max(maxT, (int)T);
   }
-  LrProfScope prof(variant >= 2 ? LR_PROF_ATTN_MFMA : LR_PROF_ATTN_GENERIC, work, st);
-  if (variant == 2) {
+  LrProfScope prof(kernel == LR_ATTN_MFMA128 ? LR_PROF_ATTN_MFMA : LR_PROF_ATTN_GENERIC, work, st);
+  if (kernel == LR_ATTN_MFMA128) {
     if (hd != 128) LR_FAIL(LR_EUNSUPPORTED, "attention variant 2 needs head_dim 128 (got %d)", hd);
     const int mq = (maxT + FA_QROWS - 1) / FA_QROWS;
     if (mq == 0) return LR_OK;
@@ -584,22 +608,19 @@ int lr_launch_attention(const u16* qkv, u16* out, const int32_t* cu, const int32
       const int lds_bytes = (one_env && one_env[0] == '1') ? 104 * 1024 : 2 * FA_STAGE_BYTES;
       if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_mfma128_kernel<true>), 104 * 1024, lds_set_stamp))
         return rc;
-      hipLaunchKernelGGL(attn_mfma128_kernel<true>, dim3(grid), dim3(256), lds_bytes, st, qkv, out, cu,
-                         prefix_len, nh, nkv, mq, n_pairs, lse);
+      hipLaunchKernelGGL(attn_mfma128_kernel<true>, dim3(grid), dim3(256), lds_bytes, st, a.qkv, a.out, a.cu,
+                         prefix_len, nh, nkv, mq, n_pairs, a.lse);
     } else
 #endif
-      hipLaunchKernelGGL(attn_mfma128_kernel<false>, dim3(grid), dim3(256), 2 * FA_STAGE_BYTES, st, qkv, out, cu,
-                         prefix_len, nh, nkv, mq, n_pairs, lse);
+      hipLaunchKernelGGL(attn_mfma128_kernel<false>, dim3(grid), dim3(256), 2 * FA_STAGE_BYTES, st, a.qkv, a.out, a.cu,
+                         prefix_len, nh, nkv, mq, n_pairs, a.lse);
     LR_CHECK_LAUNCH("attn_mfma128_kernel");
-  } else if (variant == 1) {
+  } else {
     if (hd > 256) LR_FAIL(LR_EUNSUPPORTED, "attention: head_dim %d > 256", hd);
     const int items = n_tok * nh;
-    hipLaunchKernelGGL(attn_generic_kernel, dim3((items + 3) / 4), dim3(256), 0, st, qkv, out, cu, B,
-                       n_tok, nh, nkv, hd, (const int32_t*)nullptr, lse);
+    hipLaunchKernelGGL(attn_generic_kernel, dim3((items + 3) / 4), dim3(256), 0, st, a.qkv, a.out, a.cu, B,
+                       n_tok, nh, nkv, hd, (const int32_t*)nullptr, a.lse);
     LR_CHECK_LAUNCH("attn_generic_kernel");
-  } else {
-    LR_FAIL(LR_EINVAL, "attention: unknown variant %d here (0 auto, 1 generic, 2 = head_dim-128 MFMA, 4 = head_dim-256 MFMA "
-            "without shared prefix or lse; 3 needs a workspace: lr_attention_varlen_ws)", variant);
   }
   return LR_OK;
 }
@@ -629,11 +650,4 @@ int lr_launch_attention_last(const u16* kv, const u16* q_last, u16* out_last, co
                      cu, prefix_len, nh, nkv, 0, (int)n_pairs_ll, (float*)nullptr, q_last);
   LR_CHECK_LAUNCH("attn_mfma128_kernel<last>");
   return LR_OK;
-}
-
-// forward with the softmax statistics kept for llama_attn_bwd.hip (training): variant 0 auto, 1 generic, 2 MFMA
-int lr_launch_attention_lse(const u16* qkv, u16* out, float* lse, const int32_t* cu, const int32_t* cu_host, int B,
-                            int n_tok, int nh, int nkv, int hd, int variant, hipStream_t st) {
-  if (!lse) LR_FAIL(LR_EINVAL, "attention (training): null statistics buffer");
-  return lr_launch_attention(qkv, out, cu, cu_host, nullptr, nullptr, B, n_tok, nh, nkv, hd, variant, lse, st, 0);
 }

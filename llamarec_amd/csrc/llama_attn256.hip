@@ -649,9 +649,9 @@ __global__ __launch_bounds__(256) void attn_mfma256_kernel(const u16* __restrict
 }
 
 // =====================================================================================================================
-// cu / cu_host / prefix_len as lr_launch_attention; items_ws = lr_launch_attn256_items' output for the same cu.
-int lr_launch_attention256(const u16* qkv, u16* out, const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh,
-                           int nkv, int hd, float* lse, void* items_ws, hipStream_t st, int prefix_len) {
+int lr_launch_attention256(const LrAttnArgs& a, hipStream_t st) {
+  const int32_t* cu_host = a.cu_host;
+  const int S = a.S, n_tok = a.n_tok, nh = a.nh, nkv = a.nkv, hd = a.hd, prefix_len = a.prefix_len;
   if (n_tok <= 0 || S <= 0) return LR_OK;
   if (int rc = lr_check_segments(cu_host, S, "attention (256-row tiles)")) return rc;
   if (cu_host[S] != n_tok) LR_FAIL(LR_EINVAL, "attention (256-row tiles): segments cover %d rows, n_tok = %d", cu_host[S], n_tok);
@@ -660,7 +660,7 @@ int lr_launch_attention256(const u16* qkv, u16* out, const int32_t* cu, const in
     LR_FAIL(LR_EINVAL, "attention (256-row tiles): shared prefix of %d tokens (<= 64, = segment 0)", prefix_len);
   if ((long long)n_tok * (nh + 2 * nkv) * hd * 2 > 0x7fffffffLL)
     LR_FAIL(LR_EUNSUPPORTED, "attention (256-row tiles): packed qkv of %d tokens exceeds 2 GiB (32-bit byte offsets)", n_tok);
-  if (!items_ws) LR_FAIL(LR_EINVAL, "attention (256-row tiles): no item list");
+  if (!a.items_ws) LR_FAIL(LR_EINVAL, "attention (256-row tiles): no item list");
   double work = 0;
   for (int b = 0; b < S; ++b) {
     const double P = (prefix_len > 0 && b > 0) ? prefix_len : 0;
@@ -677,11 +677,11 @@ int lr_launch_attention256(const u16* qkv, u16* out, const int32_t* cu, const in
     LR_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     if (dev >= 0 && dev < LR_MAX_DEVICES) cu_count[dev] = cus;
   }
-  int32_t* ws = (int32_t*)items_ws;
+  int32_t* ws = (int32_t*)a.items_ws;
   static bool lds_set[LR_MAX_DEVICES] = {};
   if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_mfma256_kernel), A2_LDS_BYTES, lds_set)) return rc;
-  hipLaunchKernelGGL(attn_mfma256_kernel, dim3(cus), dim3(256), A2_LDS_BYTES, st, qkv, out, cu, prefix_len, nh, nkv,
-                     (const int32_t*)ws, ws + A2_HDR_INTS, lse, (unsigned)((size_t)n_tok * (nh + 2 * nkv) * hd * 2));
+  hipLaunchKernelGGL(attn_mfma256_kernel, dim3(cus), dim3(256), A2_LDS_BYTES, st, a.qkv, a.out, a.cu, prefix_len, nh,
+                     nkv, (const int32_t*)ws, ws + A2_HDR_INTS, a.lse, (unsigned)((size_t)n_tok * (nh + 2 * nkv) * hd * 2));
   LR_CHECK_LAUNCH("attn_mfma256_kernel");
   return LR_OK;
 }

@@ -307,7 +307,6 @@ static int launch_hd256(const u16* qkv, u16* out, const int32_t* cu, const int32
 }
 
 // cu / cu_host: prompt starts [B + 1] in packed rows (no shared prefix at head_dim 256)
-int lr_launch_attention_hd256(const u16* qkv, u16* out, const int32_t* cu, const int32_t* cu_host, int B, int n_tok, int nh,
-                              int nkv, int hd, hipStream_t st) {
-  return launch_hd256<1>(qkv, out, cu, cu_host, B, n_tok, nh, nkv, hd, st);
+int lr_launch_attention_hd256(const LrAttnArgs& a, hipStream_t st) {
+  return launch_hd256<1>(a.qkv, a.out, a.cu, a.cu_host, a.S, a.n_tok, a.nh, a.nkv, a.hd, st);
 }

@@ -732,21 +732,22 @@ static int gemm256_prepare() {
 }
 
 template <int EPI>
-static int launch_splitk(const u16* A, const u16* B, u16* C, const u16* R, int M, int N, int K, int S, RopeArgs rope,
-                         float* ws, hipStream_t st, const u16* then_norm_w = nullptr, u16* then_norm_out = nullptr,
-                         float then_norm_eps = 0.f, bool* then_norm_done = nullptr, int then_norm_style = 0) {
+static int launch_splitk(const LrGemmArgs& g, int S, RopeArgs rope, hipStream_t st) {
+  const int M = g.M, N = g.N, K = g.K;
+  float* ws = g.splitk.ws;
+  const LrGemmThenNorm& tn = g.then_norm;
   LrProfScope prof(LR_PROF_GEMM256, 2.0 * M * (double)N * K, st, LR_PROF_GEMM_TAG(EPI, N, K));
   if (int rc = gemm256_prepare<LR_EPI_PARTIAL>()) return rc;
   const int nwg = ((M + 255) / 256) * (N / 256);
-  hipLaunchKernelGGL(gemm256rb_kernel<LR_EPI_PARTIAL>, dim3(nwg, S), dim3(512), 2 * G2_STAGE_BYTES, st, A, B,
+  hipLaunchKernelGGL(gemm256rb_kernel<LR_EPI_PARTIAL>, dim3(nwg, S), dim3(512), 2 * G2_STAGE_BYTES, st, g.A, g.B,
                      reinterpret_cast<u16*>(ws), nullptr, M, N, K, gemm256_group_m(K), rope);
   LR_CHECK_LAUNCH("gemm256rb_kernel<partial>");
-  if (EPI == LR_EPI_RESIDUAL && then_norm_w && then_norm_out && then_norm_done && lr_reduce_residual_rmsnorm_fits(N)) {
-    *then_norm_done = true;   // the reduce pass also writes RMSNorm(C) for the next projection
-    return lr_launch_reduce_residual_rmsnorm(ws, S, C, R, M, N, then_norm_w, then_norm_out, then_norm_eps, st, then_norm_style);
+  if (EPI == LR_EPI_RESIDUAL && tn.w && tn.out && tn.done && lr_reduce_residual_rmsnorm_fits(N)) {
+    *tn.done = true;   // the reduce pass also writes RMSNorm(C) for the next projection
+    return lr_launch_reduce_residual_rmsnorm(ws, S, g.C, g.R, M, N, tn.w, tn.out, tn.eps, st, tn.style);
   }
   const size_t quads = (LR_EPI_IS_GATED(EPI) ? (size_t)M * (N >> 1) : (size_t)M * N) / 4;
-  hipLaunchKernelGGL(splitk_reduce_kernel<EPI>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, ws, S, C, R, M,
+  hipLaunchKernelGGL(splitk_reduce_kernel<EPI>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, ws, S, g.C, g.R, M,
                      N, rope);
   LR_CHECK_LAUNCH("splitk_reduce_kernel");
   return LR_OK;
@@ -754,8 +755,8 @@ static int launch_splitk(const u16* A, const u16* B, u16* C, const u16* R, int M
 
 // =============================================================================================
 template <int EPI>
-static int launch_epi(const u16* A, const u16* B, u16* C, const u16* R, int M, int N, int K, int variant,
-                      RopeArgs rope, hipStream_t st) {
+static int launch_epi(const LrGemmArgs& g, int variant, RopeArgs rope, hipStream_t st) {
+  const int M = g.M, N = g.N, K = g.K;
   LrProfScope prof(variant >= 2 ? LR_PROF_GEMM256 : LR_PROF_GEMM_GENERIC, 2.0 * M * (double)N * K, st,
                    LR_PROF_GEMM_TAG(EPI, N, K));
   if (variant == 4) {
@@ -764,7 +765,7 @@ static int launch_epi(const u16* A, const u16* B, u16* C, const u16* R, int M, i
     if constexpr (EPI == LR_EPI_ROPE || EPI == LR_EPI_SWIGLU) {
       if (rope.row_scale) {  // folded RMSNorm: the instantiation that scales its accumulator rows
         if (int rc = gemm256_prepare<EPI, true>()) return rc;
-        hipLaunchKernelGGL((gemm256rb_kernel<EPI, true>), dim3(nwg), dim3(512), 2 * G2_STAGE_BYTES + 1024, st, A, B, C, R, M, N, K,
+        hipLaunchKernelGGL((gemm256rb_kernel<EPI, true>), dim3(nwg), dim3(512), 2 * G2_STAGE_BYTES + 1024, st, g.A, g.B, g.C, g.R, M, N, K,
                            gemm256_group_m(K), rope);
         launched = true;
       }
@@ -777,7 +778,7 @@ static int launch_epi(const u16* A, const u16* B, u16* C, const u16* R, int M, i
         if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(gemm256rb_kernel<EPI, false, true>),
                                            2 * G2_STAGE_BYTES, done))
           return rc;
-        hipLaunchKernelGGL((gemm256rb_kernel<EPI, false, true>), dim3(nwg), dim3(512), 2 * G2_STAGE_BYTES, st, A, B, C, R, M, N,
+        hipLaunchKernelGGL((gemm256rb_kernel<EPI, false, true>), dim3(nwg), dim3(512), 2 * G2_STAGE_BYTES, st, g.A, g.B, g.C, g.R, M, N,
                            K, gemm256_group_m(K), rope);
         launched = true;
       }
@@ -785,13 +786,13 @@ static int launch_epi(const u16* A, const u16* B, u16* C, const u16* R, int M, i
 #endif
     if (!launched) {
       if (int rc = gemm256_prepare<EPI>()) return rc;
-      hipLaunchKernelGGL(gemm256rb_kernel<EPI>, dim3(nwg), dim3(512), 2 * G2_STAGE_BYTES, st, A, B, C, R, M, N, K,
+      hipLaunchKernelGGL(gemm256rb_kernel<EPI>, dim3(nwg), dim3(512), 2 * G2_STAGE_BYTES, st, g.A, g.B, g.C, g.R, M, N, K,
                          gemm256_group_m(K), rope);
     }
     LR_CHECK_LAUNCH("gemm256rb_kernel");
   } else {
     dim3 grid((N + GG_BN - 1) / GG_BN, (M + GG_BM - 1) / GG_BM);
-    hipLaunchKernelGGL(gemm_generic_kernel<EPI>, grid, dim3(256), 0, st, A, B, C, R, M, N, K, rope);
+    hipLaunchKernelGGL(gemm_generic_kernel<EPI>, grid, dim3(256), 0, st, g.A, g.B, g.C, g.R, M, N, K, rope);
     LR_CHECK_LAUNCH("gemm_generic_kernel");
   }
   return LR_OK;
@@ -806,12 +807,10 @@ extern "C" int lr_debug_gemm_stamps(unsigned long long* out, int n_workgroups) {
 }
 #endif
 
-int lr_launch_gemm(const u16* A, const u16* B, u16* C, const u16* R, int M, int N, int K, int epi,
-                   int variant, hipStream_t st, const int32_t* tok_pos, const float* rope_cs, int head_dim,
-                   int rot_cols, float* splitk_ws, size_t splitk_ws_bytes, const float* row_scale,
-                   const unsigned* rope_cs16, const u16* then_norm_w, u16* then_norm_out, float then_norm_eps,
-                   bool* then_norm_done, int then_norm_style) {
-  if (then_norm_done) *then_norm_done = false;
+int lr_launch_gemm(const LrGemmArgs& g, hipStream_t st) {
+  const int M = g.M, N = g.N, K = g.K, epi = g.epi;
+  int variant = g.variant;
+  if (g.then_norm.done) *g.then_norm.done = false;
   if (M <= 0) return LR_OK;
   if (N <= 0 || K <= 0) LR_FAIL(LR_EINVAL, "gemm: N=%d K=%d", N, K);
   const bool fast_ok = (N % 256 == 0) && (K % 64 == 0) && M >= 1;
@@ -822,39 +821,37 @@ int lr_launch_gemm(const u16* A, const u16* B, u16* C, const u16* R, int M, int 
   if (variant == 4 && !fast_ok)
     LR_FAIL(LR_EUNSUPPORTED, "gemm variant 4 needs N%%256==0 and K%%64==0 (N=%d K=%d)", N, K);
   if (LR_EPI_IS_GATED(epi) && (N % 32 != 0)) LR_FAIL(LR_EINVAL, "gated-MLP epilogue needs N%%32==0 (N=%d)", N);
-  if (epi == LR_EPI_RESIDUAL && !R) LR_FAIL(LR_EINVAL, "residual epilogue without residual pointer");
-  RopeArgs rope{tok_pos, rope_cs, head_dim, rot_cols, row_scale, rope_cs16};
-  if (row_scale && epi != LR_EPI_ROPE && epi != LR_EPI_SWIGLU)
+  if (epi == LR_EPI_RESIDUAL && !g.R) LR_FAIL(LR_EINVAL, "residual epilogue without residual pointer");
+  const RopeArgs rope{g.rope.tok_pos, g.rope.cs, g.rope.head_dim, g.rope.rot_cols, g.row_scale, g.rope.cs16};
+  if (g.row_scale && epi != LR_EPI_ROPE && epi != LR_EPI_SWIGLU)
     LR_FAIL(LR_EINVAL, "gemm: a row scale (folded RMSNorm) is only applied by the rope and swiglu epilogues");
   if (epi == LR_EPI_ROPE) {
-    if (!tok_pos || !rope_cs || head_dim < 2 || head_dim % 4 != 0 || rot_cols % 4 != 0 || rot_cols > N)
-      LR_FAIL(LR_EINVAL, "rope epilogue: bad arguments (head_dim=%d rot_cols=%d)", head_dim, rot_cols);
+    if (!rope.tok_pos || !rope.cs || rope.head_dim < 2 || rope.head_dim % 4 != 0 || rope.rot_cols % 4 != 0 || rope.rot_cols > N)
+      LR_FAIL(LR_EINVAL, "rope epilogue: bad arguments (head_dim=%d rot_cols=%d)", rope.head_dim, rope.rot_cols);
   }
   if (variant == 5) {
     const int S = splitk_factor(M, N, K);
     if (S >= 2) {
-      if (!splitk_ws || (size_t)S * M * N * sizeof(float) > splitk_ws_bytes)
+      if (!g.splitk.ws || (size_t)S * M * N * sizeof(float) > g.splitk.bytes)
         LR_FAIL(LR_EWORKSPACE, "gemm variant 5: split-K x%d of %dx%d needs %zu workspace bytes, have %zu", S, M, N,
-                (size_t)S * M * N * sizeof(float), splitk_ws ? splitk_ws_bytes : (size_t)0);
+                (size_t)S * M * N * sizeof(float), g.splitk.ws ? g.splitk.bytes : (size_t)0);
       switch (epi) {
-        case LR_EPI_STORE: return launch_splitk<LR_EPI_STORE>(A, B, C, R, M, N, K, S, rope, splitk_ws, st);
-        case LR_EPI_RESIDUAL:
-          return launch_splitk<LR_EPI_RESIDUAL>(A, B, C, R, M, N, K, S, rope, splitk_ws, st, then_norm_w, then_norm_out,
-                                                then_norm_eps, then_norm_done, then_norm_style);
-        case LR_EPI_SWIGLU: return launch_splitk<LR_EPI_SWIGLU>(A, B, C, R, M, N, K, S, rope, splitk_ws, st);
-        case LR_EPI_GEGLU: return launch_splitk<LR_EPI_GEGLU>(A, B, C, R, M, N, K, S, rope, splitk_ws, st);
-        case LR_EPI_ROPE: return launch_splitk<LR_EPI_ROPE>(A, B, C, R, M, N, K, S, rope, splitk_ws, st);
+        case LR_EPI_STORE: return launch_splitk<LR_EPI_STORE>(g, S, rope, st);
+        case LR_EPI_RESIDUAL: return launch_splitk<LR_EPI_RESIDUAL>(g, S, rope, st);
+        case LR_EPI_SWIGLU: return launch_splitk<LR_EPI_SWIGLU>(g, S, rope, st);
+        case LR_EPI_GEGLU: return launch_splitk<LR_EPI_GEGLU>(g, S, rope, st);
+        case LR_EPI_ROPE: return launch_splitk<LR_EPI_ROPE>(g, S, rope, st);
       }
       LR_FAIL(LR_EINVAL, "gemm: unknown epilogue %d", epi);
     }
     variant = 4;
   }
   switch (epi) {
-    case LR_EPI_STORE: return launch_epi<LR_EPI_STORE>(A, B, C, R, M, N, K, variant, rope, st);
-    case LR_EPI_RESIDUAL: return launch_epi<LR_EPI_RESIDUAL>(A, B, C, R, M, N, K, variant, rope, st);
-    case LR_EPI_SWIGLU: return launch_epi<LR_EPI_SWIGLU>(A, B, C, R, M, N, K, variant, rope, st);
-    case LR_EPI_GEGLU: return launch_epi<LR_EPI_GEGLU>(A, B, C, R, M, N, K, variant, rope, st);
-    case LR_EPI_ROPE: return launch_epi<LR_EPI_ROPE>(A, B, C, R, M, N, K, variant, rope, st);
+    case LR_EPI_STORE: return launch_epi<LR_EPI_STORE>(g, variant, rope, st);
+    case LR_EPI_RESIDUAL: return launch_epi<LR_EPI_RESIDUAL>(g, variant, rope, st);
+    case LR_EPI_SWIGLU: return launch_epi<LR_EPI_SWIGLU>(g, variant, rope, st);
+    case LR_EPI_GEGLU: return launch_epi<LR_EPI_GEGLU>(g, variant, rope, st);
+    case LR_EPI_ROPE: return launch_epi<LR_EPI_ROPE>(g, variant, rope, st);
   }
   LR_FAIL(LR_EINVAL, "gemm: unknown epilogue %d", epi);
 }

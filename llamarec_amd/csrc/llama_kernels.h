@@ -72,21 +72,39 @@ int lr_launch_head(const unsigned short* x, const int32_t* rows /*[B]; nullptr: 
                    const int32_t* poison = nullptr /* device word: non-zero -> every score of the call is NaN */,
                    int norm_style = 0);
 
-// C[M][N] (+epilogue) = A[M][K] * B[N][K]^T. variant: 0 auto, 1 generic, 4 = 256x256x64 MFMA tile,
-// 5 = variant 4 with split-K when the tiles alone would leave most CUs idle (needs splitk_ws).
-int lr_launch_gemm(const unsigned short* A, const unsigned short* B, unsigned short* C,
-                   const unsigned short* R, int M, int N, int K, int epi, int variant, hipStream_t st,
-                   const int32_t* tok_pos = nullptr, const float* rope_cs = nullptr, int head_dim = 0,
-                   int rot_cols = 0, float* splitk_ws = nullptr, size_t splitk_ws_bytes = 0,
-                   const float* row_scale = nullptr /* rope / swiglu epilogues: accumulator row m times row_scale[m] */,
-                   const unsigned* rope_cs16 = nullptr /* the rope table as packed bf16 pairs (lr_launch_rope_table): lets
-                   the 256-tile kernel stage a tile's (cos, sin) rows through LDS instead of 262 KB of half-line loads */,
-                   const unsigned short* then_norm_w = nullptr, unsigned short* then_norm_out = nullptr,
-                   float then_norm_eps = 0.f, bool* then_norm_done = nullptr /* residual epilogue only: the caller runs
-                   RMSNorm(C) with this weight into then_norm_out next. If the product is split over K, its reduce pass
-                   does that too (same bits) and *then_norm_done is set; otherwise it is left false and the caller launches
-                   lr_launch_rmsnorm itself */,
-                   int then_norm_style = 0);
+// C[M][N] (+epilogue) = A[M][K] * B[N][K]^T. Call sites name what they pass (designated initialisers); a member left
+// out is absent. variant: 0 auto, 1 generic, 4 = 256x256x64 MFMA tile, 5 = variant 4 with split-K when the tiles alone
+// would leave most CUs idle (needs splitk).
+struct LrGemmRope {                 // LR_EPI_ROPE only
+  const int32_t* tok_pos = nullptr; // [M] position of each row inside its prompt
+  const float* cs = nullptr;        // lr_launch_rope_table's fp32 table
+  const unsigned* cs16 = nullptr;   // the same table as packed bf16 pairs (optional): lets the 256-tile kernel stage a tile's
+                                    // (cos, sin) rows through LDS instead of 262 KB of half-line loads
+  int head_dim = 0, rot_cols = 0;   // columns [0, rot_cols) are q and k heads
+};
+struct LrGemmSplitK { float* ws = nullptr; size_t bytes = 0; };  // fp32 partial planes for variant 5
+// Residual epilogue only: the caller runs RMSNorm(C) with weight w into out next. If the product is split over K, its
+// reduce pass does that too (same bits) and *done is set; otherwise *done is left false and the caller launches
+// lr_launch_rmsnorm itself.
+struct LrGemmThenNorm {
+  const unsigned short* w = nullptr;
+  unsigned short* out = nullptr;
+  float eps = 0.f;
+  int style = 0;
+  bool* done = nullptr;
+};
+struct LrGemmArgs {
+  const unsigned short *A, *B;
+  unsigned short* C;
+  const unsigned short* R = nullptr;  // residual epilogue: the rows added (may alias C)
+  int M, N, K;
+  int epi = LR_EPI_STORE, variant = 0;
+  LrGemmRope rope;
+  const float* row_scale = nullptr;  // rope / swiglu epilogues: accumulator row m times row_scale[m] (folded RMSNorm)
+  LrGemmSplitK splitk;
+  LrGemmThenNorm then_norm;
+};
+int lr_launch_gemm(const LrGemmArgs& g, hipStream_t st);
 // split-K reduce (S fp32 planes of M x N) + residual + RMSNorm of the result in one pass (llama_elem.hip)
 bool lr_reduce_residual_rmsnorm_fits(int N);
 int lr_launch_reduce_residual_rmsnorm(const float* part, int S, unsigned short* C, const unsigned short* R, int M, int N,
@@ -98,41 +116,94 @@ int lr_launch_rms_rstd(const unsigned short* x, float* rstd, int rows, int d, fl
 int lr_launch_fold_norm(const unsigned short* w, const unsigned short* norm_w, unsigned short* out, size_t rows, int cols,
                         hipStream_t st);
 
-// The segment rule of every attention entry point (include/llamarec_mi355x.h, cu_seqlens_host): cu_host[0] == 0 and
-// cu_host strictly increasing -- every segment holds at least one row. The kernels derive work items, tile counts and
-// buffer offsets from segment lengths, so an empty or negative segment must be refused here, before any launch.
-static inline int lr_check_segments(const int32_t* cu_host, int S, const char* who) {
+// The segment rule of every attention entry point and prompt batch (include/llamarec_mi355x.h, cu_seqlens_host):
+// cu_host[0] == 0 and cu_host strictly increasing -- every segment holds at least one row. The kernels derive work items,
+// tile counts and buffer offsets from segment lengths, so an empty or negative segment must be refused here, before any
+// launch. shortest / longest (optional) receive the extreme segment lengths.
+static inline int lr_check_segments(const int32_t* cu_host, int S, const char* who, int* shortest = nullptr,
+                                    int* longest = nullptr) {
   if (!cu_host || S < 1) LR_FAIL(LR_EINVAL, "%s: %d segments", who, S);
   if (cu_host[0] != 0) LR_FAIL(LR_EINVAL, "%s: cu_seqlens[0] = %d (must be 0)", who, cu_host[0]);
-  for (int b = 0; b < S; ++b)
-    if (cu_host[b + 1] <= cu_host[b])
-      LR_FAIL(LR_EINVAL, "%s: segment %d is empty or negative (cu_seqlens %d -> %d)", who, b, cu_host[b], cu_host[b + 1]);
+  int lo = 0x7fffffff, hi = 0;
+  for (int b = 0; b < S; ++b) {
+    const int t = cu_host[b + 1] - cu_host[b];
+    if (t < 1) LR_FAIL(LR_EINVAL, "%s: segment %d is empty or negative (cu_seqlens %d -> %d)", who, b, cu_host[b], cu_host[b + 1]);
+    lo = t < lo ? t : lo;
+    hi = t > hi ? t : hi;
+  }
+  if (shortest) *shortest = lo;
+  if (longest) *longest = hi;
   return LR_OK;
 }
 
-// attention variant 4 (llama_attn_hd256.hip): head_dim-256 MFMA flash attention, cu / cu_host = prompt starts, no prefix
-int lr_launch_attention_hd256(const unsigned short* qkv, unsigned short* out, const int32_t* cu, const int32_t* cu_host, int B,
-                              int n_tok, int nh, int nkv, int hd, hipStream_t st);
-// varlen causal attention over packed qkv (RoPE applied). variant: 0 auto, 1 generic, 2 MFMA hd=128, 4 MFMA hd=256.
-// cu / cu_host = segment starts; prefix_len > 0: segment 0 is the prefix the other segments continue (MFMA kernel only)
+// ---- varlen causal attention over packed qkv (RoPE applied) ----------------------------------------------------------------
+// The kernels (a requested variant 1 .. 4 asks for the kernel of the same number, 0 = auto):
+//   GENERIC  any head_dim <= 256, scalar                                  (llama_attn.hip)
+//   MFMA128  head_dim 128, 128-row query tiles, reads a shared prefix     (llama_attn.hip)
+//   ROWS256  head_dim 128, 256-row query tiles over a device-built item list, shared prefix <= 64 (llama_attn256.hip)
+//   HD256    head_dim 256, no shared prefix, no lse                       (llama_attn_hd256.hip)
+enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 3, LR_ATTN_HD256 = 4 };
+
+// Which kernel a request runs on -- the one place that decides it, for the four routes
+//   prefill    run_body (api_llama.hip): lse never wanted, the handle's workspace always has room for an item list
+//   varlen     lr_attention_varlen: no lse, no workspace
+//   varlen_ws  lr_attention_varlen_ws: lse and workspace optional
+//   train      lr_attention_varlen_lse and the LoRA forward: lse wanted, no workspace
+// prefix_len is 0 outside prefill. Prefill drops a shared prefix (runs every prompt whole) unless lr_attention_reads_prefix:
+// head_dim != 128 or variant 1 -- and with a single prompt. First matching row:
+//
+//   variant  head_dim  prefix  lse  item ws  route        result
+//   0        128       0       any  yes      varlen_ws    ROWS256
+//   0        128       any     any  any      any          MFMA128  (prefill has the item workspace and still takes this one: on
+//                                                                   its prompts of 460 .. 1 125 tokens two 128-row workgroups
+//                                                                   per CU are ahead of the 256-row kernel)
+//   0        256       0       no   yes      prefill      HD256
+//   0        any       0       any  any      any          GENERIC  (head_dim 256 too outside prefill: the entry points' auto
+//                                                                   is older than HD256 and its results are kept)
+//   1        any       0       any  any      any          GENERIC
+//   2        any       any     any  any      any          MFMA128
+//   3        any       0       any  no       varlen, train  LR_EINVAL  (no item workspace exists on these routes)
+//   3        != 128    any     any  yes      any          LR_EUNSUPPORTED
+//   3        128       <= 64   any  yes      any          ROWS256
+//   3        128       > 64    no   yes      prefill      MFMA128  (only a 256-row tile's block 0 may hold shared-prefix keys)
+//   4        any       any     yes  any      any          LR_EINVAL  (HD256 writes no statistics)
+//   4        != 256    any     no   yes      prefill      LR_EUNSUPPORTED
+//   4        any       0       no   any      any          HD256    (outside prefill a head_dim other than 256 is refused by
+//                                                                   the launcher, LR_EUNSUPPORTED, behind its
+//                                                                   num_heads % num_kv_heads check, LR_EINVAL, as before)
+//   other                                                 LR_EINVAL
+//
+// varlen_ws counts a variant-3 request as "item ws yes" whatever it was given: the item-list builder then reports a missing
+// or short workspace as LR_EWORKSPACE. lr_launch_attention still refuses what the resolved kernel cannot take: GENERIC above
+// head_dim 256 and MFMA128 off head_dim 128 (LR_EUNSUPPORTED; a one-layer pruned prefill launches neither, so these checks
+// cannot move up here), a shared prefix or lse on HD256.
+static inline bool lr_attention_reads_prefix(int variant, int hd) { return hd == 128 && variant != 1; }
+struct LrAttnRequest { int variant, hd, prefix_len = 0; bool want_lse = false, have_items_ws = false, prefill = false; };
+int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel);
+
+// cu / cu_host = segment starts [S + 1] in packed rows; prefix_len = P > 0: segment 0 is the shared prefix (P rows) the
+// other segments continue. lse (optional) = [n_tok][nh] log-sum-exp output; items_ws = lr_launch_attn256_items' output for
+// the same (cu, S, nh, prefix_len), read by ROWS256 only.
+struct LrAttnArgs {
+  const unsigned short* qkv;
+  unsigned short* out;
+  float* lse = nullptr;
+  const int32_t *cu, *cu_host;
+  int S, n_tok, nh, nkv, hd, prefix_len = 0;
+  void* items_ws = nullptr;
+};
+int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st);
+// The pruned last layer (MFMA128's body): one query row per (prompt, head) over the prompt's keys
 int lr_launch_attention_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
                              const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int hd,
                              hipStream_t st, int prefix_len);
-int lr_launch_attention(const unsigned short* qkv, unsigned short* out, const int32_t* cu,
-                        const int32_t* cu_host, const int32_t* tok_pos, const int32_t* tok_seq, int B,
-                        int n_tok, int nh, int nkv, int hd, int variant, void* scratch, hipStream_t st,
-                        int prefix_len = 0);
-
-// attention variant 3 (llama_attn256.hip): 256-row query tiles, one wave per SIMD, persistent workgroups over a
-// device-built item list. lr_launch_attn256_items builds the list for (cu, S, nh, prefix_len) into items_ws
-// (lr_attn256_ws_bytes); any number of lr_launch_attention256 calls over the same segments may follow (one per layer).
-// prefix_len must be <= 64 (lr_attention256_takes): only a tile's block 0 may hold shared-prefix keys.
+// ROWS256's item list for (cu, S, nh, prefix_len) into items_ws (lr_attn256_ws_bytes), built once per call; any number of
+// lr_launch_attention calls over the same segments may follow (one per layer)
 size_t lr_attn256_ws_bytes(int n_tok, int S, int nh);
-static inline bool lr_attention256_takes(int hd, int prefix_len) { return hd == 128 && prefix_len <= 64; }
 int lr_launch_attn256_items(const int32_t* cu, int S, int n_tok, int nh, int prefix_len, void* items_ws, size_t ws_bytes,
                             hipStream_t st);
-int lr_launch_attention256(const unsigned short* qkv, unsigned short* out, const int32_t* cu, const int32_t* cu_host, int S,
-                           int n_tok, int nh, int nkv, int hd, float* lse /* optional [n_tok][nh] */, void* items_ws,
-                           hipStream_t st, int prefix_len);
+// the per-file launchers behind lr_launch_attention
+int lr_launch_attention256(const LrAttnArgs& a, hipStream_t st);
+int lr_launch_attention_hd256(const LrAttnArgs& a, hipStream_t st);
 
 #endif

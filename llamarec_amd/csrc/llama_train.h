@@ -38,10 +38,7 @@ int lr_launch_lora_adamw(float* p, float* g, float* m, float* v, size_t n, float
                          hipStream_t st);
 uint32_t lr_lora_drop_stream(uint64_t seed, uint32_t pass, uint32_t layer);
 
-// attention with the softmax statistics kept (lse[n][nh], natural log) and its backward (llama_attn_bwd.hip)
-int lr_launch_attention_lse(const unsigned short* qkv, unsigned short* out, float* lse, const int32_t* cu,
-                            const int32_t* cu_host, int B, int n_tok, int nh, int nkv, int hd, int variant,
-                            hipStream_t st);
+// backward of lr_launch_attention with the softmax statistics kept (lse[n][nh], natural log; llama_attn_bwd.hip).
 // dqkv [n][(nh+2nkv)*hd], fully written: the gradient w.r.t. the rotated q, k and v -- or, when rope_cs / tok_pos are
 // given, w.r.t. the UNROTATED ones (the inverse rotation is pair-local in the packed layout and rides in the MFMA
 // passes' epilogues). dsum: [n][nh] fp32 scratch, dkv32: [n][2*nkv*hd] fp32 scratch (generic path only).

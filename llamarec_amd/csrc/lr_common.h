@@ -27,6 +27,8 @@ void lr_set_error(const char* fmt, ...);
     if (e_ != hipSuccess) LR_FAIL(LR_EHIP, "launch %s: %s", name, hipGetErrorString(e_)); \
   } while (0)
 
+#define LR_RUN(call) do { if (int rc_ = (call)) return rc_; } while (0)  // pass a launcher's error code up
+
 static inline size_t lr_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: a launcher keeps one `done`

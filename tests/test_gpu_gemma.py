@@ -226,6 +226,30 @@ def test_gemma_handle_refuses_lora_and_folded_norms(golden_dir):
     assert np.abs(model.last_logits(seqs).cpu().numpy() - z["logits_bf16"]).max() < 3e-2
 
 
+def test_geglu_handle_with_llama_norm_refuses_folded_norms():
+    """Arch (norm_style 0, mlp_act 1): no preset builds it, but the C ABI accepts it. A folded gate-up product needs a
+    row scale, which the GeGLU epilogue does not take, so the handle must refuse folded matrices (it used to run SwiGLU)."""
+    from llamarec_amd import _abi as A
+    from llamarec_amd._lib import lib
+
+    w = torch.zeros(64 * 64, dtype=torch.int16, device="cuda")
+    cfg = A.LrLlamaConfig(vocab_size=64, hidden_size=64, intermediate_size=64, num_layers=1, num_heads=1, num_kv_heads=1,
+                          head_dim=64, max_positions=16, rms_eps=1e-6, rope_theta=10000.0)
+    layers = (A.LrLlamaLayerWeights * 1)()
+    for field in ("input_norm", "wqkv", "wo", "post_norm", "wgu", "wdown"):
+        setattr(layers[0], field, w.data_ptr())
+    desc = A.LrLlamaWeightsDesc(embed=w.data_ptr(), final_norm=w.data_ptr(), lm_head=w.data_ptr(), layers=layers)
+    arch = A.LrLlamaArch(norm_style=0, mlp_act=1, embed_scale=1.0)
+    h = C.c_void_p()
+    assert lib().lr_llama_create_ex(C.byref(cfg), C.byref(arch), C.byref(desc), C.byref(h)) == 0
+    try:
+        arr = (C.c_void_p * 1)(w.data_ptr())
+        assert lib().lr_llama_set_folded_norms(h, arr, arr) == -2 and b"GeGLU" in lib().lr_last_error()
+        assert lib().lr_llama_set_folded_norms(h, None, None) == 0
+    finally:
+        lib().lr_llama_destroy(h)
+
+
 @pytest.mark.parametrize("which,lens", [("2b", [460, 1125, 700, 5]), ("7b", [600, 1000])])
 def test_full_width_gemma_fast_vs_generic_and_restatement(which, lens):
     """Gemma-2B (8 x 256 MQA heads on 2048) and Gemma-7B (16 x 256 on 3072: nh * hd != hidden) layer shapes, 2 layers,
