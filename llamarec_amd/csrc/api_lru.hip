@@ -144,6 +144,14 @@ extern "C" int lr_lru_set_encoder_pipeline(lr_lru_t* h, int32_t enable) {
 
 static size_t q_bytes(int B) { return lr_align_up((size_t)B * 64 * sizeof(float), 256); }
 
+// A caller's workspace is [q [B][64] | rest]: the encoder's scratch, then the top-K's (never live together).
+struct QSplit { float* q; char* rest; size_t rest_bytes; };
+static int split_q(const char* fn, const void* workspace, size_t workspace_bytes, int B, QSplit* s) {
+  if (workspace_bytes < q_bytes(B)) LR_FAIL(LR_EWORKSPACE, "%s: workspace too small", fn);
+  *s = {(float*)workspace, (char*)workspace + q_bytes(B), workspace_bytes - q_bytes(B)};
+  return LR_OK;
+}
+
 // Encoder dispatch: the batched MFMA encoder when the caller's workspace has room for it (what
 // lr_lru_workspace_bytes asks for), else the one-workgroup-per-user kernel (no workspace); LR_ENCODER=1 forces
 // the latter for A/B runs. Both produce the same bits.
@@ -193,23 +201,20 @@ extern "C" int lr_lru_retrieve_topk(lr_lru_t* h, const int64_t* ids, int32_t B, 
   if (rc) return rc;
   if (!out_idx || !workspace) LR_FAIL(LR_EINVAL, "lr_lru_retrieve_topk: null output/workspace");
   if (K < 1 || K > LR_MAX_TOPK) LR_FAIL(LR_EINVAL, "lr_lru_retrieve_topk: K=%d outside 1..%d", K, LR_MAX_TOPK);
-  if (workspace_bytes < q_bytes(B)) LR_FAIL(LR_EWORKSPACE, "lr_lru_retrieve_topk: workspace too small");
-  float* q = (float*)workspace;
+  QSplit w;
+  LR_RUN(split_q("lr_lru_retrieve_topk", workspace, workspace_bytes, B, &w));
   hipStream_t st = (hipStream_t)hip_stream;
-  rc = encode(h, ids, B, L, q, (char*)workspace + q_bytes(B), workspace_bytes - q_bytes(B), st);
-  if (rc) return rc;
-  return lr_launch_item_topk(h, q, ids, B, L, K, exclude_history, out_idx, out_score,
-                             (char*)workspace + q_bytes(B), workspace_bytes - q_bytes(B), st);
+  LR_RUN(encode(h, ids, B, L, w.q, w.rest, w.rest_bytes, st));
+  return lr_launch_item_topk(h, w.q, ids, B, L, K, exclude_history, out_idx, out_score, w.rest, w.rest_bytes, st);
 }
 
 extern "C" int lr_lru_topk_path(const lr_lru_t* h, int32_t B, int32_t L, int32_t K, int32_t exclude_history,
                                 const void* workspace, size_t workspace_bytes, int32_t* out_path, void* hip_stream) {
   if (!h || !workspace || !out_path) LR_FAIL(LR_EINVAL, "lr_lru_topk_path: null argument");
-  if (workspace_bytes < q_bytes(B)) LR_FAIL(LR_EWORKSPACE, "lr_lru_topk_path: workspace too small");
+  QSplit w;
+  LR_RUN(split_q("lr_lru_topk_path", workspace, workspace_bytes, B, &w));
   int path = 0;
-  const int rc = lr_topk_path(h, B, K, L, exclude_history, (const char*)workspace + q_bytes(B), workspace_bytes - q_bytes(B), &path,
-                              (hipStream_t)hip_stream);
-  if (rc) return rc;
+  LR_RUN(lr_topk_path(h, B, K, L, exclude_history, w.rest, w.rest_bytes, &path, (hipStream_t)hip_stream));
   *out_path = path;
   return LR_OK;
 }
@@ -220,10 +225,9 @@ extern "C" int lr_lru_scores_last(lr_lru_t* h, const int64_t* ids, int32_t B, in
   int rc = check_ids("lr_lru_scores_last", h, ids, B, L);
   if (rc) return rc;
   if (!out_scores || !workspace) LR_FAIL(LR_EINVAL, "lr_lru_scores_last: null output/workspace");
-  if (workspace_bytes < q_bytes(B)) LR_FAIL(LR_EWORKSPACE, "lr_lru_scores_last: workspace too small");
-  float* q = (float*)workspace;
+  QSplit w;
+  LR_RUN(split_q("lr_lru_scores_last", workspace, workspace_bytes, B, &w));
   hipStream_t st = (hipStream_t)hip_stream;
-  rc = encode(h, ids, B, L, q, (char*)workspace + q_bytes(B), workspace_bytes - q_bytes(B), st);
-  if (rc) return rc;
-  return lr_launch_item_scores(h, q, ids, B, L, exclude_history, out_scores, st);
+  LR_RUN(encode(h, ids, B, L, w.q, w.rest, w.rest_bytes, st));
+  return lr_launch_item_scores(h, w.q, ids, B, L, exclude_history, out_scores, st);
 }

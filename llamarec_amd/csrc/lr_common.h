@@ -8,6 +8,7 @@
 
 #include "../../include/llamarec_mi355x.h"
 #include "lr_math.h"
+#include "lru_topk_plan.h"  // lr_align_up, lr_topk_workspace_bytes and the top-K plan (host arithmetic only, no HIP)
 
 // ---- error plumbing (no C++ exception crosses the ABI) -------------------------------------
 void lr_set_error(const char* fmt, ...);
@@ -28,8 +29,6 @@ void lr_set_error(const char* fmt, ...);
   } while (0)
 
 #define LR_RUN(call) do { if (int rc_ = (call)) return rc_; } while (0)  // pass a launcher's error code up
-
-static inline size_t lr_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: a launcher keeps one `done`
 // array per kernel and calls this before every launch (one hipGetDevice on the fast path). A racing first call from
@@ -136,7 +135,6 @@ int lr_launch_lru_encode(const lr_lru* h, const int64_t* ids, int B, int L, floa
 size_t lr_encoder_mfma_workspace_bytes(int B, int L);
 int lr_launch_lru_encode_mfma(const lr_lru* h, const int64_t* ids, int B, int L, float* out_q, void* ws,
                               size_t ws_bytes, hipStream_t st);
-size_t lr_topk_workspace_bytes(int B, int K, int L, int n_tiles);
 int lr_topk_path(const lr_lru* h, int B, int K, int L, int exclude_history, const void* ws, size_t ws_bytes, int* out_path,
                  hipStream_t st);
 int lr_launch_item_topk(const lr_lru* h, const float* q, const int64_t* ids, int B, int L, int K,

@@ -1147,16 +1147,46 @@ static size_t em_chunk_users(int L) {
   return u < 1 ? 1 : u;
 }
 
-size_t lr_encoder_mfma_workspace_bytes(int B, int L) {
-  const size_t users = (size_t)B < em_chunk_users(L) ? (size_t)B : em_chunk_users(L);
-  const size_t rows = users * L;
+// The workspace for (B, L), laid out over `base` (null: only the sizes are wanted): the six integer arrays of an EmChunk
+// back to back | X | Y | Ul | Yl, every region 256-byte aligned. A call of more than em_chunk_users(L) users reuses it
+// chunk by chunk.
+struct EmWs {
+  EmChunk c;                    // the integer arrays; the other fields are set per chunk (lr_launch_lru_encode_mfma)
+  size_t users_cap, rows_cap;   // users and rows of the largest chunk
+  float *X, *Y;                 // [rows_cap][64]
+  float *Ul, *Yl;               // [users_cap][256] recurrence state and [users_cap][64] Y of the users' last rows
+  size_t total;
+};
+static EmWs em_carve(int B, int L, char* base) {
+  EmWs w = {};
+  w.users_cap = (size_t)B < em_chunk_users(L) ? (size_t)B : em_chunk_users(L);
+  w.rows_cap = w.users_cap * L;
   size_t o = 0;
-  o += lr_align_up((2 * users + (users + 1) + (EM_MAX_WGS + 1) + 2 * rows) * sizeof(int), 256);
-  o += lr_align_up(rows * 64 * sizeof(float), 256) * 2;   // X, Y
-  o += lr_align_up(users * 256 * sizeof(float), 256);     // recurrence state of the last rows
-  o += lr_align_up(users * 64 * sizeof(float), 256);      // Y of the last rows
-  return o;
+  auto ints = [&](size_t n) {
+    const size_t at = o;
+    o += n * sizeof(int);
+    return base ? (int*)(base + at) : nullptr;
+  };
+  auto floats = [&](size_t n) {
+    const size_t at = o = lr_align_up(o, 256);
+    o += n * sizeof(float);
+    return base ? (float*)(base + at) : nullptr;
+  };
+  w.c.n = ints(w.users_cap);
+  w.c.off = ints(w.users_cap + 1);
+  w.c.last_row = ints(w.users_cap);
+  w.c.wg_row = ints(EM_MAX_WGS + 1);
+  w.c.row_tag = ints(w.rows_cap);
+  w.c.row_item = ints(w.rows_cap);
+  w.X = floats(w.rows_cap * 64);
+  w.Y = floats(w.rows_cap * 64);
+  w.Ul = floats(w.users_cap * 256);
+  w.Yl = floats(w.users_cap * 64);
+  w.total = lr_align_up(o, 256);
+  return w;
 }
+
+size_t lr_encoder_mfma_workspace_bytes(int B, int L) { return em_carve(B, L, nullptr).total; }
 
 // LR_EM_PIPE=0 in the environment (A/B runs) or lr_lru_set_encoder_pipeline(h, 0) (the bit-identity test of the two kernels,
 // tests/test_gpu_lru.py): the LRU layer on em_layer_kernel (one tile at a time) instead of em_pipe_kernel. Same bits.
@@ -1199,39 +1229,21 @@ static int em_launch_layer(int grid, size_t lds, hipStream_t st, const EmLayer& 
 int lr_launch_lru_encode_mfma(const lr_lru* h, const int64_t* ids, int B, int L, float* out_q, void* ws,
                               size_t ws_bytes, hipStream_t st) {
   if (B <= 0) return LR_OK;
-  if (ws_bytes < lr_encoder_mfma_workspace_bytes(B, L))
-    LR_FAIL(LR_EWORKSPACE, "encoder: workspace needs %zu bytes, have %zu", lr_encoder_mfma_workspace_bytes(B, L), ws_bytes);
+  const EmWs w = em_carve(B, L, (char*)ws);
+  if (ws_bytes < w.total) LR_FAIL(LR_EWORKSPACE, "encoder: workspace needs %zu bytes, have %zu", w.total, ws_bytes);
   const LrLruLayout& lay = h->lay;
   const float* img = h->img;
   const size_t cu = em_chunk_users(L);
-  const size_t users_cap = (size_t)B < cu ? (size_t)B : cu;
-  const size_t rows_cap = users_cap * L;
-  char* p = (char*)ws;
-  auto take = [&](size_t bytes) {
-    char* at = p;
-    p += lr_align_up(bytes, 256);
-    return at;
-  };
-  int* ibuf = (int*)take((2 * users_cap + (users_cap + 1) + (EM_MAX_WGS + 1) + 2 * rows_cap) * sizeof(int));
-  float* X = (float*)take(rows_cap * 64 * sizeof(float));
-  float* Y = (float*)take(rows_cap * 64 * sizeof(float));
-  float* Ul = (float*)take(users_cap * 256 * sizeof(float));
-  float* Yl = (float*)take(users_cap * 64 * sizeof(float));
+  float *const X = w.X, *const Y = w.Y, *const Ul = w.Ul, *const Yl = w.Yl;
   const size_t lds = (size_t)(64 * EM_WS + EM_ST * EM_US + EM_ST * EM_XS + 2 * 16 * 64 + 128 + EM_ST + LR_ERF_NINT * EM_ERF_ROW + 512) * sizeof(float);
   LrProfScope prof(LR_PROF_LRU_ENCODE, (double)B, st);
   const int nb = lay.num_blocks;
   for (size_t u0 = 0; u0 < (size_t)B; u0 += cu) {
-    EmChunk c;
+    EmChunk c = w.c;
     c.users = (int)(((size_t)B - u0) < cu ? ((size_t)B - u0) : cu);
     c.L = L;
     c.num_items = lay.num_items;
     c.ids = ids + u0 * L;
-    c.n = ibuf;
-    c.off = ibuf + users_cap;
-    c.last_row = c.off + (users_cap + 1);
-    c.wg_row = c.last_row + users_cap;
-    c.row_tag = c.wg_row + (EM_MAX_WGS + 1);
-    c.row_item = c.row_tag + rows_cap;
     const size_t max_st = ((size_t)c.users * L + EM_ST - 1) / EM_ST;   // super tiles if every position were live
     c.G = (int)(max_st < EM_MAX_WGS ? max_st : EM_MAX_WGS);
     const int last_st = (c.users + EM_ST - 1) / EM_ST;

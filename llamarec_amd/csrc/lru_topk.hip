@@ -31,11 +31,9 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 #define TK_WAVES 4
-#define TK_USERS 128      // users per workgroup
 #define TK_CAP 128        // candidate slots per user (K <= 64 kept + insertion slack)
 #define TK_BSTRIDE 129    // slot stride between users (odd: lanes of different users hit different banks)
-#define TK_MAX_CHUNKS 256
-#define TK_MAX_WGS 1024   // chunks are added only while user tiles x chunks stays below this
+// TK_USERS (users per workgroup), TK_MAX_CHUNKS, TK_MAX_WGS and the bound path's TK_BOUND_*: lru_topk_plan.h
 
 struct TopkParams {
   const float* emb;   // [rows_padded][64]
@@ -491,13 +489,6 @@ extern "C" int lr_debug_topk_stamps(unsigned long long* out, int n) {
 // tiles) 0.53 % of 12 086 items = 64 candidates per user against 275 inserts without the bound.
 #include "lru_topk_bf16.h"
 
-#define TK_BOUND_MAX_TILES 2048  // 32 maxima per lane in bound_select_kernel: one per tile for catalogs up to 65 536 items,
-                                 // one per group of 2^gshift tiles beyond (bound_group_shift): the R-th largest GROUP maximum
-                                 // still certifies R different items at or above it, so the bound's proof is unchanged; a
-                                 // group of 512 items at rank R of 1 954 (1 M items, R = 251) sits at the same item quantile
-                                 // (2.7e-4, ~270 items + the 2 delta band) as a 32-item tile at the same rank fraction
-#define TK_BOUND_MAX_GSHIFT 6
-
 // One wave per user: T[user] = (R-th largest of tmax[user][0..n_tiles)) - delta, R = K + masked ids; -inf if there are
 // fewer than R tiles (no bound: the exact pass then starts from -inf as it does without the pre-pass).
 template <int NS>  // NS x 64 >= n_tiles key slots per wave
@@ -870,227 +861,88 @@ __global__ void mask_history_kernel(float* scores, int n_rows, const int64_t* id
   if (threadIdx.x == 0) scores[(size_t)user * n_rows] = LR_MASK_SCORE;
 }
 
-// Split the item tiles into chunks so that (user tiles x chunks) fills the 256 CUs in whole rounds:
-// minimise rounds x (tiles per chunk + the per-chunk fixed cost). The fixed cost -- the unfiltered first tiles
-// while the thresholds settle, plus compaction + sort of 128 users' lists at the end -- measures ~130 tile-times
-// (Beauty sweep: 1.41 / 1.97 / 2.27 / 2.00 / 2.28 ms for 1..5 chunks = rounds x (0.36 ms + 2.8 us x tiles)).
-// With a seeded threshold (bound pre-pass) a chunk's fixed cost is what is left of that: the prologue and the final
-// compaction + sort (~ TK_FIXED_SEEDED tile-times), so more, shorter chunks are worth it where they fill the last round.
-#define TK_FIXED_PLAIN 128
-#define TK_FIXED_SEEDED 24
-static void topk_geometry(int n_tiles, int B, bool seeded, int* n_chunks, int* tiles_per_chunk) {
-  const int n_ut = (B + TK_USERS - 1) / TK_USERS;
-  int max_chunks = TK_MAX_WGS / n_ut;
-  if (max_chunks > TK_MAX_CHUNKS) max_chunks = TK_MAX_CHUNKS;
-  if (max_chunks > n_tiles) max_chunks = n_tiles;
-  if (max_chunks < 1) max_chunks = 1;
-  long best_cost = -1;
-  int best = 1;
-  for (int c = 1; c <= max_chunks; ++c) {
-    const int tpc = (n_tiles + c - 1) / c;
-    const int real = (n_tiles + tpc - 1) / tpc;
-    const long rounds = ((long)n_ut * real + 255) / 256;
-    const long cost = rounds * (tpc + (seeded ? TK_FIXED_SEEDED : TK_FIXED_PLAIN));
-    if (best_cost < 0 || cost < best_cost) {
-      best_cost = cost;
-      best = c;
-    }
-  }
-  static int forced = -1;  // LR_TOPK_CHUNKS=n: tuning knob (0 / unset = the model above)
-  if (forced < 0) {
-    const char* e = getenv("LR_TOPK_CHUNKS");
-    forced = e ? atoi(e) : 0;
-  }
-  if (forced > 0 && forced <= max_chunks) best = forced;
-  *tiles_per_chunk = (n_tiles + best - 1) / best;
-  *n_chunks = (n_tiles + *tiles_per_chunk - 1) / *tiles_per_chunk;
-}
-
-static size_t partial_bytes_max(int B, int K) {
-  // user tiles x chunks <= TK_MAX_WGS (+ one chunk minimum) => B x chunks <= max(B, 128 * TK_MAX_WGS)
-  size_t rows = (size_t)B;
-  if (rows < (size_t)TK_USERS * TK_MAX_WGS) rows = (size_t)TK_USERS * TK_MAX_WGS;
-  return lr_align_up(rows * K * sizeof(unsigned long long), 256);
-}
-
-// the bound pre-pass runs for catalogs of TK_BOUND_MIN_TILES .. TK_BOUND_MAX_TILES tiles (LR_TOPK_BOUND=0 switches it off)
-#define TK_BOUND_MIN_TILES 64
-// ... and only where EVERY user is sure to get a bound: rank R = K + masked ids <= K + L + 1 must not exceed the tile count
-// (ML-100k: L = 200 against 115 tiles -- its users keep the exact full pass)
-// tiles per maximum = 2^shift: the smallest shift (0, or >= 2 so that a group is whole float4 iterations of the kernel)
-// that leaves at most TK_BOUND_MAX_TILES maxima per user; -1: the catalog is beyond 2^TK_BOUND_MAX_GSHIFT x that
-static int bound_group_shift(int n_tiles) {
-  int gs = 0;
-  while (((n_tiles + (1 << gs) - 1) >> gs) > TK_BOUND_MAX_TILES) ++gs;
-  if (gs == 1) gs = 2;
-  return gs <= TK_BOUND_MAX_GSHIFT ? gs : -1;
-}
-static int bound_groups(int n_tiles) {
-  const int gs = bound_group_shift(n_tiles);
-  return gs < 0 ? 0 : (n_tiles + (1 << gs) - 1) >> gs;
-}
-static bool bound_enabled(int n_tiles, int K, int L) {
-  static int env = -1;
-  if (env < 0) {
-    const char* e = getenv("LR_TOPK_BOUND");
-    env = (e && e[0] == '0') ? 0 : 1;
-  }
-  return env && n_tiles >= TK_BOUND_MIN_TILES && bound_group_shift(n_tiles) >= 0 && K + L + 1 <= bound_groups(n_tiles);
-}
-// tmax [B][ld] | thresh [B] | cand_thresh [B] | cand_count [B] + overflow flag | cand [B][TK_CAND_CAP]
-static size_t bound_bytes(int B, int n_tiles) {
-  const size_t ld = lr_align_up((size_t)bound_groups(n_tiles), 4);
-  return lr_align_up((size_t)B * ld * sizeof(float), 256) + 2 * lr_align_up((size_t)B * sizeof(float), 256) +
-         lr_align_up(((size_t)B + 1) * sizeof(int), 256) + lr_align_up((size_t)B * TK_CAND_CAP * sizeof(int32_t), 256);
-}
-
-// Sized for EVERY call of up to (B users, K, L): whether the bound pre-pass runs depends on K + L + 1 <= n_tiles, which a
-// later call with a smaller K or L can satisfy when the sizing call did not -- so its scratch is included whenever the
-// catalog's tile count is in the pre-pass's range, whatever K and L (the size is monotone in B, K and L).
-size_t lr_topk_workspace_bytes(int B, int K, int L, int n_tiles) {
-  const bool in_range = n_tiles >= TK_BOUND_MIN_TILES && bound_group_shift(n_tiles) >= 0;
-  return partial_bytes_max(B, K) + lr_align_up((size_t)B * (L > 0 ? L : 1) * sizeof(int32_t), 256) +
-         (in_range ? bound_bytes(B, n_tiles) : 0);
-}
-
+// One call: the plan (lru_topk_plan.h: path, geometry, workspace layout), then history sort; if the bound serves the shape,
+// bound -> select -> candidates -> exact rescoring; the exact pass and its merge (behind the candidate path they run only
+// if a candidate list overflowed).
 int lr_launch_item_topk(const lr_lru* h, const float* q, const int64_t* ids, int B, int L, int K,
                         int exclude_history, int32_t* out_idx, float* out_score, void* ws,
                         size_t ws_bytes, hipStream_t st) {
   if (B <= 0) return LR_OK;
-  TopkParams p;
-  p.emb = h->img + h->lay.item_emb;
-  p.bias = h->img + h->lay.item_bias;
-  p.n_rows = h->lay.num_items + 1;
-  p.n_tiles = h->lay.rows_padded / LR_ITEM_TILE;
-  p.q = q;
-  p.B = B;
-  p.L = L;
-  p.K = K;
-  p.exclude = exclude_history ? 1 : 0;
-  const bool seeded = bound_enabled(p.n_tiles, K, L);
-  topk_geometry(p.n_tiles, B, seeded, &p.n_chunks, &p.tiles_per_chunk);
-  const size_t need_partial = lr_align_up((size_t)B * p.n_chunks * K * sizeof(unsigned long long), 256);
-  const size_t need_hist = p.exclude ? lr_align_up((size_t)B * L * sizeof(int32_t), 256) : 0;
-  const size_t need_bound = seeded ? bound_bytes(B, p.n_tiles) : 0;
-  if (need_partial + need_hist + need_bound > ws_bytes)
-    LR_FAIL(LR_EWORKSPACE, "top-K workspace: need %zu bytes, have %zu", need_partial + need_hist + need_bound, ws_bytes);
-  p.partial = reinterpret_cast<unsigned long long*>(ws);
-  int32_t* hist_sorted = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ws) + need_partial);
-  p.hist_sorted = p.exclude ? hist_sorted : nullptr;
-  p.thresh = nullptr;
-  p.run_flag = nullptr;
-  int* overflow_flag = nullptr;
+  const int n_rows = h->lay.num_items + 1, n_tiles = h->lay.rows_padded / LR_ITEM_TILE, exclude = exclude_history ? 1 : 0;
+  const TkPlan plan = tk_plan(n_tiles, B, K, L, exclude);
+  if (plan.total > ws_bytes) LR_FAIL(LR_EWORKSPACE, "top-K workspace: need %zu bytes, have %zu", plan.total, ws_bytes);
+  char* const w = reinterpret_cast<char*>(ws);
+  int32_t* const hist_sorted = reinterpret_cast<int32_t*>(w + plan.off[TK_HIST]);
+  // the bound path's regions (empty, and unused, when the plan is not seeded)
+  float* const thresh = reinterpret_cast<float*>(w + plan.off[TK_THRESH]);
+  float* const cand_thresh = reinterpret_cast<float*>(w + plan.off[TK_CAND_THRESH]);
+  int* const cand_count = reinterpret_cast<int*>(w + plan.off[TK_CAND_COUNT]);
+  int* const overflow_flag = reinterpret_cast<int*>(w + plan.overflow_flag);
+  int32_t* const cand = reinterpret_cast<int32_t*>(w + plan.off[TK_CAND]);
+  const TopkParams p = {
+      .emb = h->img + h->lay.item_emb, .bias = h->img + h->lay.item_bias, .n_rows = n_rows, .n_tiles = n_tiles, .q = q,
+      .hist_sorted = exclude ? hist_sorted : nullptr, .B = B, .L = L, .K = K, .exclude = exclude,
+      .tiles_per_chunk = plan.tiles_per_chunk, .n_chunks = plan.n_chunks,
+      .partial = reinterpret_cast<unsigned long long*>(w + plan.off[TK_PARTIAL]),
+      // behind the candidate path the exact full pass starts from the bound and runs only if a candidate list overflowed
+      .thresh = plan.seeded ? thresh : nullptr, .run_flag = plan.seeded ? overflow_flag : nullptr};
 
-  LrProfScope prof(LR_PROF_ITEM_TOPK, 2.0 * 64 * (double)p.n_rows * B, st);
-  if (p.exclude) {
+  LrProfScope prof(LR_PROF_ITEM_TOPK, 2.0 * 64 * (double)n_rows * B, st);
+  if (exclude) {
     int Lp = 2;
     while (Lp < L) Lp <<= 1;
     if (Lp > 8192) LR_FAIL(LR_EUNSUPPORTED, "history length %d > 8192 is not supported by the mask pre-pass", L);
     if (L <= 64) {
-      hipLaunchKernelGGL(hist_sort_wave_kernel, dim3((B + 3) / 4), dim3(256), 0, st, ids, B, L, p.n_rows, hist_sorted);
+      hipLaunchKernelGGL(hist_sort_wave_kernel, dim3((B + 3) / 4), dim3(256), 0, st, ids, B, L, n_rows, hist_sorted);
       LR_CHECK_LAUNCH("hist_sort_wave_kernel");
     } else {
-      hipLaunchKernelGGL(hist_sort_kernel, dim3(B), dim3(256), (size_t)Lp * sizeof(int32_t), st, ids, L, Lp, p.n_rows,
+      hipLaunchKernelGGL(hist_sort_kernel, dim3(B), dim3(256), (size_t)Lp * sizeof(int32_t), st, ids, L, Lp, n_rows,
                          hist_sorted);
       LR_CHECK_LAUNCH("hist_sort_kernel");
     }
   }
-  if (seeded) {
-    BoundParams bp;
-    bp.emb16 = reinterpret_cast<const unsigned short*>(h->img + h->lay.item_emb_bf16);
-    bp.bias = p.bias;
-    bp.bias_tail = h->img + h->lay.item_stats + 32;
-    bp.n_rows = p.n_rows;
-    bp.n_tiles = p.n_tiles;
-    bp.q = q;
-    bp.B = B;
-    bp.gshift = bound_group_shift(p.n_tiles);
-    const int n_groups = bound_groups(p.n_tiles);
-    bp.ld = (int)lr_align_up((size_t)n_groups, 4);
-    char* bw = reinterpret_cast<char*>(ws) + need_partial + need_hist;
-    bp.tmax = reinterpret_cast<float*>(bw);
-    bw += lr_align_up((size_t)B * bp.ld * sizeof(float), 256);
-    float* thresh = reinterpret_cast<float*>(bw);
-    bw += lr_align_up((size_t)B * sizeof(float), 256);
-    float* cand_thresh = reinterpret_cast<float*>(bw);
-    bw += lr_align_up((size_t)B * sizeof(float), 256);
-    int* cand_count = reinterpret_cast<int*>(bw);   // [B], then the overflow flag
-    overflow_flag = cand_count + B;
-    bw += lr_align_up(((size_t)B + 1) * sizeof(int), 256);
-    int32_t* cand = reinterpret_cast<int32_t*>(bw);
-    const int upw = lr_bf16_users_per_wg(B);
-    const int n_ut = (B + upw - 1) / upw;
-    int chunks = (1024 + n_ut - 1) / n_ut;                 // two rounds of the 512 resident workgroups (two per CU)
-    // ... but never more than lr_bf16_max_chunk_tiles(B) tiles per chunk, however many user tiles there are: the candidate
-    // pass's per-chunk LDS lists hold 20-40 entries per user with 16-bit offsets (16 k users used to get
-    // 32 chunks of ~1 000 tiles at 1 M items, ~12 expected candidates per user and chunk against 24 slots)
-    const int min_chunks = (p.n_tiles + lr_bf16_max_chunk_tiles(B) - 1) / lr_bf16_max_chunk_tiles(B);
-    {
-      static int target_wgs = -1;   // LR_BF16_WGS=n: tuning knob (workgroups per launch; 0 / unset = 1024)
-      if (target_wgs < 0) {
-        const char* e = getenv("LR_BF16_WGS");
-        target_wgs = e ? atoi(e) : 0;
-      }
-      if (target_wgs > 0) chunks = (target_wgs + n_ut - 1) / n_ut;
-    }
-    if (chunks < min_chunks) chunks = min_chunks;
-    const int unit = bp.gshift >= 2 ? (4 << bp.gshift) : 4;  // a chunk is whole float4 iterations / whole quads of tile groups
-    const int units = (p.n_tiles + unit - 1) / unit;
-    if (chunks > units) chunks = units;
-    bp.tiles_per_chunk = unit * ((units + chunks - 1) / chunks);
-    chunks = (p.n_tiles + bp.tiles_per_chunk - 1) / bp.tiles_per_chunk;
-    if (int rc = lr_launch_item_bound(bp, chunks, st)) return rc;
-#define TK_SELECT(NS_)                                                                                               \
-  hipLaunchKernelGGL(bound_select_kernel<NS_>, dim3((B + 3) / 4), dim3(256), 0, st, bp.tmax, bp.ld, n_groups, q, ids, L, \
-                     p.n_rows, p.exclude, B, K, h->img + h->lay.item_stats, thresh, cand_thresh, cand_count, overflow_flag)
-    if (n_groups <= 128) TK_SELECT(2);
-    else if (n_groups <= 512) TK_SELECT(8);
+  if (plan.seeded) {
+    const BoundParams bp = {
+        .emb16 = reinterpret_cast<const unsigned short*>(h->img + h->lay.item_emb_bf16), .bias = p.bias,
+        .bias_tail = h->img + h->lay.item_stats + 32, .n_rows = n_rows, .n_tiles = n_tiles, .q = q, .B = B,
+        .tmax = reinterpret_cast<float*>(w + plan.off[TK_TMAX]), .ld = plan.ld, .tiles_per_chunk = plan.bf16_tiles_per_chunk,
+        .gshift = plan.gshift, .n_chunks = plan.bf16_chunks, .n_user_groups = plan.n_user_groups};
+    LR_RUN(lr_launch_item_bound(bp, st));
+#define TK_SELECT(NS_)                                                                                                    \
+  hipLaunchKernelGGL(bound_select_kernel<NS_>, dim3((B + 3) / 4), dim3(256), 0, st, bp.tmax, bp.ld, plan.n_groups, q, ids, L, \
+                     n_rows, exclude, B, K, h->img + h->lay.item_stats, thresh, cand_thresh, cand_count, overflow_flag)
+    if (plan.n_groups <= 128) TK_SELECT(2);
+    else if (plan.n_groups <= 512) TK_SELECT(8);
     else TK_SELECT(TK_BOUND_MAX_TILES / 64);
 #undef TK_SELECT
     LR_CHECK_LAUNCH("bound_select_kernel");
-    CandParams cp;
-    cp.emb16 = bp.emb16;
-    cp.bias = p.bias;
-    cp.bias_tail = bp.bias_tail;
-    cp.n_tiles = p.n_tiles;
-    cp.q = q;
-    cp.B = B;
-    cp.cand_thresh = cand_thresh;
-    cp.cand_count = cand_count;
-    cp.cand = cand;
-    cp.tiles_per_chunk = bp.tiles_per_chunk;
-    if (int rc = lr_launch_item_cand(cp, chunks, st)) return rc;
+    const CandParams cp = {
+        .emb16 = bp.emb16, .bias = p.bias, .bias_tail = bp.bias_tail, .n_tiles = n_tiles, .q = q, .B = B,
+        .cand_thresh = cand_thresh, .cand_count = cand_count, .cand = cand, .tiles_per_chunk = plan.bf16_tiles_per_chunk,
+        .n_chunks = plan.bf16_chunks, .n_user_groups = plan.n_user_groups};
+    LR_RUN(lr_launch_item_cand(cp, st));
     hipLaunchKernelGGL(cand_rescore_kernel, dim3((B + 3) / 4), dim3(256), 0, st, p.emb, p.bias, q, p.hist_sorted, L,
-                       p.exclude, B, K, p.n_rows, cand_count, cand, thresh, overflow_flag, out_idx, out_score);
+                       exclude, B, K, n_rows, cand_count, cand, thresh, overflow_flag, out_idx, out_score);
     LR_CHECK_LAUNCH("cand_rescore_kernel");
-    // behind the candidate path: the exact full pass, which runs only if a candidate list overflowed
-    p.thresh = thresh;
-    p.run_flag = overflow_flag;
   }
   const size_t lds = (2 * 32 * TK_ESTRIDE + 128) * sizeof(float) +
                      (size_t)TK_USERS * TK_BSTRIDE * 8;
   static bool lds_set[LR_MAX_DEVICES] = {};
-  if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(item_topk_kernel<false>), (int)lds, lds_set)) return rc;
+  LR_RUN(lr_ensure_dynamic_lds(reinterpret_cast<const void*>(item_topk_kernel<false>), (int)lds, lds_set));
   dim3 grid(p.n_chunks, (B + TK_USERS - 1) / TK_USERS);
 #ifdef LR_EXPERIMENTS
   static bool lds_set_stamp[LR_MAX_DEVICES] = {};
   const char* stamp_env = getenv("LR_TOPK_STAMPS");
   if (stamp_env && stamp_env[0] == '1') {
-    if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(item_topk_kernel<true>), (int)lds, lds_set_stamp)) return rc;
+    LR_RUN(lr_ensure_dynamic_lds(reinterpret_cast<const void*>(item_topk_kernel<true>), (int)lds, lds_set_stamp));
     hipLaunchKernelGGL(item_topk_kernel<true>, grid, dim3(256), lds, st, p);
   } else
 #endif
     hipLaunchKernelGGL(item_topk_kernel<false>, grid, dim3(256), lds, st, p);
   LR_CHECK_LAUNCH("item_topk_kernel");
 
-  MergeParams m;
-  m.partial = p.partial;
-  m.B = B;
-  m.K = K;
-  m.n_chunks = p.n_chunks;
-  m.out_idx = out_idx;
-  m.out_score = out_score;
-  m.run_flag = p.run_flag;
+  const MergeParams m = {.partial = p.partial, .B = B, .K = K, .n_chunks = p.n_chunks, .out_idx = out_idx, .out_score = out_score,
+                         .run_flag = p.run_flag};
   if (p.n_chunks > 1 && p.n_chunks * K <= TK_MERGE_KEYS)
     hipLaunchKernelGGL(topk_merge_small_kernel, dim3((B + 3) / 4), dim3(256), 0, st, m);
   else
@@ -1101,24 +953,17 @@ int lr_launch_item_topk(const lr_lru* h, const float* q, const int64_t* ids, int
 
 // Which path the LAST lr_launch_item_topk call with exactly these (B, K, L) on this workspace took: 0 = the exact full
 // pass (the bound does not serve this shape), 1 = bound -> candidates -> exact rescoring, 2 = that path overflowed a
-// candidate list and the exact full pass redid the call. Reads the call's overflow flag where the call carved it.
+// candidate list and the exact full pass redid the call. Reads the call's overflow flag where the call's plan put it.
 int lr_topk_path(const lr_lru* h, int B, int K, int L, int exclude_history, const void* ws, size_t ws_bytes, int* out_path,
                  hipStream_t st) {
-  const int n_tiles = h->lay.rows_padded / LR_ITEM_TILE;
-  if (!bound_enabled(n_tiles, K, L) || B <= 0) {
+  const TkPlan plan = B > 0 ? tk_plan(h->lay.rows_padded / LR_ITEM_TILE, B, K, L, exclude_history) : TkPlan{};
+  if (!plan.seeded) {
     *out_path = 0;
     return LR_OK;
   }
-  int n_chunks, tpc;
-  topk_geometry(n_tiles, B, true, &n_chunks, &tpc);
-  const size_t need_partial = lr_align_up((size_t)B * n_chunks * K * sizeof(unsigned long long), 256);
-  const size_t need_hist = exclude_history ? lr_align_up((size_t)B * L * sizeof(int32_t), 256) : 0;
-  if (need_partial + need_hist + bound_bytes(B, n_tiles) > ws_bytes) LR_FAIL(LR_EWORKSPACE, "lr_topk_path: workspace too small");
-  const size_t ld = lr_align_up((size_t)bound_groups(n_tiles), 4);
-  const char* bw = reinterpret_cast<const char*>(ws) + need_partial + need_hist + lr_align_up((size_t)B * ld * sizeof(float), 256) +
-                   2 * lr_align_up((size_t)B * sizeof(float), 256);
+  if (plan.total > ws_bytes) LR_FAIL(LR_EWORKSPACE, "lr_topk_path: workspace too small");
   int flag = 0;
-  LR_CHECK_HIP(hipMemcpyAsync(&flag, reinterpret_cast<const int*>(bw) + B, sizeof(int), hipMemcpyDeviceToHost, st));
+  LR_CHECK_HIP(hipMemcpyAsync(&flag, reinterpret_cast<const char*>(ws) + plan.overflow_flag, sizeof(int), hipMemcpyDeviceToHost, st));
   LR_CHECK_HIP(hipStreamSynchronize(st));
   *out_path = flag ? 2 : 1;
   return LR_OK;

@@ -308,18 +308,14 @@ __global__ __launch_bounds__(512, 4) void item_cand_kernel(CandParams p) {
 // 512 users per workgroup (two column tiles of 32 users per wave). Four column tiles (every fragment and bias read from
 // LDS feeding 16 MFMAs instead of 8) were built and measured in round 4: bq alone is then 64 of the 128 VGPRs that two
 // workgroups per CU leave a wave, hipcc spills 9-34 registers, and the passes ran 431 / 616 us at 1 M items against
-// 449 / 566 us, 83 / 104 us against 53 / 84 us on Beauty. The kernels keep the template parameter.
-int lr_bf16_users_per_wg(int B) { (void)B; return 512; }
+// 449 / 566 us, 83 / 104 us against 53 / 84 us on Beauty. The kernels keep the template parameter;
+// lr_bf16_users_per_wg() (lru_topk_plan.h) holds the number.
 
-int lr_launch_item_bound(const BoundParams& p0, int chunks, hipStream_t st) {
-  BoundParams p = p0;
+int lr_launch_item_bound(const BoundParams& p, hipStream_t st) {
   // a chunk is whole float4 iterations (one maximum per tile) or whole QUADS of tile groups (grouped: four groups' maxima leave
   // as one 16-byte store)
   if (p.gshift < 0 || p.gshift == 1 || p.tiles_per_chunk % (p.gshift >= 2 ? (4 << p.gshift) : 4) != 0)
     LR_FAIL(LR_EINVAL, "item_bound_kernel: gshift=%d tiles_per_chunk=%d", p.gshift, p.tiles_per_chunk);
-  const int upw = lr_bf16_users_per_wg(p.B);
-  p.n_chunks = chunks;
-  p.n_user_groups = (p.B + upw - 1) / upw;
   const dim3 grid(tk_grid(p.n_chunks, p.n_user_groups));
   if (p.gshift == 0) hipLaunchKernelGGL((item_bound_kernel<false, 2>), grid, dim3(512), 0, st, p);
   else hipLaunchKernelGGL((item_bound_kernel<true, 2>), grid, dim3(512), 0, st, p);
@@ -327,13 +323,9 @@ int lr_launch_item_bound(const BoundParams& p0, int chunks, hipStream_t st) {
   return LR_OK;
 }
 
-int lr_launch_item_cand(const CandParams& p0, int chunks, hipStream_t st) {
-  CandParams p = p0;
-  const int upw = lr_bf16_users_per_wg(p.B);
+int lr_launch_item_cand(const CandParams& p, hipStream_t st) {
   if (p.tiles_per_chunk > lr_bf16_max_chunk_tiles(p.B))
     LR_FAIL(LR_EINVAL, "item_cand_kernel: %d tiles per chunk, at most %d", p.tiles_per_chunk, lr_bf16_max_chunk_tiles(p.B));
-  p.n_chunks = chunks;
-  p.n_user_groups = (p.B + upw - 1) / upw;
   const dim3 grid(tk_grid(p.n_chunks, p.n_user_groups));
   hipLaunchKernelGGL((item_cand_kernel<2>), grid, dim3(512), 0, st, p);
   LR_CHECK_LAUNCH("item_cand_kernel");

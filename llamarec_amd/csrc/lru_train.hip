@@ -844,8 +844,9 @@ struct TrWs {
   float *d64c, *d256b;        // row-panel path: dy0 and da stay live until the block's weight-gradient launch
   float* ce;                  // cross-entropy scratch: the fused path's partials + lse, or the stored logits
   bool materialise;           // small problem: store the [R][V+1] logits (<= 256 MB), three plain GEMM passes over them
-  // deterministic mode (lr_det.h): 64-bit fixed-point shadows of [gradient buffer | derived region | d x | 8 scalars]
-  long long* shadow;
+  // deterministic mode (lr_det.h): 64-bit fixed-point shadows of [gradient buffer | derived region | d x | 8 scalars],
+  // one buffer of shadow_n elements starting at shadow[0].p (null / 0 elements when the mode is off)
+  struct { long long* p; size_t n; } shadow[4];
   size_t derived_floats, shadow_n;
   size_t total;
 };
@@ -928,9 +929,13 @@ static TrWs tr_carve(const TrLayout& lay, const LrLruTrainConfig& cfg, int R, ch
     const size_t generic = (size_t)R * (((size_t)lay.V + 1 + 3) & ~(size_t)3), panels = lr_train_scores_ws_floats(R, lay.V + 1);
     w.ce = take(w.materialise ? (generic > panels ? generic : panels) : lr_train_ce_part_floats(R, lay.V + 1));
   }
-  w.shadow = nullptr;
-  w.shadow_n = det ? lay.total + doff + (size_t)R * 64 + 8 : 0;
-  if (det) w.shadow = (long long*)take(2 * w.shadow_n);
+  const size_t shadow_len[4] = {lay.total, doff, (size_t)R * 64, 8};
+  w.shadow_n = det ? shadow_len[0] + shadow_len[1] + shadow_len[2] + shadow_len[3] : 0;
+  long long* sh = det ? (long long*)take(2 * w.shadow_n) : nullptr;
+  for (int k = 0; k < 4; ++k) {
+    w.shadow[k] = {sh, det ? shadow_len[k] : 0};
+    sh += w.shadow[k].n;
+  }
   w.total = o;
   return w;
 }
@@ -1158,11 +1163,7 @@ static int tr_enqueue_loss_grad(lr_lru_train_t* h, const int64_t* tokens, const 
   const unsigned grid_rows = (unsigned)((R + 3) / 4);
   float* dx = ws.d64b;   // gradient of the blocks' output, then of each block's input
   const bool det = h->deterministic != 0;
-  // shadow layout: [gradient buffer | derived region | d x | scalars]
-  long long* const sh_g = ws.shadow;
-  long long* const sh_d = ws.shadow ? ws.shadow + lay.total : nullptr;
-  long long* const sh_x = ws.shadow ? sh_d + ws.derived_floats : nullptr;
-  long long* const sh_s = ws.shadow ? sh_x + (size_t)R * 64 : nullptr;
+  long long *const sh_g = ws.shadow[0].p, *const sh_d = ws.shadow[1].p, *const sh_x = ws.shadow[2].p, *const sh_s = ws.shadow[3].p;
   auto fold = [&](float* f, const long long* sh, size_t n, double scale) {
     hipLaunchKernelGGL(lr_det_fold_kernel, dim3((unsigned)((n + 1023) / 1024 < 1024 ? (n + 1023) / 1024 : 1024)), dim3(256), 0, st, f, sh, n,
                        1.0 / scale);
@@ -1171,7 +1172,7 @@ static int tr_enqueue_loss_grad(lr_lru_train_t* h, const int64_t* tokens, const 
     if (!h->fused)
       LR_FAIL(LR_EUNSUPPORTED, "lr_lru_train_loss_grad: deterministic mode runs the row-panel kernels only (lr_lru_train_set_fused(h, 1)): "
                                "the generic GEMM launches split K with atomics into activation buffers");
-    hipLaunchKernelGGL(lr_det_zero_kernel, dim3(1024), dim3(256), 0, st, ws.shadow, ws.shadow_n);
+    hipLaunchKernelGGL(lr_det_zero_kernel, dim3(1024), dim3(256), 0, st, ws.shadow[0].p, ws.shadow_n);
     LR_CHECK_LAUNCH("lr_det_zero_kernel");
   }
   {  // seed, zero fills (gradients, derived-weight gradients, d x), label counts
@@ -1393,11 +1394,10 @@ extern "C" int lr_lru_train_loss_grad(lr_lru_train_t* h, const int64_t* tokens, 
     if (w.total > workspace_bytes)
       LR_FAIL(LR_EWORKSPACE, "lr_lru_train_loss_grad: workspace needs %zu bytes in deterministic mode, have %zu", w.total, workspace_bytes);
     LrDetMap m = {};
-    const size_t R_ = (size_t)B * L;
-    m.base[0] = h->g;       m.bytes[0] = h->lay.total * 4;       m.shadow[0] = w.shadow;                                     m.scale[0] = (float)LR_DET_GRAD_SCALE;
-    m.base[1] = w.derived;  m.bytes[1] = w.derived_floats * 4;   m.shadow[1] = w.shadow + h->lay.total;                      m.scale[1] = (float)LR_DET_GRAD_SCALE;
-    m.base[2] = w.d64b;     m.bytes[2] = R_ * 64 * 4;            m.shadow[2] = m.shadow[1] + w.derived_floats;               m.scale[2] = (float)LR_DET_GRAD_SCALE;
-    m.base[3] = h->scal;    m.bytes[3] = 8 * 4;                  m.shadow[3] = m.shadow[2] + R_ * 64;                        m.scale[3] = (float)LR_DET_SCAL_SCALE;
+    m.base[0] = h->g;       m.bytes[0] = w.shadow[0].n * 4;   m.shadow[0] = w.shadow[0].p;   m.scale[0] = (float)LR_DET_GRAD_SCALE;
+    m.base[1] = w.derived;  m.bytes[1] = w.shadow[1].n * 4;   m.shadow[1] = w.shadow[1].p;   m.scale[1] = (float)LR_DET_GRAD_SCALE;
+    m.base[2] = w.d64b;     m.bytes[2] = w.shadow[2].n * 4;   m.shadow[2] = w.shadow[2].p;   m.scale[2] = (float)LR_DET_GRAD_SCALE;
+    m.base[3] = h->scal;    m.bytes[3] = w.shadow[3].n * 4;   m.shadow[3] = w.shadow[3].p;   m.scale[3] = (float)LR_DET_SCAL_SCALE;
     m.on = 1;
     if (int rc = tr_det_publish(m, (hipStream_t)hip_stream)) return rc;
   } else if (g_det_current.on) {   // another engine of this process left its map behind: this pass adds in place
