@@ -506,6 +506,14 @@ typedef struct LrLoraTrainConfig {
   uint64_t seed;        /* dropout stream (own counter-based generator) */
 } LrLoraTrainConfig;
 
+/* Which Linears of every decoder layer carry an adapter (the reference's --lora_target_modules, config.py:260).
+ * modules: bit 0 q_proj, 1 v_proj, 2 k_proj, 3 o_proj, 4 gate_proj, 5 up_proj, 6 down_proj; at least one.
+ * Unknown bits or non-zero reserved words: LR_EINVAL. */
+typedef struct LrLoraTargets {
+  uint32_t modules;
+  uint32_t reserved[7];
+} LrLoraTargets;
+
 typedef struct lr_llama_lora lr_llama_lora_t;
 
 /* dst[c][r] = src[r][c], bf16, DEVICE pointers. */
@@ -517,12 +525,21 @@ size_t lr_llama_lora_state_bytes(const lr_llama_t* base, const LrLoraTrainConfig
  * through lr_llama_lora_buffers (peft: A ~ kaiming-uniform, B = 0). `base` must outlive the handle. */
 int lr_llama_lora_create(lr_llama_t* base, const LrLlamaWeightsTDesc* wt, const LrLoraTrainConfig* cfg,
                          void* state_dev, size_t state_bytes, void* hip_stream, lr_llama_lora_t** out);
+/* The same two with the adapted modules chosen; targets == NULL means q_proj | v_proj, which is what the
+ * two calls above pass. State and workspace grow only with the selected modules. */
+size_t lr_llama_lora_state_bytes_ex(const lr_llama_t* base, const LrLoraTrainConfig* cfg, const LrLoraTargets* targets);
+int lr_llama_lora_create_ex(lr_llama_t* base, const LrLlamaWeightsTDesc* wt, const LrLoraTrainConfig* cfg,
+                            const LrLoraTargets* targets, void* state_dev, size_t state_bytes, void* hip_stream,
+                            lr_llama_lora_t** out);
 void lr_llama_lora_destroy(lr_llama_lora_t* h);
-/* Flat fp32 DEVICE buffers of n floats each. Per layer: q_proj.lora_A [r][hidden], q_proj.lora_B
- * [nh*hd][r], v_proj.lora_A [r][hidden], v_proj.lora_B [nkv*hd][r] -- peft's layouts and HF's
- * (unpermuted) row order. Data-parallel training all-reduces `grads` between loss_grad and apply. */
+/* Flat fp32 DEVICE buffers of n floats each. Per layer, in the order q, v, k, o, gate, up, down with the
+ * modules the handle does not adapt skipped: lora_A [r][in], lora_B [out][r] -- peft's layouts and HF's
+ * (unpermuted) row order; a q|v handle: q_proj.lora_A [r][hidden], q_proj.lora_B [nh*hd][r],
+ * v_proj.lora_A [r][hidden], v_proj.lora_B [nkv*hd][r]. Data-parallel training all-reduces `grads`
+ * between loss_grad and apply. */
 int lr_llama_lora_buffers(lr_llama_lora_t* h, float** params, float** grads, float** m, float** v, size_t* n);
-/* which: 0 q_proj, 1 v_proj; ab: 0 lora_A, 1 lora_B. */
+/* which: 0 q_proj, 1 v_proj, 2 k_proj, 3 o_proj, 4 gate_proj, 5 up_proj, 6 down_proj (LR_EINVAL for a module
+ * the handle does not adapt); ab: 0 lora_A, 1 lora_B. */
 int lr_llama_lora_param_range(const lr_llama_lora_t* h, int32_t layer, int32_t which, int32_t ab,
                               size_t* offset, size_t* count);
 size_t lr_llama_lora_workspace_bytes(const lr_llama_lora_t* h, int32_t max_tokens, int32_t max_seqs,

@@ -141,6 +141,15 @@ class LrLoraTrainConfig(C.Structure):
                 ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("seed", C.c_uint64)]
 
 
+class LrLoraTargets(C.Structure):
+    """include/llamarec_mi355x.h: LrLoraTargets (bit i of `modules` = LORA_MODULES[i])."""
+    _fields_ = [("modules", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+# bit order of LrLoraTargets.modules = `which` of lr_llama_lora_param_range = per-layer order of the flat buffers
+LORA_MODULES = ("q_proj", "v_proj", "k_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+
+
 def lru_desc_from_state_dict(sd) -> tuple[LrLruWeightsDesc, list]:
     """Build the C weight descriptor from an LRURec state_dict (torch tensors or numpy arrays).
 

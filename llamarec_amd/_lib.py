@@ -108,6 +108,10 @@ PROTOTYPES = {
     "lr_llama_lora_state_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(A.LrLoraTrainConfig)]),
     "lr_llama_lora_create": (C.c_int, [C.c_void_p, C.POINTER(A.LrLlamaWeightsTDesc), C.POINTER(A.LrLoraTrainConfig),
                                        C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lr_llama_lora_state_bytes_ex": (C.c_size_t, [C.c_void_p, C.POINTER(A.LrLoraTrainConfig), C.POINTER(A.LrLoraTargets)]),
+    "lr_llama_lora_create_ex": (C.c_int, [C.c_void_p, C.POINTER(A.LrLlamaWeightsTDesc), C.POINTER(A.LrLoraTrainConfig),
+                                          C.POINTER(A.LrLoraTargets), C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.POINTER(C.c_void_p)]),
     "lr_llama_lora_destroy": (None, [C.c_void_p]),
     "lr_llama_lora_buffers": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),

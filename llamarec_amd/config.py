@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import argparse
 
+from ._abi import LORA_MODULES
 from .prompt import DEFAULT_INPUT_TEMPLATE, DEFAULT_SYSTEM_TEMPLATE
 
 EXPERIMENT_ROOT = "experiments"   # config.py:5-9
@@ -60,6 +61,10 @@ def build_parser():
     p.add_argument("--lora_alpha", type=int, default=32)
     # ranker LoRA fine-tuning (config.py:203,236-241,257-269; defaults filled in set_template like config.py:81-102)
     p.add_argument("--lora_dropout", type=float, default=0.05)
+    # config.py:260. The reference's `type=list` splits a command-line string into characters; here the names are separate
+    # arguments and "all-linear" is peft's shorthand for the seven Linears of a layer (rank_train.normalize_target_modules)
+    p.add_argument("--lora_target_modules", nargs="+", default=["q_proj", "v_proj"],
+                   choices=list(LORA_MODULES) + ["all-linear"])
     p.add_argument("--lora_num_epochs", type=int, default=1)
     p.add_argument("--lora_val_iterations", type=int, default=None)
     p.add_argument("--lora_val_delay", type=int, default=None)
@@ -150,6 +155,8 @@ def set_template(args):
         args.lora_early_stopping_patience = 20
     if args.lora_max_steps is None:
         args.lora_max_steps = -1
+    if "all-linear" in args.lora_target_modules:           # peft's shorthand: every Linear of a decoder layer
+        args.lora_target_modules = list(LORA_MODULES)
     if args.rerank_best_metric is None:                    # config.py:142-143
         args.rerank_best_metric = "NDCG@10"
     if args.model_code == "llm":

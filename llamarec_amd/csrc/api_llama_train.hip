@@ -28,6 +28,9 @@ struct lr_llama_lora {
   int* ctr;                        // [4]: 0 optimizer steps
   uint32_t pass;                   // host-side pass counter (dropout streams)
   int qcols, kcols, vcols;
+  // adapted modules (LrLoraTargets bits: 0 q, 1 v, 2 k, 3 o, 4 gate, 5 up, 6 down). q|v is the layout and the code path
+  // this step always had; every other module goes through the generic rank-r passes (LoraMods below)
+  uint32_t mods;
   // The adapter-only kernels (rank-r products, dA / dB reductions: ~5 % of a step, a few hundred workgroups each) run
   // on a low-priority side stream next to the big GEMM they are independent of, and fill the CUs its last, partly
   // empty round of tiles leaves idle (7 k tokens: 448 tiles on 256 CUs). LR_LORA_OVERLAP=0 keeps everything in order.
@@ -50,14 +53,65 @@ static int join_side(lr_llama_lora* h, hipStream_t main) {
   return LR_OK;
 }
 
+#define LT_MOD_QV 3u
+#define LT_MOD_ALL 0x7fu
+enum { MQ = 0, MV, MK, MO, MGATE, MUP, MDOWN, LT_NMOD };
+// Where every selected module lives: fp32 masters per layer in the order q, v, k, o, gate, up, down with absent modules
+// skipped (A [r][in] then B [out][r]); bf16 working copies per layer = the q/v block of always (a_cat, bq_t, bv_t) followed
+// by the extra modules' (a_w [LT_RP][in], b_t [LT_RP][out]; gate and up share a [2*LT_RP][d] / [2*LT_RP][2f] pair so that one
+// 32-column product serves both); t columns of the extra modules in the saved [n][tw] tile (gate and up adjacent).
+struct LoraMods {
+  uint32_t mask;
+  int in[LT_NMOD], out[LT_NMOD];
+  size_t pa[LT_NMOD], pb[LT_NMOD];  // fp32 offsets within a layer's parameters
+  size_t per_layer;
+  size_t wk_a, wk_b, wo_a, wo_b, wgu_a, wgu_b, wdn_a, wdn_b, work_per_layer;  // bf16 element offsets
+  int tk, to, tgu, tdn, tw;         // t column offsets of the extra modules, tw = their total width (0: none)
+  bool has(int m) const { return (mask >> m) & 1u; }
+  bool gu() const { return has(MGATE) || has(MUP); }
+};
+static LoraMods lora_mods(const LrLlamaConfig& c, int r, uint32_t mask) {
+  LoraMods m;
+  memset(&m, 0, sizeof(m));
+  m.mask = mask;
+  const int d = c.hidden_size, f = c.intermediate_size, qc = c.num_heads * c.head_dim, kv = c.num_kv_heads * c.head_dim;
+  const int in[LT_NMOD] = {d, d, d, qc, d, d, f}, out[LT_NMOD] = {qc, kv, kv, d, f, f, d};
+  size_t o = 0;
+  for (int i = 0; i < LT_NMOD; ++i) {
+    m.in[i] = in[i];
+    m.out[i] = out[i];
+    if (!m.has(i)) continue;
+    m.pa[i] = o;
+    o += (size_t)r * in[i];
+    m.pb[i] = o;
+    o += (size_t)r * out[i];
+  }
+  m.per_layer = o;
+  size_t w = 2 * (size_t)LT_RP * d + (size_t)LT_RP * (qc + kv);
+  int t = 0;
+  auto take = [&](size_t n) {
+    size_t at = w;
+    w += n;
+    return at;
+  };
+  m.tk = m.to = m.tgu = m.tdn = -1;
+  if (m.has(MK)) m.wk_a = take((size_t)LT_RP * d), m.wk_b = take((size_t)LT_RP * kv), m.tk = t, t += LT_RP;
+  if (m.has(MO)) m.wo_a = take((size_t)LT_RP * qc), m.wo_b = take((size_t)LT_RP * d), m.to = t, t += LT_RP;
+  if (m.gu()) m.wgu_a = take(2 * (size_t)LT_RP * d), m.wgu_b = take(2 * (size_t)LT_RP * 2 * f), m.tgu = t, t += 2 * LT_RP;
+  if (m.has(MDOWN)) m.wdn_a = take((size_t)LT_RP * f), m.wdn_b = take((size_t)LT_RP * d), m.tdn = t, t += LT_RP;
+  m.work_per_layer = w;
+  m.tw = t;
+  return m;
+}
+
 struct LoraStateLayout {
   size_t params, grads, m, v, work, scratch, ctr, total;
 };
-static LoraStateLayout state_layout(const LrLlamaConfig& c, int r) {
+static LoraStateLayout state_layout(const LrLlamaConfig& c, int r, uint32_t mask) {
   LoraStateLayout s;
-  const size_t qcols = (size_t)c.num_heads * c.head_dim, vcols = (size_t)c.num_kv_heads * c.head_dim;
-  const size_t n = (size_t)c.num_layers * (2 * (size_t)r * c.hidden_size + (size_t)r * (qcols + vcols));
-  const size_t wl = 2 * (size_t)LT_RP * c.hidden_size + (size_t)LT_RP * (qcols + vcols);
+  const LoraMods md = lora_mods(c, r, mask);
+  const size_t n = (size_t)c.num_layers * md.per_layer;
+  const size_t wl = md.work_per_layer;
   size_t o = 0;
   auto take = [&](size_t bytes) {
     size_t at = o;
@@ -85,15 +139,43 @@ static int check_cfg(const lr_llama_t* base, const LrLoraTrainConfig* cfg, const
   if (c.head_dim % 8 != 0) LR_FAIL(LR_EUNSUPPORTED, "%s: head_dim %d (must be a multiple of 8)", who, c.head_dim);
   return LR_OK;
 }
+// NULL = q_proj | v_proj
+static int check_targets(const lr_llama_t* base, const LrLoraTargets* t, const char* who, uint32_t* mask) {
+  *mask = LT_MOD_QV;
+  if (!t) return LR_OK;
+  for (int i = 0; i < 7; ++i)
+    if (t->reserved[i]) LR_FAIL(LR_EINVAL, "%s: LrLoraTargets.reserved[%d] is not zero", who, i);
+  if (t->modules == 0 || (t->modules & ~LT_MOD_ALL))
+    LR_FAIL(LR_EINVAL, "%s: LrLoraTargets.modules = 0x%x (bits 0..6, at least one)", who, t->modules);
+  if ((t->modules & 0x70u) && base->cfg.intermediate_size % 64 != 0)
+    LR_FAIL(LR_EUNSUPPORTED, "%s: adapters on gate / up / down need an intermediate size that is a multiple of 64 (%d)", who,
+            base->cfg.intermediate_size);
+  *mask = t->modules;
+  return LR_OK;
+}
 
+extern "C" size_t lr_llama_lora_state_bytes_ex(const lr_llama_t* base, const LrLoraTrainConfig* cfg,
+                                               const LrLoraTargets* targets) {
+  uint32_t mask;
+  if (check_cfg(base, cfg, "lr_llama_lora_state_bytes") || check_targets(base, targets, "lr_llama_lora_state_bytes", &mask))
+    return 0;
+  return state_layout(base->cfg, cfg->r, mask).total;
+}
 extern "C" size_t lr_llama_lora_state_bytes(const lr_llama_t* base, const LrLoraTrainConfig* cfg) {
-  if (check_cfg(base, cfg, "lr_llama_lora_state_bytes")) return 0;
-  return state_layout(base->cfg, cfg->r).total;
+  return lr_llama_lora_state_bytes_ex(base, cfg, nullptr);
 }
 
 extern "C" int lr_llama_lora_create(lr_llama_t* base, const LrLlamaWeightsTDesc* wt, const LrLoraTrainConfig* cfg,
                                     void* state, size_t state_bytes, void* hip_stream, lr_llama_lora_t** out) {
+  return lr_llama_lora_create_ex(base, wt, cfg, nullptr, state, state_bytes, hip_stream, out);
+}
+extern "C" int lr_llama_lora_create_ex(lr_llama_t* base, const LrLlamaWeightsTDesc* wt, const LrLoraTrainConfig* cfg,
+                                       const LrLoraTargets* targets, void* state, size_t state_bytes, void* hip_stream,
+                                       lr_llama_lora_t** out) {
   int rc = check_cfg(base, cfg, "lr_llama_lora_create");
+  if (rc) return rc;
+  uint32_t mask;
+  rc = check_targets(base, targets, "lr_llama_lora_create", &mask);
   if (rc) return rc;
   if (base->arch.norm_style != 0 || base->arch.mlp_act != 0 || base->arch.embed_scale != 1.0f)
     LR_FAIL(LR_EUNSUPPORTED, "lr_llama_lora_create: fine-tuning needs a Llama base (no GeGLU / Gemma-norm backward)");
@@ -104,7 +186,8 @@ extern "C" int lr_llama_lora_create(lr_llama_t* base, const LrLlamaWeightsTDesc*
     if (!t.wqkv_t || !t.wo_t || !t.wgu_t || !t.wdown_t)
       LR_FAIL(LR_EINVAL, "lr_llama_lora_create: layer %d has a null transposed weight", l);
   }
-  const LoraStateLayout s = state_layout(c, cfg->r);
+  const LoraStateLayout s = state_layout(c, cfg->r, mask);
+  const LoraMods md = lora_mods(c, cfg->r, mask);
   if (state_bytes < s.total)
     LR_FAIL(LR_EWORKSPACE, "lr_llama_lora_create: state needs %zu bytes, have %zu", s.total, state_bytes);
   lr_llama_lora* h = (lr_llama_lora*)calloc(1, sizeof(lr_llama_lora));
@@ -124,9 +207,10 @@ extern "C" int lr_llama_lora_create(lr_llama_t* base, const LrLlamaWeightsTDesc*
   h->ctr = (int*)(b + s.ctr);
   h->qcols = c.num_heads * c.head_dim;
   h->kcols = h->vcols = c.num_kv_heads * c.head_dim;
-  h->per_layer = 2 * (size_t)cfg->r * c.hidden_size + (size_t)cfg->r * (h->qcols + h->vcols);
+  h->mods = mask;
+  h->per_layer = md.per_layer;
   h->n_params = (size_t)c.num_layers * h->per_layer;
-  h->work_per_layer = 2 * (size_t)LT_RP * c.hidden_size + (size_t)LT_RP * (h->qcols + h->vcols);
+  h->work_per_layer = md.work_per_layer;
   const char* ov = getenv("LR_LORA_OVERLAP");
   if (!ov || ov[0] != '0') {
     // NORMAL priority (round 5). The side stream used to be created with the device's lowest priority, so that the rank-r products
@@ -179,19 +263,18 @@ extern "C" int lr_llama_lora_buffers(lr_llama_lora_t* h, float** params, float**
   return LR_OK;
 }
 
-// which: 0 q_proj, 1 v_proj; ab: 0 lora_A [r][hidden], 1 lora_B [out][r] (peft's layouts)
+// which: 0 q_proj, 1 v_proj, 2 k_proj, 3 o_proj, 4 gate_proj, 5 up_proj, 6 down_proj; ab: 0 lora_A [r][in], 1 lora_B [out][r]
+// (peft's layouts)
 extern "C" int lr_llama_lora_param_range(const lr_llama_lora_t* h, int32_t layer, int32_t which, int32_t ab,
                                          size_t* offset, size_t* count) {
   if (!h || !offset || !count) LR_FAIL(LR_EINVAL, "lr_llama_lora_param_range: null argument");
   const LrLlamaConfig& c = h->base->cfg;
-  if (layer < 0 || layer >= c.num_layers || which < 0 || which > 1 || ab < 0 || ab > 1)
+  if (layer < 0 || layer >= c.num_layers || which < 0 || which >= LT_NMOD || ab < 0 || ab > 1)
     LR_FAIL(LR_EINVAL, "lr_llama_lora_param_range: layer=%d which=%d ab=%d", layer, which, ab);
-  const size_t r = h->cfg.r, d = c.hidden_size;
-  const size_t aq = 0, bq = r * d, av = bq + r * h->qcols, bv = av + r * d;
-  const size_t off[2][2] = {{aq, bq}, {av, bv}};
-  const size_t cnt[2][2] = {{r * d, r * (size_t)h->qcols}, {r * d, r * (size_t)h->vcols}};
-  *offset = (size_t)layer * h->per_layer + off[which][ab];
-  *count = cnt[which][ab];
+  const LoraMods md = lora_mods(c, h->cfg.r, h->mods);
+  if (!md.has(which)) LR_FAIL(LR_EINVAL, "lr_llama_lora_param_range: module %d is not adapted by this handle", which);
+  *offset = (size_t)layer * h->per_layer + (ab ? md.pb[which] : md.pa[which]);
+  *count = (size_t)h->cfg.r * (ab ? md.out[which] : md.in[which]);
   return LR_OK;
 }
 
@@ -199,6 +282,7 @@ extern "C" int lr_llama_lora_param_range(const lr_llama_lora_t* h, int32_t layer
 struct LoraLayerSave {
   u16 *x, *xn, *qkv, *att, *xmid, *gu, *t;
   float* lse;
+  u16* t2;  // [n][tw]: drop(input) A^T of the extra modules
 };
 struct LoraWs {
   int32_t *tok_pos, *last_rows;
@@ -207,12 +291,15 @@ struct LoraWs {
   u16 *dx, *dh, *dxn, *datt, *dqkv, *dt;  // backward
   float *dsum, *dkv32;
   u16 *xg, *hn, *logits, *dhn;            // loss head, m rows
+  u16 *dt2, *xn2_b, *hmid_b;              // extra modules' backward: d t [n][tw]; recomputed inputs of gate/up and of down
+  size_t o_t2;
   size_t save0, save_stride;              // per-layer saved activations: base + l * save_stride
   size_t o_x, o_xn, o_qkv, o_att, o_xmid, o_gu, o_t, o_lse;
   char* base;
   size_t total;
 };
-static LoraWs carve(const LrLlamaConfig& c, int n_tok, int B, int m, int slots, bool training, char* base) {
+static LoraWs carve(const LrLlamaConfig& c, const LoraMods& md, int n_tok, int B, int m, int slots, bool training,
+                    char* base) {
   LoraWs w;
   memset(&w, 0, sizeof(w));
   w.base = base;
@@ -244,6 +331,7 @@ static LoraWs carve(const LrLlamaConfig& c, int n_tok, int B, int m, int slots, 
   w.o_gu = stake(n * 2 * f * 2);
   w.o_t = stake(n * 2 * LT_RP * 2);
   w.o_lse = stake(n * c.num_heads * 4);
+  w.o_t2 = stake(n * md.tw * 2);
   w.save_stride = so;
   w.save0 = take(so * (size_t)slots);
   // transients: forward's (xn2, hmid) share memory with backward's (dxn, dh)
@@ -261,6 +349,11 @@ static LoraWs carve(const LrLlamaConfig& c, int n_tok, int B, int m, int slots, 
     w.hn = (u16*)(base + take(mm * d * 2));
     w.logits = (u16*)(base + take(mm * c.vocab_size * 2));
     w.dhn = (u16*)(base + take(mm * d * 2));
+    // The inputs of gate/up (xn2) and down (hmid) live in shared forward transients: the backward recomputes them (one rmsnorm /
+    // swiglu pass per layer on the side stream) instead of saving n * (d + f) more bytes per layer
+    if (md.tw) w.dt2 = (u16*)(base + take(n * md.tw * 2));
+    if (md.gu()) w.xn2_b = (u16*)(base + take(n * d * 2));
+    if (md.has(MDOWN)) w.hmid_b = (u16*)(base + take(n * f * 2));
   }
   w.total = o;
   return w;
@@ -276,6 +369,7 @@ static LoraLayerSave slot(const LoraWs& w, int l) {
   s.gu = (u16*)(b + w.o_gu);
   s.t = (u16*)(b + w.o_t);
   s.lse = (float*)(b + w.o_lse);
+  s.t2 = (u16*)(b + w.o_t2);
   return s;
 }
 
@@ -283,12 +377,14 @@ extern "C" size_t lr_llama_lora_workspace_bytes(const lr_llama_lora_t* h, int32_
                                                 int32_t max_loss_rows) {
   if (!h || max_tokens < 1) return 0;
   if (max_seqs < 1) max_seqs = 1;
-  return carve(h->base->cfg, max_tokens, max_seqs, max_loss_rows, h->base->cfg.num_layers, true, nullptr).total;
+  const LrLlamaConfig& c = h->base->cfg;
+  return carve(c, lora_mods(c, h->cfg.r, h->mods), max_tokens, max_seqs, max_loss_rows, c.num_layers, true, nullptr).total;
 }
 extern "C" size_t lr_llama_lora_eval_workspace_bytes(const lr_llama_lora_t* h, int32_t max_tokens, int32_t max_seqs) {
   if (!h || max_tokens < 1) return 0;
   if (max_seqs < 1) max_seqs = 1;
-  return carve(h->base->cfg, max_tokens, max_seqs, 0, 1, false, nullptr).total;
+  const LrLlamaConfig& c = h->base->cfg;
+  return carve(c, lora_mods(c, h->cfg.r, h->mods), max_tokens, max_seqs, 0, 1, false, nullptr).total;
 }
 
 static u16* work_of(const lr_llama_lora* h, int l) { return h->work + (size_t)l * h->work_per_layer; }
@@ -297,12 +393,31 @@ static u16* work_of(const lr_llama_lora* h, int l) { return h->work + (size_t)l 
 static int prep_adapters(lr_llama_lora* h, hipStream_t st) {
   const LrLlamaConfig& c = h->base->cfg;
   const size_t r = h->cfg.r, d = c.hidden_size;
+  const LoraMods md = lora_mods(c, h->cfg.r, h->mods);
   for (int l = 0; l < c.num_layers; ++l) {
     const float* p = h->params + (size_t)l * h->per_layer;
     u16* w = work_of(h, l);
-    LR_RUN(lr_launch_prep_lora(p, p + r * d, p + r * d + r * h->qcols, p + 2 * r * d + r * h->qcols, (int)r, (int)d,
-                               h->qcols, h->vcols, c.head_dim, w, w + 2 * LT_RP * d, w + 2 * LT_RP * d + LT_RP * h->qcols,
-                               st));
+    if (h->mods == LT_MOD_QV) {
+      LR_RUN(lr_launch_prep_lora(p, p + r * d, p + r * d + r * h->qcols, p + 2 * r * d + r * h->qcols, (int)r, (int)d,
+                                 h->qcols, h->vcols, c.head_dim, w, w + 2 * LT_RP * d, w + 2 * LT_RP * d + LT_RP * h->qcols,
+                                 st));
+      continue;
+    }
+    // the copies of a module that is not adapted are never written: they stay zero from the state's initial memset
+    u16 *bq_t = w + 2 * LT_RP * d, *bv_t = bq_t + LT_RP * (size_t)h->qcols;
+    const int f2 = 2 * c.intermediate_size;
+    struct { int m, perm; u16 *a, *b; int ldb; } job[LT_NMOD] = {
+        {MQ, 1, w, bq_t, h->qcols},
+        {MV, 0, w + LT_RP * d, bv_t, h->vcols},
+        {MK, 1, w + md.wk_a, w + md.wk_b, h->kcols},
+        {MO, 0, w + md.wo_a, w + md.wo_b, (int)d},
+        {MGATE, 2, w + md.wgu_a, w + md.wgu_b, f2},
+        {MUP, 3, w + md.wgu_a + LT_RP * d, w + md.wgu_b + (size_t)LT_RP * f2, f2},
+        {MDOWN, 0, w + md.wdn_a, w + md.wdn_b, (int)d}};
+    for (const auto& j : job)
+      if (md.has(j.m))
+        LR_RUN(lr_launch_prep_module(p + md.pa[j.m], p + md.pb[j.m], (int)r, md.in[j.m], md.out[j.m], j.perm, c.head_dim, j.a,
+                                     j.b, j.ldb, st));
   }
   return LR_OK;
 }
@@ -324,6 +439,8 @@ static int forward(lr_llama_lora* h, const int32_t* ids, const int32_t* cu, cons
   const int qw = (nh + 2 * nkv) * hd;
   const float scaling = h->cfg.alpha / (float)h->cfg.r;
   const int gv = h->base->gemm_variant == 5 ? 0 : h->base->gemm_variant;
+  const LoraMods md = lora_mods(c, h->cfg.r, h->mods);
+  const int r = h->cfg.r, tw = md.tw, L = c.num_layers;
   LrAttnKernel attn_kernel;  // the backward needs the statistics: lse wanted
   LR_RUN(lr_resolve_attention({.variant = h->base->attn_variant, .hd = hd, .want_lse = true}, &attn_kernel));
   LR_RUN(lr_launch_token_meta(cu, B, 0, nullptr, ws.tok_pos, nullptr, ws.last_rows, st));
@@ -340,19 +457,52 @@ static int forward(lr_llama_lora* h, const int32_t* ids, const int32_t* cu, cons
     hipStream_t sd;
     LR_RUN(fork_side(h, st, &sd));  // t = drop(xn) A^T next to the QKV GEMM: both only read xn
     LR_RUN(lr_launch_skinny(s.xn, d, n, d, a_cat, 2, s.t, 2 * LT_RP, 0, 1.0f, stream, drop_p, sd));
+    if (md.has(MK)) LR_RUN(lr_launch_skinny(s.xn, d, n, d, wk + md.wk_a, 1, s.t2, tw, md.tk, 1.0f, stream, drop_p, sd));
     LR_RUN(lr_launch_gemm({.A = s.xn, .B = w.wqkv, .C = s.qkv, .M = n, .N = qw, .K = d, .variant = gv}, st));
     LR_RUN(join_side(h, st));
+    // k's delta rides in the same sweep, before the rotation like q's
     LR_RUN(lr_launch_lora_rope_fwd(s.qkv, n, qw, h->qcols, h->kcols, hd, s.t, bq_t, bv_t, h->cfg.r, scaling, ws.tok_pos,
-                                   ws.rope, st));
+                                   ws.rope, st, s.t2, tw, md.tk, md.has(MK) ? wk + md.wk_b : nullptr));
     LR_RUN(lr_launch_attention({.qkv = s.qkv, .out = s.att, .lse = s.lse, .cu = cu, .cu_host = cu_host, .S = B, .n_tok = n,
                                 .nh = nh, .nkv = nkv, .hd = hd}, attn_kernel, st));
+    // the extra modules: t = drop(input) A^T on the side stream next to the GEMM that reads the same input, the delta
+    // s * t B^T added behind the GEMM (o and down: behind its residual epilogue; gate / up: before swiglu reads gu, so
+    // that the saved gu holds the pre-activation values the backward differentiates at)
+    if (md.has(MO)) {
+      LR_RUN(fork_side(h, st, &sd));
+      LR_RUN(lr_launch_skinny(s.att, h->qcols, n, h->qcols, wk + md.wo_a, 1, s.t2, tw, md.to, 1.0f,
+                              lr_lora_drop_stream(h->cfg.seed, h->pass, (uint32_t)(l + L)), drop_p, sd));
+    }
     LR_RUN(lr_launch_gemm({.A = s.att, .B = w.wo, .C = s.xmid, .R = s.x, .M = n, .N = d, .K = nh * hd, .epi = LR_EPI_RESIDUAL,
                            .variant = gv}, st));
+    if (md.has(MO)) {
+      LR_RUN(join_side(h, st));
+      LR_RUN(lr_launch_lora_expand(s.xmid, d, n, d, s.t2, tw, md.to, wk + md.wo_b, r, scaling, 0, 0.f, st));
+    }
     LR_RUN(lr_launch_rmsnorm(s.xmid, w.post_norm, ws.xn2, n, d, c.rms_eps, nullptr, st));
+    if (md.gu()) {
+      LR_RUN(fork_side(h, st, &sd));
+      LR_RUN(lr_launch_skinny(ws.xn2, d, n, d, wk + md.wgu_a, 2, s.t2, tw, md.tgu, 1.0f,
+                              lr_lora_drop_stream(h->cfg.seed, h->pass, (uint32_t)(l + 2 * L)), drop_p, sd));
+    }
     LR_RUN(lr_launch_gemm({.A = ws.xn2, .B = w.wgu, .C = s.gu, .M = n, .N = 2 * f, .K = d, .variant = gv}, st));
-    LR_RUN(lr_launch_swiglu_fwd(s.gu, ws.hmid, n, f, st));
+    if (md.gu()) {  // the delta rides in the pass that reads gu
+      LR_RUN(join_side(h, st));
+      LR_RUN(lr_launch_swiglu_lora_fwd(s.gu, ws.hmid, n, f, s.t2, tw, md.tgu, wk + md.wgu_b, r, scaling, st));
+    } else {
+      LR_RUN(lr_launch_swiglu_fwd(s.gu, ws.hmid, n, f, st));
+    }
+    if (md.has(MDOWN)) {
+      LR_RUN(fork_side(h, st, &sd));
+      LR_RUN(lr_launch_skinny(ws.hmid, f, n, f, wk + md.wdn_a, 1, s.t2, tw, md.tdn, 1.0f,
+                              lr_lora_drop_stream(h->cfg.seed, h->pass, (uint32_t)(l + 3 * L)), drop_p, sd));
+    }
     LR_RUN(lr_launch_gemm({.A = ws.hmid, .B = w.wdown, .C = x_next, .R = s.xmid, .M = n, .N = d, .K = f, .epi = LR_EPI_RESIDUAL,
                            .variant = gv}, st));
+    if (md.has(MDOWN)) {
+      LR_RUN(join_side(h, st));
+      LR_RUN(lr_launch_lora_expand(x_next, d, n, d, s.t2, tw, md.tdn, wk + md.wdn_b, r, scaling, 0, 0.f, st));
+    }
   }
   return LR_OK;
 }
@@ -369,14 +519,17 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
   int n, maxT;
   LR_RUN(validate_batch(h, cu_seqlens_host, B, &n, &maxT));
   if (m > n) LR_FAIL(LR_EINVAL, "lr_llama_lora_loss_grad: %d labelled rows for %d tokens", m, n);
-  const LoraWs ws = carve(c, n, B, m, c.num_layers, true, (char*)workspace);
+  const LoraMods md = lora_mods(c, h->cfg.r, h->mods);
+  const LoraWs ws = carve(c, md, n, B, m, c.num_layers, true, (char*)workspace);
   if (ws.total > workspace_bytes)
     LR_FAIL(LR_EWORKSPACE, "lr_llama_lora_loss_grad: workspace needs %zu bytes for %d tokens, have %zu", ws.total, n,
             workspace_bytes);
   const int d = c.hidden_size, f = c.intermediate_size, nh = c.num_heads, nkv = c.num_kv_heads, hd = c.head_dim;
   const int qw = (nh + 2 * nkv) * hd, r = h->cfg.r;
   const float scaling = h->cfg.alpha / (float)r, drop_p = h->cfg.dropout;
+  const float drop_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
   const int gv = h->base->gemm_variant == 5 ? 0 : h->base->gemm_variant;
+  const int tw = md.tw, L = c.num_layers;
   h->pass += 1;
   if (!accumulate) LR_CHECK_HIP(hipMemsetAsync(h->grads, 0, h->n_params * sizeof(float), st));
   LR_CHECK_HIP(hipMemsetAsync(h->scratch, 0, 2 * sizeof(float), st));
@@ -402,31 +555,95 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
     const u16* wk = work_of(h, l);
     const u16 *a_cat = wk, *bq_t = wk + 2 * LT_RP * (size_t)d, *bv_t = bq_t + LT_RP * (size_t)h->qcols;
     float* g = h->grads + (size_t)l * h->per_layer;
-    float *daq = g, *dbq = g + (size_t)r * d, *dav = dbq + (size_t)r * h->qcols, *dbv = dav + (size_t)r * d;
+    auto grad_of = [&](int mod, int ab) { return md.has(mod) ? g + (ab ? md.pb[mod] : md.pa[mod]) : (float*)nullptr; };
+    float *daq = grad_of(MQ, 0), *dbq = grad_of(MQ, 1), *dav = grad_of(MV, 0), *dbv = grad_of(MV, 1);
     const uint32_t stream = lr_lora_drop_stream(h->cfg.seed, h->pass, (uint32_t)l);
+    hipStream_t sd;
+    // One extra module with input X [n][in], output gradient dY [n][.]: on the side stream, next to the data-gradient GEMM that
+    // reads the same dY,  d B += s t^T dY,  d t = s dY B,  d A += drop(X)^T d t;  behind the GEMM,  d X += mask .* (d t A).
     // MLP: x_out = xmid + down(silu(gate) * up)
-    LR_RUN(lr_launch_gemm({.A = ws.dx, .B = wt.wdown_t, .C = ws.dh, .M = n, .N = f, .K = d, .variant = gv}, st));
+    if (md.has(MDOWN)) {
+      const uint32_t s3 = lr_lora_drop_stream(h->cfg.seed, h->pass, (uint32_t)(l + 3 * L));
+      LR_RUN(fork_side(h, st, &sd));
+      LR_RUN(lr_launch_lora_tn(1, s.t2, tw, md.tdn, ws.dx, d, n, d, scaling, grad_of(MDOWN, 1), nullptr, r, 1, 0, 0, 0.f, sd));
+      LR_RUN(lr_launch_skinny(ws.dx, d, n, d, wk + md.wdn_b, 1, ws.dt2, tw, md.tdn, scaling, 0, 0.f, sd));
+      LR_RUN(lr_launch_swiglu_fwd(s.gu, ws.hmid_b, n, f, sd));  // down's input, recomputed before swiglu_bwd overwrites gu
+      LR_RUN(lr_launch_lora_tn(1, ws.dt2, tw, md.tdn, ws.hmid_b, f, n, f, 1.0f, grad_of(MDOWN, 0), nullptr, r, 0, 0, s3, drop_p,
+                               sd));
+      LR_RUN(lr_launch_gemm({.A = ws.dx, .B = wt.wdown_t, .C = ws.dh, .M = n, .N = f, .K = d, .variant = gv}, st));
+      LR_RUN(join_side(h, st));
+      LR_RUN(lr_launch_lora_expand(ws.dh, f, n, f, ws.dt2, tw, md.tdn, wk + md.wdn_a, r, drop_scale, s3, drop_p, st));
+    } else {
+      LR_RUN(lr_launch_gemm({.A = ws.dx, .B = wt.wdown_t, .C = ws.dh, .M = n, .N = f, .K = d, .variant = gv}, st));
+    }
     LR_RUN(lr_launch_swiglu_bwd(s.gu, ws.dh, n, f, st));
-    LR_RUN(lr_launch_gemm({.A = s.gu, .B = wt.wgu_t, .C = ws.dxn, .M = n, .N = d, .K = 2 * f, .variant = gv}, st));
-    LR_RUN(lr_launch_rmsnorm_bwd(ws.dxn, s.xmid, w.post_norm, ws.dx, ws.dx, n, d, c.rms_eps, nullptr, nullptr, nullptr, 0,
-                                 0, 0.f, st));
+    if (md.gu()) {  // s.gu now holds d gu in the interleaved layout; b_gu's zero half-columns make it a plain weight
+      const uint32_t s2 = lr_lora_drop_stream(h->cfg.seed, h->pass, (uint32_t)(l + 2 * L));
+      LR_RUN(fork_side(h, st, &sd));
+      LR_RUN(lr_launch_lora_tn(2, s.t2, tw, md.tgu, s.gu, 2 * f, n, 2 * f, scaling, grad_of(MGATE, 1), grad_of(MUP, 1), r, 3, 0, 0,
+                               0.f, sd));
+      LR_RUN(lr_launch_skinny(s.gu, 2 * f, n, 2 * f, wk + md.wgu_b, 2, ws.dt2, tw, md.tgu, scaling, 0, 0.f, sd));
+      LR_RUN(lr_launch_rmsnorm(s.xmid, w.post_norm, ws.xn2_b, n, d, c.rms_eps, nullptr, sd));  // gate / up's input, recomputed
+      LR_RUN(lr_launch_lora_tn(2, ws.dt2, tw, md.tgu, ws.xn2_b, d, n, d, 1.0f, grad_of(MGATE, 0), grad_of(MUP, 0), r, 0, 0, s2,
+                               drop_p, sd));
+      LR_RUN(lr_launch_gemm({.A = s.gu, .B = wt.wgu_t, .C = ws.dxn, .M = n, .N = d, .K = 2 * f, .variant = gv}, st));
+      LR_RUN(join_side(h, st));
+      // d xn2 += mask .* (d t_gate A_gate + d t_up A_up) rides in the norm's LoRA arm, as q / v's does in the input norm's
+      LR_RUN(lr_launch_rmsnorm_bwd(ws.dxn, s.xmid, w.post_norm, ws.dx, ws.dx, n, d, c.rms_eps, nullptr, ws.dt2 + md.tgu,
+                                   wk + md.wgu_a, r, s2, drop_p, st, tw));
+    } else {
+      LR_RUN(lr_launch_gemm({.A = s.gu, .B = wt.wgu_t, .C = ws.dxn, .M = n, .N = d, .K = 2 * f, .variant = gv}, st));
+      LR_RUN(lr_launch_rmsnorm_bwd(ws.dxn, s.xmid, w.post_norm, ws.dx, ws.dx, n, d, c.rms_eps, nullptr, nullptr, nullptr, 0,
+                                   0, 0.f, st));
+    }
     // attention block: xmid = x + o_proj(attention(q, k, v))
-    LR_RUN(lr_launch_gemm({.A = ws.dx, .B = wt.wo_t, .C = ws.datt, .M = n, .N = nh * hd, .K = d, .variant = gv}, st));
+    if (md.has(MO)) {
+      const uint32_t s1 = lr_lora_drop_stream(h->cfg.seed, h->pass, (uint32_t)(l + L));
+      LR_RUN(fork_side(h, st, &sd));
+      LR_RUN(lr_launch_lora_tn(1, s.t2, tw, md.to, ws.dx, d, n, d, scaling, grad_of(MO, 1), nullptr, r, 1, 0, 0, 0.f, sd));
+      LR_RUN(lr_launch_skinny(ws.dx, d, n, d, wk + md.wo_b, 1, ws.dt2, tw, md.to, scaling, 0, 0.f, sd));
+      LR_RUN(lr_launch_lora_tn(1, ws.dt2, tw, md.to, s.att, h->qcols, n, h->qcols, 1.0f, grad_of(MO, 0), nullptr, r, 0, 0, s1,
+                               drop_p, sd));
+      LR_RUN(lr_launch_gemm({.A = ws.dx, .B = wt.wo_t, .C = ws.datt, .M = n, .N = nh * hd, .K = d, .variant = gv}, st));
+      LR_RUN(join_side(h, st));
+      LR_RUN(lr_launch_lora_expand(ws.datt, h->qcols, n, h->qcols, ws.dt2, tw, md.to, wk + md.wo_a, r, drop_scale, s1,
+                                   drop_p, st));
+    } else {
+      LR_RUN(lr_launch_gemm({.A = ws.dx, .B = wt.wo_t, .C = ws.datt, .M = n, .N = nh * hd, .K = d, .variant = gv}, st));
+    }
     // ... down to the gradient of the UNROTATED q, k, v (the inverse rotation rides in the attention passes)
     LR_RUN(lr_launch_attention_bwd(s.qkv, s.att, ws.datt, s.lse, ws.dqkv, ws.dsum, ws.dkv32, cu_seqlens, cu_seqlens_host, B,
                                    n, nh, nkv, hd, h->base->attn_variant, st, ws.tok_pos, ws.rope));
     // adapters (side stream, next to the qkv data-gradient GEMM; both only read dqkv):
     // d B, d t = scaling * (d q B_q | d v B_v), d A
-    hipStream_t sd;
     LR_RUN(fork_side(h, st, &sd));
-    LR_RUN(lr_launch_lora_db(ws.dqkv, n, qw, h->qcols, h->kcols, hd, s.t, r, scaling, dbq, dbv, sd));
+    if (dbq && dbv) {
+      LR_RUN(lr_launch_lora_db(ws.dqkv, n, qw, h->qcols, h->kcols, hd, s.t, r, scaling, dbq, dbv, sd));
+    } else {
+      if (dbq) LR_RUN(lr_launch_lora_tn(1, s.t, 2 * LT_RP, 0, ws.dqkv, qw, n, h->qcols, scaling, dbq, nullptr, r, 2, hd, 0, 0.f, sd));
+      if (dbv)
+        LR_RUN(lr_launch_lora_tn(1, s.t, 2 * LT_RP, LT_RP, ws.dqkv + h->qcols + h->kcols, qw, n, h->vcols, scaling, dbv, nullptr,
+                                 r, 1, hd, 0, 0.f, sd));
+    }
+    // (the working copies of a q / v that is not adapted are zero: its d t columns come out zero for the norm's LoRA arm)
     LR_RUN(lr_launch_skinny(ws.dqkv, qw, n, h->qcols, bq_t, 1, ws.dt, 2 * LT_RP, 0, scaling, 0, 0.f, sd));
     LR_RUN(lr_launch_skinny(ws.dqkv + h->qcols + h->kcols, qw, n, h->vcols, bv_t, 1, ws.dt, 2 * LT_RP, LT_RP, scaling, 0,
                             0.f, sd));
-    LR_RUN(lr_launch_lora_da(s.xn, n, d, ws.dt, r, stream, drop_p, daq, dav, sd));
+    if (daq && dav) LR_RUN(lr_launch_lora_da(s.xn, n, d, ws.dt, r, stream, drop_p, daq, dav, sd));
+    else if (daq || dav)
+      LR_RUN(lr_launch_lora_tn(1, ws.dt, 2 * LT_RP, daq ? 0 : LT_RP, s.xn, d, n, d, 1.0f, daq ? daq : dav, nullptr, r, 0, 0,
+                               stream, drop_p, sd));
+    if (md.has(MK)) {
+      LR_RUN(lr_launch_lora_tn(1, s.t2, tw, md.tk, ws.dqkv + h->qcols, qw, n, h->kcols, scaling, grad_of(MK, 1), nullptr, r, 2, hd,
+                               0, 0.f, sd));
+      LR_RUN(lr_launch_skinny(ws.dqkv + h->qcols, qw, n, h->kcols, wk + md.wk_b, 1, ws.dt2, tw, md.tk, scaling, 0, 0.f, sd));
+      LR_RUN(lr_launch_lora_tn(1, ws.dt2, tw, md.tk, s.xn, d, n, d, 1.0f, grad_of(MK, 0), nullptr, r, 0, 0, stream, drop_p, sd));
+    }
     if (l > 0)  // below layer 0 only the frozen embedding is left: its input gradient has no reader
       LR_RUN(lr_launch_gemm({.A = ws.dqkv, .B = wt.wqkv_t, .C = ws.dxn, .M = n, .N = d, .K = qw, .variant = gv}, st));
     LR_RUN(join_side(h, st));
+    if (l > 0 && md.has(MK))  // k shares q / v's input and its mask
+      LR_RUN(lr_launch_lora_expand(ws.dxn, d, n, d, ws.dt2, tw, md.tk, wk + md.wk_a, r, drop_scale, stream, drop_p, st));
     if (l > 0)
       LR_RUN(lr_launch_rmsnorm_bwd(ws.dxn, s.x, w.input_norm, ws.dx, ws.dx, n, d, c.rms_eps, nullptr, ws.dt, a_cat, r,
                                    stream, drop_p, st));
@@ -454,7 +671,7 @@ extern "C" int lr_llama_lora_prefill_verbalize(lr_llama_lora_t* h, const int32_t
   const LrLlamaConfig& c = h->base->cfg;
   int n, maxT;
   LR_RUN(validate_batch(h, cu_seqlens_host, B, &n, &maxT));
-  const LoraWs ws = carve(c, n, B, 0, 1, false, (char*)workspace);
+  const LoraWs ws = carve(c, lora_mods(c, h->cfg.r, h->mods), n, B, 0, 1, false, (char*)workspace);
   if (ws.total > workspace_bytes)
     LR_FAIL(LR_EWORKSPACE, "lr_llama_lora_prefill_verbalize: workspace needs %zu bytes for %d tokens, have %zu",
             ws.total, n, workspace_bytes);

@@ -15,19 +15,31 @@ int lr_launch_skinny(const unsigned short* X, int ldx, int n, int K, const unsig
                      int ldo, int ocol, float scale, uint32_t drop_stream, float drop_p, hipStream_t st);
 int lr_launch_lora_rope_fwd(unsigned short* qkv, int n, int qw, int qcols, int kcols, int hd, const unsigned short* t,
                             const unsigned short* bq_t, const unsigned short* bv_t, int r, float scaling,
-                            const int32_t* tok_pos, const float* rope_cs, hipStream_t st);
+                            const int32_t* tok_pos, const float* rope_cs, hipStream_t st,
+                            const unsigned short* tk = nullptr, int ldtk = 0, int tkcol = 0,
+                            const unsigned short* bk_t = nullptr);  // bk_t: k_proj's adapter, t from tk [n][ldtk] column tkcol
 int lr_launch_rope_bwd(unsigned short* dqkv, int n, int qw, int rot_cols, int hd, const int32_t* tok_pos,
                        const float* rope_cs, hipStream_t st);
 int lr_launch_lora_db(const unsigned short* dqkv, int n, int qw, int qcols, int kcols, int hd, const unsigned short* t,
                       int r, float scaling, float* dbq, float* dbv, hipStream_t st);
 int lr_launch_lora_da(const unsigned short* xn, int n, int d, const unsigned short* dt, int r, uint32_t drop_stream,
                       float drop_p, float* daq, float* dav, hipStream_t st);
+// adapters on any Linear: launch_tn exposed (layouts: llama_train.hip), one module's working copies, the expand-add sweep
+int lr_launch_lora_tn(int nj, const unsigned short* T, int ldt, int tcol, const unsigned short* X, int ldx, int n, int cols,
+                      float scale, float* out0, float* out1, int r, int layout, int hd, uint32_t drop_stream, float drop_p,
+                      hipStream_t st);
+int lr_launch_prep_module(const float* a, const float* b, int r, int in, int out, int perm, int hd, unsigned short* a_w,
+                          unsigned short* b_t, int ldb, hipStream_t st);
+int lr_launch_lora_expand(unsigned short* Y, int ldy, int n, int cols, const unsigned short* T, int ldt, int tcol,
+                          const unsigned short* W, int r, float s, uint32_t drop_stream, float drop_p, hipStream_t st);
 int lr_launch_swiglu_fwd(const unsigned short* gu, unsigned short* h, int n, int f, hipStream_t st);
+int lr_launch_swiglu_lora_fwd(unsigned short* gu, unsigned short* h, int n, int f, const unsigned short* t, int ldt, int tcol,
+                              const unsigned short* W, int r, float s, hipStream_t st);
 int lr_launch_swiglu_bwd(unsigned short* gu, const unsigned short* dh, int n, int f, hipStream_t st);
 int lr_launch_rmsnorm_bwd(const unsigned short* dy, const unsigned short* x, const unsigned short* w,
                           const unsigned short* res, unsigned short* out, int rows, int d, float eps,
                           const int32_t* out_rows, const unsigned short* dt, const unsigned short* a_cat, int r,
-                          uint32_t drop_stream, float drop_p, hipStream_t st);
+                          uint32_t drop_stream, float drop_p, hipStream_t st, int ldt = 2 * LT_RP);  // ldt: row stride of dt
 int lr_launch_ce_bf16(unsigned short* logits, int m, int V, const int32_t* targets, float gscale, float* scal,
                       hipStream_t st);
 int lr_launch_finish_loss(const float* scal, int m, float* out, hipStream_t st);

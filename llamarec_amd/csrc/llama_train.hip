@@ -202,17 +202,24 @@ int lr_launch_skinny(const u16* X, int ldx, int n, int K, const u16* W, int nt, 
 // A workgroup sweeps LT_ROWS rows; a thread owns 8 consecutive columns (4 rotation pairs, one 16-byte access) of all of
 // them, so the r rows of B^T it needs are fetched (from L2) once per LT_ROWS activation rows.
 #define LT_ROWS 4
+// HASK: k_proj carries an adapter too: its t columns come from tk [n][ldtk] (column tkcol), its B^T from bk_t, and its
+// delta is added before the rotation like q's
+template <bool HASK>
 __global__ __launch_bounds__(256) void lt_lora_rope_fwd_kernel(u16* qkv, int n, int qw, int qcols, int kcols, int hd,
                                                                const u16* t /*[n][2*LT_RP]*/, const u16* bq_t,
                                                                const u16* bv_t, int r, float scaling,
-                                                               const int32_t* tok_pos, const float* rope_cs) {
-  __shared__ float ts[LT_ROWS][2 * LT_RP];
+                                                               const int32_t* tok_pos, const float* rope_cs,
+                                                               const u16* tk, int ldtk, int tkcol, const u16* bk_t) {
+  __shared__ float ts[LT_ROWS][(HASK ? 3 : 2) * LT_RP];
   __shared__ int pos[LT_ROWS];
   const int row0 = blockIdx.x * LT_ROWS;
   const int nrows = min(LT_ROWS, n - row0);
   if (threadIdx.x < LT_ROWS * 2 * LT_RP) {
     const int rr = threadIdx.x / (2 * LT_RP), j = threadIdx.x % (2 * LT_RP);
     ts[rr][j] = rr < nrows ? bf2f(t[(size_t)(row0 + rr) * 2 * LT_RP + j]) : 0.f;
+  } else if (HASK && threadIdx.x < LT_ROWS * 3 * LT_RP) {
+    const int i = threadIdx.x - LT_ROWS * 2 * LT_RP, rr = i / LT_RP, j = i % LT_RP;
+    ts[rr][2 * LT_RP + j] = rr < nrows ? bf2f(tk[(size_t)(row0 + rr) * ldtk + tkcol + j]) : 0.f;
   }
   if (threadIdx.x < LT_ROWS) pos[threadIdx.x] = threadIdx.x < nrows ? tok_pos[row0 + threadIdx.x] : 0;
   __syncthreads();
@@ -226,9 +233,9 @@ __global__ __launch_bounds__(256) void lt_lora_rope_fwd_kernel(u16* qkv, int n, 
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[rr][e] = bf2f(in[e]);
     }
-    if (isq || isv) {
-      const u16* bt = isq ? bq_t + c : bv_t + (c - qcols - kcols);
-      const int ld = isq ? qcols : vcols, toff = isq ? 0 : LT_RP;
+    if (isq || isv || HASK) {
+      const u16* bt = isq ? bq_t + c : isv ? bv_t + (c - qcols - kcols) : bk_t + (c - qcols);
+      const int ld = isq ? qcols : isv ? vcols : kcols, toff = isq ? 0 : isv ? LT_RP : 2 * LT_RP;
       float l[LT_ROWS][8];
 #pragma unroll
       for (int rr = 0; rr < LT_ROWS; ++rr)
@@ -272,12 +279,16 @@ __global__ __launch_bounds__(256) void lt_lora_rope_fwd_kernel(u16* qkv, int n, 
 }
 int lr_launch_lora_rope_fwd(u16* qkv, int n, int qw, int qcols, int kcols, int hd, const u16* t, const u16* bq_t,
                             const u16* bv_t, int r, float scaling, const int32_t* tok_pos, const float* rope_cs,
-                            hipStream_t st) {
+                            hipStream_t st, const u16* tk, int ldtk, int tkcol, const u16* bk_t) {
   if (n < 1) return LR_OK;
   if (hd % 8 != 0 || qcols % 8 != 0 || kcols % 8 != 0 || qw % 8 != 0)
     LR_FAIL(LR_EUNSUPPORTED, "lora + rotary sweep: head_dim and projection widths must be multiples of 8");
-  hipLaunchKernelGGL(lt_lora_rope_fwd_kernel, dim3((n + LT_ROWS - 1) / LT_ROWS), dim3(256), 0, st, qkv, n, qw, qcols,
-                     kcols, hd, t, bq_t, bv_t, r, scaling, tok_pos, rope_cs);
+  if (bk_t)
+    hipLaunchKernelGGL(lt_lora_rope_fwd_kernel<true>, dim3((n + LT_ROWS - 1) / LT_ROWS), dim3(256), 0, st, qkv, n, qw, qcols,
+                       kcols, hd, t, bq_t, bv_t, r, scaling, tok_pos, rope_cs, tk, ldtk, tkcol, bk_t);
+  else
+    hipLaunchKernelGGL(lt_lora_rope_fwd_kernel<false>, dim3((n + LT_ROWS - 1) / LT_ROWS), dim3(256), 0, st, qkv, n, qw, qcols,
+                       kcols, hd, t, bq_t, bv_t, r, scaling, tok_pos, rope_cs, tk, ldtk, tkcol, bk_t);
   LR_CHECK_LAUNCH("lt_lora_rope_fwd_kernel");
   return LR_OK;
 }
@@ -323,7 +334,9 @@ int lr_launch_rope_bwd(u16* dqkv, int n, int qw, int rot_cols, int hd, const int
 // fragment), a workgroup 256, and walks one chunk of tokens; partial sums leave with one fp32 atomic per (j, c).
 //   layout 0: out_t[j * cols + c]                          (d A: [r][hidden], tile t -> out0 / out1)
 //   layout 1: out0[c * r + j]                              (d B_v: [cols][r])
-//   layout 2: out0[orig(c) * r + j], packed -> HF column   (d B_q)
+//   layout 2: out0[orig(c) * r + j], packed -> HF column   (d B_q, d B_k)
+//   layout 3: X = the interleaved gate/up gradient (16 gate columns, 16 up columns, ...): tile 0 keeps the gate columns
+//             (out0[f_col * r + j]), tile 1 the up columns (out1); a null out0 / out1 = that adapter is not trained
 template <int NJ>
 __global__ __launch_bounds__(256) void lt_tn_kernel(const u16* __restrict__ T, int ldt, int tcol,
                                                     const u16* __restrict__ X, int ldx, int n, int cols, int chunk,
@@ -368,6 +381,7 @@ __global__ __launch_bounds__(256) void lt_tn_kernel(const u16* __restrict__ T, i
 #pragma unroll
   for (int a = 0; a < NJ; ++a) {
     float* out = a == 0 ? out0 : out1;
+    if (!out) continue;   // a tile whose adapter is not trained
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {
       const int c = c0 + ct * 16 + li;
@@ -380,6 +394,9 @@ __global__ __launch_bounds__(256) void lt_tn_kernel(const u16* __restrict__ T, i
           at = (size_t)j * cols + c;
         } else if (layout == 1) {
           at = (size_t)c * r + j;
+        } else if (layout == 3) {
+          if (((c >> 4) & 1) != a) continue;
+          at = (size_t)((c >> 5) * 16 + (c & 15)) * r + j;
         } else {
           const int head = c / hd, within = c % hd;
           at = (size_t)(head * hd + (within & 1) * half + (within >> 1)) * r + j;
@@ -485,6 +502,7 @@ __global__ __launch_bounds__(256) void lt_tn_lds_kernel(const u16* __restrict__ 
 #pragma unroll
   for (int a = 0; a < NJ; ++a) {
     float* out = a == 0 ? out0 : out1;
+    if (!out) continue;   // a tile whose adapter is not trained
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {
       const int c = c0 + ct * 16 + li;
@@ -497,6 +515,9 @@ __global__ __launch_bounds__(256) void lt_tn_lds_kernel(const u16* __restrict__ 
           at = (size_t)j * cols + c;
         } else if (layout == 1) {
           at = (size_t)c * r + j;
+        } else if (layout == 3) {
+          if (((c >> 4) & 1) != a) continue;
+          at = (size_t)((c >> 5) * 16 + (c & 15)) * r + j;
         } else {
           const int head = c / hd, within = c % hd;
           at = (size_t)(head * hd + (within & 1) * half + (within >> 1)) * r + j;
@@ -559,6 +580,110 @@ int lr_launch_lora_da(const u16* xn, int n, int d, const u16* dt, int r, uint32_
   return launch_tn(2, dt, 2 * LT_RP, 0, xn, d, n, d, 1.0f, daq, dav, r, 0, 0, drop_stream, drop_p, st);
 }
 
+int lr_launch_lora_tn(int nj, const u16* T, int ldt, int tcol, const u16* X, int ldx, int n, int cols, float scale,
+                      float* out0, float* out1, int r, int layout, int hd, uint32_t drop_stream, float drop_p,
+                      hipStream_t st) {
+  return launch_tn(nj, T, ldt, tcol, X, ldx, n, cols, scale, out0, out1, r, layout, hd, drop_stream, drop_p, st);
+}
+
+// =============================================================================================
+// adapters on any Linear (k, o, gate, up, down): working copies, and the rank-r expand-add sweep
+// =============================================================================================
+// One module's bf16 working copies from its fp32 masters (peft's A [r][in], B [out][r]):
+//   a_w [LT_RP][in]      rows >= r zero
+//   b_t [LT_RP][ldb]     b_t[j][dest(o)] = B[o][j]: the transpose, in the column order of the activation it is added to
+//     perm 0 plain; 1 rotary pair interleave within each head (q, k); 2 / 3 the gate / up columns of the interleaved
+//     gate-up activation (ldb = 2 * out; the other half's columns of these rows are never written and stay zero from
+//     the state's initial memset: the [2*LT_RP][2f] pair is then a plain weight for the d t product over d gu)
+__global__ __launch_bounds__(256) void lt_prep_module_kernel(const float* a, const float* b, int r, int in, int out,
+                                                             int perm, int hd, u16* a_w, u16* b_t, int ldb) {
+  const int na = LT_RP * in, nb = LT_RP * out;
+  const int half = hd >> 1;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < na + nb; i += gridDim.x * 256) {
+    if (i < na) {
+      const int j = i / in, c = i % in;
+      a_w[i] = j < r ? f2bf(a[(size_t)j * in + c]) : (u16)0;
+    } else {
+      const int k = i - na, j = k / out, c = k % out;
+      int orig = c, dest = c;
+      if (perm == 1) {
+        const int head = c / hd, within = c % hd;
+        orig = head * hd + (within & 1) * half + (within >> 1);
+      } else if (perm >= 2) {
+        dest = (c >> 4) * 32 + (perm == 3 ? 16 : 0) + (c & 15);
+      }
+      b_t[(size_t)j * ldb + dest] = j < r ? f2bf(b[(size_t)orig * r + j]) : (u16)0;
+    }
+  }
+}
+int lr_launch_prep_module(const float* a, const float* b, int r, int in, int out, int perm, int hd, u16* a_w, u16* b_t,
+                          int ldb, hipStream_t st) {
+  const int total = LT_RP * (in + out);
+  hipLaunchKernelGGL(lt_prep_module_kernel, dim3(min(1024, (total + 255) / 256)), dim3(256), 0, st, a, b, r, in, out,
+                     perm, hd, a_w, b_t, ldb);
+  LR_CHECK_LAUNCH("lt_prep_module_kernel");
+  return LR_OK;
+}
+
+// Y[row][c] = bf16(Y[row][c] + keep(row, c) * bf16(bf16(sum_j T[row][tcol + j] * W[j][c]) * s))
+//   forward  (Y = xmid / x_next behind o_proj's / down_proj's residual GEMM, T = drop(X) A^T, W = B^T, s = alpha / r, no mask):
+//            the adapter's delta, rounded like peft's bf16 lora_B output and its scaling under autocast
+//   backward (Y = the gradient of the adapter's INPUT, T = d t, W = A, s = 1 / (1 - p), mask = the input's dropout mask)
+// (k's and gate / up's deltas ride in lt_lora_rope_fwd_kernel, lt_swiglu_lora_fwd_kernel and the norm backward's LoRA arm.)
+// A workgroup sweeps LT_ROWS rows; a thread owns 8 consecutive columns (one 16-byte access, whole 128-byte lines per 8 lanes) of
+// all of them, so the r rows of W it needs come from L2 once per LT_ROWS activation rows -- lt_lora_rope_fwd_kernel's shape.
+__global__ __launch_bounds__(256) void lt_lora_expand_kernel(u16* Y, int ldy, int n, int cols, const u16* T, int ldt,
+                                                             int tcol, const u16* W, int r, float s,
+                                                             uint32_t drop_stream, uint32_t drop_thresh) {
+  __shared__ float ts[LT_ROWS][LT_RP];
+  const int row0 = blockIdx.x * LT_ROWS;
+  const int nrows = min(LT_ROWS, n - row0);
+  if (threadIdx.x < LT_ROWS * LT_RP) {
+    const int rr = threadIdx.x / LT_RP, j = threadIdx.x % LT_RP;
+    ts[rr][j] = rr < nrows ? bf2f(T[(size_t)(row0 + rr) * ldt + tcol + j]) : 0.f;
+  }
+  __syncthreads();
+  for (int c = threadIdx.x * 8; c < cols; c += 256 * 8) {
+    float l[LT_ROWS][8];
+#pragma unroll
+    for (int rr = 0; rr < LT_ROWS; ++rr)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) l[rr][e] = 0.f;
+    for (int j = 0; j < r; ++j) {
+      const u16x8 b = *reinterpret_cast<const u16x8*>(W + (size_t)j * cols + c);
+#pragma unroll
+      for (int rr = 0; rr < LT_ROWS; ++rr) {
+        const float tj = ts[rr][j];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) l[rr][e] = __builtin_fmaf(tj, bf2f(b[e]), l[rr][e]);
+      }
+    }
+#pragma unroll
+    for (int rr = 0; rr < LT_ROWS; ++rr) {
+      if (rr >= nrows) continue;
+      u16* yp = Y + (size_t)(row0 + rr) * ldy + c;
+      const u16x8 in = *reinterpret_cast<const u16x8*>(yp);
+      u16x8 o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const bool keep = !drop_thresh || lt_keep(drop_stream, row0 + rr, c + e, drop_thresh);
+        o[e] = keep ? f2bf(bf2f(in[e]) + bf2f(f2bf(bf2f(f2bf(l[rr][e])) * s))) : in[e];
+      }
+      *reinterpret_cast<u16x8*>(yp) = o;
+    }
+  }
+}
+int lr_launch_lora_expand(u16* Y, int ldy, int n, int cols, const u16* T, int ldt, int tcol, const u16* W, int r, float s,
+                          uint32_t drop_stream, float drop_p, hipStream_t st) {
+  if (n < 1) return LR_OK;
+  if (cols % 8 != 0 || ldy % 8 != 0 || ((uintptr_t)Y & 15) != 0)
+    LR_FAIL(LR_EUNSUPPORTED, "rank-r expand-add: cols=%d ld=%d", cols, ldy);
+  hipLaunchKernelGGL(lt_lora_expand_kernel, dim3((n + LT_ROWS - 1) / LT_ROWS), dim3(256), 0, st, Y, ldy, n, cols, T, ldt,
+                     tcol, W, r, s, drop_stream, lt_drop_thresh(drop_p));
+  LR_CHECK_LAUNCH("lt_lora_expand_kernel");
+  return LR_OK;
+}
+
 // =============================================================================================
 // SwiGLU on the interleaved gate/up layout of the packed wgu GEMM (16 gate columns, 16 up columns, ...)
 // =============================================================================================
@@ -575,6 +700,67 @@ __global__ __launch_bounds__(256) void lt_swiglu_fwd_kernel(const u16* gu, u16* 
     for (int e = 0; e < 8; ++e) o[e] = swiglu_bf16(bf2f(g[e]), bf2f(u[e]));
     *reinterpret_cast<u16x8*>(h + row * f + c) = o;
   }
+}
+// The same pass with the gate / up adapters' delta: gu += s * t W (t [n][ldt] from column tcol: 16 gate ranks, 16 up ranks;
+// W [2*LT_RP][2f] = their B^T in gu's interleaved column order), written BACK to gu -- the saved pre-activation values the
+// backward differentiates at -- and h = swiglu of the sum. Rounded like lt_lora_rope_fwd_kernel's q / v delta. A workgroup
+// takes LT_ROWS rows so that the 2r rows of W a thread needs come from L2 once per LT_ROWS activation rows.
+__global__ __launch_bounds__(256) void lt_swiglu_lora_fwd_kernel(u16* gu, u16* h, int n, int f, const u16* t, int ldt, int tcol,
+                                                                 const u16* W, int r, float s) {
+  __shared__ float ts[LT_ROWS][2 * LT_RP];
+  const int row0 = blockIdx.x * LT_ROWS;
+  const int nrows = min(LT_ROWS, n - row0);
+  if (threadIdx.x < LT_ROWS * 2 * LT_RP) {
+    const int rr = threadIdx.x / (2 * LT_RP), j = threadIdx.x % (2 * LT_RP);
+    ts[rr][j] = rr < nrows ? bf2f(t[(size_t)(row0 + rr) * ldt + tcol + j]) : 0.f;
+  }
+  __syncthreads();
+  for (int c = threadIdx.x * 8; c < f; c += 256 * 8) {
+    const int pc = (c >> 4) * 32 + (c & 15);  // gate columns pc .. pc+7, up columns pc+16 .. pc+23
+    float lg[LT_ROWS][8], lu[LT_ROWS][8];
+#pragma unroll
+    for (int rr = 0; rr < LT_ROWS; ++rr)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) lg[rr][e] = lu[rr][e] = 0.f;
+    for (int j = 0; j < r; ++j) {
+      const u16x8 bg = *reinterpret_cast<const u16x8*>(W + (size_t)j * 2 * f + pc);
+      const u16x8 bu = *reinterpret_cast<const u16x8*>(W + (size_t)(LT_RP + j) * 2 * f + pc + 16);
+#pragma unroll
+      for (int rr = 0; rr < LT_ROWS; ++rr) {
+        const float tg = ts[rr][j], tu = ts[rr][LT_RP + j];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          lg[rr][e] = __builtin_fmaf(tg, bf2f(bg[e]), lg[rr][e]);
+          lu[rr][e] = __builtin_fmaf(tu, bf2f(bu[e]), lu[rr][e]);
+        }
+      }
+    }
+#pragma unroll
+    for (int rr = 0; rr < LT_ROWS; ++rr) {
+      if (rr >= nrows) continue;
+      u16* p = gu + (size_t)(row0 + rr) * 2 * f + pc;
+      u16x8 g = *reinterpret_cast<const u16x8*>(p), u = *reinterpret_cast<const u16x8*>(p + 16);
+      u16x8 o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        g[e] = f2bf(bf2f(g[e]) + bf2f(f2bf(bf2f(f2bf(lg[rr][e])) * s)));
+        u[e] = f2bf(bf2f(u[e]) + bf2f(f2bf(bf2f(f2bf(lu[rr][e])) * s)));
+        o[e] = swiglu_bf16(bf2f(g[e]), bf2f(u[e]));
+      }
+      *reinterpret_cast<u16x8*>(p) = g;
+      *reinterpret_cast<u16x8*>(p + 16) = u;
+      *reinterpret_cast<u16x8*>(h + (size_t)(row0 + rr) * f + c) = o;
+    }
+  }
+}
+int lr_launch_swiglu_lora_fwd(u16* gu, u16* h, int n, int f, const u16* t, int ldt, int tcol, const u16* W, int r, float s,
+                              hipStream_t st) {
+  if (n < 1) return LR_OK;
+  if (f % 16 != 0) LR_FAIL(LR_EUNSUPPORTED, "swiglu: intermediate size %d", f);
+  hipLaunchKernelGGL(lt_swiglu_lora_fwd_kernel, dim3((n + LT_ROWS - 1) / LT_ROWS), dim3(256), 0, st, gu, h, n, f, t, ldt, tcol,
+                     W, r, s);
+  LR_CHECK_LAUNCH("lt_swiglu_lora_fwd_kernel");
+  return LR_OK;
 }
 // in place: (gate, up) -> (d gate, d up) given d h
 __global__ __launch_bounds__(256) void lt_swiglu_bwd_kernel(u16* gu, const u16* dh, size_t total8, int f) {
@@ -631,7 +817,7 @@ __global__ __launch_bounds__(256) void lt_rmsnorm_bwd_kernel(const u16* dy, cons
                                                              u16* out, int n, int d, float eps, const int32_t* out_rows,
                                                              const u16* dt, const u16* a_cat, int r,
                                                              uint32_t drop_stream, uint32_t drop_thresh,
-                                                             float drop_scale) {
+                                                             float drop_scale, int ldt) {
   __shared__ float sh[4][2 * ROWS];
   __shared__ float ts[ROWS][2 * LT_RP];
   const int row0 = blockIdx.x * ROWS;
@@ -640,7 +826,7 @@ __global__ __launch_bounds__(256) void lt_rmsnorm_bwd_kernel(const u16* dy, cons
   if (LORA) {
     if (threadIdx.x < ROWS * 2 * LT_RP) {
       const int rr = threadIdx.x / (2 * LT_RP), j = threadIdx.x % (2 * LT_RP);
-      ts[rr][j] = rr < nrows ? bf2f(dt[(size_t)(row0 + rr) * 2 * LT_RP + j]) : 0.f;
+      ts[rr][j] = rr < nrows ? bf2f(dt[(size_t)(row0 + rr) * ldt + j]) : 0.f;
     }
     __syncthreads();
   }
@@ -737,7 +923,7 @@ __global__ __launch_bounds__(256) void lt_rmsnorm_bwd_kernel(const u16* dy, cons
 }
 int lr_launch_rmsnorm_bwd(const u16* dy, const u16* x, const u16* w, const u16* res, u16* out, int rows, int d, float eps,
                           const int32_t* out_rows, const u16* dt, const u16* a_cat, int r, uint32_t drop_stream,
-                          float drop_p, hipStream_t st) {
+                          float drop_p, hipStream_t st, int ldt) {
   if (rows < 1) return LR_OK;
   if (d % 8 != 0 || d > 256 * 8 * LT_NORM_CHUNKS)
     LR_FAIL(LR_EUNSUPPORTED, "rmsnorm backward: hidden_size %d (multiple of 8, <= %d)", d, 256 * 8 * LT_NORM_CHUNKS);
@@ -745,7 +931,7 @@ int lr_launch_rmsnorm_bwd(const u16* dy, const u16* x, const u16* w, const u16* 
   const float ds = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
 #define LT_NORM_LAUNCH(ROWS, CH, LORA)                                                                              \
   hipLaunchKernelGGL((lt_rmsnorm_bwd_kernel<ROWS, CH, LORA>), dim3((rows + ROWS - 1) / ROWS), dim3(256), 0, st, dy, x, w, \
-                     res, out, rows, d, eps, out_rows, dt, a_cat, r, drop_stream, th, ds)
+                     res, out, rows, d, eps, out_rows, dt, a_cat, r, drop_stream, th, ds, ldt)
   const int chunks = (d + 2047) / 2048;
   if (dt) {
     if (chunks <= 1) LT_NORM_LAUNCH(4, 1, true);

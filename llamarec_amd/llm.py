@@ -5,14 +5,15 @@ Reference interface being replaced (paths into the reference tree):
   LlamaForCausalLM.forward(input_ids[B,T], attention_mask[B,T], labels=...) ->
       CausalLMOutputWithPast(loss=tensor(-1.0), logits=fp32[B,vocab])   model/llm.py:35-145
   ManualVerbalizer.process_logits(logits) -> fp32[B,20]                 trainer/verb.py:546-586
-  weights: bf16 compute over NF4-quantised base + LoRA(q_proj,v_proj)   train_ranker.py:49-79;
-           here bf16 weights with the adapter merged at load (W + (alpha/r) B A).
+  weights: bf16 compute over NF4-quantised base + LoRA(--lora_target_modules)   train_ranker.py:49-79;
+           here bf16 weights with the adapter merged at load (W + (alpha/r) B A) into each Linear it targets.
 """
 from __future__ import annotations
 
 import ctypes as C
 import json
 import os
+import re
 from dataclasses import dataclass
 
 import numpy as np
@@ -116,17 +117,88 @@ def unpad_left(input_ids, attention_mask=None):
     return out
 
 
+# the Linears of a decoder layer an adapter may sit on (_abi.LORA_MODULES: the one list, in the kernels' order) -> HF block
+LORA_MODULE_BLOCK = {m: "mlp" if m in ("gate_proj", "up_proj", "down_proj") else "self_attn" for m in A.LORA_MODULES}
+_LORA_KEY = re.compile(r"^model\.layers\.(\d+)\.(self_attn|mlp)\.([a-z]+_proj)\.lora_([AB])\.weight$")
+
+
+def expand_target_modules(target_modules):
+    """peft's `target_modules` (a list of names, or the string "all-linear") -> tuple of names in the kernels' order.
+    A name that is no Linear of a Llama decoder layer (phi-3's fused qkv_proj, lm_head, ...) raises."""
+    if isinstance(target_modules, str):
+        target_modules = [target_modules]
+    names = set()
+    for m in target_modules or ():
+        names.update(LORA_MODULE_BLOCK if m == "all-linear" else [m])
+    bad = sorted(names - set(LORA_MODULE_BLOCK))
+    if bad:
+        raise NotImplementedError(f"target_modules {bad}: adapters are supported on {', '.join(LORA_MODULE_BLOCK)}")
+    if not names:
+        raise ValueError("target_modules is empty")
+    return tuple(m for m in LORA_MODULE_BLOCK if m in names)
+
+
+def check_adapter_config(ac):
+    """adapter_config.json -> (r, alpha, target modules). Anything that changes what W + (alpha/r) B A means is refused by the
+    name of its field (it would otherwise load and score silently wrong); missing optional keys take peft's defaults."""
+    def refuse(field, why):
+        raise NotImplementedError(f"adapter_config.json: {field}={ac.get(field)!r}: {why}")
+
+    if str(ac.get("peft_type", "LORA")).upper() != "LORA":
+        refuse("peft_type", "only LoRA adapters are merged at load")
+    if ac.get("use_dora", False):
+        refuse("use_dora", "DoRA's magnitude vectors are not implemented")
+    if ac.get("use_rslora", False):
+        refuse("use_rslora", "the scaling is alpha / r, not alpha / sqrt(r)")
+    for field in ("rank_pattern", "alpha_pattern"):
+        if ac.get(field):
+            refuse(field, "per-module ranks / alphas are not implemented")
+    if ac.get("bias", "none") != "none":
+        refuse("bias", "trained biases are not implemented (the base Linears have none)")
+    if ac.get("fan_in_fan_out", False):
+        refuse("fan_in_fan_out", "transposed base weights are not implemented")
+    if ac.get("modules_to_save"):
+        refuse("modules_to_save", "fully trained copies of base modules are not implemented")
+    if "r" not in ac or "lora_alpha" not in ac:
+        raise ValueError("adapter_config.json: r and lora_alpha are required")
+    tm = ac.get("target_modules")
+    return ac["r"], ac["lora_alpha"], (expand_target_modules(tm) if tm else None)
+
+
+def adapter_weights(tensors, r, target_modules=None):
+    """{PEFT tensor name: array} -> {"model.layers.{l}.{block}.{module}.lora_{A,B}.weight": fp32 array}. Every tensor must belong
+    to a Linear of a decoder layer (one of `target_modules` when the config names them), have rank r, and come as an A/B pair."""
+    w = {}
+    for k, v in tensors.items():
+        name = k.replace("base_model.model.", "", 1).replace(".default", "")
+        m = _LORA_KEY.match(name)
+        if not m or LORA_MODULE_BLOCK.get(m.group(3)) != m.group(2):
+            raise NotImplementedError(f"adapter tensor {k!r} maps to no Linear of a decoder layer "
+                                      f"({', '.join(LORA_MODULE_BLOCK)})")
+        if target_modules is not None and m.group(3) not in target_modules:
+            raise ValueError(f"adapter tensor {k!r} is not among adapter_config.json's target_modules {list(target_modules)}")
+        v = np.asarray(v, dtype=np.float32)
+        if v.ndim != 2 or v.shape[0 if m.group(4) == "A" else 1] != r:
+            raise ValueError(f"adapter tensor {k!r} has shape {v.shape}: rank {r} expected")
+        w[name] = v
+    for name in w:
+        other = name.replace("lora_A", "lora_B") if "lora_A" in name else name.replace("lora_B", "lora_A")
+        if other not in w:
+            raise ValueError(f"adapter tensor {name!r} has no partner {other!r}")
+    return w
+
+
 def load_peft_adapter(adapter_path):
     """A local PEFT LoRA directory (adapter_config.json + adapter_model.safetensors) -> the `lora` argument of
-    LlamaRanker.from_state_dict."""
+    LlamaRanker.from_state_dict. Runs on the host alone."""
     from safetensors import safe_open
 
-    ac = json.load(open(os.path.join(adapter_path, "adapter_config.json")))
-    w = {}
+    r, alpha, modules = check_adapter_config(json.load(open(os.path.join(adapter_path, "adapter_config.json"))))
+    t = {}
     with safe_open(os.path.join(adapter_path, "adapter_model.safetensors"), framework="pt", device="cpu") as f:
         for k in f.keys():
-            w[k.replace("base_model.model.", "").replace(".default", "")] = f.get_tensor(k).float().numpy()
-    return dict(r=ac["r"], alpha=ac["lora_alpha"], weights=w)
+            t[k] = f.get_tensor(k).float().numpy()
+    return dict(r=r, alpha=alpha, weights=adapter_weights(t, r, modules), target_modules=modules)
 
 
 class LlamaRanker:
@@ -196,6 +268,12 @@ class LlamaRanker:
             return w
 
         L = config["num_hidden_layers"]
+        if lora is not None:   # a key no Linear below would pick up (another layer count, lm_head, ...) must not vanish silently
+            known = {f"model.layers.{i}.{blk}.{m}.lora_{ab}.weight" for i in range(L) for m, blk in LORA_MODULE_BLOCK.items()
+                     for ab in "AB"}
+            stray = sorted(set(lora["weights"]) - known)
+            if stray:
+                raise NotImplementedError(f"adapter tensors that map to no Linear of this model's decoder layers: {stray[:4]}")
         T = self._tensors
         T["embed"] = t("model.embed_tokens.weight").to(torch.bfloat16).contiguous()
         T["final_norm"] = t("model.norm.weight").to(torch.bfloat16).contiguous()
@@ -205,9 +283,9 @@ class LlamaRanker:
             q, k, v = (merged(p + f"self_attn.{n}_proj.weight") for n in "qkv")
             T[f"{i}.wqkv"] = torch.cat([self._interleave_rope_rows(q), self._interleave_rope_rows(k), v],
                                        0).to(torch.bfloat16).contiguous()
-            T[f"{i}.wo"] = linear(p + "self_attn.o_proj.weight").to(torch.bfloat16).contiguous()
-            T[f"{i}.wgu"] = self._interleave_gate_up(linear(p + "mlp.gate_proj.weight"), linear(p + "mlp.up_proj.weight"))
-            T[f"{i}.wdown"] = linear(p + "mlp.down_proj.weight").to(torch.bfloat16).contiguous()
+            T[f"{i}.wo"] = merged(p + "self_attn.o_proj.weight").to(torch.bfloat16).contiguous()
+            T[f"{i}.wgu"] = self._interleave_gate_up(merged(p + "mlp.gate_proj.weight"), merged(p + "mlp.up_proj.weight"))
+            T[f"{i}.wdown"] = merged(p + "mlp.down_proj.weight").to(torch.bfloat16).contiguous()
             T[f"{i}.input_norm"] = t(p + "input_layernorm.weight").to(torch.bfloat16).contiguous()
             T[f"{i}.post_norm"] = t(p + "post_attention_layernorm.weight").to(torch.bfloat16).contiguous()
         self._create()

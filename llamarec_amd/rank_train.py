@@ -1,6 +1,6 @@
 """Ranker LoRA fine-tuning -- host-side mirror of the reference's `LLMTrainer.train()` path
 (trainer/llm.py:76-136 over the patched LlamaForCausalLM of model/llm.py:89-127 with peft LoRA on
-q_proj / v_proj, train_ranker.py:71-79), backed by the HIP training step of
+the Linears --lora_target_modules names, q_proj / v_proj by default, train_ranker.py:71-79), backed by the HIP training step of
 `csrc/api_llama_train.hip` (no torch compute, no fallback).
 
   LoraTrainEngine   one replica: frozen bf16 base (a LlamaRanker built WITHOUT a merged adapter), fp32 LoRA
@@ -23,10 +23,37 @@ import torch
 
 from . import _abi as A
 from ._lib import check, lib, stream_ptr
-from .llm import LlamaRanker, pack_prompts
+from .llm import LORA_MODULE_BLOCK, LlamaRanker, expand_target_modules, pack_prompts
 
 IGNORE = -100
-PEFT_KEY = "base_model.model.model.layers.{l}.self_attn.{p}_proj.lora_{ab}.weight"
+PEFT_KEY = "base_model.model.model.layers.{l}.{block}.{p}_proj.lora_{ab}.weight"
+DEFAULT_TARGET_MODULES = ("q_proj", "v_proj")
+
+
+def peft_key(layer, module, ab):
+    """adapter_model.safetensors key of layers.{layer}.{module}.lora_{ab} (module: "q_proj", ...; ab: "A" | "B")."""
+    return PEFT_KEY.format(l=layer, block=LORA_MODULE_BLOCK[module], p=module[:-len("_proj")], ab=ab)
+
+
+def lora_shapes(config, r, target_modules, head_dim=None):
+    """{(module, "A" | "B"): shape} in peft's layouts (A [r][in], B [out][r]) for a HF Llama config."""
+    d, f = config["hidden_size"], config["intermediate_size"]
+    hd = head_dim or config.get("head_dim") or d // config["num_attention_heads"]
+    qc, kv = config["num_attention_heads"] * hd, config["num_key_value_heads"] * hd
+    io = {"q_proj": (d, qc), "k_proj": (d, kv), "v_proj": (d, kv), "o_proj": (qc, d), "gate_proj": (d, f),
+          "up_proj": (d, f), "down_proj": (f, d)}
+    out = {}
+    for mod in expand_target_modules(target_modules):
+        out[(mod, "A")] = (r, io[mod][0])
+        out[(mod, "B")] = (io[mod][1], r)
+    return out
+
+
+def adapter_config(r, alpha, target_modules, base_model=""):
+    """The adapter_config.json save_adapter writes (what LlamaRanker.from_pretrained / peft read back)."""
+    return {"peft_type": "LORA", "task_type": "CAUSAL_LM", "r": r, "lora_alpha": alpha, "lora_dropout": 0.0,
+            "bias": "none", "target_modules": list(expand_target_modules(target_modules)),
+            "base_model_name_or_path": base_model, "fan_in_fan_out": False, "inference_mode": True}
 
 
 def loss_rows_and_targets(seqs, labels):
@@ -46,9 +73,19 @@ def loss_rows_and_targets(seqs, labels):
 
 class LoraTrainEngine:
     def __init__(self, ranker: LlamaRanker, r=8, alpha=32, dropout=0.05, seed=42, beta1=0.9, beta2=0.999, eps=1e-8,
-                 weight_decay=0.0, init=None):
+                 weight_decay=0.0, init=None, target_modules=DEFAULT_TARGET_MODULES, create_call=None):
+        """create_call: which of the C ABI's three routes makes the handle -- "plain" (lr_llama_lora_create), "ex_null"
+        (lr_llama_lora_create_ex with targets == NULL) or "ex" (with the module mask). Default: "plain" for q_proj | v_proj,
+        the call this class always made, "ex" otherwise. The first two exist only for q_proj | v_proj."""
         self.ranker, self.device = ranker, ranker.device
         self.r, self.alpha = int(r), float(alpha)
+        self.target_modules = expand_target_modules(target_modules)
+        targets = A.LrLoraTargets(modules=sum(1 << A.LORA_MODULES.index(m) for m in self.target_modules))
+        qv = set(self.target_modules) == set(DEFAULT_TARGET_MODULES)
+        create_call = create_call or ("plain" if qv else "ex")
+        if create_call not in ("plain", "ex_null", "ex") or (create_call != "ex" and not qv):
+            raise ValueError(f"create_call={create_call!r} with target_modules {self.target_modules}")
+        tp = C.byref(targets) if create_call == "ex" else None
         c = ranker.config
         self.L = c["num_hidden_layers"]
         T, L_ = ranker._tensors, lib()
@@ -69,14 +106,19 @@ class LoraTrainEngine:
             desc = A.LrLlamaWeightsTDesc(layers=arr, lm_head_t=self._t["lm_head_t"].data_ptr())
             cfg = A.LrLoraTrainConfig(r=self.r, alpha=self.alpha, dropout=float(dropout), beta1=beta1, beta2=beta2,
                                       eps=eps, weight_decay=weight_decay, seed=int(seed))
-            nbytes = L_.lr_llama_lora_state_bytes(ranker._h, C.byref(cfg))
+            nbytes = (L_.lr_llama_lora_state_bytes(ranker._h, C.byref(cfg)) if create_call == "plain" else
+                      L_.lr_llama_lora_state_bytes_ex(ranker._h, C.byref(cfg), tp))
             if nbytes == 0:
                 check(1, "lr_llama_lora_state_bytes")
             self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             h = C.c_void_p()
-            check(L_.lr_llama_lora_create(ranker._h, C.byref(desc), C.byref(cfg), self._state.data_ptr(), nbytes,
-                                          stream_ptr(), C.byref(h)), "lr_llama_lora_create")
-            self._h, self._arr = h, arr
+            if create_call == "plain":
+                check(L_.lr_llama_lora_create(ranker._h, C.byref(desc), C.byref(cfg), self._state.data_ptr(), nbytes,
+                                              stream_ptr(), C.byref(h)), "lr_llama_lora_create")
+            else:
+                check(L_.lr_llama_lora_create_ex(ranker._h, C.byref(desc), C.byref(cfg), tp, self._state.data_ptr(), nbytes,
+                                                 stream_ptr(), C.byref(h)), "lr_llama_lora_create_ex")
+            self._h, self._arr, self._desc = h, arr, desc
             ptrs = [C.c_void_p() for _ in range(4)]
             n = C.c_size_t()
             check(L_.lr_llama_lora_buffers(h, *[C.byref(p) for p in ptrs], C.byref(n)), "lr_llama_lora_buffers")
@@ -99,20 +141,18 @@ class LoraTrainEngine:
         return off.value, cnt.value
 
     def shapes(self):
-        c = self.ranker.config
-        d, hd = c["hidden_size"], self.ranker.hd
-        return {("q", "A"): (self.r, d), ("q", "B"): (c["num_attention_heads"] * hd, self.r),
-                ("v", "A"): (self.r, d), ("v", "B"): (c["num_key_value_heads"] * hd, self.r)}
+        """{(module, "A" | "B"): shape} of the selected modules ("q_proj", ...), peft's layouts."""
+        return lora_shapes(self.ranker.config, self.r, self.target_modules, self.ranker.hd)
 
     def named(self, buf=None):
-        """{"layers.{l}.{q,v}_proj.lora_{A,B}": view into the flat buffer (default: parameters)}."""
+        """{"layers.{l}.{module}.lora_{A,B}": view into the flat buffer (default: parameters)}."""
         buf = self.params if buf is None else buf
         out, sh = {}, self.shapes()
         for l in range(self.L):
-            for wi, p in enumerate("qv"):
+            for mod in self.target_modules:
                 for ai, ab in enumerate("AB"):
-                    off, cnt = self._range(l, wi, ai)
-                    out[f"layers.{l}.{p}_proj.lora_{ab}"] = buf[off:off + cnt].view(sh[(p, ab)])
+                    off, cnt = self._range(l, A.LORA_MODULES.index(mod), ai)
+                    out[f"layers.{l}.{mod}.lora_{ab}"] = buf[off:off + cnt].view(sh[(mod, ab)])
         return out
 
     def peft_init(self, seed):
@@ -123,9 +163,9 @@ class LoraTrainEngine:
             for l in range(self.L):
                 if ab == "A":
                     bound = 1.0 / math.sqrt(shape[1])
-                    out[f"layers.{l}.{p}_proj.lora_A"] = (torch.rand(shape, generator=g) * 2 - 1) * bound
+                    out[f"layers.{l}.{p}.lora_A"] = (torch.rand(shape, generator=g) * 2 - 1) * bound
                 else:
-                    out[f"layers.{l}.{p}_proj.lora_B"] = torch.zeros(shape)
+                    out[f"layers.{l}.{p}.lora_B"] = torch.zeros(shape)
         return out
 
     def load(self, weights):
@@ -140,8 +180,8 @@ class LoraTrainEngine:
         """PEFT-named CPU tensors (adapter_model.safetensors keys)."""
         out = {}
         for k, v in self.named().items():
-            parts = k.split(".")   # layers.{l}.{q,v}_proj.lora_{A,B}
-            out[PEFT_KEY.format(l=parts[1], p=parts[2][0], ab=parts[3][-1])] = v.detach().cpu().clone()
+            parts = k.split(".")   # layers.{l}.{module}.lora_{A,B}
+            out[peft_key(parts[1], parts[2], parts[3][-1])] = v.detach().cpu().clone()
         return out
 
     def save_adapter(self, path, base_model=""):
@@ -149,9 +189,7 @@ class LoraTrainEngine:
         from safetensors.torch import save_file
 
         os.makedirs(path, exist_ok=True)
-        json.dump({"peft_type": "LORA", "task_type": "CAUSAL_LM", "r": self.r, "lora_alpha": self.alpha,
-                   "lora_dropout": 0.0, "bias": "none", "target_modules": ["q_proj", "v_proj"],
-                   "base_model_name_or_path": base_model, "fan_in_fan_out": False, "inference_mode": True},
+        json.dump(adapter_config(self.r, self.alpha, self.target_modules, base_model),
                   open(os.path.join(path, "adapter_config.json"), "w"), indent=1)
         save_file(self.export(), os.path.join(path, "adapter_model.safetensors"))
 
@@ -230,19 +268,37 @@ class LoraTrainEngine:
     prefill_verbalize = scores   # the evaluator's call (llamarec_amd.rerank.LLMEvaluator)
 
     def merge_into_base_(self):
-        """W_q, W_v += (alpha/r) B A in the ranker's packed bf16 weights (what LlamaRanker.from_state_dict(lora=...) does
+        """W += (alpha/r) B A for every adapted module in the ranker's packed bf16 weights (what LlamaRanker.from_state_dict(lora=...) does
         at load) so that the plain scoring path serves the tuned model. The engine must not be trained further: its
         transposed copies and the now-merged base no longer describe 'base + adapter'."""
         rk, s = self.ranker, self.alpha / self.r
         c = rk.config
         nq, nkv = c["num_attention_heads"] * rk.hd, c["num_key_value_heads"] * rk.hd
         p = self.named()
+        f = c["intermediate_size"]
+
+        def add_(w, delta):
+            w.copy_((w.float() + delta).to(torch.bfloat16))
+
         for l in range(self.L):
+            def delta(mod):
+                return s * (p[f"layers.{l}.{mod}.lora_B"] @ p[f"layers.{l}.{mod}.lora_A"])
+
             w = rk._tensors[f"{l}.wqkv"]
-            dq = rk._interleave_rope_rows(s * (p[f"layers.{l}.q_proj.lora_B"] @ p[f"layers.{l}.q_proj.lora_A"]))
-            dv = s * (p[f"layers.{l}.v_proj.lora_B"] @ p[f"layers.{l}.v_proj.lora_A"])
-            w[:nq] = (w[:nq].float() + dq).to(torch.bfloat16)
-            w[nq + nkv:] = (w[nq + nkv:].float() + dv).to(torch.bfloat16)
+            for mod in self.target_modules:
+                if mod == "q_proj":
+                    add_(w[:nq], rk._interleave_rope_rows(delta(mod)))
+                elif mod == "k_proj":
+                    add_(w[nq:nq + nkv], rk._interleave_rope_rows(delta(mod)))
+                elif mod == "v_proj":
+                    add_(w[nq + nkv:], delta(mod))
+                elif mod == "o_proj":
+                    add_(rk._tensors[f"{l}.wo"], delta(mod))
+                elif mod == "down_proj":
+                    add_(rk._tensors[f"{l}.wdown"], delta(mod))
+                else:   # rows of wgu: 16 of gate, 16 of up, ...
+                    gu = rk._tensors[f"{l}.wgu"].view(f // 16, 2, 16, -1)
+                    add_(gu[:, 0 if mod == "gate_proj" else 1], delta(mod).view(f // 16, 16, -1))
         if rk.fold_norms:
             rk.set_fold_norms(True)   # the scoring path's wqkv * diag(input_norm) copies follow the merged weights
         self.merged = True

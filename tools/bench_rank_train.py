@@ -16,6 +16,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def main():
+    from llamarec_amd._abi import LORA_MODULES
+
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--batch", type=int, default=16)       # config.py:90-97: lora_micro_batch_size 16 (8 on beauty)
@@ -23,6 +25,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--accum", type=int, default=1)
     ap.add_argument("--dropout", type=float, default=0.05)
+    ap.add_argument("--lora_target_modules", nargs="+", default=["q_proj", "v_proj"],
+                    choices=list(LORA_MODULES) + ["all-linear"])
     a = ap.parse_args()
     from llamarec_amd.llm import LLAMA2_7B, LlamaRanker
     from llamarec_amd.rank_train import LoraTrainEngine
@@ -30,7 +34,7 @@ def main():
     cfg = dict(LLAMA2_7B, num_hidden_layers=a.layers)
     t0 = time.time()
     ranker = LlamaRanker.random_init(cfg, seed=1)
-    eng = LoraTrainEngine(ranker, dropout=a.dropout)
+    eng = LoraTrainEngine(ranker, dropout=a.dropout, target_modules=a.lora_target_modules)
     # non-zero B so that every kernel of the backward sees real numbers
     init = eng.peft_init(3)
     for k in init:

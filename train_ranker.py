@@ -92,7 +92,8 @@ def main(argv=None, export_root=None):
             raise SystemExit("--llm_adapter_path is merged at load: combine it with --eval_only, or train from the base")
         from llamarec_amd.rank_train import LLMTrainSamples, LoraRankerTrainer, LoraTrainEngine
 
-        engine = LoraTrainEngine(model, r=args.lora_r, alpha=args.lora_alpha, dropout=args.lora_dropout, seed=args.seed)
+        engine = LoraTrainEngine(model, r=args.lora_r, alpha=args.lora_alpha, dropout=args.lora_dropout, seed=args.seed,
+                                 target_modules=args.lora_target_modules)
         samples = LLMTrainSamples(args, dataset["train"], dataset["meta"], tokenizer,
                                   rng=np.random.RandomState(args.seed + rank))
         val_items = build_val_items(dataset, retrieved, tokenizer, args)
