@@ -544,6 +544,14 @@ int lr_llama_lora_param_range(const lr_llama_lora_t* h, int32_t layer, int32_t w
                               size_t* offset, size_t* count);
 size_t lr_llama_lora_workspace_bytes(const lr_llama_lora_t* h, int32_t max_tokens, int32_t max_seqs,
                                      int32_t max_loss_rows);
+/* Default 0. With enable != 0 two calls of lr_llama_lora_loss_grad / lr_llama_lora_apply on the same inputs and the same
+ * handle state give the same bits, whatever else runs on the device. Ask lr_llama_lora_workspace_bytes AFTER enabling.
+ * The mode is a field of the handle and its extra memory a region of the caller's workspace: any number of
+ * deterministic and other handles may be in flight at once. No fp32 atomic then decides a value: token reductions
+ * store per-chunk partial tiles that one fold sums in chunk order, the loss and the gradient norm are summed in a
+ * fixed order, the generic attention backward computes dK / dV per owner. Not promised: the same bits under another
+ * grouping of the batch, another LR_TN_CHUNK or another world size. */
+int lr_llama_lora_set_deterministic(lr_llama_lora_t* h, int32_t enable);
 /* One micro-batch: forward over the packed prompts (as lr_llama_prefill_verbalize packs them), loss
  * = mean over the m labelled rows of -log softmax(logits[loss_rows[i]])[loss_targets[i]] (row p of a
  * prompt predicts token p+1: the caller passes the rows whose NEXT token is labelled, each once),

@@ -107,8 +107,9 @@ def build_parser():
     p.add_argument("--dist_backend", type=str, default=None, help="torch.distributed backend under torchrun (default nccl = RCCL)")
     p.add_argument("--share_gpu", action="store_true", help="rehearsal: every rank uses cuda:0 (with --dist_backend gloo)")
     p.add_argument("--max_train_iterations", type=int, default=None, help="stop after this many optimizer steps")
-    p.add_argument("--deterministic", action="store_true", help="retriever training: run-to-run identical bits (fixed-point "
-                   "accumulation instead of fp32 atomics; ~0.1 ms per step on Beauty)")
+    p.add_argument("--deterministic", action="store_true", help="run-to-run identical bits. train_retriever.py: fixed-point "
+                   "accumulation instead of fp32 atomics (~0.1 ms per step on Beauty); train_ranker.py: the LoRA step's token "
+                   "reductions, loss and gradient norm summed in a fixed order (LoraTrainEngine.set_deterministic)")
     return p
 
 

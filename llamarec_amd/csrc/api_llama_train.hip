@@ -36,6 +36,9 @@ struct lr_llama_lora {
   // empty round of tiles leaves idle (7 k tokens: 448 tiles on 256 CUs). LR_LORA_OVERLAP=0 keeps everything in order.
   hipStream_t side;
   hipEvent_t ev_fork, ev_join;
+  // lr_llama_lora_set_deterministic: a field of the handle, read on the host when a call is issued and handed to the launchers
+  // as arguments; the mode's extra memory (LoraWs::det_loss, det_part) is carved from the caller's workspace
+  int deterministic;
 };
 
 static int fork_side(lr_llama_lora* h, hipStream_t main, hipStream_t* work) {
@@ -292,6 +295,11 @@ struct LoraWs {
   float *dsum, *dkv32;
   u16 *xg, *hn, *logits, *dhn;            // loss head, m rows
   u16 *dt2, *xn2_b, *hmid_b;              // extra modules' backward: d t [n][tw]; recomputed inputs of gate/up and of down
+  // deterministic mode only (null otherwise). det_loss [2 + m]: rows without a token id, per-row losses. det_part: the token
+  // reductions' per-chunk partial tiles, sized for the largest of them. ONE region serves them all: every token reduction of a
+  // call is issued on one stream (the side stream, or the caller's without one), which runs partials, fold, next partials in
+  // order; the main stream never touches the region.
+  float *det_loss, *det_part;
   size_t o_t2;
   size_t save0, save_stride;              // per-layer saved activations: base + l * save_stride
   size_t o_x, o_xn, o_qkv, o_att, o_xmid, o_gu, o_t, o_lse;
@@ -299,7 +307,7 @@ struct LoraWs {
   size_t total;
 };
 static LoraWs carve(const LrLlamaConfig& c, const LoraMods& md, int n_tok, int B, int m, int slots, bool training,
-                    char* base) {
+                    char* base, int r = 0, bool deterministic = false) {
   LoraWs w;
   memset(&w, 0, sizeof(w));
   w.base = base;
@@ -354,6 +362,21 @@ static LoraWs carve(const LrLlamaConfig& c, const LoraMods& md, int n_tok, int B
     if (md.tw) w.dt2 = (u16*)(base + take(n * md.tw * 2));
     if (md.gu()) w.xn2_b = (u16*)(base + take(n * d * 2));
     if (md.has(MDOWN)) w.hmid_b = (u16*)(base + take(n * f * 2));
+    if (deterministic) {
+      w.det_loss = (float*)(base + take((2 + mm) * 4));
+      // the shapes loss_grad hands to lr_launch_lora_tn / _db / _da: (tiles, columns, layout)
+      const int dd = (int)d, ff = (int)f;
+      size_t part = 0;
+      auto shape = [&](bool on, int nj, int cols, int layout) {
+        const size_t need = on ? lr_lora_tn_partial_floats(nj, n_tok, cols, r, layout) : 0;
+        if (need > part) part = need;
+      };
+      shape(md.has(MQ), 1, (int)qcols, 2), shape(md.has(MV) || md.has(MK), 1, (int)kv, 1);
+      shape(md.has(MQ) || md.has(MV), 2, dd, 0), shape(md.has(MK) || md.has(MDOWN) || md.has(MO), 1, dd, 0);
+      shape(md.has(MO), 1, (int)qcols, 0);
+      shape(md.gu(), 2, 2 * ff, 3), shape(md.gu(), 2, dd, 0), shape(md.has(MDOWN), 1, ff, 0);
+      w.det_part = (float*)(base + take(part * 4));
+    }
   }
   w.total = o;
   return w;
@@ -378,7 +401,13 @@ extern "C" size_t lr_llama_lora_workspace_bytes(const lr_llama_lora_t* h, int32_
   if (!h || max_tokens < 1) return 0;
   if (max_seqs < 1) max_seqs = 1;
   const LrLlamaConfig& c = h->base->cfg;
-  return carve(c, lora_mods(c, h->cfg.r, h->mods), max_tokens, max_seqs, max_loss_rows, c.num_layers, true, nullptr).total;
+  return carve(c, lora_mods(c, h->cfg.r, h->mods), max_tokens, max_seqs, max_loss_rows, c.num_layers, true, nullptr, h->cfg.r,
+               h->deterministic != 0).total;
+}
+extern "C" int lr_llama_lora_set_deterministic(lr_llama_lora_t* h, int32_t enable) {
+  if (!h) LR_FAIL(LR_EINVAL, "lr_llama_lora_set_deterministic: null handle");
+  h->deterministic = enable != 0;
+  return LR_OK;
 }
 extern "C" size_t lr_llama_lora_eval_workspace_bytes(const lr_llama_lora_t* h, int32_t max_tokens, int32_t max_seqs) {
   if (!h || max_tokens < 1) return 0;
@@ -520,7 +549,8 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
   LR_RUN(validate_batch(h, cu_seqlens_host, B, &n, &maxT));
   if (m > n) LR_FAIL(LR_EINVAL, "lr_llama_lora_loss_grad: %d labelled rows for %d tokens", m, n);
   const LoraMods md = lora_mods(c, h->cfg.r, h->mods);
-  const LoraWs ws = carve(c, md, n, B, m, c.num_layers, true, (char*)workspace);
+  const bool det = h->deterministic != 0;
+  const LoraWs ws = carve(c, md, n, B, m, c.num_layers, true, (char*)workspace, h->cfg.r, det);
   if (ws.total > workspace_bytes)
     LR_FAIL(LR_EWORKSPACE, "lr_llama_lora_loss_grad: workspace needs %zu bytes for %d tokens, have %zu", ws.total, n,
             workspace_bytes);
@@ -532,7 +562,9 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
   const int tw = md.tw, L = c.num_layers;
   h->pass += 1;
   if (!accumulate) LR_CHECK_HIP(hipMemsetAsync(h->grads, 0, h->n_params * sizeof(float), st));
-  LR_CHECK_HIP(hipMemsetAsync(h->scratch, 0, 2 * sizeof(float), st));
+  float* const scal = det ? ws.det_loss : h->scratch;  // loss sum / per-row losses, rows without a token id
+  float* const dp = ws.det_part;                       // null in the default mode: the launchers then add atomically
+  LR_CHECK_HIP(hipMemsetAsync(scal, 0, 2 * sizeof(float), st));
   LR_RUN(prep_adapters(h, st));
   LR_RUN(forward(h, packed_ids, cu_seqlens, cu_seqlens_host, B, n, maxT, ws, true, drop_p, st));
 
@@ -540,8 +572,8 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
   LR_RUN(lr_launch_gather_rows(ws.x_final, loss_rows, m, d, ws.xg, st));
   LR_RUN(lr_launch_rmsnorm(ws.xg, h->base->final_norm, ws.hn, m, d, c.rms_eps, nullptr, st));
   LR_RUN(lr_launch_gemm({.A = ws.hn, .B = h->base->lm_head, .C = ws.logits, .M = m, .N = c.vocab_size, .K = d, .variant = gv}, st));
-  LR_RUN(lr_launch_ce_bf16(ws.logits, m, c.vocab_size, loss_targets, grad_scale / (float)m, h->scratch, st));
-  LR_RUN(lr_launch_finish_loss(h->scratch, m, out, st));
+  LR_RUN(lr_launch_ce_bf16(ws.logits, m, c.vocab_size, loss_targets, grad_scale / (float)m, scal, st, det));
+  LR_RUN(lr_launch_finish_loss(scal, m, out, st, det));
   LR_RUN(lr_launch_gemm({.A = ws.logits, .B = h->lm_head_t, .C = ws.dhn, .M = m, .N = d, .K = c.vocab_size, .variant = gv}, st));
   LR_CHECK_HIP(hipMemsetAsync(ws.dx, 0, (size_t)n * d * 2, st));
   LR_RUN(lr_launch_rmsnorm_bwd(ws.dhn, ws.xg, h->base->final_norm, nullptr, ws.dx, m, d, c.rms_eps, loss_rows, nullptr,
@@ -565,11 +597,11 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
     if (md.has(MDOWN)) {
       const uint32_t s3 = lr_lora_drop_stream(h->cfg.seed, h->pass, (uint32_t)(l + 3 * L));
       LR_RUN(fork_side(h, st, &sd));
-      LR_RUN(lr_launch_lora_tn(1, s.t2, tw, md.tdn, ws.dx, d, n, d, scaling, grad_of(MDOWN, 1), nullptr, r, 1, 0, 0, 0.f, sd));
+      LR_RUN(lr_launch_lora_tn(1, s.t2, tw, md.tdn, ws.dx, d, n, d, scaling, grad_of(MDOWN, 1), nullptr, r, 1, 0, 0, 0.f, sd, dp));
       LR_RUN(lr_launch_skinny(ws.dx, d, n, d, wk + md.wdn_b, 1, ws.dt2, tw, md.tdn, scaling, 0, 0.f, sd));
       LR_RUN(lr_launch_swiglu_fwd(s.gu, ws.hmid_b, n, f, sd));  // down's input, recomputed before swiglu_bwd overwrites gu
       LR_RUN(lr_launch_lora_tn(1, ws.dt2, tw, md.tdn, ws.hmid_b, f, n, f, 1.0f, grad_of(MDOWN, 0), nullptr, r, 0, 0, s3, drop_p,
-                               sd));
+                               sd, dp));
       LR_RUN(lr_launch_gemm({.A = ws.dx, .B = wt.wdown_t, .C = ws.dh, .M = n, .N = f, .K = d, .variant = gv}, st));
       LR_RUN(join_side(h, st));
       LR_RUN(lr_launch_lora_expand(ws.dh, f, n, f, ws.dt2, tw, md.tdn, wk + md.wdn_a, r, drop_scale, s3, drop_p, st));
@@ -581,11 +613,11 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
       const uint32_t s2 = lr_lora_drop_stream(h->cfg.seed, h->pass, (uint32_t)(l + 2 * L));
       LR_RUN(fork_side(h, st, &sd));
       LR_RUN(lr_launch_lora_tn(2, s.t2, tw, md.tgu, s.gu, 2 * f, n, 2 * f, scaling, grad_of(MGATE, 1), grad_of(MUP, 1), r, 3, 0, 0,
-                               0.f, sd));
+                               0.f, sd, dp));
       LR_RUN(lr_launch_skinny(s.gu, 2 * f, n, 2 * f, wk + md.wgu_b, 2, ws.dt2, tw, md.tgu, scaling, 0, 0.f, sd));
       LR_RUN(lr_launch_rmsnorm(s.xmid, w.post_norm, ws.xn2_b, n, d, c.rms_eps, nullptr, sd));  // gate / up's input, recomputed
       LR_RUN(lr_launch_lora_tn(2, ws.dt2, tw, md.tgu, ws.xn2_b, d, n, d, 1.0f, grad_of(MGATE, 0), grad_of(MUP, 0), r, 0, 0, s2,
-                               drop_p, sd));
+                               drop_p, sd, dp));
       LR_RUN(lr_launch_gemm({.A = s.gu, .B = wt.wgu_t, .C = ws.dxn, .M = n, .N = d, .K = 2 * f, .variant = gv}, st));
       LR_RUN(join_side(h, st));
       // d xn2 += mask .* (d t_gate A_gate + d t_up A_up) rides in the norm's LoRA arm, as q / v's does in the input norm's
@@ -600,10 +632,10 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
     if (md.has(MO)) {
       const uint32_t s1 = lr_lora_drop_stream(h->cfg.seed, h->pass, (uint32_t)(l + L));
       LR_RUN(fork_side(h, st, &sd));
-      LR_RUN(lr_launch_lora_tn(1, s.t2, tw, md.to, ws.dx, d, n, d, scaling, grad_of(MO, 1), nullptr, r, 1, 0, 0, 0.f, sd));
+      LR_RUN(lr_launch_lora_tn(1, s.t2, tw, md.to, ws.dx, d, n, d, scaling, grad_of(MO, 1), nullptr, r, 1, 0, 0, 0.f, sd, dp));
       LR_RUN(lr_launch_skinny(ws.dx, d, n, d, wk + md.wo_b, 1, ws.dt2, tw, md.to, scaling, 0, 0.f, sd));
       LR_RUN(lr_launch_lora_tn(1, ws.dt2, tw, md.to, s.att, h->qcols, n, h->qcols, 1.0f, grad_of(MO, 0), nullptr, r, 0, 0, s1,
-                               drop_p, sd));
+                               drop_p, sd, dp));
       LR_RUN(lr_launch_gemm({.A = ws.dx, .B = wt.wo_t, .C = ws.datt, .M = n, .N = nh * hd, .K = d, .variant = gv}, st));
       LR_RUN(join_side(h, st));
       LR_RUN(lr_launch_lora_expand(ws.datt, h->qcols, n, h->qcols, ws.dt2, tw, md.to, wk + md.wo_a, r, drop_scale, s1,
@@ -613,31 +645,31 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
     }
     // ... down to the gradient of the UNROTATED q, k, v (the inverse rotation rides in the attention passes)
     LR_RUN(lr_launch_attention_bwd(s.qkv, s.att, ws.datt, s.lse, ws.dqkv, ws.dsum, ws.dkv32, cu_seqlens, cu_seqlens_host, B,
-                                   n, nh, nkv, hd, h->base->attn_variant, st, ws.tok_pos, ws.rope));
+                                   n, nh, nkv, hd, h->base->attn_variant, st, ws.tok_pos, ws.rope, det));
     // adapters (side stream, next to the qkv data-gradient GEMM; both only read dqkv):
     // d B, d t = scaling * (d q B_q | d v B_v), d A
     LR_RUN(fork_side(h, st, &sd));
     if (dbq && dbv) {
-      LR_RUN(lr_launch_lora_db(ws.dqkv, n, qw, h->qcols, h->kcols, hd, s.t, r, scaling, dbq, dbv, sd));
+      LR_RUN(lr_launch_lora_db(ws.dqkv, n, qw, h->qcols, h->kcols, hd, s.t, r, scaling, dbq, dbv, sd, dp));
     } else {
-      if (dbq) LR_RUN(lr_launch_lora_tn(1, s.t, 2 * LT_RP, 0, ws.dqkv, qw, n, h->qcols, scaling, dbq, nullptr, r, 2, hd, 0, 0.f, sd));
+      if (dbq) LR_RUN(lr_launch_lora_tn(1, s.t, 2 * LT_RP, 0, ws.dqkv, qw, n, h->qcols, scaling, dbq, nullptr, r, 2, hd, 0, 0.f, sd, dp));
       if (dbv)
         LR_RUN(lr_launch_lora_tn(1, s.t, 2 * LT_RP, LT_RP, ws.dqkv + h->qcols + h->kcols, qw, n, h->vcols, scaling, dbv, nullptr,
-                                 r, 1, hd, 0, 0.f, sd));
+                                 r, 1, hd, 0, 0.f, sd, dp));
     }
     // (the working copies of a q / v that is not adapted are zero: its d t columns come out zero for the norm's LoRA arm)
     LR_RUN(lr_launch_skinny(ws.dqkv, qw, n, h->qcols, bq_t, 1, ws.dt, 2 * LT_RP, 0, scaling, 0, 0.f, sd));
     LR_RUN(lr_launch_skinny(ws.dqkv + h->qcols + h->kcols, qw, n, h->vcols, bv_t, 1, ws.dt, 2 * LT_RP, LT_RP, scaling, 0,
                             0.f, sd));
-    if (daq && dav) LR_RUN(lr_launch_lora_da(s.xn, n, d, ws.dt, r, stream, drop_p, daq, dav, sd));
+    if (daq && dav) LR_RUN(lr_launch_lora_da(s.xn, n, d, ws.dt, r, stream, drop_p, daq, dav, sd, dp));
     else if (daq || dav)
       LR_RUN(lr_launch_lora_tn(1, ws.dt, 2 * LT_RP, daq ? 0 : LT_RP, s.xn, d, n, d, 1.0f, daq ? daq : dav, nullptr, r, 0, 0,
-                               stream, drop_p, sd));
+                               stream, drop_p, sd, dp));
     if (md.has(MK)) {
       LR_RUN(lr_launch_lora_tn(1, s.t2, tw, md.tk, ws.dqkv + h->qcols, qw, n, h->kcols, scaling, grad_of(MK, 1), nullptr, r, 2, hd,
-                               0, 0.f, sd));
+                               0, 0.f, sd, dp));
       LR_RUN(lr_launch_skinny(ws.dqkv + h->qcols, qw, n, h->kcols, wk + md.wk_b, 1, ws.dt2, tw, md.tk, scaling, 0, 0.f, sd));
-      LR_RUN(lr_launch_lora_tn(1, ws.dt2, tw, md.tk, s.xn, d, n, d, 1.0f, grad_of(MK, 0), nullptr, r, 0, 0, stream, drop_p, sd));
+      LR_RUN(lr_launch_lora_tn(1, ws.dt2, tw, md.tk, s.xn, d, n, d, 1.0f, grad_of(MK, 0), nullptr, r, 0, 0, stream, drop_p, sd, dp));
     }
     if (l > 0)  // below layer 0 only the frozen embedding is left: its input gradient has no reader
       LR_RUN(lr_launch_gemm({.A = ws.dqkv, .B = wt.wqkv_t, .C = ws.dxn, .M = n, .N = d, .K = qw, .variant = gv}, st));
@@ -656,7 +688,7 @@ extern "C" int lr_llama_lora_apply(lr_llama_lora_t* h, float lr, float max_grad_
   if (!h) LR_FAIL(LR_EINVAL, "lr_llama_lora_apply: null handle");
   return lr_launch_lora_adamw(h->params, h->grads, h->m, h->v, h->n_params, h->scratch + 2, h->ctr, lr, max_grad_norm,
                               h->cfg.beta1, h->cfg.beta2, h->cfg.eps, h->cfg.weight_decay, out_norm,
-                              (hipStream_t)hip_stream);
+                              (hipStream_t)hip_stream, h->deterministic != 0);
 }
 
 // scoring with the adapters as they are now (validation during training, trainer/llm.py:123-126): the forward

@@ -8,6 +8,7 @@
 //     dV = P^T dO,   dP = dO V^T,   dS = P .* (dP - D),   dQ = scale dS K,   dK = scale dS^T Q.
 //
 //  attn_bwd_generic_kernel : any head_dim <= 256, GQA; one wave per (token, head), fp32 atomics for dK/dV. Test models.
+//  attn_bwd_dkv_owner_kernel : the generic path's dK / dV in deterministic mode: one wave per (key token, kv head), no atomics.
 //  attn_bwd_dq_kernel / attn_bwd_dkv_kernel : head_dim 128 on v_mfma_f32_16x16x32_bf16, no atomics. Two passes, each
 //    recomputing S and dP (7 tile products instead of 5), so each output has exactly one owner:
 //      dQ pass  : a workgroup owns 128 query rows (like the forward); everything transposed: S^T = K Q^T and
@@ -32,6 +33,8 @@ typedef u16 u16x4 __attribute__((ext_vector_type(4)));
 // =============================================================================================
 // generic
 // =============================================================================================
+// DKV = false (deterministic mode): dQ only; dK / dV come from attn_bwd_dkv_owner_kernel
+template <bool DKV>
 __global__ __launch_bounds__(256) void attn_bwd_generic_kernel(const u16* qkv, const u16* d_out, const float* lse,
                                                                const float* dsum, u16* dqkv, float* dkv32,
                                                                const int32_t* cu, int B, int n_tok, int nh, int nkv,
@@ -84,8 +87,10 @@ __global__ __launch_bounds__(256) void attn_bwd_generic_kernel(const u16* qkv, c
         const int d = lane + 64 * i;
         if (d < hd) {
           dq[i] = __builtin_fmaf(dsj, bf2f(kp[d]), dq[i]);
-          atomicAdd(dk + d, dsj * qs[wave][d]);
-          atomicAdd(dv + d, pj * dos[wave][d]);
+          if (DKV) {
+            atomicAdd(dk + d, dsj * qs[wave][d]);
+            atomicAdd(dv + d, pj * dos[wave][d]);
+          }
         }
       }
     }
@@ -94,6 +99,75 @@ __global__ __launch_bounds__(256) void attn_bwd_generic_kernel(const u16* qkv, c
   for (int i = 0; i < 4; ++i) {
     const int d = lane + 64 * i;
     if (d < hd) dqkv[(size_t)tok * stride + h * hd + d] = f2bf(dq[i]);
+  }
+}
+
+// Owner-computes dK / dV (deterministic mode). One wave per (key token, kv head): it walks the query heads of its group in
+// ascending order and, for each, the queries at or after the key in ascending order, 64 at a time -- a lane computes one query's
+// P and dS against this key exactly as the kernel above does (the same fmaf chain over d), then all lanes add the 64 queries'
+// contributions, in order, to the head dimensions they own. bf16 dK / dV are written directly: every element has one writer and
+// one summation order, whatever the schedule. Serves test models like the kernel above; not tuned.
+__global__ __launch_bounds__(256) void attn_bwd_dkv_owner_kernel(const u16* qkv, const u16* d_out, const float* lse,
+                                                                 const float* dsum, u16* dqkv, const int32_t* cu, int B,
+                                                                 int n_tok, int nh, int nkv, int hd) {
+  __shared__ float ks[4][256], vs[4][256];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int item = blockIdx.x * 4 + wave;  // (key token, kv head)
+  if (item >= n_tok * nkv) return;
+  const int tok = item / nkv, kvh = item % nkv;
+  const int grp = nh / nkv;
+  const int stride = (nh + 2 * nkv) * hd;
+  int lo = 0, hi = B;
+  while (hi - lo > 1) {
+    int mid = (lo + hi) >> 1;
+    if (cu[mid] <= tok) lo = mid; else hi = mid;
+  }
+  const int s1 = cu[lo + 1];  // end of the key's prompt
+  for (int d = lane; d < hd; d += 64) {
+    ks[wave][d] = bf2f(qkv[(size_t)tok * stride + (nh + kvh) * hd + d]);
+    vs[wave][d] = bf2f(qkv[(size_t)tok * stride + (nh + nkv + kvh) * hd + d]);
+  }
+  __builtin_amdgcn_wave_barrier();
+  const float scale = 1.0f / sqrtf((float)hd);
+  float dk[4] = {0.f, 0.f, 0.f, 0.f}, dv[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int h = kvh * grp; h < (kvh + 1) * grp; ++h) {
+    for (int q0 = tok; q0 < s1; q0 += 64) {
+      const int qi = q0 + lane;
+      float p = 0.f, ds = 0.f;
+      if (qi < s1) {
+        const u16* qp = qkv + (size_t)qi * stride + h * hd;
+        const u16* dop = d_out + (size_t)qi * nh * hd + h * hd;
+        float acc = 0.f, dp = 0.f;
+        for (int d = 0; d < hd; ++d) {
+          acc = __builtin_fmaf(bf2f(qp[d]), ks[wave][d], acc);
+          dp = __builtin_fmaf(bf2f(dop[d]), vs[wave][d], dp);
+        }
+        p = __expf(acc * scale - lse[(size_t)qi * nh + h]);
+        ds = p * (dp - dsum[(size_t)qi * nh + h]) * scale;
+      }
+      const int nq = min(64, s1 - q0);
+      for (int j = 0; j < nq; ++j) {
+        const float pj = __shfl(p, j, 64), dsj = __shfl(ds, j, 64);
+        const u16* qp = qkv + (size_t)(q0 + j) * stride + h * hd;
+        const u16* dop = d_out + (size_t)(q0 + j) * nh * hd + h * hd;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int d = lane + 64 * i;
+          if (d < hd) {
+            dk[i] = __builtin_fmaf(dsj, bf2f(qp[d]), dk[i]);
+            dv[i] = __builtin_fmaf(pj, bf2f(dop[d]), dv[i]);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int d = lane + 64 * i;
+    if (d < hd) {
+      dqkv[(size_t)tok * stride + (nh + kvh) * hd + d] = f2bf(dk[i]);
+      dqkv[(size_t)tok * stride + (nh + nkv + kvh) * hd + d] = f2bf(dv[i]);
+    }
   }
 }
 
@@ -472,7 +546,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const u16* __restr
 // =============================================================================================
 int lr_launch_attention_bwd(const u16* qkv, const u16* out, const u16* d_out, const float* lse, u16* dqkv, float* dsum,
                             float* dkv32, const int32_t* cu, const int32_t* cu_host, int B, int n_tok, int nh, int nkv,
-                            int hd, int variant, hipStream_t st, const int32_t* tok_pos, const float* rope_cs) {
+                            int hd, int variant, hipStream_t st, const int32_t* tok_pos, const float* rope_cs,
+                            bool deterministic) {
   if (n_tok <= 0 || B <= 0) return LR_OK;
   if (nh % nkv != 0) LR_FAIL(LR_EINVAL, "attention backward: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
   if (hd > 256) LR_FAIL(LR_EUNSUPPORTED, "attention backward: head_dim %d > 256", hd);
@@ -503,16 +578,25 @@ int lr_launch_attention_bwd(const u16* qkv, const u16* out, const u16* d_out, co
                        nh, nkv, rope_cs);
     LR_CHECK_LAUNCH("attn_bwd_dkv_kernel");
   } else if (variant == 1) {
-    if (!dkv32) LR_FAIL(LR_EINVAL, "attention backward (generic): null fp32 scratch");
-    const int kvcols = 2 * nkv * hd;
-    LR_CHECK_HIP(hipMemsetAsync(dkv32, 0, (size_t)n_tok * kvcols * sizeof(float), st));
-    hipLaunchKernelGGL(attn_bwd_generic_kernel, dim3((n_tok * nh + 3) / 4), dim3(256), 0, st, qkv, d_out, lse, dsum,
-                       dqkv, dkv32, cu, B, n_tok, nh, nkv, hd);
-    LR_CHECK_LAUNCH("attn_bwd_generic_kernel");
-    const size_t total = (size_t)n_tok * kvcols;
-    hipLaunchKernelGGL(attn_bwd_kv_to_bf16_kernel, dim3((unsigned)min((size_t)4096, (total + 255) / 256)), dim3(256), 0,
-                       st, dkv32, dqkv, n_tok, nh * hd, kvcols);
-    LR_CHECK_LAUNCH("attn_bwd_kv_to_bf16_kernel");
+    if (deterministic) {
+      hipLaunchKernelGGL(attn_bwd_generic_kernel<false>, dim3((n_tok * nh + 3) / 4), dim3(256), 0, st, qkv, d_out, lse, dsum,
+                         dqkv, nullptr, cu, B, n_tok, nh, nkv, hd);
+      LR_CHECK_LAUNCH("attn_bwd_generic_kernel");
+      hipLaunchKernelGGL(attn_bwd_dkv_owner_kernel, dim3((n_tok * nkv + 3) / 4), dim3(256), 0, st, qkv, d_out, lse, dsum, dqkv,
+                         cu, B, n_tok, nh, nkv, hd);
+      LR_CHECK_LAUNCH("attn_bwd_dkv_owner_kernel");
+    } else {
+      if (!dkv32) LR_FAIL(LR_EINVAL, "attention backward (generic): null fp32 scratch");
+      const int kvcols = 2 * nkv * hd;
+      LR_CHECK_HIP(hipMemsetAsync(dkv32, 0, (size_t)n_tok * kvcols * sizeof(float), st));
+      hipLaunchKernelGGL(attn_bwd_generic_kernel<true>, dim3((n_tok * nh + 3) / 4), dim3(256), 0, st, qkv, d_out, lse, dsum,
+                         dqkv, dkv32, cu, B, n_tok, nh, nkv, hd);
+      LR_CHECK_LAUNCH("attn_bwd_generic_kernel");
+      const size_t total = (size_t)n_tok * kvcols;
+      hipLaunchKernelGGL(attn_bwd_kv_to_bf16_kernel, dim3((unsigned)min((size_t)4096, (total + 255) / 256)), dim3(256), 0,
+                         st, dkv32, dqkv, n_tok, nh * hd, kvcols);
+      LR_CHECK_LAUNCH("attn_bwd_kv_to_bf16_kernel");
+    }
     if (rope_cs) {
       if (!tok_pos) LR_FAIL(LR_EINVAL, "attention backward: rotary table without token positions");
       rc = lr_launch_rope_bwd(dqkv, n_tok, (nh + 2 * nkv) * hd, (nh + nkv) * hd, hd, tok_pos, rope_cs, st);

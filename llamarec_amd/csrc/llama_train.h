@@ -21,13 +21,17 @@ int lr_launch_lora_rope_fwd(unsigned short* qkv, int n, int qw, int qcols, int k
 int lr_launch_rope_bwd(unsigned short* dqkv, int n, int qw, int rot_cols, int hd, const int32_t* tok_pos,
                        const float* rope_cs, hipStream_t st);
 int lr_launch_lora_db(const unsigned short* dqkv, int n, int qw, int qcols, int kcols, int hd, const unsigned short* t,
-                      int r, float scaling, float* dbq, float* dbv, hipStream_t st);
+                      int r, float scaling, float* dbq, float* dbv, hipStream_t st, float* det_part = nullptr);
 int lr_launch_lora_da(const unsigned short* xn, int n, int d, const unsigned short* dt, int r, uint32_t drop_stream,
-                      float drop_p, float* daq, float* dav, hipStream_t st);
-// adapters on any Linear: launch_tn exposed (layouts: llama_train.hip), one module's working copies, the expand-add sweep
+                      float drop_p, float* daq, float* dav, hipStream_t st, float* det_part = nullptr);
+// adapters on any Linear: launch_tn exposed (layouts: llama_train.hip), one module's working copies, the expand-add sweep.
+// det_part (here and in _db / _da above) != nullptr selects the deterministic form of the token reductions: per-chunk partial
+// tiles stored there (lr_lora_tn_partial_floats floats, the largest any batch of at most n tokens needs) and folded in chunk
+// order. Launches that may run at the same time need separate partials.
+size_t lr_lora_tn_partial_floats(int nj, int n, int cols, int r, int layout);
 int lr_launch_lora_tn(int nj, const unsigned short* T, int ldt, int tcol, const unsigned short* X, int ldx, int n, int cols,
                       float scale, float* out0, float* out1, int r, int layout, int hd, uint32_t drop_stream, float drop_p,
-                      hipStream_t st);
+                      hipStream_t st, float* det_part = nullptr);
 int lr_launch_prep_module(const float* a, const float* b, int r, int in, int out, int perm, int hd, unsigned short* a_w,
                           unsigned short* b_t, int ldb, hipStream_t st);
 int lr_launch_lora_expand(unsigned short* Y, int ldy, int n, int cols, const unsigned short* T, int ldt, int tcol,
@@ -40,23 +44,27 @@ int lr_launch_rmsnorm_bwd(const unsigned short* dy, const unsigned short* x, con
                           const unsigned short* res, unsigned short* out, int rows, int d, float eps,
                           const int32_t* out_rows, const unsigned short* dt, const unsigned short* a_cat, int r,
                           uint32_t drop_stream, float drop_p, hipStream_t st, int ldt = 2 * LT_RP);  // ldt: row stride of dt
+// deterministic: scal is [2 + m] floats (1: rows without a token id, 2 + i: row i's loss) and the sum is taken in row order
 int lr_launch_ce_bf16(unsigned short* logits, int m, int V, const int32_t* targets, float gscale, float* scal,
-                      hipStream_t st);
-int lr_launch_finish_loss(const float* scal, int m, float* out, hipStream_t st);
+                      hipStream_t st, bool deterministic = false);
+int lr_launch_finish_loss(const float* scal, int m, float* out, hipStream_t st, bool deterministic = false);
 int lr_launch_rowdot(const unsigned short* o, const unsigned short* d_o, int n, int nh, int hd, float* out,
                      hipStream_t st);
 int lr_launch_lora_adamw(float* p, float* g, float* m, float* v, size_t n, float* scratch, int* ctr, float lr,
                          float max_grad_norm, float beta1, float beta2, float eps, float wd, float* out_norm,
-                         hipStream_t st);
+                         hipStream_t st, bool deterministic = false);  // deterministic: the norm summed in a fixed order
 uint32_t lr_lora_drop_stream(uint64_t seed, uint32_t pass, uint32_t layer);
 
 // backward of lr_launch_attention with the softmax statistics kept (lse[n][nh], natural log; llama_attn_bwd.hip).
 // dqkv [n][(nh+2nkv)*hd], fully written: the gradient w.r.t. the rotated q, k and v -- or, when rope_cs / tok_pos are
 // given, w.r.t. the UNROTATED ones (the inverse rotation is pair-local in the packed layout and rides in the MFMA
 // passes' epilogues). dsum: [n][nh] fp32 scratch, dkv32: [n][2*nkv*hd] fp32 scratch (generic path only).
+// deterministic: the generic path computes dK / dV per owner instead of adding them atomically (dkv32 unused); the head_dim-128
+// passes have no atomics either way.
 int lr_launch_attention_bwd(const unsigned short* qkv, const unsigned short* out, const unsigned short* d_out,
                             const float* lse, unsigned short* dqkv, float* dsum, float* dkv32, const int32_t* cu,
                             const int32_t* cu_host, int B, int n_tok, int nh, int nkv, int hd, int variant,
-                            hipStream_t st, const int32_t* tok_pos = nullptr, const float* rope_cs = nullptr);
+                            hipStream_t st, const int32_t* tok_pos = nullptr, const float* rope_cs = nullptr,
+                            bool deterministic = false);
 
 #endif

@@ -337,7 +337,50 @@ int lr_launch_rope_bwd(u16* dqkv, int n, int qw, int rot_cols, int hd, const int
 //   layout 2: out0[orig(c) * r + j], packed -> HF column   (d B_q, d B_k)
 //   layout 3: X = the interleaved gate/up gradient (16 gate columns, 16 up columns, ...): tile 0 keeps the gate columns
 //             (out0[f_col * r + j]), tile 1 the up columns (out1); a null out0 / out1 = that adapter is not trained
-template <int NJ>
+// Where a (column block, token chunk) workgroup's accumulators leave (column = activation column li of the tile, rows j = 4g + i).
+// Default: one fp32 atomic per (j, c) into the gradient. DET (lr_llama_lora_set_deterministic): out0 / out1 are chunk 0's
+// partial tiles instead, laid out like the gradient they stand for (E elements each, chunk k's pair NJ * E floats further on), and
+// the scaled tile is STORED to its chunk's: 16 lanes = 64 contiguous bytes per j in layout 0; in the [column][r] layouts a lane's
+// four j are adjacent, so with r a multiple of 4 a lane stores 16 bytes and a 16-lane group r * 64 contiguous ones.
+// lt_tn_fold_kernel then adds the chunks in ascending order. (A macro, not a function: the default instantiations of both bodies
+// compile to the instructions they had before the mode existed.)
+#define LT_TN_STORE()                                                                                     \
+  const int half = hd >> 1;                                                                               \
+  _Pragma("unroll") for (int a = 0; a < NJ; ++a) {                                                        \
+    float* out = a == 0 ? out0 : out1;                                                                    \
+    if (!out) continue; /* a tile whose adapter is not trained */                                         \
+    if (DET) out += (size_t)blockIdx.y * NJ * ((size_t)r * cols >> (layout == 3));                        \
+    _Pragma("unroll") for (int ct = 0; ct < 4; ++ct) {                                                    \
+      const int c = c0 + ct * 16 + li;                                                                    \
+      if (DET && layout != 0 && (r & 3) == 0) {                                                           \
+        if (g * 4 >= r || (layout == 3 && ((c >> 4) & 1) != a)) continue;                                 \
+        int row = c;                                                                                      \
+        if (layout == 3) row = (c >> 5) * 16 + (c & 15);                                                  \
+        else if (layout == 2) row = c / hd * hd + (c % hd & 1) * half + (c % hd >> 1);                    \
+        *reinterpret_cast<floatx4*>(out + (size_t)row * r + g * 4) = acc[a][ct] * scale;                  \
+        continue;                                                                                         \
+      }                                                                                                   \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                     \
+        const int j = g * 4 + i;                                                                          \
+        if (j >= r) continue;                                                                             \
+        size_t at;                                                                                        \
+        if (layout == 0) {                                                                                \
+          at = (size_t)j * cols + c;                                                                      \
+        } else if (layout == 1) {                                                                         \
+          at = (size_t)c * r + j;                                                                         \
+        } else if (layout == 3) {                                                                         \
+          if (((c >> 4) & 1) != a) continue;                                                              \
+          at = (size_t)((c >> 5) * 16 + (c & 15)) * r + j;                                                \
+        } else {                                                                                          \
+          const int head = c / hd, within = c % hd;                                                       \
+          at = (size_t)(head * hd + (within & 1) * half + (within >> 1)) * r + j;                         \
+        }                                                                                                 \
+        if (DET) out[at] = acc[a][ct][i] * scale;                                                         \
+        else atomicAdd(out + at, acc[a][ct][i] * scale);                                                  \
+      }                                                                                                   \
+    }                                                                                                     \
+  }
+template <int NJ, bool DET>
 __global__ __launch_bounds__(256) void lt_tn_kernel(const u16* __restrict__ T, int ldt, int tcol,
                                                     const u16* __restrict__ X, int ldx, int n, int cols, int chunk,
                                                     float scale, float* out0, float* out1, int r, int layout, int hd,
@@ -376,35 +419,7 @@ __global__ __launch_bounds__(256) void lt_tn_kernel(const u16* __restrict__ T, i
         acc[a][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, tf[a]),
                                                              __builtin_bit_cast(bf16x8, xf[ct]), acc[a][ct], 0, 0, 0);
   }
-  // accumulator: column = activation column li of the tile, rows j = 4g + i
-  const int half = hd >> 1;
-#pragma unroll
-  for (int a = 0; a < NJ; ++a) {
-    float* out = a == 0 ? out0 : out1;
-    if (!out) continue;   // a tile whose adapter is not trained
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-      const int c = c0 + ct * 16 + li;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int j = g * 4 + i;
-        if (j >= r) continue;
-        size_t at;
-        if (layout == 0) {
-          at = (size_t)j * cols + c;
-        } else if (layout == 1) {
-          at = (size_t)c * r + j;
-        } else if (layout == 3) {
-          if (((c >> 4) & 1) != a) continue;
-          at = (size_t)((c >> 5) * 16 + (c & 15)) * r + j;
-        } else {
-          const int head = c / hd, within = c % hd;
-          at = (size_t)(head * hd + (within & 1) * half + (within >> 1)) * r + j;
-        }
-        atomicAdd(out + at, acc[a][ct][i] * scale);
-      }
-    }
-  }
+  LT_TN_STORE()
 }
 // The same reduction with both operands staged through LDS: 16-byte global loads in memory order (8 lanes per token row of the
 // wave's 64 columns, 2 lanes per row of T's 16 columns), then ds_read_b64_tr_b16 hands every lane its 8 consecutive TOKENS of one
@@ -412,7 +427,7 @@ __global__ __launch_bounds__(256) void lt_tn_kernel(const u16* __restrict__ T, i
 // per call at 7 k tokens against ~15 us of HBM time for X). Same fragments, same MFMA order: bit-identical sums. The next
 // 32-token step's loads are in flight while this one's products run; the LDS tiles are wave-private (no barrier).
 // Needs 16-byte-aligned rows of X and T (launch_tn checks and otherwise takes the kernel above).
-template <int NJ>
+template <int NJ, bool DET>
 __global__ __launch_bounds__(256) void lt_tn_lds_kernel(const u16* __restrict__ T, int ldt, int tcol,
                                                         const u16* __restrict__ X, int ldx, int n, int cols, int chunk,
                                                         float scale, float* out0, float* out1, int r, int layout, int hd,
@@ -498,47 +513,55 @@ __global__ __launch_bounds__(256) void lt_tn_lds_kernel(const u16* __restrict__ 
         acc[a][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, tf[a]),
                                                              __builtin_bit_cast(bf16x8, xf[ct]), acc[a][ct], 0, 0, 0);
   }
-  const int half = hd >> 1;
-#pragma unroll
-  for (int a = 0; a < NJ; ++a) {
-    float* out = a == 0 ? out0 : out1;
-    if (!out) continue;   // a tile whose adapter is not trained
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-      const int c = c0 + ct * 16 + li;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int j = g * 4 + i;
-        if (j >= r) continue;
-        size_t at;
-        if (layout == 0) {
-          at = (size_t)j * cols + c;
-        } else if (layout == 1) {
-          at = (size_t)c * r + j;
-        } else if (layout == 3) {
-          if (((c >> 4) & 1) != a) continue;
-          at = (size_t)((c >> 5) * 16 + (c & 15)) * r + j;
-        } else {
-          const int head = c / hd, within = c % hd;
-          at = (size_t)(head * hd + (within & 1) * half + (within >> 1)) * r + j;
-        }
-        atomicAdd(out + at, acc[a][ct][i] * scale);
-      }
-    }
-  }
+  LT_TN_STORE()
 }
-static int lt_tn_chunk(int n) {
+static int lt_tn_forced_chunk() {
   static int forced = -1;
   if (forced < 0) {
     const char* e = getenv("LR_TN_CHUNK");  // tuning knob: tokens per workgroup (multiple of 32)
     forced = e ? atoi(e) / 32 * 32 : 0;
   }
+  return forced;
+}
+static int lt_tn_chunk(int n) {
+  const int forced = lt_tn_forced_chunk();
   if (forced > 0) return forced;
   return n >= 4096 ? 256 : (n >= 512 ? 128 : 32);  // 7 k tokens: 128-256 measured best (512: too few workgroups)
 }
+// Deterministic mode's fold: out[e] += part[0][e] + part[1][e] + ... in ascending chunk order -- ONE read-modify-write of the
+// gradient per element, so a zeroed and an accumulating buffer both work. part: [chunks][tiles][E] as lt_tn_store left it,
+// E a multiple of 4; a thread owns 4 adjacent elements (16-byte accesses, whole lines per wave), blockIdx.y = the tile.
+__global__ __launch_bounds__(256) void lt_tn_fold_kernel(const float* __restrict__ part, size_t stride, int chunks, size_t E,
+                                                         float* out0, float* out1) {
+  float* out = blockIdx.y == 0 ? out0 : out1;
+  const size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (!out || e >= E) return;
+  const float* p = part + blockIdx.y * E + e;
+  floatx4 s = *reinterpret_cast<const floatx4*>(p);
+#pragma unroll 4
+  for (int k = 1; k < chunks; ++k) s += *reinterpret_cast<const floatx4*>(p + k * stride);
+  floatx4* o = reinterpret_cast<floatx4*>(out + e);
+  *o = *o + s;
+}
+// floats of partial tiles one deterministic token reduction over AT MOST n tokens may need. The chunk count is not monotonic in
+// n (511 tokens: 16 chunks of 32; 512: 4 of 128), and a workspace sized for max_tokens serves every smaller batch.
+size_t lr_lora_tn_partial_floats(int nj, int n, int cols, int r, int layout) {
+  if (n < 1) return 0;
+  size_t chunks;
+  if (const int forced = lt_tn_forced_chunk()) {
+    chunks = ((size_t)n + forced - 1) / forced;
+  } else {
+    chunks = (size_t)(min(n, 511) + 31) / 32;
+    if (n >= 512) chunks = max(chunks, (size_t)(min(n, 4095) + 127) / 128);
+    if (n >= 4096) chunks = max(chunks, ((size_t)n + 255) / 256);
+  }
+  return chunks * nj * ((size_t)r * cols >> (layout == 3));
+}
+// det_part != nullptr: deterministic mode, with lr_lora_tn_partial_floats floats there that no launch which may run at the same
+// time uses. The chunk length stays a function of n alone: the summation tree is fixed by the batch.
 static int launch_tn(int nj, const u16* T, int ldt, int tcol, const u16* X, int ldx, int n, int cols, float scale,
                      float* out0, float* out1, int r, int layout, int hd, uint32_t drop_stream, float drop_p,
-                     hipStream_t st) {
+                     hipStream_t st, float* det_part) {
   if (n < 1) return LR_OK;
   if (cols % 64 != 0) LR_FAIL(LR_EUNSUPPORTED, "token reduction: %d columns (must be a multiple of 64)", cols);
   const int chunk = lt_tn_chunk(n);
@@ -551,39 +574,51 @@ static int launch_tn(int nj, const u16* T, int ldt, int tcol, const u16* X, int 
     gather = e && e[0] == '1';
   }
   const bool aligned = !gather && ((uintptr_t)X & 15) == 0 && ((uintptr_t)(T + tcol) & 15) == 0 && ldx % 8 == 0 && ldt % 8 == 0;
-  if (aligned && nj == 1)
-    hipLaunchKernelGGL(lt_tn_lds_kernel<1>, grid, dim3(256), 0, st, T, ldt, tcol, X, ldx, n, cols, chunk, scale, out0, out1, r,
-                       layout, hd, drop_stream, th, ds);
-  else if (aligned)
-    hipLaunchKernelGGL(lt_tn_lds_kernel<2>, grid, dim3(256), 0, st, T, ldt, tcol, X, ldx, n, cols, chunk, scale, out0, out1, r,
-                       layout, hd, drop_stream, th, ds);
-  else if (nj == 1)
-    hipLaunchKernelGGL(lt_tn_kernel<1>, grid, dim3(256), 0, st, T, ldt, tcol, X, ldx, n, cols, chunk, scale, out0, out1, r,
-                       layout, hd, drop_stream, th, ds);
-  else
-    hipLaunchKernelGGL(lt_tn_kernel<2>, grid, dim3(256), 0, st, T, ldt, tcol, X, ldx, n, cols, chunk, scale, out0, out1, r,
-                       layout, hd, drop_stream, th, ds);
+#define LT_TN_LAUNCH(KERNEL, NJ, DET, O0, O1)                                                                              \
+  hipLaunchKernelGGL((KERNEL<NJ, DET>), grid, dim3(256), 0, st, T, ldt, tcol, X, ldx, n, cols, chunk, scale, O0, O1, r, layout, \
+                     hd, drop_stream, th, ds)
+  if (det_part) {
+    if (nj == 1) out1 = nullptr;
+    const size_t E = (size_t)r * cols >> (layout == 3);
+    if ((((uintptr_t)det_part | (uintptr_t)out0 | (uintptr_t)out1) & 15) != 0)
+      LR_FAIL(LR_EUNSUPPORTED, "deterministic token reduction: gradients and partial tiles must be 16-byte aligned");
+    float *p0 = out0 ? det_part : nullptr, *p1 = out1 ? det_part + E : nullptr;
+    if (aligned && nj == 1) LT_TN_LAUNCH(lt_tn_lds_kernel, 1, true, p0, p1);
+    else if (aligned) LT_TN_LAUNCH(lt_tn_lds_kernel, 2, true, p0, p1);
+    else if (nj == 1) LT_TN_LAUNCH(lt_tn_kernel, 1, true, p0, p1);
+    else LT_TN_LAUNCH(lt_tn_kernel, 2, true, p0, p1);
+    LR_CHECK_LAUNCH("lt_tn_kernel");
+    hipLaunchKernelGGL(lt_tn_fold_kernel, dim3((unsigned)((E / 4 + 255) / 256), nj), dim3(256), 0, st, det_part, nj * E,
+                       (int)grid.y, E, out0, out1);
+    LR_CHECK_LAUNCH("lt_tn_fold_kernel");
+    return LR_OK;
+  }
+  if (aligned && nj == 1) LT_TN_LAUNCH(lt_tn_lds_kernel, 1, false, out0, out1);
+  else if (aligned) LT_TN_LAUNCH(lt_tn_lds_kernel, 2, false, out0, out1);
+  else if (nj == 1) LT_TN_LAUNCH(lt_tn_kernel, 1, false, out0, out1);
+  else LT_TN_LAUNCH(lt_tn_kernel, 2, false, out0, out1);
+#undef LT_TN_LAUNCH
   LR_CHECK_LAUNCH("lt_tn_kernel");
   return LR_OK;
 }
 // d B_q += scaling * dq_pre^T t_q,  d B_v += scaling * dv^T t_v      (dqkv: gradient w.r.t. the UNROTATED q, k, v)
 int lr_launch_lora_db(const u16* dqkv, int n, int qw, int qcols, int kcols, int hd, const u16* t, int r, float scaling,
-                      float* dbq, float* dbv, hipStream_t st) {
-  int rc = launch_tn(1, t, 2 * LT_RP, 0, dqkv, qw, n, qcols, scaling, dbq, nullptr, r, 2, hd, 0, 0.f, st);
+                      float* dbq, float* dbv, hipStream_t st, float* det_part) {
+  int rc = launch_tn(1, t, 2 * LT_RP, 0, dqkv, qw, n, qcols, scaling, dbq, nullptr, r, 2, hd, 0, 0.f, st, det_part);
   if (rc) return rc;
   return launch_tn(1, t, 2 * LT_RP, LT_RP, dqkv + qcols + kcols, qw, n, qw - qcols - kcols, scaling, dbv, nullptr, r, 1,
-                   hd, 0, 0.f, st);
+                   hd, 0, 0.f, st, det_part);
 }
 // d A_q[j][c], d A_v[j][c] += sum_rows dt[row][j (+LT_RP)] * drop(xn)[row][c]   (dt already carries `scaling`)
 int lr_launch_lora_da(const u16* xn, int n, int d, const u16* dt, int r, uint32_t drop_stream, float drop_p, float* daq,
-                      float* dav, hipStream_t st) {
-  return launch_tn(2, dt, 2 * LT_RP, 0, xn, d, n, d, 1.0f, daq, dav, r, 0, 0, drop_stream, drop_p, st);
+                      float* dav, hipStream_t st, float* det_part) {
+  return launch_tn(2, dt, 2 * LT_RP, 0, xn, d, n, d, 1.0f, daq, dav, r, 0, 0, drop_stream, drop_p, st, det_part);
 }
 
 int lr_launch_lora_tn(int nj, const u16* T, int ldt, int tcol, const u16* X, int ldx, int n, int cols, float scale,
                       float* out0, float* out1, int r, int layout, int hd, uint32_t drop_stream, float drop_p,
-                      hipStream_t st) {
-  return launch_tn(nj, T, ldt, tcol, X, ldx, n, cols, scale, out0, out1, r, layout, hd, drop_stream, drop_p, st);
+                      hipStream_t st, float* det_part) {
+  return launch_tn(nj, T, ldt, tcol, X, ldx, n, cols, scale, out0, out1, r, layout, hd, drop_stream, drop_p, st, det_part);
 }
 
 // =============================================================================================
@@ -952,6 +987,9 @@ int lr_launch_rmsnorm_bwd(const u16* dy, const u16* x, const u16* w, const u16* 
 // =============================================================================================
 // model/llm.py:113-126: logits = lm_head(h).float(); CrossEntropyLoss() = mean over the labelled tokens.
 // scal[0] += sum of -log p(target); d logits = (softmax - onehot) * gscale, gscale = grad_scale / n_labelled.
+// DET (deterministic mode): scal is a buffer of 2 + m floats and row i's loss is STORED to scal[2 + i] (0 for a row without a
+// token id) for lt_finish_loss_det_kernel to sum in a fixed order. scal[1] counts in both modes: adding 1.0f is exact in any order.
+template <bool DET>
 __global__ __launch_bounds__(256) void lt_ce_kernel(u16* logits, int V, const int32_t* targets, float gscale,
                                                     float* scal) {
   __shared__ float sh[4];
@@ -960,7 +998,10 @@ __global__ __launch_bounds__(256) void lt_ce_kernel(u16* logits, int V, const in
   const int tgt = targets[row];
   if (tgt < 0 || tgt >= V) {  // not a token id: no loss, no gradient, counted
     for (int j = threadIdx.x; j < V; j += 256) x[j] = 0;
-    if (threadIdx.x == 0) atomicAdd(scal + 1, 1.0f);
+    if (threadIdx.x == 0) {
+      atomicAdd(scal + 1, 1.0f);
+      if (DET) scal[2 + row] = 0.f;
+    }
     return;
   }
   float mx = -__builtin_inff();
@@ -976,11 +1017,16 @@ __global__ __launch_bounds__(256) void lt_ce_kernel(u16* logits, int V, const in
     const float p = __expf(bf2f(x[j]) - mx) * inv;
     x[j] = f2bf((p - (j == tgt ? 1.0f : 0.0f)) * gscale);
   }
-  if (threadIdx.x == 0) atomicAdd(scal, logf(se) + mx - picked);
+  if (threadIdx.x == 0) {
+    if (DET) scal[2 + row] = logf(se) + mx - picked;
+    else atomicAdd(scal, logf(se) + mx - picked);
+  }
 }
-int lr_launch_ce_bf16(u16* logits, int m, int V, const int32_t* targets, float gscale, float* scal, hipStream_t st) {
+int lr_launch_ce_bf16(u16* logits, int m, int V, const int32_t* targets, float gscale, float* scal, hipStream_t st,
+                      bool deterministic) {
   if (m < 1) return LR_OK;
-  hipLaunchKernelGGL(lt_ce_kernel, dim3(m), dim3(256), 0, st, logits, V, targets, gscale, scal);
+  if (deterministic) hipLaunchKernelGGL(lt_ce_kernel<true>, dim3(m), dim3(256), 0, st, logits, V, targets, gscale, scal);
+  else hipLaunchKernelGGL(lt_ce_kernel<false>, dim3(m), dim3(256), 0, st, logits, V, targets, gscale, scal);
   LR_CHECK_LAUNCH("lt_ce_kernel");
   return LR_OK;
 }
@@ -991,8 +1037,26 @@ __global__ void lt_finish_loss_kernel(const float* scal, int m, float* out) {
   out[1] = (float)m;
   out[2] = scal[1];
 }
-int lr_launch_finish_loss(const float* scal, int m, float* out, hipStream_t st) {
-  hipLaunchKernelGGL(lt_finish_loss_kernel, dim3(1), dim3(1), 0, st, scal, m, out);
+// One workgroup's sum of g[0 .. n) (or of their squares) in an order fixed by n alone: thread t adds elements t, t + 256, ... in
+// ascending order, the 64 lanes of a wave and then the 4 waves combine in lt_block_sum's fixed tree. Every thread gets the sum.
+template <bool SQUARE>
+__device__ __forceinline__ float lt_ordered_sum(const float* g, size_t n, float* sh) {
+  float s = 0.f;
+  for (size_t i = threadIdx.x; i < n; i += 256) s += SQUARE ? g[i] * g[i] : g[i];
+  return lt_block_sum(s, sh);
+}
+// deterministic mode: the same three outputs from lt_ce_kernel<true>'s per-row losses (scal[2 + i]), summed in row order
+__global__ __launch_bounds__(256) void lt_finish_loss_det_kernel(const float* scal, int m, float* out) {
+  __shared__ float sh[4];
+  const float sum = lt_ordered_sum<false>(scal + 2, (size_t)m, sh);
+  if (threadIdx.x != 0) return;
+  out[0] = m > 0 ? sum / (float)m : 0.f;
+  out[1] = (float)m;
+  out[2] = scal[1];
+}
+int lr_launch_finish_loss(const float* scal, int m, float* out, hipStream_t st, bool deterministic) {
+  if (deterministic) hipLaunchKernelGGL(lt_finish_loss_det_kernel, dim3(1), dim3(256), 0, st, scal, m, out);
+  else hipLaunchKernelGGL(lt_finish_loss_kernel, dim3(1), dim3(1), 0, st, scal, m, out);
   LR_CHECK_LAUNCH("lt_finish_loss_kernel");
   return LR_OK;
 }
@@ -1033,6 +1097,32 @@ __global__ __launch_bounds__(256) void lt_sumsq_kernel(const float* g, size_t n,
   s = lt_block_sum(s, sh);
   if (threadIdx.x == 0) atomicAdd(out, s);
 }
+// Deterministic mode's squared gradient norm: lr_llama_lora_apply has no workspace and the handle's scratch no room for
+// per-workgroup partials, so ONE workgroup of 1024 threads sums the whole buffer. Thread t takes the 16-byte groups t, t + 1024,
+// ... in ascending order into four running sums (one per float of the group), adds them 0..3, the tail n % 4 goes to thread 0;
+// lanes, then waves, combine in a fixed tree. 20 M gradients (Llama-2-7b, all seven modules, r = 8) are 80 MB through one CU.
+__global__ __launch_bounds__(1024) void lt_sumsq_det_kernel(const float* g, size_t n, float* out) {
+  __shared__ float sh[16];
+  floatx4 s4 = floatx4{0.f, 0.f, 0.f, 0.f};
+  const size_t n4 = n >> 2;
+#pragma unroll 4
+  for (size_t i = threadIdx.x; i < n4; i += 1024) {
+    const floatx4 v = *reinterpret_cast<const floatx4*>(g + 4 * i);
+    s4 += v * v;
+  }
+  float s = ((s4[0] + s4[1]) + s4[2]) + s4[3];
+  if (threadIdx.x == 0)
+    for (size_t i = n4 << 2; i < n; ++i) s += g[i] * g[i];
+#pragma unroll
+  for (int sft = 32; sft >= 1; sft >>= 1) s += __shfl_xor(s, sft, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = sh[0];
+    for (int w = 1; w < 16; ++w) t += sh[w];
+    out[0] = t;
+  }
+}
 // hyper[0] lr, hyper[1] max_grad_norm (<= 0: no clipping); ctr[0] = optimizer steps taken so far
 __global__ __launch_bounds__(256) void lt_adamw_kernel(float* p, float* g, float* m, float* v, size_t n,
                                                        const float* sumsq, const float* hyper, const int* ctr,
@@ -1062,12 +1152,17 @@ __global__ void lt_set_hyper_kernel(float* hyper, float lr, float limit, float* 
 __global__ void lt_bump_kernel(int* ctr) { ctr[0] += 1; }
 int lr_launch_lora_adamw(float* p, float* g, float* m, float* v, size_t n, float* scratch /*[4]*/, int* ctr, float lr,
                          float max_grad_norm, float beta1, float beta2, float eps, float wd, float* out_norm,
-                         hipStream_t st) {
+                         hipStream_t st, bool deterministic) {
   float* sumsq = scratch;
   float* hyper = scratch + 1;
   hipLaunchKernelGGL(lt_set_hyper_kernel, dim3(1), dim3(1), 0, st, hyper, lr, max_grad_norm, sumsq);
   const unsigned blocks = (unsigned)min((size_t)1024, (n + 255) / 256);
-  hipLaunchKernelGGL(lt_sumsq_kernel, dim3(blocks), dim3(256), 0, st, g, n, sumsq);
+  if (deterministic) {
+    if (((uintptr_t)g & 15) != 0) LR_FAIL(LR_EUNSUPPORTED, "deterministic gradient norm: the buffer must be 16-byte aligned");
+    hipLaunchKernelGGL(lt_sumsq_det_kernel, dim3(1), dim3(1024), 0, st, g, n, sumsq);
+  } else {
+    hipLaunchKernelGGL(lt_sumsq_kernel, dim3(blocks), dim3(256), 0, st, g, n, sumsq);
+  }
   hipLaunchKernelGGL(lt_adamw_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, sumsq, hyper, ctr, beta1, beta2,
                      eps, wd, out_norm);
   hipLaunchKernelGGL(lt_bump_kernel, dim3(1), dim3(1), 0, st, ctr);

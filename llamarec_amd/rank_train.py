@@ -213,6 +213,18 @@ class LoraTrainEngine:
 
     merged = False
 
+    def set_deterministic(self, enable=True):
+        """Run-to-run identical bits for loss_and_grads / apply (include/llamarec_mi355x.h, lr_llama_lora_set_deterministic): no
+        fp32 atomic decides a value any more. The mode is a property of this engine's handle -- other engines, deterministic
+        or not, may run next to it -- and its partial sums live in the workspace, which is therefore dropped here and sized
+        anew by the next call. Not promised: the same bits under another --lora_token_budget grouping, LR_TN_CHUNK or world size."""
+        check(lib().lr_llama_lora_set_deterministic(self._h, int(bool(enable))), "lr_llama_lora_set_deterministic")
+        self.deterministic = bool(enable)
+        self._ws = None
+        return self
+
+    deterministic = False
+
     def loss_and_grads(self, seqs, labels, grad_scale=1.0, accumulate=False):
         """One micro-batch. Returns the loss as a device scalar (mean over the labelled tokens); gradients * grad_scale
         are written to (or, with accumulate, added to) `self.grads`."""

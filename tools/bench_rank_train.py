@@ -3,6 +3,10 @@
 (forward + backward), per optimizer step, tokens/s and model FLOP/s. SURVEY.md 8(f) #4.
 
   python tools/bench_rank_train.py [--layers 32] [--batch 16] [--tokens 460] [--steps 5] [--accum 1]
+
+--deterministic: the cost of LoraTrainEngine.set_deterministic. A second engine on the same base runs the same batch in
+deterministic mode; default and deterministic steps ALTERNATE in one process (same clocks, same thermal state) and the line
+reports each mode's median and min..max per step and the added workspace.
 """
 import argparse
 import os
@@ -27,6 +31,7 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.05)
     ap.add_argument("--lora_target_modules", nargs="+", default=["q_proj", "v_proj"],
                     choices=list(LORA_MODULES) + ["all-linear"])
+    ap.add_argument("--deterministic", action="store_true")
     a = ap.parse_args()
     from llamarec_amd.llm import LLAMA2_7B, LlamaRanker
     from llamarec_amd.rank_train import LoraTrainEngine
@@ -81,6 +86,37 @@ def main():
     flops = L * (2 * n * lin + 3.5 * attn)                       # forward + data gradients (no weight gradients: frozen)
     print(f"layers={L} B={a.batch} tokens={n}: fwd+bwd {fb:.1f} ms/micro-batch, clip+AdamW {ap_ms:.3f} ms, "
           f"{n / fb * 1e3:.0f} tokens/s, {a.batch / fb * 1e3:.1f} samples/s, {flops / fb / 1e9:.0f} TFLOP/s (bf16)")
+    if not a.deterministic:
+        return
+    det = LoraTrainEngine(ranker, dropout=a.dropout, target_modules=a.lora_target_modules, init=init).set_deterministic(True)
+    engines = {"default": eng, "deterministic": det}
+    for e in engines.values():          # same state on both sides; one untimed step sizes the deterministic workspace
+        e.load(init)
+        e.m.zero_()
+        e.v.zero_()
+        e.loss_and_grads(seqs, labels)
+    torch.cuda.synchronize()
+    ws_mb = {k: e._ws.numel() / 2**20 for k, e in engines.items()}
+    times = {k: ([], []) for k in engines}
+    for _ in range(max(a.steps, 3)):
+        for k, e in engines.items():
+            e0.record()
+            for i in range(a.accum):
+                e.loss_and_grads(seqs, labels, grad_scale=1.0 / a.accum, accumulate=i > 0)
+            e1.record()
+            e.apply(2e-4, 1.0)
+            e2.record()
+            torch.cuda.synchronize()
+            times[k][0].append(e0.elapsed_time(e1) / a.accum)
+            times[k][1].append(e1.elapsed_time(e2))
+    for k, (t_fb, t_ap) in times.items():
+        print(f"{k}: fwd+bwd median {np.median(t_fb):.2f} ms (min {min(t_fb):.2f}, max {max(t_fb):.2f}, {len(t_fb)} alternating "
+              f"steps), clip+AdamW median {np.median(t_ap):.3f} ms (min {min(t_ap):.3f}, max {max(t_ap):.3f}), "
+              f"workspace {ws_mb[k]:.1f} MiB")
+    d_fb = np.median(times["deterministic"][0]) - np.median(times["default"][0])
+    d_ap = np.median(times["deterministic"][1]) - np.median(times["default"][1])
+    print(f"deterministic mode: fwd+bwd {d_fb:+.2f} ms ({100 * d_fb / np.median(times['default'][0]):+.2f} %), clip+AdamW "
+          f"{d_ap:+.3f} ms, workspace {ws_mb['deterministic'] - ws_mb['default']:+.1f} MiB")
 
 
 if __name__ == "__main__":

@@ -94,6 +94,8 @@ def main(argv=None, export_root=None):
 
         engine = LoraTrainEngine(model, r=args.lora_r, alpha=args.lora_alpha, dropout=args.lora_dropout, seed=args.seed,
                                  target_modules=args.lora_target_modules)
+        if args.deterministic:    # run-to-run identical adapters: every host-side draw above and below is seeded from --seed
+            engine.set_deterministic(True)
         samples = LLMTrainSamples(args, dataset["train"], dataset["meta"], tokenizer,
                                   rng=np.random.RandomState(args.seed + rank))
         val_items = build_val_items(dataset, retrieved, tokenizer, args)
