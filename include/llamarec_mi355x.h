@@ -552,6 +552,23 @@ size_t lr_llama_lora_workspace_bytes(const lr_llama_lora_t* h, int32_t max_token
  * fixed order, the generic attention backward computes dK / dV per owner. Not promised: the same bits under another
  * grouping of the batch, another LR_TN_CHUNK or another world size. */
 int lr_llama_lora_set_deterministic(lr_llama_lora_t* h, int32_t enable);
+/* The part of a handle's persistent state that is in no buffer of lr_llama_lora_buffers: the number of
+ * lr_llama_lora_apply calls so far (AdamW's bias correction reads it on the device) and the number of
+ * lr_llama_lora_loss_grad calls (it selects the dropout streams). Together with params, m and v they are everything
+ * a later step depends on: gradients, the bf16 working copies and the scratch scalars are rebuilt by every pass. A
+ * handle that is given another handle's params / m / v and progress (same base, config and targets) continues with
+ * that handle's bits. reserved: zero. */
+typedef struct LrLoraProgress {
+  int64_t optimizer_steps;
+  int64_t passes;
+  int64_t reserved[2];
+} LrLoraProgress;
+/* get: the values as they stand after everything already queued on hip_stream; copies on that stream and waits for
+ * it. set: ordered on hip_stream before later calls, does not wait. LR_EINVAL (with a message) for a null argument
+ * and, in set, a negative value, optimizer_steps > INT32_MAX or passes > UINT32_MAX (the handle's counter types) or
+ * a non-zero reserved word; the handle is unchanged then. */
+int lr_llama_lora_get_progress(lr_llama_lora_t* h, LrLoraProgress* out, void* hip_stream);
+int lr_llama_lora_set_progress(lr_llama_lora_t* h, const LrLoraProgress* in, void* hip_stream);
 /* One micro-batch: forward over the packed prompts (as lr_llama_prefill_verbalize packs them), loss
  * = mean over the m labelled rows of -log softmax(logits[loss_rows[i]])[loss_targets[i]] (row p of a
  * prompt predicts token p+1: the caller passes the rows whose NEXT token is labelled, each once),

@@ -146,6 +146,11 @@ class LrLoraTargets(C.Structure):
     _fields_ = [("modules", C.c_uint32), ("reserved", C.c_uint32 * 7)]
 
 
+class LrLoraProgress(C.Structure):
+    """include/llamarec_mi355x.h: LrLoraProgress (lr_llama_lora_get_progress / lr_llama_lora_set_progress)."""
+    _fields_ = [("optimizer_steps", C.c_int64), ("passes", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
 # bit order of LrLoraTargets.modules = `which` of lr_llama_lora_param_range = per-layer order of the flat buffers
 LORA_MODULES = ("q_proj", "v_proj", "k_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
 

@@ -119,6 +119,8 @@ PROTOTYPES = {
                                             C.POINTER(C.c_size_t)]),
     "lr_llama_lora_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "lr_llama_lora_set_deterministic": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lr_llama_lora_get_progress": (C.c_int, [C.c_void_p, C.POINTER(A.LrLoraProgress), C.c_void_p]),
+    "lr_llama_lora_set_progress": (C.c_int, [C.c_void_p, C.POINTER(A.LrLoraProgress), C.c_void_p]),
     "lr_llama_lora_loss_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                           C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_size_t, C.c_void_p]),

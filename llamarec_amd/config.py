@@ -81,6 +81,13 @@ def build_parser():
     p.add_argument("--llm_adapter_path", type=str, default=None, help="local PEFT adapter directory")
     p.add_argument("--lora_token_budget", type=int, default=16384, help="tokens per forward/backward pass when an "
                    "optimizer step's micro-batches are regrouped (same summed gradient; 0 = the reference's micro-batches)")
+    # HF Trainer's save_strategy="steps" layout (trainer/llm.py:103-136 sets save_steps = lora_val_iterations and
+    # save_total_limit = 3). Off by default here: existing runs keep writing exactly adapter/ and best_adapter/ 
+    p.add_argument("--lora_save_steps", type=int, default=0, help="write <export_root>/checkpoint-<step> after every N-th "
+                   "optimizer step and after the last one (0 = none)")
+    p.add_argument("--lora_save_total_limit", type=int, default=3, help="keep the K newest checkpoint-<step> directories")
+    p.add_argument("--resume_from_checkpoint", type=str, default=None, help="a checkpoint-<step> directory, or 'last' = the "
+                   "highest complete one under the export root (none there: start fresh)")
     p.add_argument("--eval_token_budget", type=int, default=None, help="prompt tokens per evaluation prefill (default "
                    "packing.TOKEN_BUDGET; 0 = fixed batches of --test_batch_size prompts like the reference's loader)")
     p.add_argument("--synthetic", action="store_true", help="fabricate dataset / weights (nothing exists offline)")

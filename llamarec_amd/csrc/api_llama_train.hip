@@ -8,6 +8,7 @@
 // Llama-2-7b, nothing against 288 GB, and the backward then runs at the forward's GEMM rate. Every activation the
 // backward needs is kept (~100 KB per token and layer): no recomputation (the reference checkpoints, config.py:269,
 // because its cards are 24-80 GB).
+#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -407,6 +408,42 @@ extern "C" size_t lr_llama_lora_workspace_bytes(const lr_llama_lora_t* h, int32_
 extern "C" int lr_llama_lora_set_deterministic(lr_llama_lora_t* h, int32_t enable) {
   if (!h) LR_FAIL(LR_EINVAL, "lr_llama_lora_set_deterministic: null handle");
   h->deterministic = enable != 0;
+  return LR_OK;
+}
+// The two counters of a handle that sit in no buffer of lr_llama_lora_buffers: ctr[0] on the device (lt_adamw_kernel's bias
+// correction) and the host's pass counter (the dropout streams). Everything else a trajectory depends on is params / m / v;
+// grads, the bf16 working copies and the scratch scalars are rebuilt by every pass.
+static int check_progress(const lr_llama_lora* h, const LrLoraProgress* p, const char* who) {
+  if (!h || !p) LR_FAIL(LR_EINVAL, "%s: null argument", who);
+  return LR_OK;
+}
+extern "C" int lr_llama_lora_get_progress(lr_llama_lora_t* h, LrLoraProgress* out, void* hip_stream) {
+  LR_RUN(check_progress(h, out, "lr_llama_lora_get_progress"));
+  hipStream_t st = (hipStream_t)hip_stream;
+  int steps = 0;
+  LR_CHECK_HIP(hipMemcpyAsync(&steps, h->ctr, sizeof(int), hipMemcpyDeviceToHost, st));
+  LR_CHECK_HIP(hipStreamSynchronize(st));
+  memset(out, 0, sizeof(*out));
+  out->optimizer_steps = steps;
+  out->passes = h->pass;
+  return LR_OK;
+}
+extern "C" int lr_llama_lora_set_progress(lr_llama_lora_t* h, const LrLoraProgress* in, void* hip_stream) {
+  LR_RUN(check_progress(h, in, "lr_llama_lora_set_progress"));
+  for (int i = 0; i < 2; ++i)
+    if (in->reserved[i]) LR_FAIL(LR_EINVAL, "lr_llama_lora_set_progress: LrLoraProgress.reserved[%d] is not zero", i);
+  if (in->optimizer_steps < 0 || in->passes < 0)
+    LR_FAIL(LR_EINVAL, "lr_llama_lora_set_progress: negative count (optimizer_steps=%lld, passes=%lld)",
+            (long long)in->optimizer_steps, (long long)in->passes);
+  if (in->optimizer_steps > (int64_t)INT32_MAX)   // ctr[0] is an int on the device
+    LR_FAIL(LR_EINVAL, "lr_llama_lora_set_progress: optimizer_steps=%lld exceeds the handle's 31-bit step counter",
+            (long long)in->optimizer_steps);
+  if (in->passes > (int64_t)UINT32_MAX)           // the pass counter is a uint32_t
+    LR_FAIL(LR_EINVAL, "lr_llama_lora_set_progress: passes=%lld exceeds the handle's 32-bit pass counter",
+            (long long)in->passes);
+  // the value travels in the command itself: no host buffer has to outlive the call
+  LR_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)h->ctr, (int)in->optimizer_steps, 1, (hipStream_t)hip_stream));
+  h->pass = (uint32_t)in->passes;
   return LR_OK;
 }
 extern "C" size_t lr_llama_lora_eval_workspace_bytes(const lr_llama_lora_t* h, int32_t max_tokens, int32_t max_seqs) {

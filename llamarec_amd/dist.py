@@ -49,6 +49,17 @@ def barrier():
         dist.barrier()
 
 
+def all_gather_int(x: int, device=None) -> list:
+    """[x of rank 0, x of rank 1, ...] on every rank ([x] for a single process)."""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        world = dist.get_world_size()
+        t = torch.zeros(world, dtype=torch.int64, device=device)
+        t[dist.get_rank()] = int(x)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return [int(v) for v in t.cpu()]
+    return [int(x)]
+
+
 def all_reduce_max_float(x: float, device=None) -> float:
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         t = torch.tensor([x], dtype=torch.float64, device=device)

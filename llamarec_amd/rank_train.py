@@ -9,7 +9,8 @@ the Linears --lora_target_modules names, q_proj / v_proj by default, train_ranke
                     the answer letter appended, labels[:-2] = -100
   LoraRankerTrainer the Trainer loop: gradient accumulation (train_batch_size / lora_micro_batch_size), linear warm-up
                     and decay, clipping at 1.0, validation every lora_val_iterations with best-adapter checkpoint and
-                    early stopping on rerank_best_metric, adapter saved in PEFT's on-disk format
+                    early stopping on rerank_best_metric, adapter saved in PEFT's on-disk format; with lora_save_steps HF
+                    Trainer's checkpoint-<step> directories, and resume_from_checkpoint continues from one
 """
 from __future__ import annotations
 
@@ -17,6 +18,8 @@ import ctypes as C
 import json
 import math
 import os
+import re
+import shutil
 
 import numpy as np
 import torch
@@ -71,6 +74,16 @@ def loss_rows_and_targets(seqs, labels):
     return np.concatenate(rows).astype(np.int32), np.concatenate(tgts).astype(np.int32)
 
 
+def check_layout(mine, theirs):
+    """LoraTrainEngine.layout() of this engine against a saved one: the first field that differs is a ValueError."""
+    for k, v in mine.items():
+        if k not in theirs:
+            raise ValueError(f"engine state: field {k!r} is missing")
+        w = list(theirs[k]) if k == "target_modules" else theirs[k]
+        if w != v:
+            raise ValueError(f"engine state: {k} is {w!r} in the checkpoint and {v!r} in this engine")
+
+
 class LoraTrainEngine:
     def __init__(self, ranker: LlamaRanker, r=8, alpha=32, dropout=0.05, seed=42, beta1=0.9, beta2=0.999, eps=1e-8,
                  weight_decay=0.0, init=None, target_modules=DEFAULT_TARGET_MODULES, create_call=None):
@@ -79,6 +92,7 @@ class LoraTrainEngine:
         the call this class always made, "ex" otherwise. The first two exist only for q_proj | v_proj."""
         self.ranker, self.device = ranker, ranker.device
         self.r, self.alpha = int(r), float(alpha)
+        self.dropout, self.seed = float(dropout), int(seed)
         self.target_modules = expand_target_modules(target_modules)
         targets = A.LrLoraTargets(modules=sum(1 << A.LORA_MODULES.index(m) for m in self.target_modules))
         qv = set(self.target_modules) == set(DEFAULT_TARGET_MODULES)
@@ -176,13 +190,30 @@ class LoraTrainEngine:
             v.copy_(src.to(torch.float32).reshape(v.shape))
         return self
 
-    def export(self):
-        """PEFT-named CPU tensors (adapter_model.safetensors keys)."""
+    def export(self, buf=None):
+        """PEFT-named CPU tensors (adapter_model.safetensors keys) of a flat buffer (default: the parameters)."""
         out = {}
-        for k, v in self.named().items():
+        for k, v in self.named(buf).items():
             parts = k.split(".")   # layers.{l}.{module}.lora_{A,B}
             out[peft_key(parts[1], parts[2], parts[3][-1])] = v.detach().cpu().clone()
         return out
+
+    def import_flat(self, tensors):
+        """export()'s inverse: PEFT-named fp32 tensors -> one flat CPU buffer in the kernels' order."""
+        flat = torch.empty(self.params.numel(), dtype=torch.float32)
+        views = self.named(flat)
+        missing = sorted(peft_key(*self._key_parts(k)) for k in views if peft_key(*self._key_parts(k)) not in tensors)
+        if missing or len(tensors) != len(views):
+            raise ValueError(f"adapter tensors do not match this engine's modules (missing {missing[:2]}, "
+                             f"{len(tensors)} given for {len(views)})")
+        for k, v in views.items():
+            v.copy_(tensors[peft_key(*self._key_parts(k))].to(torch.float32).reshape(v.shape))
+        return flat
+
+    @staticmethod
+    def _key_parts(name):
+        parts = name.split(".")
+        return parts[1], parts[2], parts[3][-1]
 
     def save_adapter(self, path, base_model=""):
         """adapter_config.json + adapter_model.safetensors, loadable by peft and by LlamaRanker.from_pretrained."""
@@ -192,6 +223,50 @@ class LoraTrainEngine:
         json.dump(adapter_config(self.r, self.alpha, self.target_modules, base_model),
                   open(os.path.join(path, "adapter_config.json"), "w"), indent=1)
         save_file(self.export(), os.path.join(path, "adapter_model.safetensors"))
+
+    # -- everything a later step depends on ---------------------------------------------------------------
+    LAYOUT_BASE_FIELDS = ("hidden_size", "num_hidden_layers", "num_attention_heads", "num_key_value_heads", "head_dim",
+                          "intermediate_size")
+
+    def layout(self):
+        """What two engines must share for one's flat buffers to mean the same in the other (and, with `dropout` and `seed`,
+        to continue with the same bits)."""
+        c = self.ranker.config
+        base = {k: int(self.ranker.hd if k == "head_dim" else c[k]) for k in self.LAYOUT_BASE_FIELDS}
+        return dict(r=self.r, alpha=self.alpha, dropout=self.dropout, seed=self.seed,
+                    target_modules=list(self.target_modules), n_params=int(self.params.numel()), **base)
+
+    def progress(self):
+        """(optimizer steps, passes) after everything queued on the current stream; waits for it."""
+        p = A.LrLoraProgress()
+        with torch.cuda.device(self.device):
+            check(lib().lr_llama_lora_get_progress(self._h, C.byref(p), stream_ptr()), "lr_llama_lora_get_progress")
+        return int(p.optimizer_steps), int(p.passes)
+
+    def set_progress(self, optimizer_steps, passes):
+        p = A.LrLoraProgress(optimizer_steps=int(optimizer_steps), passes=int(passes))
+        with torch.cuda.device(self.device):
+            check(lib().lr_llama_lora_set_progress(self._h, C.byref(p), stream_ptr()), "lr_llama_lora_set_progress")
+        return self
+
+    def state_dict(self):
+        """The handle's persistent state on the host: the flat fp32 parameters and AdamW moments, the two counters no buffer
+        shows (lr_llama_lora_get_progress) and the layout record. Gradients, the bf16 working copies and the scratch scalars
+        are rebuilt by every pass and are not part of it."""
+        steps, passes = self.progress()
+        return dict(params=self.params.detach().cpu().clone(), exp_avg=self.m.detach().cpu().clone(),
+                    exp_avg_sq=self.v.detach().cpu().clone(), optimizer_steps=steps, passes=passes, **self.layout())
+
+    def load_state_dict(self, sd):
+        """Continue where the engine that wrote `sd` stood. A layout field that differs is a ValueError naming it; the
+        deterministic flag, the workspace and the output scalars are left alone."""
+        check_layout(self.layout(), sd)
+        for name, buf in (("params", self.params), ("exp_avg", self.m), ("exp_avg_sq", self.v)):
+            src = sd[name]
+            if src.dtype != torch.float32 or src.numel() != buf.numel():
+                raise ValueError(f"{name}: {src.numel()} {src.dtype} values for a buffer of {buf.numel()} float32")
+            buf.copy_(src.reshape(-1))
+        return self.set_progress(sd["optimizer_steps"], sd["passes"])
 
     # -- the step ---------------------------------------------------------------------------------------
     def reserve(self, shapes):
@@ -389,6 +464,42 @@ def linear_schedule(warmup_steps, total_steps):
 
 
 # ---------------------------------------------------------------------------------------------
+# checkpoint-<step> directories (HF Trainer's save_strategy="steps" layout, trainer/llm.py:103-136)
+# ---------------------------------------------------------------------------------------------
+CHECKPOINT_DIR = re.compile(r"^checkpoint-(\d+)$")
+TRAINER_STATE = "trainer_state.json"
+# what a resumed run must share with the run that wrote the checkpoint: each decides which samples a step sees, how they are
+# grouped into passes or what the step does with them. Everything else (lora_max_steps, lora_num_epochs, the save / validation
+# cadences, the patience, the export root, --deterministic) may differ and only changes what comes after.
+FINGERPRINT_ARGS = {"lora_micro_batch_size": None, "train_batch_size": None, "lora_token_budget": 16384, "seed": None,
+                    "warmup_steps": None, "lora_lr": None, "llm_train_on_inputs": False}   # name: value when args lacks it
+
+
+def list_checkpoints(root):
+    """[(step, path)] of the complete checkpoint-<int> directories under `root`, by step. A `.tmp` directory (a write that did
+    not finish) and a directory without trainer_state.json are no checkpoints."""
+    out = []
+    if root and os.path.isdir(root):
+        for name in os.listdir(root):
+            m = CHECKPOINT_DIR.match(name)
+            path = os.path.join(root, name)
+            if m and os.path.isfile(os.path.join(path, TRAINER_STATE)):
+                out.append((int(m.group(1)), path))
+    return sorted(out)
+
+
+def rng_state_to_json(state):
+    """np.random.RandomState.get_state() -> a JSON-able dict (no pickle: a checkpoint is loaded from disk)."""
+    kind, key, pos, has_gauss, cached = state
+    return {"kind": str(kind), "key": [int(k) for k in key], "pos": int(pos), "has_gauss": int(has_gauss),
+            "cached_gaussian": float(cached)}
+
+
+def rng_state_from_json(d):
+    return (d["kind"], np.asarray(d["key"], dtype=np.uint32), int(d["pos"]), int(d["has_gauss"]), float(d["cached_gaussian"]))
+
+
+# ---------------------------------------------------------------------------------------------
 # the Trainer loop
 # ---------------------------------------------------------------------------------------------
 class LoraRankerTrainer:
@@ -425,6 +536,12 @@ class LoraRankerTrainer:
         # tokens per forward/backward pass when an optimizer step's samples are regrouped (repack); None = the reference's
         # micro-batches as they come. 16 384 rows = 64 row tiles: whole 256-CU rounds for N = 4096 / 12288 (packing.py)
         self.train_token_budget = getattr(args, "lora_token_budget", 16384) or None
+        # checkpoint-<step> directories: off unless asked for (a namespace without the flags behaves as before them)
+        self.save_steps = int(getattr(args, "lora_save_steps", 0) or 0)
+        self.save_total_limit = getattr(args, "lora_save_total_limit", 3)
+        self.resume_from = getattr(args, "resume_from_checkpoint", None)
+        if self.save_steps > 0 and not export_root:
+            raise ValueError("lora_save_steps needs an export root to write checkpoint-<step> directories into")
 
     def _order(self, epoch):
         return np.random.RandomState(self.args.seed + epoch).permutation(len(self.samples))
@@ -492,6 +609,102 @@ class LoraRankerTrainer:
             self.bad_evals += 1
         return self.bad_evals >= a.lora_early_stopping_patience
 
+    # -- checkpoints ------------------------------------------------------------------------------------
+    def fingerprint(self):
+        a = self.args
+        fp = {"world_size": int(self.world), "num_train_samples": len(self.samples)}
+        for k, default in FINGERPRINT_ARGS.items():
+            fp[k] = getattr(a, k, default)
+        return fp
+
+    def save_checkpoint(self, step, epoch, step_in_epoch):
+        """<export_root>/checkpoint-<step>: the adapter as peft and LlamaRanker.from_pretrained read it, the AdamW moments, the
+        best adapter so far, the loop's bookkeeping and every rank's sampler state. Written to checkpoint-<step>.tmp by all
+        ranks (one node, a shared file system), renamed by rank 0 once everybody is through, then rotated."""
+        from safetensors.torch import save_file
+
+        from . import dist as DD
+
+        a, eng = self.args, self.engine
+        final = os.path.join(self.export_root, f"checkpoint-{step}")
+        tmp = final + ".tmp"
+        if self.rank == 0:
+            shutil.rmtree(tmp, ignore_errors=True)                    # left behind by a write that did not finish
+            os.makedirs(tmp)
+        DD.barrier()
+        sd = eng.state_dict()
+        passes = DD.all_gather_int(sd["passes"], eng.device)          # the token-budget grouping may differ between ranks
+        rng = getattr(self.samples, "rng", None)
+        if rng is not None:
+            json.dump(rng_state_to_json(rng.get_state()), open(os.path.join(tmp, f"rng_state_{self.rank}.json"), "w"))
+        if self.rank == 0:
+            eng.save_adapter(tmp, getattr(a, "llm_base_model", ""))
+            save_file({"exp_avg": sd["exp_avg"], "exp_avg_sq": sd["exp_avg_sq"]}, os.path.join(tmp, "optimizer.safetensors"))
+            if self.best_state is not None:
+                save_file(eng.export(self.best_state), os.path.join(tmp, "best_adapter_model.safetensors"))
+            tok = getattr(self.samples, "tokenizer", None)
+            if hasattr(tok, "save_pretrained"):
+                tok.save_pretrained(tmp)
+            layout = {k: v for k, v in sd.items() if k not in ("params", "exp_avg", "exp_avg_sq", "optimizer_steps", "passes")}
+            state = {"global_step": step, "epoch": epoch, "step_in_epoch": step_in_epoch,
+                     "optimizer_steps": sd["optimizer_steps"], "passes": passes[0], "passes_per_rank": passes,
+                     "best_metric": self.best_metric, "bad_evals": self.bad_evals, "log_history": self.history,
+                     "engine": layout, "fingerprint": self.fingerprint()}
+            json.dump(state, open(os.path.join(tmp, TRAINER_STATE), "w"), indent=1)
+        DD.barrier()
+        if self.rank == 0:
+            shutil.rmtree(final, ignore_errors=True)
+            os.rename(tmp, final)
+            limit = self.save_total_limit
+            if limit is not None and limit > 0:
+                for _, old in list_checkpoints(self.export_root)[:-limit]:
+                    shutil.rmtree(old, ignore_errors=True)
+        return final
+
+    def resolve_checkpoint(self):
+        """--resume_from_checkpoint -> a complete checkpoint directory, or None for a fresh start ('last' with nothing there:
+        a requeued job's first run)."""
+        want = self.resume_from
+        if not want:
+            return None
+        if want == "last":
+            found = list_checkpoints(self.export_root)
+            if not found:
+                self.log(f"resume_from_checkpoint last: no checkpoint under {self.export_root}, starting fresh")
+                return None
+            return found[-1][1]
+        if not os.path.isfile(os.path.join(want, TRAINER_STATE)):
+            raise SystemExit(f"--resume_from_checkpoint {want}: no complete checkpoint there ({TRAINER_STATE} is missing)")
+        return want
+
+    def load_checkpoint(self, path):
+        """Everything save_checkpoint wrote -> engine, loop bookkeeping and this rank's sampler. Returns (step, epoch,
+        step_in_epoch)."""
+        from safetensors.torch import load_file
+
+        eng = self.engine
+        st = json.load(open(os.path.join(path, TRAINER_STATE)))
+        mine = self.fingerprint()
+        for k, v in mine.items():
+            if k not in st["fingerprint"] or st["fingerprint"][k] != v:
+                raise SystemExit(f"--resume_from_checkpoint {path}: {k} is {st['fingerprint'].get(k)!r} in the checkpoint and "
+                                 f"{v!r} in this run; a resumed run keeps it")
+        rng = getattr(self.samples, "rng", None)
+        rng_file = os.path.join(path, f"rng_state_{self.rank}.json")
+        if rng is not None and not os.path.isfile(rng_file):
+            raise SystemExit(f"--resume_from_checkpoint {path}: rng_state_{self.rank}.json is missing")
+        moments = load_file(os.path.join(path, "optimizer.safetensors"))
+        eng.load_state_dict(dict(st["engine"], params=eng.import_flat(load_file(os.path.join(path, "adapter_model.safetensors"))),
+                                 exp_avg=moments["exp_avg"], exp_avg_sq=moments["exp_avg_sq"],
+                                 optimizer_steps=st["optimizer_steps"], passes=st["passes_per_rank"][self.rank]))
+        best = os.path.join(path, "best_adapter_model.safetensors")
+        self.best_state = eng.import_flat(load_file(best)).to(eng.params.device) if os.path.isfile(best) else None
+        self.best_metric, self.bad_evals, self.history = st["best_metric"], int(st["bad_evals"]), list(st["log_history"])
+        if rng is not None:
+            rng.set_state(rng_state_from_json(json.load(open(rng_file))))
+        self.log(f"resumed from {path}: step {st['global_step']}, epoch {st['epoch']} + {st['step_in_epoch']} steps")
+        return int(st["global_step"]), int(st["epoch"]), int(st["step_in_epoch"])
+
     def train(self):
         from . import prompt as P
         from .train import average_gradients_
@@ -500,10 +713,15 @@ class LoraRankerTrainer:
         step, epoch, losses = 0, 0, []
         eos = getattr(getattr(self.samples, "tokenizer", None), "eos_token_id", 2)
         stop = False
+        skip = 0                                                     # optimizer steps of `epoch` a checkpoint already took
+        resumed = self.resolve_checkpoint()
+        if resumed:
+            step, epoch, skip = self.load_checkpoint(resumed)
+            stop = self.bad_evals >= a.lora_early_stopping_patience  # the checkpoint was written before the stop test
         while step < self.total_steps and not stop:
             order = self._order(epoch)
             per_step = self.micro * self.accum * self.world
-            for s0 in range(0, len(order) - per_step + 1, per_step):
+            for s0 in range(skip * per_step, len(order) - per_step + 1, per_step):
                 micro = []
                 for k in range(self.accum):
                     lo = s0 + (k * self.world + self.rank) * self.micro
@@ -525,9 +743,13 @@ class LoraRankerTrainer:
                 if self._maybe_validate(step):
                     self.log(f"early stopping at step {step}")
                     stop = True
+                # after the validation, so that the checkpoint carries its best_* / bad_evals; and after the last step
+                if self.save_steps > 0 and (step % self.save_steps == 0 or stop or step >= self.total_steps):
+                    self.save_checkpoint(step, epoch, s0 // per_step + 1)
                 if stop or step >= self.total_steps:
                     break
             epoch += 1
+            skip = 0
         if self.best_state is not None:                              # load_best_model_at_end=True
             eng.params.copy_(self.best_state)
         if self.export_root and self.rank == 0:

@@ -7,6 +7,11 @@ SURVEY.md 8(f) #4) -- then `trainer.test(test_retrieval)` (:111). Pass a local b
 into the bf16 weights at load) only the scoring half runs. Nothing is downloaded. --synthetic
 fabricates a tiny model + tokenizer. The tuned adapter is written in PEFT's format to
 <export_root>/adapter (and the best one by --rerank_best_metric to <export_root>/best_adapter).
+With --lora_save_steps N every N-th optimizer step (and the last) also leaves
+<export_root>/checkpoint-<step> (HF Trainer's layout, the --lora_save_total_limit newest kept): a
+PEFT adapter directory that additionally holds the optimizer moments, the loop's bookkeeping and
+every rank's sampler state. --resume_from_checkpoint <checkpoint-N | last> continues such a run;
+with --deterministic the continued run writes the bits the uninterrupted one would have.
 
 Outputs keep the reference layout: experiments/<model>/<dataset>/{subset,overall}_metrics.json.
 Data parallel: launch with torch.distributed.run; ranks shard the retrieved users and all-reduce
@@ -37,6 +42,9 @@ def main(argv=None, export_root=None):
         raise SystemExit("--llm_retrieved_path experiments/lru/<dataset> is required")
     if args.llm == "gemma" and not args.eval_only:
         raise SystemExit(TRAIN_LLAMA_ONLY)
+    if args.resume_from_checkpoint and (args.eval_only or args.llm_adapter_path):
+        raise SystemExit("--resume_from_checkpoint continues a training run: it goes with neither --eval_only nor "
+                         "--llm_adapter_path (to score a checkpoint, pass it as --eval_only --llm_adapter_path <checkpoint-N>)")
     export_root = export_root or args.export_root or os.path.join(
         cfg.EXPERIMENT_ROOT, args.llm_base_model.rstrip("/").split("/")[-1], args.dataset_code)
     retrieved = pickle.load(open(os.path.join(args.llm_retrieved_path, "retrieved.pkl"), "rb"))
