@@ -239,23 +239,31 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
 // =============================================================================================
 // 256 x 256 x 64 kernel, ping-pong pipeline, balanced fragment reads + region-recycling DMA (variant 4)
 // =============================================================================================
-// The K tile is processed in 4 phases (one 64x32 quadrant of the wave's 128x64 output per phase, 16 MFMAs each):
-//     LOAD_p : ds_read the quadrant's new fragments + issue 2 global->LDS DMAs + counted s_waitcnt | s_barrier |
-//     MFMA_p : 16 x v_mfma_f32_16x16x32_bf16                                                       | s_barrier |
+// The K tile t (LDS stage s = t & 1) is processed in 2 phases, one 64x64 row half of the wave's 128x64 output each:
+//     L_x : 12 ds_read_b128 of fragments + issue 4 global->LDS DMAs + counted s_waitcnt + lgkmcnt(0) | s_barrier |
+//     M_x : 32 x v_mfma_f32_16x16x32_bf16 (ks-major over the 16 accumulators of two quadrants)       | s_barrier |
+//   L_a(t): B(nh1) of t from R1 -> b1, A(mh0) of t from R0A -> afr | DMA R2 of t+1 -> stage s^1, R0B of t+2 -> stage s
+//   M_a(t): quadrant (0,0) with b0cur, (0,1) with b1
+//   L_b(t): A(mh1) of t from R2 -> afr, B(nh0) of t+1 from R0B of stage s^1 -> b0nxt | DMA R0A, R1 of t+2 -> stage s
+//   M_b(t): quadrant (1,1) with b1, (1,0) with b0cur                  (tiles alternate b0x / b0y as b0cur / b0nxt)
 // The two wave groups (wm = 0 / 1; one wave of each per SIMD) run ONE BARRIER APART, so on every SIMD one wave's
-// MFMA segment overlaps the other wave's LOAD segment. s_memtime stamps on the first ping-pong version (DESIGN.md
-// section 4, experiment log) showed every LOAD segment longer than the partner's 16-MFMA segment -- 12 ds_read_b128
-// land in ~380 cycles, a pair of DMAs takes ~190 cycles to issue, DMA issue -> landed ~ 1 us. Hence this schedule
-//  * reads (8,4,8,4) fragments per phase instead of (12,4,8,0): the next tile's B(nh0) fragments are
-//    read in LOAD_3 of the current tile into a second register set (tiles alternate b0x / b0y);
-//  * recycles each LDS region two phases after its last read, so every DMA is issued SIX phases
-//    (~1.5 K tiles) before its first reader waits for it:
-//        LOAD_0(t): R2 (A rows mh1) of tile t+1      LOAD_1(t): R0B (B rows nh0) of tile t+2
-//        LOAD_2(t): R0A (A rows mh0) of tile t+2     LOAD_3(t): R1 (B rows nh1) of tile t+2
-//    a reader needs "all but my newest 10" complete (uniform s_waitcnt vmcnt(10)).
-// Hazards: a region is overwritten only after both wave groups retired their reads of it (issue at
-// LOAD_{p+2} for reads of LOAD_p: two barriers later for either group); every wait is followed by a
-// barrier that each reader passes before its read.
+// M slot overlaps the other wave's L slot. Four barriers per K tile and group; until this schedule the tile ran as four
+// phases of 16 MFMAs with (8, 4, 8, 4) fragment reads and eight barriers (same-box A/B: docs/EXPERIMENTS.md). Every
+// accumulator still takes ks 0 then ks 1 of K tiles in ascending order: bit-identical to the generic kernel.
+// Hazards, slot by slot (g = a global barrier count; group 0 runs L_a(t) in interval g, group 1 in interval g + 1):
+//  RAW: a region is read one L slot after the wait + barrier that retires it. A wave issues 4 DMAs per L slot, so
+//    "all but my newest 8" (s_waitcnt vmcnt(8)) at the end of L_a(t) retires what L_a(t-1) issued (R2 of t, R0B of t+1:
+//    read in L_b(t)), and at the end of L_b(t) what L_b(t-1) issued (R0A, R1 of t+1: read in L_a(t+1)). Group 1 passes
+//    that wait and its barrier in interval g + 1, group 0 reads in interval g + 2. With no tile t+2 the slot waits
+//    vmcnt(0). The wait sits at the END OF THE L SLOT for both groups: in front of the M-ending barrier (one slot more
+//    lead) it is a race for group 1's pieces -- group 1 would pass it in the interval in which group 0 already reads.
+//    For group 0 alone that placement is sound; built and measured, it gave +1 % over the four-phase loop where this one
+//    gives +4 % (docs/EXPERIMENTS.md).
+//  WAR: every region is refilled in the L slot after the one that read it (R0B, R2 read in L_b(t-1), refilled in
+//    L_a(t); R0A, R1 read in L_a(t), refilled in L_b(t)). For group 1's DMAs that is three barriers after group 0's
+//    read; for group 0's it is ONE barrier after group 1's read, so every L-ending barrier is preceded by
+//    s_waitcnt lgkmcnt(0): a group's fragment reads have returned when it passes. (The prologue's read of b0x gets
+//    the same: L_a(0) refills R0B of stage 0.)
 // Split-K (EPI == LR_EPI_PARTIAL): blockIdx.y = split s works on K tiles [s*T/S, (s+1)*T/S) and stores its
 // fp32 partial plane at ((float*)C)[s][M][N]; splitk_reduce_kernel sums the planes in order and applies the
 // real epilogue.
@@ -396,18 +404,31 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
     dst[nt] = *reinterpret_cast<const bf16x8*>((buf) + b_base + ((nh)*32 + nt * 16) * 128 + fo0);     \
     dst[2 + nt] = *reinterpret_cast<const bf16x8*>((buf) + b_base + ((nh)*32 + nt * 16) * 128 + fo1); \
   }
-#define RB_MFMA(bfrag, mh, nh)                                                                        \
+  // 32 MFMAs on row half mh: ks-major over the 16 accumulators of quadrants (mh, nha) and (mh, nhb), so the two MFMAs on one
+  // accumulator (ks 0, then ks 1) are 16 apart
+  // (the lgkmcnt(0) in front of the run is already satisfied -- RB_END_L waited for the same reads before its barrier; it stays
+  // as the fence that pins the run behind its operands whatever the L slot does)
+#define RB_MFMA2(bfa, nha, bfb, nhb, mh)                                                              \
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                  \
   __builtin_amdgcn_sched_barrier(0);                                                                  \
-  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                    \
-  _Pragma("unroll") for (int mt = 0; mt < 4; ++mt)                                                    \
-  _Pragma("unroll") for (int nt = 0; nt < 2; ++nt)                                                    \
-    acc[(mh)*4 + mt][(nh)*2 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                          \
-        bfrag[ks * 2 + nt], afr[ks * 4 + mt], acc[(mh)*4 + mt][(nh)*2 + nt], 0, 0, 0);
-#define RB_WAIT(steady)                               \
-  if (steady) { PP_WAIT_VM(10); } else { PP_WAIT_VM(0); }
+  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                  \
+    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt)                                                  \
+    _Pragma("unroll") for (int nt = 0; nt < 2; ++nt)                                                  \
+      acc[(mh)*4 + mt][(nha)*2 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                       \
+          bfa[ks * 2 + nt], afr[ks * 4 + mt], acc[(mh)*4 + mt][(nha)*2 + nt], 0, 0, 0);               \
+    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt)                                                  \
+    _Pragma("unroll") for (int nt = 0; nt < 2; ++nt)                                                  \
+      acc[(mh)*4 + mt][(nhb)*2 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                       \
+          bfb[ks * 2 + nt], afr[ks * 4 + mt], acc[(mh)*4 + mt][(nhb)*2 + nt], 0, 0, 0);               \
+  }
+  // End of an L slot: my DMA pieces older than the newest two L slots have landed (RAW), and my fragment reads have
+  // returned (WAR: group 0 refills a region one barrier after group 1 read it) -- then the barrier
+#define RB_END_L(steady)                                                                              \
+  if (steady) { PP_WAIT_VM(8); } else { PP_WAIT_VM(0); }                                              \
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                  \
+  PP_BARRIER();
 
-  // One K tile; b0cur holds this tile's B(nh0) fragments (read during the previous tile's LOAD_3 or the
+  // One K tile; b0cur holds this tile's B(nh0) fragments (read during the previous tile's L_b or the
   // prologue), b0nxt receives the next tile's.
 #define RB_TILE(kt, b0cur, b0nxt)                                                                     \
   {                                                                                                   \
@@ -415,33 +436,22 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
     const char* nxt = smem + (((kt) + 1) & 1) * G2_STAGE_BYTES;                                       \
     const bool more = (kt) + 1 < nkt;                                                                 \
     const bool more2 = (kt) + 2 < nkt;                                                                \
-    /* phase 0: quadrant (0,0) */                                                                     \
+    /* L_a: B(nh1) from R1, A(mh0) from R0A */                                                        \
+    RB_LOAD_B(b1, cur, 1)                                                                             \
     RB_LOAD_A(cur, 0)                                                                                 \
     if (more) RB_DMA(3, (kt) + 1);                                                                    \
-    RB_WAIT(more2)                                                                                    \
-    PP_BARRIER();                                                                                     \
-    RB_MFMA(b0cur, 0, 0)                                                                              \
-    PP_BARRIER();                                                                                     \
-    /* phase 1: quadrant (0,1) */                                                                     \
-    RB_LOAD_B(b1, cur, 1)                                                                             \
     if (more2) RB_DMA(1, (kt) + 2);                                                                   \
-    RB_WAIT(more2)                                                                                    \
+    RB_END_L(more2)                                                                                   \
+    /* M_a: quadrants (0,0), (0,1) */                                                                 \
+    RB_MFMA2(b0cur, 0, b1, 1, 0)                                                                      \
     PP_BARRIER();                                                                                     \
-    RB_MFMA(b1, 0, 1)                                                                                 \
-    PP_BARRIER();                                                                                     \
-    /* phase 2: quadrant (1,1) */                                                                     \
+    /* L_b: A(mh1) from R2, the next tile's B(nh0) from R0B of the other stage */                     \
     RB_LOAD_A(cur, 1)                                                                                 \
-    if (more2) RB_DMA(0, (kt) + 2);                                                                   \
-    RB_WAIT(more2)                                                                                    \
-    PP_BARRIER();                                                                                     \
-    RB_MFMA(b1, 1, 1)                                                                                 \
-    PP_BARRIER();                                                                                     \
-    /* phase 3: quadrant (1,0); reads the next tile's B(nh0) */                                       \
     if (more) { RB_LOAD_B(b0nxt, nxt, 0) }                                                            \
-    if (more2) RB_DMA(2, (kt) + 2);                                                                   \
-    RB_WAIT(more2)                                                                                    \
-    PP_BARRIER();                                                                                     \
-    RB_MFMA(b0cur, 1, 0)                                                                              \
+    if (more2) { RB_DMA(0, (kt) + 2); RB_DMA(2, (kt) + 2); }                                          \
+    RB_END_L(more2)                                                                                   \
+    /* M_b: quadrants (1,1), (1,0) */                                                                 \
+    RB_MFMA2(b1, 1, b0cur, 0, 1)                                                                      \
     PP_BARRIER();                                                                                     \
   }
 
@@ -451,19 +461,26 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
   constexpr bool has_rs = FOLD && (EPI == LR_EPI_ROPE || LR_EPI_IS_GATED(EPI));
   float* const rs_lds = reinterpret_cast<float*>(smem + 2 * G2_STAGE_BYTES);
   if (has_rs && tid < 256) rs_lds[tid] = rope.row_scale[min(m0 + tid, M - 1)];   // (visible behind the K loop's barriers)
-  // ---- prologue: all of tile 0, then R0B, R0A, R1 of tile 1 (steady-state issue order)
-#pragma unroll
-  for (int reg = 0; reg < 4; ++reg) RB_DMA(reg, 0);
+  // ---- prologue: what tile 0's L_a and the b0x read below need (R0A, R1, R0B of tile 0), then, in steady-state issue
+  // order, what L_a(-1) and L_b(-1) would have issued: R2 of tile 0, R0B of tile 1 | R0A, R1 of tile 1. The wait retires
+  // the first three regions (all but the newest 8 pieces, or the newest 2 when there is no tile 1).
+  RB_DMA(0, 0);
+  RB_DMA(2, 0);
+  RB_DMA(1, 0);
+  RB_DMA(3, 0);
   if (nkt > 1) {
     RB_DMA(1, 1);
     RB_DMA(0, 1);
     RB_DMA(2, 1);
-    PP_WAIT_VM(6);
+    PP_WAIT_VM(8);
   } else {
-    PP_WAIT_VM(0);
+    PP_WAIT_VM(2);
   }
   PP_BARRIER();
   RB_LOAD_B(b0x, smem, 0)
+  // L_a(0) refills R0B of stage 0 (tile 2): every wave's b0x read has returned before any wave gets there
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  PP_BARRIER();
   GEMM_STAMP(1)
   if (wm == 1) {
     // Static priority for the second-dispatched half (waves 4-7), NO per-segment s_setprio flips around the MFMA runs
@@ -483,8 +500,8 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
 #undef RB_DMA
 #undef RB_LOAD_A
 #undef RB_LOAD_B
-#undef RB_MFMA
-#undef RB_WAIT
+#undef RB_MFMA2
+#undef RB_END_L
 #undef RB_TILE
 
   // A lane holds 4 consecutive columns (8 bytes) of its row per 16-column tile. v_permlane16_swap on the packed pairs of

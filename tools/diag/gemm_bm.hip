@@ -9,6 +9,9 @@
 // hand-counted vmcnt: through plain C++ loads hipcc waited for every phase's fresh loads in front of that phase's barrier,
 // 11-26 k cycles per K tile). Result at 128 rows: 1 832 cycles per K tile against 1 856 with LDS-DMA -- the form of the request is
 // not what the LOAD phases wait for. (At 256 rows the variant spills 34 registers: timings meaningless.)
+// NOTE: this harness models the product loop as it was when these measurements were taken -- FOUR phases per K tile (16 MFMAs,
+// fragment reads 8, 4, 8, 4, two DMA pieces per phase, eight barriers). The product kernel has since merged them pairwise into
+// two 32-MFMA phases with four barriers (llama_gemm.hip, RB_TILE; docs/EXPERIMENTS.md): the cycle counts below no longer mirror it.
 // hipcc --offload-arch=gfx950 -O3 -o /tmp/gemm_bm tools/diag/gemm_bm.hip && /tmp/gemm_bm
 #include <hip/hip_runtime.h>
 #include <algorithm>
