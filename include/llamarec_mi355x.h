@@ -599,6 +599,19 @@ int lr_attention_varlen_bwd(const uint16_t* qkv, const uint16_t* out, const uint
                             uint16_t* dqkv, const int32_t* cu_seqlens, const int32_t* cu_seqlens_host, int32_t B,
                             int32_t num_heads, int32_t num_kv_heads, int32_t head_dim, int32_t variant,
                             void* scratch, size_t scratch_bytes, void* hip_stream);
+/* lr_attention_varlen_bwd with the training step's options (the plain entry is this one with nulls and zeros).
+ * rope_cs: DEVICE, the table lr_rope_table wrote for head_dim with rope_positions positions; when given, dqkv is the
+ * gradient w.r.t. the UNROTATED q and k (v as before). tok_pos: DEVICE int32[total], required with rope_cs, and must hold
+ * each row's position INSIDE ITS PROMPT (row - cu_seqlens[b]): the head_dim-128 MFMA passes index the table by that
+ * position directly and the generic path reads tok_pos, so any other content makes the two disagree. LR_EINVAL (with a
+ * message, nothing launched) for rope_cs without tok_pos and for a segment longer than rope_positions.
+ * deterministic != 0: the generic path (variant 1) computes dK / dV per owner instead of with fp32 atomics -- the same
+ * bits on every run; the MFMA passes have no atomics either way. */
+int lr_attention_varlen_bwd_ex(const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out, const float* lse,
+                               uint16_t* dqkv, const int32_t* cu_seqlens, const int32_t* cu_seqlens_host, int32_t B,
+                               int32_t num_heads, int32_t num_kv_heads, int32_t head_dim, int32_t variant,
+                               void* scratch, size_t scratch_bytes, const int32_t* tok_pos, const float* rope_cs,
+                               int32_t rope_positions, int32_t deterministic, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -774,19 +774,37 @@ extern "C" size_t lr_attention_bwd_scratch_bytes(int32_t total, int32_t num_head
   return lr_align_up((size_t)total * num_heads * 4, 256) + (size_t)total * 2 * num_kv_heads * head_dim * 4;
 }
 
-extern "C" int lr_attention_varlen_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out,
-                                       const float* lse, uint16_t* dqkv, const int32_t* cu_seqlens,
-                                       const int32_t* cu_seqlens_host, int32_t B, int32_t num_heads,
-                                       int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* scratch,
-                                       size_t scratch_bytes, void* hip_stream) {
+extern "C" int lr_attention_varlen_bwd_ex(const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out,
+                                          const float* lse, uint16_t* dqkv, const int32_t* cu_seqlens,
+                                          const int32_t* cu_seqlens_host, int32_t B, int32_t num_heads,
+                                          int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* scratch,
+                                          size_t scratch_bytes, const int32_t* tok_pos, const float* rope_cs,
+                                          int32_t rope_positions, int32_t deterministic, void* hip_stream) {
   if (!qkv || !out || !d_out || !lse || !dqkv || !cu_seqlens || !cu_seqlens_host || !scratch || B < 1)
     LR_FAIL(LR_EINVAL, "lr_attention_varlen_bwd: bad argument");
   if (int rc = lr_check_segments(cu_seqlens_host, B, "lr_attention_varlen_bwd")) return rc;
+  if (rope_cs) {
+    if (!tok_pos) LR_FAIL(LR_EINVAL, "lr_attention_varlen_bwd: rotary table without token positions");
+    for (int b = 0; b < B; ++b)  // the MFMA epilogues index the table by the position inside the prompt
+      if (cu_seqlens_host[b + 1] - cu_seqlens_host[b] > rope_positions)
+        LR_FAIL(LR_EINVAL, "lr_attention_varlen_bwd: segment %d has %d tokens, the rotary table %d positions", b,
+                cu_seqlens_host[b + 1] - cu_seqlens_host[b], rope_positions);
+  }
   const int n = cu_seqlens_host[B];
   if (scratch_bytes < lr_attention_bwd_scratch_bytes(n, num_heads, num_kv_heads, head_dim))
     LR_FAIL(LR_EWORKSPACE, "lr_attention_varlen_bwd: scratch too small");
   float* dsum = (float*)scratch;
   float* dkv32 = (float*)((char*)scratch + lr_align_up((size_t)n * num_heads * 4, 256));
   return lr_launch_attention_bwd(qkv, out, d_out, lse, dqkv, dsum, dkv32, cu_seqlens, cu_seqlens_host, B, n, num_heads,
-                                 num_kv_heads, head_dim, variant, (hipStream_t)hip_stream);
+                                 num_kv_heads, head_dim, variant, (hipStream_t)hip_stream, tok_pos, rope_cs,
+                                 deterministic != 0);
+}
+
+extern "C" int lr_attention_varlen_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out,
+                                       const float* lse, uint16_t* dqkv, const int32_t* cu_seqlens,
+                                       const int32_t* cu_seqlens_host, int32_t B, int32_t num_heads,
+                                       int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* scratch,
+                                       size_t scratch_bytes, void* hip_stream) {
+  return lr_attention_varlen_bwd_ex(qkv, out, d_out, lse, dqkv, cu_seqlens, cu_seqlens_host, B, num_heads, num_kv_heads,
+                                    head_dim, variant, scratch, scratch_bytes, nullptr, nullptr, 0, 0, hip_stream);
 }

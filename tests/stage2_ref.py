@@ -1,7 +1,8 @@
-"""float64 references with per-element error bounds for the stage-2 kernels (attention, the GEMM epilogues, the RoPE
-table), plus mutants of each: the same reference with one plausible bug, to prove that a test built on the bound can fail.
+"""float64 references with per-element error bounds for the stage-2 kernels (attention and its backward, the GEMM epilogues,
+the RoPE table), plus mutants of each: the same reference with one plausible bug, to prove that a test built on the bound can fail.
 
-A plain helper module: test_stage2_ref.py pins it on the CPU, test_gpu_stage2_bounds.py compares the HIP kernels with it.
+A plain helper module: test_stage2_ref.py pins it on the CPU, test_gpu_stage2_bounds.py and test_gpu_stage2_bwd_bounds.py
+compare the HIP kernels with it.
 
 Attention bound (attention_ref64). The kernels (llama_attn.hip variants 1 / 2, llama_attn256.hip variant 3,
 llama_attn_hd256.hip variant 4) compute, per query row i with T = i + 1 keys, exact softmax weights p_j = exp(s_j - m),
@@ -23,6 +24,41 @@ the spare 2^-9 S of the S coefficient. eps is the one term a bound without score
 on unit-scale data and is computed from the data, not fitted.
 lse (natural log of l times e^m, fp32): |got - ref| <= 2^-8 + eps + 2^-20 |ref|  (relative error of l, fp32 log and add).
 
+Attention backward bound (attention_bwd_ref64). llama_attn_bwd.hip computes, from the inputs AS GIVEN (qkv, dO, the
+forward's O and lse), P = exp(scale q.k - lse), D = rowsum(dO o O), dP = dO V^T, dS = P o (dP - D), dQ = scale dS K,
+dK = scale dS^T Q, dV = P^T dO (dK, dV summed over the query heads of a group). The reference is that function of those
+arrays in float64 -- it does not re-derive O or lse, so the forward's own error (already bounded above) stays out of this
+bound, and the same reference serves a call fed the rounded float64 forward and one fed the forward kernel's outputs.
+Rounding points, T = prompt length, rep = nh / nkv, row i = a query, column j = a key:
+  - scores in fp32 (hd exact products summed: absolute 2^-24 hd scale |q_i||k_j|, Cauchy-Schwarz), then the exponent
+    fma(s, scale log2 e, -lse log2 e) of the MFMA passes (the rounded constants, the product lse * log2 e and the fma's result:
+    < 2^-24 (2 |s| + 2.5 |lse|) in natural-log units) or acc * scale - lse and __expf of the generic kernels (four roundings of
+    values <= |s| + |lse|), then v_exp_f32 (1 ulp). Together a relative error of p_ij, row-wise
+        eps_i = 2^-24 scale hd |q_i| max_{j<=i} |k_j|  +  2^-22 (max_j |s_ij| + |lse_i|)  +  2^-21
+    -- the forward's eps plus the |lse| term, which the forward does not have (it subtracts a running maximum, not lse).
+  - dP in fp32 over hd products: absolute ddP_ij = 2^-24 hd |dO_i||v_j|; D in fp32 over hd products (lt_rowdot_kernel):
+    absolute dD_i = 2^-24 hd sum_d |dO_id O_id|. Both enter dS multiplied by p_ij, NOT relative to dS: where dP - D cancels
+    this is the term that matters.
+  - P (for dV) and dS (for dQ, dK) rounded to bf16 before the second MFMA: relative 2^-9. The generic kernels keep both
+    in fp32 (plus one rounding of each product): covered with slack.
+  - the second product accumulated in fp32 over at most T terms (dQ) or T rep terms (dK, dV), in any order -- the generic
+    path adds dK / dV with fp32 atomics: relative N 2^-24 of the sum of the terms' magnitudes.
+  - the scale multiply (2^-24) and the bf16 output rounding: relative 2^-9 of the result.
+First order, with c_i(N) = 2^-8 + 2 eps_i + N 2^-24 (2^-9 for the bf16 operand; the other 2^-9 and the second eps_i hold
+the second-order products, the subtraction's and the products' own fp32 roundings) and
+        E_ij(N) = c_i(N) |dS_ij| + 2 p_ij (ddP_ij + dD_i):
+    |dQ - ref| <= scale sum_j E_ij(T) |k_j|          + 2^-8 |dQ|
+    |dK - ref| <= scale sum_{h,i} E_ij(T rep) |q_i|  + 2^-8 |dK|
+    |dV - ref| <= sum_{h,i} c_i(T rep) p_ij |dO_i|   + 2^-8 |dV|
+(2^-8, not 2^-9, on the result: the generic path with a rotary table rounds to bf16 twice, see below), plus 2^-100: weights and
+products below fp32's normal range may be flushed to zero, and rows whose gradient is exactly zero have a zero bound otherwise.
+With rope = (pos, cos, sin) the gradient is taken back through the rotation of q and k: a' = a c + b s, b' = b c - a s on
+each packed pair (a, b), c / s the bf16 table entries, exact in both computations. The MFMA passes rotate the fp32
+accumulators in their epilogues (three fp32 roundings, then bf16); the generic path rounds to bf16, lt_rope_bwd_kernel
+rotates in fp32 and rounds again. Either way, with B_a, B_b the bounds above (which already hold the first rounding):
+        B_a' = |c| B_a + |s| B_b + 2^-22 (|a c| + |b s|) + 2^-8 |a'|          (and the same for b').
+Every term is computed from the data; none is fitted to a kernel's result.
+
 Epilogue references follow include/llamarec_mi355x.h (lr_gemm_bf16_nt_epi) and llama_kernels.h at the documented rounding
 points, with the rotation stated in the kernel's operation order and no contraction (the library builds with
 -ffp-contract=off). RoPE works in HF's rotate-half layout and maps through the pair interleave of lr_llama_pack_qkv
@@ -35,6 +71,7 @@ import numpy as np
 from llamarec_amd.synth import bf16_round
 
 ATTN_MUTANTS = ("diag", "late_block", "first_block", "gqa_mod", "half_scale")
+BWD_MUTANTS = ("diag", "tail", "gqa_mod", "no_D", "half_scale", "d_other_head", "rotate_forward")
 ROPE_MUTANTS = ("pos_plus1", "freq_plus1", "hf_layout")
 CHUNK = 512
 
@@ -145,6 +182,165 @@ def attention_emul32(qkv, cu, nh, nkv, hd, l_from_bf16_p=False):
     return out, lse
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# attention backward
+# ---------------------------------------------------------------------------------------------------------------------
+def rope_rotate64(x, pos, cos, sin, transpose=False):
+    """The rotation of epi_rope in float64 without its rounding, on packed heads x [n][heads][hd] (pair (a, b) = columns
+    (2i, 2i + 1)): a c - b s, b c + a s with c / s = cos / sin[pos][i]; transpose: its adjoint a c + b s, b c - a s."""
+    x = np.asarray(x, dtype=np.float64)
+    c = np.asarray(cos, dtype=np.float64)[np.asarray(pos, dtype=np.int64)][:, None, :]
+    s = np.asarray(sin, dtype=np.float64)[np.asarray(pos, dtype=np.int64)][:, None, :]
+    if transpose:
+        s = -s
+    a, b = x[..., 0::2], x[..., 1::2]
+    y = np.empty_like(x)
+    y[..., 0::2], y[..., 1::2] = a * c - b * s, b * c + a * s
+    return y
+
+
+def _rope_bound(x, bound, rot, pos, cos, sin):
+    """Bound of the rotated gradient `rot` of x (module docstring): |c| B_a + |s| B_b + 2^-22 (|a c| + |b s|) + 2^-8 |a'|."""
+    c = np.abs(np.asarray(cos, dtype=np.float64))[np.asarray(pos, dtype=np.int64)][:, None, :]
+    s = np.abs(np.asarray(sin, dtype=np.float64))[np.asarray(pos, dtype=np.int64)][:, None, :]
+    a, b = np.abs(x[..., 0::2]), np.abs(x[..., 1::2])
+    Ba, Bb = bound[..., 0::2], bound[..., 1::2]
+    out = np.empty_like(bound)
+    out[..., 0::2] = c * Ba + s * Bb + 2.0 ** -22 * (a * c + b * s)
+    out[..., 1::2] = c * Bb + s * Ba + 2.0 ** -22 * (b * c + a * s)
+    return out + 2.0 ** -8 * np.abs(rot)
+
+
+def attention_bwd_ref64(qkv, d_out, out, lse, cu, nh, nkv, hd, mutant=None, rope=None):
+    """Exact float64 backward of the causal attention as a function of the kernel's inputs as given: qkv
+    [n][(nh + 2 nkv) hd] and d_out, out [n][nh hd] (bf16 values), lse [n][nh] (fp32 values), segments cu. rope = (pos, cos,
+    sin), pos [n] = each row's position inside its prompt, cos / sin [positions][hd/2]: the gradient w.r.t. the unrotated
+    q and k. Returns (dqkv, bound), both [n][(nh + 2 nkv) hd] float64 (module docstring). mutant: one of BWD_MUTANTS."""
+    qkv = np.asarray(qkv, dtype=np.float64)
+    cu = np.asarray(cu, dtype=np.int64)
+    n = qkv.shape[0]
+    q, k, v = _split_qkv(qkv, nh, nkv, hd)
+    do = np.asarray(d_out, dtype=np.float64).reshape(n, nh, hd)
+    o = np.asarray(out, dtype=np.float64).reshape(n, nh, hd)
+    lse = np.asarray(lse, dtype=np.float64)
+    rep = nh // nkv
+    scale = 1.0 / np.sqrt(hd / 2 if mutant == "half_scale" else hd)
+    D = (do * o).sum(-1)
+    dD = 2.0 ** -24 * hd * np.abs(do * o).sum(-1)
+    if mutant == "no_D":
+        D = np.zeros_like(D)
+    elif mutant == "d_other_head":
+        D = np.roll(D, -1, axis=1)
+    dq, dk, dv = np.zeros((n, nh, hd)), np.zeros((n, nkv, hd)), np.zeros((n, nkv, hd))
+    bq, bk, bv = np.zeros((n, nh, hd)), np.zeros((n, nkv, hd)), np.zeros((n, nkv, hd))
+    for b in range(len(cu) - 1):
+        s0, e0 = int(cu[b]), int(cu[b + 1])
+        T = e0 - s0
+        assert 0 < T <= 1 << 12, T
+        rows = np.arange(T)
+        keep = rows[None, :] <= rows[:, None]
+        if mutant == "diag":
+            keep &= rows[None, :] != rows[:, None]
+        in_kv = np.ones(T)                              # queries that reach dK / dV
+        if mutant == "tail" and T % 64:
+            in_kv[T // 64 * 64:] = 0.0
+        for h in range(nh):
+            g = h % nkv if mutant == "gqa_mod" else h // rep
+            qh, kh, vh, doh = q[s0:e0, h], k[s0:e0, g], v[s0:e0, g], do[s0:e0, h]
+            s = (qh @ kh.T) * scale
+            with np.errstate(over="ignore"):
+                p = np.where(keep, np.exp(s - lse[s0:e0, h, None]), 0.0)
+            ds = p * (doh @ vh.T - D[s0:e0, h, None])
+            smax = np.where(keep, np.abs(s), 0.0).max(axis=1)
+            kmax = np.maximum.accumulate(np.linalg.norm(kh, axis=1))
+            eps = (2.0 ** -24 * scale * hd * np.linalg.norm(qh, axis=1) * kmax
+                   + 2.0 ** -22 * (smax + np.abs(lse[s0:e0, h])) + 2.0 ** -21)
+            ddp = 2.0 ** -24 * hd * np.outer(np.linalg.norm(doh, axis=1), np.linalg.norm(vh, axis=1))
+            absolute = 2.0 * p * (ddp + dD[s0:e0, h, None])
+            c_q = (2.0 ** -8 + 2 * eps + T * 2.0 ** -24)[:, None]
+            c_kv = (2.0 ** -8 + 2 * eps + T * rep * 2.0 ** -24)[:, None]
+            dq[s0:e0, h] = scale * (ds @ kh)
+            bq[s0:e0, h] = scale * ((c_q * np.abs(ds) + absolute) @ np.abs(kh))
+            dk[s0:e0, g] += scale * ((ds * in_kv[:, None]).T @ qh)
+            bk[s0:e0, g] += scale * ((c_kv * np.abs(ds) + absolute).T @ np.abs(qh))
+            dv[s0:e0, g] += (p * in_kv[:, None]).T @ doh
+            bv[s0:e0, g] += (c_kv * p).T @ np.abs(doh)
+    bq += 2.0 ** -8 * np.abs(dq)
+    bk += 2.0 ** -8 * np.abs(dk)
+    bv += 2.0 ** -8 * np.abs(dv)
+    if rope is not None:
+        pos, cos, sin = rope
+        for x, bx in ((dq, bq), (dk, bk)):
+            rot = rope_rotate64(x, pos, cos, sin, transpose=(mutant != "rotate_forward"))
+            bx[...] = _rope_bound(x, bx, rot, pos, cos, sin)
+            x[...] = rot
+    dqkv = np.concatenate([dq.reshape(n, -1), dk.reshape(n, -1), dv.reshape(n, -1)], axis=1)
+    bound = np.concatenate([bq.reshape(n, -1), bk.reshape(n, -1), bv.reshape(n, -1)], axis=1) + 2.0 ** -100
+    return dqkv, bound
+
+
+def attention_bwd_emul32(qkv, d_out, out, lse, cu, nh, nkv, hd, bf16_operands=True, rope=None, round_before_rope=False):
+    """numpy emulation of the backward kernels' arithmetic: fp32 scores, P (through exp2 of the folded argument), dP and D,
+    P and dS rounded to bf16 for the second product (bf16_operands: the MFMA passes; off: the generic kernels), fp32 sums, bf16
+    outputs; rope as in attention_bwd_ref64, rotated in fp32 from the fp32 sums or (round_before_rope: the generic path) from
+    their bf16 rounding. Returns dqkv [n][(nh + 2 nkv) hd] (bf16 values)."""
+    qkv = _f32(qkv)
+    n = qkv.shape[0]
+    q, k, v = _split_qkv(qkv, nh, nkv, hd)
+    do = _f32(d_out).reshape(n, nh, hd)
+    o = _f32(out).reshape(n, nh, hd)
+    lse = _f32(lse)
+    rep = nh // nkv
+    log2e = np.float32(1.4426950408889634)
+    scale = np.float32(1.0) / np.sqrt(np.float32(hd))
+    sl2 = np.float32(scale * log2e)
+    D = (do * o).sum(-1, dtype=np.float32)
+    rnd = bf16_round if bf16_operands else (lambda x: x)
+    dq, dk, dv = (np.zeros((n, nh, hd), np.float32), np.zeros((n, nkv, hd), np.float32), np.zeros((n, nkv, hd), np.float32))
+    for b in range(len(cu) - 1):
+        s0, e0 = int(cu[b]), int(cu[b + 1])
+        T = e0 - s0
+        keep = np.arange(T)[None, :] <= np.arange(T)[:, None]
+        for h in range(nh):
+            g = h // rep
+            qh, kh, vh, doh = q[s0:e0, h], k[s0:e0, g], v[s0:e0, g], do[s0:e0, h]
+            x = _f32(_f32(_f32(qh @ kh.T) * sl2) - _f32(lse[s0:e0, h, None] * log2e))
+            p = np.where(keep, np.exp2(x).astype(np.float32), np.float32(0.0))
+            ds = _f32(p * _f32(_f32(doh @ vh.T) - D[s0:e0, h, None]))
+            pb, dsb = rnd(p), rnd(ds)
+            dq[s0:e0, h] = _f32(dsb @ kh)
+            dk[s0:e0, g] += _f32(dsb.T @ qh)
+            dv[s0:e0, g] += _f32(pb.T @ doh)
+    dq, dk = _f32(dq * scale), _f32(dk * scale)
+    if rope is not None:
+        pos, cos, sin = rope
+        c = _f32(cos)[np.asarray(pos, dtype=np.int64)][:, None, :]
+        s = _f32(sin)[np.asarray(pos, dtype=np.int64)][:, None, :]
+        for x in (dq, dk):
+            y = bf16_round(x) if round_before_rope else x
+            a, bb = y[..., 0::2].copy(), y[..., 1::2].copy()
+            x[..., 0::2] = _f32(_f32(a * c) + _f32(bb * s))
+            x[..., 1::2] = _f32(_f32(bb * c) - _f32(a * s))
+    return bf16_round(np.concatenate([dq.reshape(n, -1), dk.reshape(n, -1), dv.reshape(n, -1)], axis=1))
+
+
+def bwd_ratios(got, ref, bound, nh, nkv, hd):
+    """ratio() of the dq, dk and dv column blocks of a packed gradient, separately: {"dq": .., "dk": .., "dv": ..}."""
+    edges = (0, nh * hd, (nh + nkv) * hd, (nh + 2 * nkv) * hd)
+    got = np.asarray(got)
+    return {name: ratio(got[:, a:b], ref[:, a:b], bound[:, a:b]) for name, a, b in zip(("dq", "dk", "dv"), edges, edges[1:])}
+
+
+def bwd_mutant_applies(mutant, nh, nkv, rope):
+    """False where a mutant of BWD_MUTANTS coincides with the correct computation: gqa_mod when h % nkv == h // (nh / nkv)
+    for every head, rotate_forward without a rotation."""
+    if mutant == "gqa_mod":
+        return nkv not in (1, nh)
+    if mutant == "rotate_forward":
+        return rope is not None
+    return True
+
+
 def ratio(got, ref, bound):
     """max |got - ref| / bound (inf where got is not finite)."""
     got = np.asarray(got, dtype=np.float64)
@@ -179,6 +375,33 @@ def attention_data(regime, cu, nh, nkv, hd, seed=0):
     elif regime != "flat":
         raise ValueError(regime)
     return bf16_round(qkv)
+
+
+ZERO_DOUT_ROWS = 70
+
+
+def zero_dout_rows(cu):
+    """The rows attention_bwd_data sets to zero: the last ZERO_DOUT_ROWS rows of the first prompt of at least 129 rows, as a slice
+    (None when no prompt is that long). 70 rows end in a partial 64-row block and start two blocks earlier."""
+    lens = np.diff(np.asarray(cu, dtype=np.int64))
+    long = np.nonzero(lens >= 129)[0]
+    if not len(long):
+        return None
+    e0 = int(cu[long[0] + 1])
+    return slice(e0 - ZERO_DOUT_ROWS, e0)
+
+
+def attention_bwd_data(cu, nh, hd, seed=0):
+    """bf16-valued d_out [n][nh hd]: unit-scale hash_uniform, the rows of zero_dout_rows(cu) exactly zero -- those rows' dq, and
+    their dk / dv as keys (every query at or after them has a zero d_out too), must then be exactly zero."""
+    from llamarec_amd.synth import hash_uniform
+
+    n = int(cu[-1])
+    d_out = bf16_round(hash_uniform(77000 + seed * 1000 + nh * 10 + hd, (n, nh * hd), 1.0))
+    z = zero_dout_rows(cu)
+    if z is not None:
+        d_out[z] = 0.0
+    return d_out
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -373,6 +373,9 @@ def test_attention_entry_points_reject_bad_segments(cu):
         "bwd": lambda: L.lr_attention_varlen_bwd(qkv.data_ptr(), out.data_ptr(), out.data_ptr(), lse.data_ptr(),
                                                  dqkv.data_ptr(), cud.data_ptr(), cu.ctypes.data, B, nh, nkv, hd, 2,
                                                  scratch.data_ptr(), sb, s),
+        "bwd_ex": lambda: L.lr_attention_varlen_bwd_ex(qkv.data_ptr(), out.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                                       dqkv.data_ptr(), cud.data_ptr(), cu.ctypes.data, B, nh, nkv, hd, 1,
+                                                       scratch.data_ptr(), sb, None, None, 0, 1, s),
     }
     for name, call in calls.items():
         rc = call()

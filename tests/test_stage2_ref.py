@@ -1,8 +1,10 @@
 """CPU: the float64 stage-2 references of tests/stage2_ref.py, pinned before any GPU result depends on them. The attention
-bound must hold for a numpy emulation of the kernels' arithmetic and must be beaten at least 4x by every mutant; the
-epilogue and RoPE references must reject their mutants; the HF RoPE table must be the oracle's, bit for bit."""
+bounds (forward and backward) must hold for a numpy emulation of the kernels' arithmetic and must be beaten at least 4x by
+every mutant; the backward reference must be torch.autograd's gradient in float64 and its rotation the adjoint of the
+forward's; the epilogue and RoPE references must reject their mutants; the HF RoPE table must be the oracle's, bit for bit."""
 import numpy as np
 import pytest
+import torch
 
 from llamarec_amd.synth import bf16_round, hash_uniform
 from oracle import llama_oracle as LO
@@ -119,3 +121,104 @@ def test_gated_references_reject_swapped_gate_and_up(fn):
     assert np.isfinite(want).all()
     rel = np.abs(fn(acc, swap=True) - want) / np.maximum(np.abs(want), 1e-3)
     assert (rel > 2.0 ** -7).mean() > 0.5
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# attention backward
+# ---------------------------------------------------------------------------------------------------------------------
+BWD_LENS = [1, 63, 64, 65, 128, 129, 257, 300]
+BWD_CU = np.concatenate([[0], np.cumsum(BWD_LENS)])
+BWD_POS = np.concatenate([np.arange(T) for T in BWD_LENS])
+
+
+def _f64_forward_rounded(qkv, cu, nh, nkv, hd):
+    out, lse, _, _ = R.attention_ref64(qkv, cu, nh, nkv, hd)
+    return bf16_round(out.astype(np.float32)), lse.astype(np.float32)
+
+
+def test_attention_bwd_ref_is_autograd_in_float64():
+    """Fed the exact float64 out and lse, the reference is the gradient torch.autograd takes of the whole-matrix formula
+    softmax(mask(q k^T / sqrt(hd))) v (grouped-query: k / v repeated over the group), ragged batch, nh / nkv = 4.
+    Tolerance: float64 sums of at most 130 x 4 terms of magnitude <= the tensor's maximum, each carrying a few 2^-53 relative
+    roundings, stay below 1e-12 of that maximum; 1e-10 leaves two orders for the exp and the two different summation orders."""
+    nh, nkv, hd = 8, 2, 32
+    lens = [1, 37, 70, 130]
+    cu = np.concatenate([[0], np.cumsum(lens)])
+    n = int(cu[-1])
+    qkv = R.attention_data("peaked", cu, nh, nkv, hd).astype(np.float64)
+    d_out = hash_uniform(11, (n, nh * hd), 1.0).astype(np.float64)
+    out, lse, _, _ = R.attention_ref64(qkv, cu, nh, nkv, hd)
+    got, _ = R.attention_bwd_ref64(qkv, d_out, out, lse, cu, nh, nkv, hd)
+    x = torch.from_numpy(qkv)
+    q = x[:, :nh * hd].reshape(n, nh, hd).clone().requires_grad_(True)
+    k = x[:, nh * hd:(nh + nkv) * hd].reshape(n, nkv, hd).clone().requires_grad_(True)
+    v = x[:, (nh + nkv) * hd:].reshape(n, nkv, hd).clone().requires_grad_(True)
+    outs, s0 = [], 0
+    for T in lens:
+        ks, vs = k[s0:s0 + T].repeat_interleave(nh // nkv, 1), v[s0:s0 + T].repeat_interleave(nh // nkv, 1)
+        s = torch.einsum("qhd,khd->hqk", q[s0:s0 + T], ks) / np.sqrt(hd)
+        s = s.masked_fill(~torch.tril(torch.ones(T, T, dtype=torch.bool))[None], float("-inf"))
+        outs.append(torch.einsum("hqk,khd->qhd", torch.softmax(s, -1), vs))
+        s0 += T
+    o = torch.cat(outs)
+    assert np.allclose(o.detach().numpy().reshape(n, -1), out, rtol=0, atol=1e-12 * np.abs(out).max())
+    o.backward(torch.from_numpy(d_out).reshape(n, nh, hd))
+    want = torch.cat([q.grad.reshape(n, -1), k.grad.reshape(n, -1), v.grad.reshape(n, -1)], 1).numpy()
+    for name, a, b in (("dq", 0, nh * hd), ("dk", nh * hd, (nh + nkv) * hd), ("dv", (nh + nkv) * hd, (nh + 2 * nkv) * hd)):
+        err, scale = np.abs(got[:, a:b] - want[:, a:b]).max(), np.abs(want[:, a:b]).max()
+        print(f"{name}: max |ref - autograd| = {err:.3g} at scale {scale:.3g}")
+        assert scale > 0 and err <= 1e-10 * scale, (name, err, scale)
+
+
+@pytest.mark.parametrize("hd", [64, 128])
+def test_rope_transpose_is_the_adjoint_of_the_epilogue_rotation(hd):
+    """rope_rotate64 is epi_rope's rotation without its rounding, and its transpose (what attention_bwd_ref64 applies) is
+    that rotation's adjoint: <R x, y> = <x, R^T y>."""
+    T, M, heads = 512, 97, 3
+    c, s, _, _ = R.rope_table_hf(T, hd, 1e4)
+    pos = np.arange(M) * 37 % T
+    x = bf16_round(hash_uniform(5, (M, heads * hd), 1.0))
+    y = hash_uniform(6, (M, heads, hd), 1.0).astype(np.float64)
+    Rx = R.rope_rotate64(x.reshape(M, heads, hd), pos, c, s)
+    rounded = R.epi_rope(x.astype(np.float64), pos, c, s, hd, heads * hd).reshape(M, heads, hd)
+    assert np.abs(Rx - rounded).max() <= 2.0 ** -8 * np.abs(Rx).max() and (bf16_round(Rx.astype(np.float32)) == rounded).mean() > 0.99
+    Rty = R.rope_rotate64(y, pos, c, s, transpose=True)
+    lhs, rhs = (Rx * y).sum(), (x.reshape(M, heads, hd).astype(np.float64) * Rty).sum()
+    assert abs(lhs - rhs) <= 1e-12 * (np.abs(Rx * y).sum()), (lhs, rhs)
+    assert abs((R.rope_rotate64(y, pos, c, s) * x.reshape(M, heads, hd)).sum() - lhs) > 1e-3 * abs(lhs)   # R is not its own adjoint
+
+
+@pytest.mark.parametrize("regime", REGIMES)
+@pytest.mark.parametrize("nh,nkv,hd", [(4, 2, 128), (8, 1, 128), (2, 2, 64), (2, 1, 256)])
+def test_attention_bwd_bound_holds_for_the_emulation_and_mutants_exceed_it(regime, nh, nkv, hd):
+    """Both forward sources (the float64 forward rounded to bf16 / fp32, and attention_emul32's own outputs), with and without
+    the rotation: the emulation of the MFMA passes (bf16 P / dS) and of the generic path (fp32 P / dS, bf16 before the rotation)
+    stays inside the bound for dq, dk and dv separately; every applicable mutant leaves it by 4x or more."""
+    qkv = R.attention_data(regime, BWD_CU, nh, nkv, hd)
+    d_out = R.attention_bwd_data(BWD_CU, nh, hd)
+    z = R.zero_dout_rows(BWD_CU)
+    assert z is not None and not d_out[z].any() and d_out[:z.start].any()
+    cos, sin, _, _ = R.rope_table_hf(max(BWD_LENS), hd, 1e4)
+    sources = {"exact": _f64_forward_rounded(qkv, BWD_CU, nh, nkv, hd), "emul32": R.attention_emul32(qkv, BWD_CU, nh, nkv, hd, True)}
+    bad = []
+    for src, (out, lse) in sources.items():
+        for rope in (None, (BWD_POS, cos, sin)):
+            tag = f"{regime} nh={nh} nkv={nkv} hd={hd} forward={src} rope={rope is not None}"
+            ref, bound = R.attention_bwd_ref64(qkv, d_out, out, lse, BWD_CU, nh, nkv, hd, rope=rope)
+            assert (bound > 0).all() and np.isfinite(bound).all()
+            for bf16_ops, pre_round in ((True, False), (False, True)):
+                emu = R.attention_bwd_emul32(qkv, d_out, out, lse, BWD_CU, nh, nkv, hd, bf16_ops, rope, pre_round)
+                r = R.bwd_ratios(emu, ref, bound, nh, nkv, hd)
+                print(f"{tag} bf16_operands={bf16_ops}: err/bound dq {r['dq']:.3f} dk {r['dk']:.3f} dv {r['dv']:.3f}")
+                if not max(r.values()) <= 1.0:
+                    bad.append((tag, bf16_ops, r))
+                assert not emu[z].any()                # the zero-d_out rows: dq, and dk / dv as keys, exactly zero
+            for m in R.BWD_MUTANTS:
+                if not R.bwd_mutant_applies(m, nh, nkv, rope):
+                    continue
+                mo, _ = R.attention_bwd_ref64(qkv, d_out, out, lse, BWD_CU, nh, nkv, hd, m, rope)
+                r = R.bwd_ratios(mo, ref, bound, nh, nkv, hd)
+                print(f"  mutant {m}: dq {r['dq']:.1f} dk {r['dk']:.1f} dv {r['dv']:.1f} x bound")
+                if not max(r.values()) >= 4.0:
+                    bad.append((tag, m, r))
+    assert not bad, bad
