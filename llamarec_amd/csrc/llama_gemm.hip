@@ -264,6 +264,12 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
 //    read; for group 0's it is ONE barrier after group 1's read, so every L-ending barrier is preceded by
 //    s_waitcnt lgkmcnt(0): a group's fragment reads have returned when it passes. (The prologue's read of b0x gets
 //    the same: L_a(0) refills R0B of stage 0.)
+// The 4 pieces stay in the L slot, behind its reads. Moving them into the FOLLOWING M slot (never the preceding one: that
+//    puts group 0's refill under group 1's reads) is sound -- the waits become vmcnt(6) / vmcnt(4) for two / four moved
+//    pieces, prologue unchanged -- and was built and measured: two pieces per slot moved cost 1.6-2.9 % of the TF/s, all
+//    four 4.3-5.3 %, i.e. 10 ns of the MFMA stream per piece whatever its lead; in front of the reads instead of behind
+//    them the rate is level (docs/EXPERIMENTS.md, profiles/r07_gemm_dma_spread_ab.txt). The L slot has the room, the M
+//    slot is the critical path.
 // Split-K (EPI == LR_EPI_PARTIAL): blockIdx.y = split s works on K tiles [s*T/S, (s+1)*T/S) and stores its
 // fp32 partial plane at ((float*)C)[s][M][N]; splitk_reduce_kernel sums the planes in order and applies the
 // real epilogue.
@@ -715,13 +721,20 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 
 // number of K splits for an M x N x K product on 256 x 256 tiles (1 = do not split): split only when the
-// tiles alone leave at least half of the 256 CUs idle, keep >= 16 K tiles per split, <= 8 splits
+// tiles alone leave at least half of the 256 CUs idle, keep >= 16 K tiles per split, <= 8 splits.
+// LR_GEMM_SPLITK_MIN_TILES lowers that 16 for tests only (tests/test_gpu_gemm_dma_spread.py: runs of one and two K tiles,
+// the shortest in which the K loop's prologue, its in-flight DMA pieces and its drain meet); read per call, not cached.
 static int splitk_factor(int M, int N, int K) {
   const int tiles = ((M + 255) / 256) * (N / 256);
   if (tiles > 128) return 1;
   int S = 256 / tiles;
   if (S > 8) S = 8;
-  const int by_k = (K >> 6) / 16;
+  int min_tiles = 16;
+  if (const char* e = getenv("LR_GEMM_SPLITK_MIN_TILES")) {
+    const int v = atoi(e);
+    if (v >= 1 && v < 16) min_tiles = v;
+  }
+  const int by_k = (K >> 6) / min_tiles;
   if (S > by_k) S = by_k;
   return S < 2 ? 1 : S;
 }
