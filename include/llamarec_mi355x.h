@@ -240,6 +240,8 @@ int lr_llama_create_ex(const LrLlamaConfig* cfg, const LrLlamaArch* arch, const 
  * path's 460 .. 1 125-token prompts, so auto keeps 2),
  * attention 4 = head_dim-256 MFMA flash attention (Gemma; 8 waves x 16 query rows per workgroup, K/V by LDS-DMA, no
  * shared prefix); auto takes it in the prefill for head_dim 256, and any other head_dim is LR_EUNSUPPORTED,
+ * attention 5 = head_dim-64 MFMA flash attention (Llama-3.2-1B; 4 waves x 32 query rows per workgroup, K/V by LDS-DMA, no
+ * shared prefix, no lse); auto takes it in the prefill for head_dim 64, and any other head_dim is LR_EUNSUPPORTED,
  * gemm 4 = the ping-pong pipelined 256x256x64 MFMA GEMM (an error if a shape does not fit).
  * gemm 5 = LATENCY MODE for the online single-user path (demo/inference.py:56-76):
  * variant 4 plus split-K wherever the output tiles alone would leave most CUs idle (a 460-token prompt
@@ -247,6 +249,25 @@ int lr_llama_create_ex(const LrLlamaConfig* cfg, const LrLlamaArch* arch, const 
  * split-K summation order depends on the token count, so unlike the default a prompt's scores are
  * then reproducible only for the same packed batch size (bf16-level differences otherwise). */
 int lr_llama_set_variants(lr_llama_t* h, int32_t gemm_variant, int32_t attention_variant);
+
+/* RoPE frequency scaling (Llama-3.1 / 3.2: rope_scaling.rope_type = "llama3" in config.json). Per frequency j of the rotary
+ * table, inv = theta^(-2j/head_dim) and wavelen = 2 pi / inv, all in fp32:
+ *   wavelen > original_max_positions / low_freq_factor  : inv / factor
+ *   wavelen < original_max_positions / high_freq_factor : inv
+ *   otherwise s = (original_max_positions / wavelen - low_freq_factor) / (high_freq_factor - low_freq_factor),
+ *             inv = (1 - s) * inv / factor + s * inv
+ * (HF's _compute_llama3_parameters; the attention factor is 1). The rule acts at EVERY position, not only past
+ * original_max_positions. LR_EINVAL for an unknown kind, a non-zero reserved word, factor < 1, original_max_positions < 1
+ * or anything but 0 < low_freq_factor < high_freq_factor. */
+typedef struct LrRopeScaling {
+  int32_t kind;                    /* 0 = none (plain RoPE), 1 = llama3 */
+  float factor, low_freq_factor, high_freq_factor;
+  int32_t original_max_positions;
+  int32_t reserved[3];             /* must be zero */
+} LrRopeScaling;
+/* The handle's prefill, and the forward and backward of every LoRA engine created from it, build their rotary table with
+ * these words from then on. NULL or kind 0: plain RoPE (the default). */
+int lr_llama_set_rope_scaling(lr_llama_t* h, const LrRopeScaling* s);
 
 /* Folded RMSNorm (optional, scoring path only). HF's layer computes  proj(norm_w * bf16(x * rstd))  with its own
  * read-and-write pass over the residual stream in front of q/k/v_proj and of gate/up_proj (LlamaRMSNorm, reached from
@@ -370,6 +391,9 @@ int lr_gemm_bf16_nt_residual_rmsnorm_ex(const uint16_t* A, const uint16_t* B, ui
  * dtype), followed by the same values packed as bf16 pairs, uint32 [max_positions][head_dim/2] = cos | sin << 16. */
 size_t lr_rope_table_bytes(int32_t max_positions, int32_t head_dim);
 int lr_rope_table(float* cs, int32_t max_positions, int32_t head_dim, float theta, void* hip_stream);
+/* The same with scaled frequencies (LrRopeScaling above). s = NULL or kind 0 writes lr_rope_table's bytes. */
+int lr_rope_table_ex(float* cs, int32_t max_positions, int32_t head_dim, float theta, const LrRopeScaling* s,
+                     void* hip_stream);
 
 /* Stand-alone varlen causal attention (exposed for parity tests):
  * qkv: DEVICE bf16 [total][(nh+2*nkv)*hd] (RoPE already applied; any consistent permutation of the

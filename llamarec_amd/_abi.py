@@ -67,6 +67,17 @@ class LrLlamaArch(C.Structure):
     ]
 
 
+class LrRopeScaling(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32),                  # 0 = none, 1 = llama3
+        ("factor", C.c_float),
+        ("low_freq_factor", C.c_float),
+        ("high_freq_factor", C.c_float),
+        ("original_max_positions", C.c_int32),
+        ("reserved", C.c_int32 * 3),
+    ]
+
+
 class LrLlamaLayerWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("input_norm", "wqkv", "wo", "post_norm", "wgu", "wdown")]
 

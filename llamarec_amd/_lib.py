@@ -55,6 +55,7 @@ PROTOTYPES = {
                                                       C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]),
     "lr_rope_table_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lr_rope_table": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    "lr_rope_table_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.POINTER(A.LrRopeScaling), C.c_void_p]),
     "lr_metrics_from_histogram": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "lr_lru_train_state_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lr_lru_train_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -76,6 +77,7 @@ PROTOTYPES = {
     "lr_llama_destroy": (None, [C.c_void_p]),
     "lr_llama_set_variants": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "lr_llama_set_last_layer_pruning": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lr_llama_set_rope_scaling": (C.c_int, [C.c_void_p, C.POINTER(A.LrRopeScaling)]),
     "lr_fold_norm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "lr_llama_set_folded_norms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lr_llama_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),

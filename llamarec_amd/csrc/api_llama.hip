@@ -56,10 +56,18 @@ extern "C" int lr_llama_create(const LrLlamaConfig* cfg, const LrLlamaWeightsDes
 
 extern "C" int lr_llama_set_variants(lr_llama_t* h, int32_t gemm_variant, int32_t attention_variant) {
   if (!h || (gemm_variant != 0 && gemm_variant != 1 && gemm_variant != 4 && gemm_variant != 5) || attention_variant < 0 ||
-      attention_variant > 4)
-    LR_FAIL(LR_EINVAL, "lr_llama_set_variants: gemm in {0, 1, 4, 5}, attention in {0, 1, 2, 3, 4}");
+      attention_variant > 5)
+    LR_FAIL(LR_EINVAL, "lr_llama_set_variants: gemm in {0, 1, 4, 5}, attention in {0, 1, 2, 3, 4, 5}");
   h->gemm_variant = gemm_variant;
   h->attn_variant = attention_variant;
+  return LR_OK;
+}
+
+extern "C" int lr_llama_set_rope_scaling(lr_llama_t* h, const LrRopeScaling* s) {
+  if (!h) LR_FAIL(LR_EINVAL, "lr_llama_set_rope_scaling: null handle");
+  LR_RUN(lr_check_rope_scaling(s, "lr_llama_set_rope_scaling"));
+  if (s) h->rope_scaling = *s;
+  else memset(&h->rope_scaling, 0, sizeof(h->rope_scaling));
   return LR_OK;
 }
 
@@ -131,8 +139,11 @@ static LlamaWs carve(const LrLlamaConfig& c, int max_tokens, int max_seqs, char*
   const size_t qkv_w = (size_t)(c.num_heads + 2 * c.num_kv_heads) * c.head_dim;
   w.tok_pos = (int32_t*)take(n * 4);
   w.tok_src = (int32_t*)take(n * 4);
-  w.rope = (float*)take((size_t)c.max_positions * (c.head_dim / 2) * 2 * sizeof(float));
-  w.rope16 = (unsigned*)take((size_t)c.max_positions * (c.head_dim / 2) * sizeof(unsigned));
+  // the table is built for the batch's longest prompt, which has at most max_tokens rows (max_positions is 131 072 in a
+  // Llama-3.1 / 3.2 config)
+  const size_t rope_rows = (size_t)(c.max_positions < max_tokens ? c.max_positions : max_tokens);
+  w.rope = (float*)take(rope_rows * (c.head_dim / 2) * 2 * sizeof(float));
+  w.rope16 = (unsigned*)take(rope_rows * (c.head_dim / 2) * sizeof(unsigned));
   w.rstd = (float*)take(n * sizeof(float));
   w.x = (u16*)take(n * c.hidden_size * 2);
   w.xn = (u16*)take(n * c.hidden_size * 2);
@@ -225,7 +236,8 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
                               &attn_kernel));
   // the MFMA kernels over ALL rows (188 us for 14.8 k tokens, 16 us for one prompt) beat the scalar kernel over the B last
   // rows (459 / 295 us), so a pruned last layer attends everything and keeps the last rows
-  const bool attn_mfma = (hd == 128 && attn_kernel != LR_ATTN_GENERIC) || attn_kernel == LR_ATTN_HD256;
+  const bool attn_mfma = (hd == 128 && attn_kernel != LR_ATTN_GENERIC) || attn_kernel == LR_ATTN_HD256 ||
+                         attn_kernel == LR_ATTN_HD64;
   const LrAttnArgs attn = {.qkv = ws.qkv, .out = ws.att, .cu = ws.seg_start, .cu_host = plan.seg_host.data(), .S = S,
                            .n_tok = n, .nh = nh, .nkv = nkv, .hd = hd, .prefix_len = P, .items_ws = ws.attn_items};
   struct LayerRows { u16 *att, *x, *xn, *hmid; int M, gemm_variant; };   // what o_proj and the MLP run on
@@ -235,7 +247,7 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
   };
   LR_RUN(lr_launch_token_meta(cu, B, P, ws.seg_start, ws.tok_pos, ws.tok_src, ws.last_rows, st, ws.last_pos, ids,
                               ws.prefix_bad));
-  LR_RUN(lr_launch_rope_table(ws.rope, plan.maxT, hd, c.rope_theta, st, ws.rope16));
+  LR_RUN(lr_launch_rope_table(ws.rope, plan.maxT, hd, c.rope_theta, st, ws.rope16, &h->rope_scaling));
   if (attn_kernel == LR_ATTN_ROWS256)
     LR_RUN(lr_launch_attn256_items(ws.seg_start, S, n, nh, P, ws.attn_items, ws.attn_items_bytes, st));
   LR_RUN(lr_launch_embed(ids, ws.tok_src, h->embed, c.vocab_size, d, ws.x, n, st, h->arch.embed_scale));
@@ -462,6 +474,13 @@ extern "C" int lr_rope_table(float* cs, int32_t max_positions, int32_t head_dim,
   if (!cs || max_positions < 1 || head_dim < 2) LR_FAIL(LR_EINVAL, "lr_rope_table: bad argument");
   return lr_launch_rope_table(cs, max_positions, head_dim, theta, (hipStream_t)hip_stream,
                               reinterpret_cast<unsigned*>(cs + (size_t)max_positions * head_dim));
+}
+
+extern "C" int lr_rope_table_ex(float* cs, int32_t max_positions, int32_t head_dim, float theta, const LrRopeScaling* s,
+                                void* hip_stream) {
+  if (!cs || max_positions < 1 || head_dim < 2) LR_FAIL(LR_EINVAL, "lr_rope_table_ex: bad argument");
+  return lr_launch_rope_table(cs, max_positions, head_dim, theta, (hipStream_t)hip_stream,
+                              reinterpret_cast<unsigned*>(cs + (size_t)max_positions * head_dim), s);
 }
 
 extern "C" int lr_attention_varlen(const uint16_t* qkv, uint16_t* out, const int32_t* cu_seqlens,

@@ -323,7 +323,8 @@ static LoraWs carve(const LrLlamaConfig& c, const LoraMods& md, int n_tok, int B
   const size_t qw = qcols + 2 * kv;
   w.tok_pos = (int32_t*)(base + take(n * 4));
   w.last_rows = (int32_t*)(base + take((size_t)(B > 0 ? B : 1) * 4));
-  w.rope = (float*)(base + take((size_t)c.max_positions * (c.head_dim / 2) * 2 * sizeof(float)));
+  // built per pass for its longest prompt, which has at most n_tok rows (max_positions is 131 072 in a Llama-3.1 / 3.2 config)
+  w.rope = (float*)(base + take((c.max_positions < n_tok ? (size_t)c.max_positions : n) * (c.head_dim / 2) * 2 * sizeof(float)));
   w.x_final = (u16*)(base + take(n * d * 2));
   // one slot of saved activations
   size_t so = 0;
@@ -510,7 +511,7 @@ static int forward(lr_llama_lora* h, const int32_t* ids, const int32_t* cu, cons
   LrAttnKernel attn_kernel;  // the backward needs the statistics: lse wanted
   LR_RUN(lr_resolve_attention({.variant = h->base->attn_variant, .hd = hd, .want_lse = true}, &attn_kernel));
   LR_RUN(lr_launch_token_meta(cu, B, 0, nullptr, ws.tok_pos, nullptr, ws.last_rows, st));
-  LR_RUN(lr_launch_rope_table(ws.rope, maxT, hd, c.rope_theta, st));
+  LR_RUN(lr_launch_rope_table(ws.rope, maxT, hd, c.rope_theta, st, nullptr, &h->base->rope_scaling));   // the base's scaling
   LR_RUN(lr_launch_embed(ids, nullptr, h->base->embed, c.vocab_size, d, slot(ws, 0).x, n, st));
   for (int l = 0; l < c.num_layers; ++l) {
     const LrLlamaLayerWeights& w = h->base->layers[l];

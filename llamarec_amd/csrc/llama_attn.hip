@@ -543,7 +543,8 @@ int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
   switch (r.variant) {
     case 0:
       if (hd == 128) *kernel = (r.have_items_ws && !r.prefill) ? LR_ATTN_ROWS256 : LR_ATTN_MFMA128;
-      else *kernel = (hd == 256 && r.prefill) ? LR_ATTN_HD256 : LR_ATTN_GENERIC;
+      else if (hd == 256 && r.prefill) *kernel = LR_ATTN_HD256;
+      else *kernel = (hd == 64 && r.prefill) ? LR_ATTN_HD64 : LR_ATTN_GENERIC;
       return LR_OK;
     case 1: *kernel = LR_ATTN_GENERIC; return LR_OK;
     case 2: *kernel = LR_ATTN_MFMA128; return LR_OK;
@@ -559,9 +560,14 @@ int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
       if (r.prefill && hd != 256) LR_FAIL(LR_EUNSUPPORTED, "attention variant 4 needs head_dim 256 (got %d)", hd);
       *kernel = LR_ATTN_HD256;
       return LR_OK;
+    case 5:
+      if (r.want_lse) LR_FAIL(LR_EINVAL, "attention variant 5 (head_dim-64 MFMA) writes no lse");
+      if (hd != 64) LR_FAIL(LR_EUNSUPPORTED, "attention variant 5 needs head_dim 64 (got %d)", hd);
+      *kernel = LR_ATTN_HD64;
+      return LR_OK;
   }
   LR_FAIL(LR_EINVAL, "attention: unknown variant %d (0 auto, 1 generic, 2 = head_dim-128 MFMA, 3 = 256-row tiles, "
-          "4 = head_dim-256 MFMA)", r.variant);
+          "4 = head_dim-256 MFMA, 5 = head_dim-64 MFMA)", r.variant);
 }
 
 int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st) {
@@ -573,6 +579,10 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
   if (kernel == LR_ATTN_HD256) {
     if (prefix_len != 0 || a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-256 MFMA kernel takes no shared prefix, writes no lse");
     return lr_launch_attention_hd256(a, st);
+  }
+  if (kernel == LR_ATTN_HD64) {
+    if (prefix_len != 0 || a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-64 MFMA kernel takes no shared prefix, writes no lse");
+    return lr_launch_attention_hd64(a, st);
   }
   if (prefix_len < 0 || (prefix_len > 0 && (kernel != LR_ATTN_MFMA128 || cu_host[1] - cu_host[0] != prefix_len)))
     LR_FAIL(LR_EINVAL, "attention: shared prefix of %d tokens needs the head_dim-128 MFMA kernel and segment 0 = the prefix",

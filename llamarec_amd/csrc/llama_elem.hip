@@ -304,6 +304,29 @@ __global__ void rope_table_kernel(float* cs /*[T][hd/2][2]*/, unsigned* cs16 /*[
   if (cs16) cs16[i] = (unsigned)c | ((unsigned)sn << 16);
 }
 
+// The llama3 rule (include/llamarec_mi355x.h, LrRopeScaling) on the same fp32 inverse frequency; a kernel of its own, so the
+// plain table's code and bits stay what they are.
+__global__ void rope_table_llama3_kernel(float* cs, unsigned* cs16, int T, int hd, float theta, float factor, float low,
+                                         float high, float orig) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  int half = hd / 2;
+  if (i >= T * half) return;
+  int pos = i / half, j = i % half;
+  float inv = 1.0f / powf(theta, (float)(2 * j) / (float)hd);
+  const float wavelen = 6.283185307179586f / inv;
+  if (wavelen > orig / low) {
+    inv = inv / factor;
+  } else if (!(wavelen < orig / high)) {
+    const float s = (orig / wavelen - low) / (high - low);
+    inv = (1.0f - s) * inv / factor + s * inv;
+  }
+  float ang = (float)pos * inv;
+  const u16 c = f2bf(cosf(ang)), sn = f2bf(sinf(ang));
+  cs[2 * i + 0] = bf2f(c);
+  cs[2 * i + 1] = bf2f(sn);
+  if (cs16) cs16[i] = (unsigned)c | ((unsigned)sn << 16);
+}
+
 // ---- final RMSNorm on each prompt's last token + dot with selected lm_head rows -------------
 // grid (B, ceil(C/32)); out[b][c] = float(bf16(sum_k xn[k] * W[row_c][k])), row_c = ids ? ids[c] : c
 template <int NS>
@@ -402,8 +425,29 @@ int lr_launch_rmsnorm(const u16* x, const u16* w, u16* out, int rows, int d, flo
   return LR_OK;
 }
 
-int lr_launch_rope_table(float* cs, int T, int hd, float theta, hipStream_t st, unsigned* cs16) {
+int lr_check_rope_scaling(const LrRopeScaling* s, const char* who) {
+  if (!s) return LR_OK;
+  for (int i = 0; i < 3; ++i)
+    if (s->reserved[i]) LR_FAIL(LR_EINVAL, "%s: rope scaling reserved word %d is not zero", who, i);
+  if (s->kind == 0) return LR_OK;
+  if (s->kind != 1) LR_FAIL(LR_EINVAL, "%s: unknown rope scaling kind %d (0 none, 1 llama3)", who, s->kind);
+  if (!(s->factor >= 1.0f) || !(s->low_freq_factor > 0.f) || !(s->low_freq_factor < s->high_freq_factor) ||
+      !(s->high_freq_factor < __builtin_inff()) || !(s->factor < __builtin_inff()) || s->original_max_positions < 1)
+    LR_FAIL(LR_EINVAL, "%s: llama3 rope scaling factor=%g low_freq_factor=%g high_freq_factor=%g original_max_positions=%d",
+            who, (double)s->factor, (double)s->low_freq_factor, (double)s->high_freq_factor, s->original_max_positions);
+  return LR_OK;
+}
+
+int lr_launch_rope_table(float* cs, int T, int hd, float theta, hipStream_t st, unsigned* cs16, const LrRopeScaling* scaling) {
   int n = T * (hd / 2);
+  LR_RUN(lr_check_rope_scaling(scaling, "rope table"));
+  if (scaling && scaling->kind == 1) {
+    hipLaunchKernelGGL(rope_table_llama3_kernel, dim3((n + 255) / 256), dim3(256), 0, st, cs, cs16, T, hd, theta,
+                       scaling->factor, scaling->low_freq_factor, scaling->high_freq_factor,
+                       (float)scaling->original_max_positions);
+    LR_CHECK_LAUNCH("rope_table_llama3_kernel");
+    return LR_OK;
+  }
   hipLaunchKernelGGL(rope_table_kernel, dim3((n + 255) / 256), dim3(256), 0, st, cs, cs16, T, hd, theta);
   LR_CHECK_LAUNCH("rope_table_kernel");
   return LR_OK;

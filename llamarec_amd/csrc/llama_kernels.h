@@ -64,7 +64,10 @@ int lr_launch_embed(const int32_t* ids, const int32_t* tok_src /*nullptr: identi
 int lr_launch_rmsnorm(const unsigned short* x, const unsigned short* w, unsigned short* out, int rows, int d,
                       float eps, const int32_t* row_map, hipStream_t st, int norm_style = 0);
 int lr_launch_rope_table(float* cs, int T, int hd, float theta, hipStream_t st,
-                         unsigned* cs16 = nullptr /* [T][hd/2] (cos | sin << 16) as bf16 pairs, optional */);
+                         unsigned* cs16 = nullptr /* [T][hd/2] (cos | sin << 16) as bf16 pairs, optional */,
+                         const LrRopeScaling* scaling = nullptr /* nullptr or kind 0: plain RoPE (the plain kernel) */);
+// LR_OK, or LR_EINVAL with the reason recorded, for the words of an LrRopeScaling (nullptr is valid: plain RoPE)
+int lr_check_rope_scaling(const LrRopeScaling* s, const char* who);
 int lr_launch_head(const unsigned short* x, const int32_t* rows /*[B]; nullptr: x holds one row per prompt*/,
                    const unsigned short* norm_w,
                    const unsigned short* lm_head, const int32_t* class_ids, int B, int C, int d, float eps,
@@ -137,12 +140,13 @@ static inline int lr_check_segments(const int32_t* cu_host, int S, const char* w
 }
 
 // ---- varlen causal attention over packed qkv (RoPE applied) ----------------------------------------------------------------
-// The kernels (a requested variant 1 .. 4 asks for the kernel of the same number, 0 = auto):
+// The kernels (a requested variant 1 .. 5 asks for the kernel of the same number, 0 = auto):
 //   GENERIC  any head_dim <= 256, scalar                                  (llama_attn.hip)
 //   MFMA128  head_dim 128, 128-row query tiles, reads a shared prefix     (llama_attn.hip)
 //   ROWS256  head_dim 128, 256-row query tiles over a device-built item list, shared prefix <= 64 (llama_attn256.hip)
 //   HD256    head_dim 256, no shared prefix, no lse                       (llama_attn_hd256.hip)
-enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 3, LR_ATTN_HD256 = 4 };
+//   HD64     head_dim 64, no shared prefix, no lse                        (llama_attn_hd64.hip)
+enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 3, LR_ATTN_HD256 = 4, LR_ATTN_HD64 = 5 };
 
 // Which kernel a request runs on -- the one place that decides it, for the four routes
 //   prefill    run_body (api_llama.hip): lse never wanted, the handle's workspace always has room for an item list
@@ -158,8 +162,9 @@ enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 
 //                                                                   its prompts of 460 .. 1 125 tokens two 128-row workgroups
 //                                                                   per CU are ahead of the 256-row kernel)
 //   0        256       0       no   yes      prefill      HD256
-//   0        any       0       any  any      any          GENERIC  (head_dim 256 too outside prefill: the entry points' auto
-//                                                                   is older than HD256 and its results are kept)
+//   0        64        0       no   yes      prefill      HD64     (faster than GENERIC on every shape of DESIGN 10)
+//   0        any       0       any  any      any          GENERIC  (head_dim 256 and 64 too outside prefill: the entry points'
+//                                                                   auto is older than HD256 / HD64 and its results are kept)
 //   1        any       0       any  any      any          GENERIC
 //   2        any       any     any  any      any          MFMA128
 //   3        any       0       any  no       varlen, train  LR_EINVAL  (no item workspace exists on these routes)
@@ -171,12 +176,15 @@ enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 
 //   4        any       0       no   any      any          HD256    (outside prefill a head_dim other than 256 is refused by
 //                                                                   the launcher, LR_EUNSUPPORTED, behind its
 //                                                                   num_heads % num_kv_heads check, LR_EINVAL, as before)
+//   5        any       any     yes  any      any          LR_EINVAL  (HD64 writes no statistics)
+//   5        != 64     any     no   any      any          LR_EUNSUPPORTED
+//   5        64        0       no   any      any          HD64
 //   other                                                 LR_EINVAL
 //
 // varlen_ws counts a variant-3 request as "item ws yes" whatever it was given: the item-list builder then reports a missing
 // or short workspace as LR_EWORKSPACE. lr_launch_attention still refuses what the resolved kernel cannot take: GENERIC above
 // head_dim 256 and MFMA128 off head_dim 128 (LR_EUNSUPPORTED; a one-layer pruned prefill launches neither, so these checks
-// cannot move up here), a shared prefix or lse on HD256.
+// cannot move up here), a shared prefix or lse on HD256 and HD64.
 static inline bool lr_attention_reads_prefix(int variant, int hd) { return hd == 128 && variant != 1; }
 struct LrAttnRequest { int variant, hd, prefix_len = 0; bool want_lse = false, have_items_ws = false, prefill = false; };
 int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel);
@@ -205,5 +213,6 @@ int lr_launch_attn256_items(const int32_t* cu, int S, int n_tok, int nh, int pre
 // the per-file launchers behind lr_launch_attention
 int lr_launch_attention256(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd256(const LrAttnArgs& a, hipStream_t st);
+int lr_launch_attention_hd64(const LrAttnArgs& a, hipStream_t st);
 
 #endif

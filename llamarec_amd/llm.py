@@ -25,6 +25,15 @@ from ._lib import check, lib, stream_ptr
 LLAMA2_7B = dict(vocab_size=32000, hidden_size=4096, intermediate_size=11008, num_hidden_layers=32,
                  num_attention_heads=32, num_key_value_heads=32, max_position_embeddings=4096,
                  rms_norm_eps=1e-5, rope_theta=10000.0)
+# meta-llama/Llama-3.2-1B, Llama-3.2-3B and Llama-3.1-8B (config.json of the checkpoints): GQA, llama3 RoPE scaling
+LLAMA3_ROPE_SCALING = dict(rope_type="llama3", factor=32.0, low_freq_factor=1.0, high_freq_factor=4.0,
+                           original_max_position_embeddings=8192)
+LLAMA32_1B = dict(model_type="llama", vocab_size=128256, hidden_size=2048, intermediate_size=8192, num_hidden_layers=16,
+                  num_attention_heads=32, num_key_value_heads=8, head_dim=64, max_position_embeddings=131072,
+                  rms_norm_eps=1e-5, rope_theta=500000.0, tie_word_embeddings=True, rope_scaling=dict(LLAMA3_ROPE_SCALING))
+LLAMA32_3B = dict(LLAMA32_1B, hidden_size=3072, num_hidden_layers=28, num_attention_heads=24, head_dim=128)
+LLAMA31_8B = dict(LLAMA32_1B, hidden_size=4096, intermediate_size=14336, num_hidden_layers=32, num_attention_heads=32,
+                  head_dim=128, tie_word_embeddings=False, rope_scaling=dict(LLAMA3_ROPE_SCALING, factor=8.0))
 # google/gemma-2b and google/gemma-7b (config.json of the checkpoints; the reference's --llm gemma loads gemma-2b)
 GEMMA_2B = dict(model_type="gemma", vocab_size=256000, hidden_size=2048, intermediate_size=16384, num_hidden_layers=18,
                 num_attention_heads=8, num_key_value_heads=1, head_dim=256, max_position_embeddings=8192,
@@ -38,17 +47,45 @@ GEMMA_FAMILY = ("gemma",)
 SUPPORTED_MODEL_TYPES = LLAMA_FAMILY + GEMMA_FAMILY
 
 
+_LLAMA3_NUMBERS = ("factor", "low_freq_factor", "high_freq_factor", "original_max_position_embeddings")
+
+
+def rope_parameters(config: dict):
+    """(rope_theta, llama3 scaling dict or None) of a HF config dict. The scaling sits in `rope_scaling` (transformers <= 4)
+    or `rope_parameters` (transformers 5, which also moves rope_theta there); its `rope_type` (legacy key `type`) is
+    "default" / absent (plain RoPE) or "llama3" with all four numbers. Anything else raises NotImplementedError: the
+    rotary table cannot be computed from it."""
+    rp = config.get("rope_parameters")
+    rs = config.get("rope_scaling")
+    theta = config.get("rope_theta")
+    if theta is None and isinstance(rp, dict):
+        theta = rp.get("rope_theta")
+    src = rs if rs is not None else rp
+    if src is None:
+        return float(theta if theta is not None else 10000.0), None
+    kind = (src.get("rope_type") or src.get("type") or "default") if isinstance(src, dict) else src
+    if kind == "default":
+        return float(theta if theta is not None else 10000.0), None
+    if kind != "llama3":
+        raise NotImplementedError(f"rope_scaling={src!r}: the rotary tables implement plain RoPE and rope_type 'llama3' only")
+    missing = [k for k in _LLAMA3_NUMBERS if src.get(k) is None]
+    if missing:
+        raise NotImplementedError(f"rope_scaling={src!r}: rope_type 'llama3' needs {', '.join(missing)}")
+    return float(theta if theta is not None else 10000.0), {k: src[k] for k in _LLAMA3_NUMBERS}
+
+
 def model_family(config: dict) -> str:
     """'llama' or 'gemma' for a HF config dict (a missing model_type means llama); anything else raises: the kernels
     implement those two families' arithmetic only, and a checkpoint of another family would load (same tensor names)
     and then score silently wrong."""
     mt = config.get("model_type") or "llama"
     if mt in LLAMA_FAMILY:
-        if config.get("rope_scaling") is not None:
-            raise NotImplementedError(f"model_type {mt!r} with rope_scaling={config['rope_scaling']!r}: the rotary tables "
-                                      "implement plain RoPE only")
+        rope_parameters(config)   # plain RoPE or a complete llama3 rule; raises otherwise
         return "llama"
     if mt in GEMMA_FAMILY:
+        if rope_parameters(config)[1] is not None:
+            raise NotImplementedError(f"gemma with rope_scaling={config.get('rope_scaling') or config.get('rope_parameters')!r}: "
+                                      "scaled RoPE is implemented for the llama family only")
         act = config.get("hidden_activation") or config.get("hidden_act") or "gelu_pytorch_tanh"
         if act not in ("gelu_pytorch_tanh", "gelu"):
             raise NotImplementedError(f"gemma with hidden_activation={act!r}: the kernels implement gelu_pytorch_tanh")
@@ -209,6 +246,7 @@ class LlamaRanker:
         self.device = torch.device(device)
         c = self.config
         self.family = model_family(c)
+        self.rope_theta, self.rope_scaling = rope_parameters(c)   # scaling: None (plain RoPE) or the llama3 numbers
         self.hd = c.get("head_dim") or c["hidden_size"] // c["num_attention_heads"]
         # Mistral's sliding window: the kernels attend to the whole causal range, so a longer prompt is refused
         self.max_prompt_len = c.get("sliding_window") if c.get("model_type") == "mistral" else None
@@ -371,7 +409,7 @@ class LlamaRanker:
             num_layers=c["num_hidden_layers"], num_heads=c["num_attention_heads"],
             num_kv_heads=c["num_key_value_heads"], head_dim=self.hd,
             max_positions=int(c.get("max_position_embeddings", 4096)), rms_eps=float(c["rms_norm_eps"]),
-            rope_theta=float(c.get("rope_theta", 10000.0)))
+            rope_theta=self.rope_theta)
         L = c["num_hidden_layers"]
         arr = (A.LrLlamaLayerWeights * L)()
         for i in range(L):
@@ -384,6 +422,12 @@ class LlamaRanker:
             torch.cuda.synchronize()
             check(lib().lr_llama_create_ex(C.byref(cfg), C.byref(self.arch()), C.byref(desc), C.byref(h)), "lr_llama_create_ex")
         self._h, self._layers_arr = h, arr
+        if self.rope_scaling is not None:
+            rs = self.rope_scaling
+            words = A.LrRopeScaling(kind=1, factor=float(rs["factor"]), low_freq_factor=float(rs["low_freq_factor"]),
+                                    high_freq_factor=float(rs["high_freq_factor"]),
+                                    original_max_positions=int(rs["original_max_position_embeddings"]))
+            check(lib().lr_llama_set_rope_scaling(self._h, C.byref(words)), "lr_llama_set_rope_scaling")
         if self.fold_norms:
             self.set_fold_norms(True)
 
