@@ -242,6 +242,10 @@ int lr_llama_create_ex(const LrLlamaConfig* cfg, const LrLlamaArch* arch, const 
  * shared prefix); auto takes it in the prefill for head_dim 256, and any other head_dim is LR_EUNSUPPORTED,
  * attention 5 = head_dim-64 MFMA flash attention (Llama-3.2-1B; 4 waves x 32 query rows per workgroup, K/V by LDS-DMA, no
  * shared prefix, no lse); auto takes it in the prefill for head_dim 64, and any other head_dim is LR_EUNSUPPORTED,
+ * attention 6 = head_dim-64 MFMA flash attention for training: variant 5's forward, optionally writing lse (without lse
+ * the same bits as 5), and the head_dim-64 MFMA backward (two passes, one owner per gradient element, no atomics); the
+ * LoRA step's auto takes the pair at head_dim 64, and any other head_dim is LR_EUNSUPPORTED. A LoRA engine on a base set to
+ * 4 or 5 fails (those kernels write no lse),
  * gemm 4 = the ping-pong pipelined 256x256x64 MFMA GEMM (an error if a shape does not fit).
  * gemm 5 = LATENCY MODE for the online single-user path (demo/inference.py:56-76):
  * variant 4 plus split-K wherever the output tiles alone would leave most CUs idle (a 460-token prompt
@@ -398,7 +402,8 @@ int lr_rope_table_ex(float* cs, int32_t max_positions, int32_t head_dim, float t
 /* Stand-alone varlen causal attention (exposed for parity tests):
  * qkv: DEVICE bf16 [total][(nh+2*nkv)*hd] (RoPE already applied; any consistent permutation of the
  * dims inside q and k heads), out: bf16 [total][nh*hd]. variant 0 = auto (2 at head_dim 128, else 1), 1 generic,
- * 2 = head_dim-128 MFMA, 4 = head_dim-256 MFMA.
+ * 2 = head_dim-128 MFMA, 4 = head_dim-256 MFMA, 5 = head_dim-64 MFMA, 6 = the same kernel, which also serves _lse and has a
+ * backward (_bwd). auto keeps the generic kernels at head_dim 64 and 256 here: these entry points' results are kept.
  * cu_seqlens_host (HOST int32 [B+1], the values of cu_seqlens): cu_seqlens_host[0] == 0 and strictly increasing, so that
  * every segment holds at least one row. lr_attention_varlen, _ws, _lse and _bwd check this on the host and return LR_EINVAL
  * before anything is launched (outputs untouched) when it does not hold. */
@@ -614,7 +619,9 @@ int lr_llama_lora_prefill_verbalize(lr_llama_lora_t* h, const int32_t* packed_id
                                     void* hip_stream);
 /* Varlen causal attention backward (exposed for parity tests): qkv as lr_attention_varlen; out / d_out
  * bf16 [total][nh*hd]; lse fp32 [total][nh] from lr_attention_varlen_lse; dqkv bf16 like qkv.
- * scratch: DEVICE, lr_attention_bwd_scratch_bytes. */
+ * scratch: DEVICE, lr_attention_bwd_scratch_bytes. variant: 0 / 1 / 2 as lr_attention_varlen, 6 = the head_dim-64 MFMA pair
+ * (LR_EUNSUPPORTED at any other head_dim; its backward uses only the first, per-(token, head) part of the scratch, whose size
+ * is the same for every variant); 4 and 5 write no lse and have no backward: LR_EINVAL. */
 int lr_attention_varlen_lse(const uint16_t* qkv, uint16_t* out, float* lse, const int32_t* cu_seqlens,
                             const int32_t* cu_seqlens_host, int32_t B, int32_t num_heads, int32_t num_kv_heads,
                             int32_t head_dim, int32_t variant, void* hip_stream);
@@ -627,10 +634,10 @@ int lr_attention_varlen_bwd(const uint16_t* qkv, const uint16_t* out, const uint
  * rope_cs: DEVICE, the table lr_rope_table wrote for head_dim with rope_positions positions; when given, dqkv is the
  * gradient w.r.t. the UNROTATED q and k (v as before). tok_pos: DEVICE int32[total], required with rope_cs, and must hold
  * each row's position INSIDE ITS PROMPT (row - cu_seqlens[b]): the head_dim-128 MFMA passes index the table by that
- * position directly and the generic path reads tok_pos, so any other content makes the two disagree. LR_EINVAL (with a
+ * position directly (so do variant 6's head_dim-64 passes) and the generic path reads tok_pos, so any other content makes the two disagree. LR_EINVAL (with a
  * message, nothing launched) for rope_cs without tok_pos and for a segment longer than rope_positions.
  * deterministic != 0: the generic path (variant 1) computes dK / dV per owner instead of with fp32 atomics -- the same
- * bits on every run; the MFMA passes have no atomics either way. */
+ * bits on every run; the MFMA passes (variants 2 and 6) have no atomics either way and ignore the flag. */
 int lr_attention_varlen_bwd_ex(const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out, const float* lse,
                                uint16_t* dqkv, const int32_t* cu_seqlens, const int32_t* cu_seqlens_host, int32_t B,
                                int32_t num_heads, int32_t num_kv_heads, int32_t head_dim, int32_t variant,

@@ -131,6 +131,8 @@ PROTOTYPES = {
     "lr_llama_lora_prefill_verbalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                   C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                                   C.c_void_p]),
+    # variant (the int32 before the scratch / stream): 1 generic, 2 = head_dim-128 MFMA, 6 = the head_dim-64 MFMA training
+    # pair (forward writing lse, two-pass backward); 4 and 5 write no lse and have no backward
     "lr_attention_varlen_lse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "lr_attention_bwd_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

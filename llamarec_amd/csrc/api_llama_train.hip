@@ -509,7 +509,7 @@ static int forward(lr_llama_lora* h, const int32_t* ids, const int32_t* cu, cons
   const LoraMods md = lora_mods(c, h->cfg.r, h->mods);
   const int r = h->cfg.r, tw = md.tw, L = c.num_layers;
   LrAttnKernel attn_kernel;  // the backward needs the statistics: lse wanted
-  LR_RUN(lr_resolve_attention({.variant = h->base->attn_variant, .hd = hd, .want_lse = true}, &attn_kernel));
+  LR_RUN(lr_resolve_attention({.variant = h->base->attn_variant, .hd = hd, .want_lse = true, .lora = true}, &attn_kernel));
   LR_RUN(lr_launch_token_meta(cu, B, 0, nullptr, ws.tok_pos, nullptr, ws.last_rows, st));
   LR_RUN(lr_launch_rope_table(ws.rope, maxT, hd, c.rope_theta, st, nullptr, &h->base->rope_scaling));   // the base's scaling
   LR_RUN(lr_launch_embed(ids, nullptr, h->base->embed, c.vocab_size, d, slot(ws, 0).x, n, st));
@@ -598,6 +598,10 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
   const float drop_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
   const int gv = h->base->gemm_variant == 5 ? 0 : h->base->gemm_variant;
   const int tw = md.tw, L = c.num_layers;
+  // the backward follows the forward's kernel (lr_resolve_attention's lora route): the head_dim-64 MFMA pair is variant 6
+  LrAttnKernel fwd_kernel;
+  LR_RUN(lr_resolve_attention({.variant = h->base->attn_variant, .hd = hd, .want_lse = true, .lora = true}, &fwd_kernel));
+  const int attn_bwd_variant = fwd_kernel == LR_ATTN_HD64 ? 6 : h->base->attn_variant;
   h->pass += 1;
   if (!accumulate) LR_CHECK_HIP(hipMemsetAsync(h->grads, 0, h->n_params * sizeof(float), st));
   float* const scal = det ? ws.det_loss : h->scratch;  // loss sum / per-row losses, rows without a token id
@@ -683,7 +687,7 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
     }
     // ... down to the gradient of the UNROTATED q, k, v (the inverse rotation rides in the attention passes)
     LR_RUN(lr_launch_attention_bwd(s.qkv, s.att, ws.datt, s.lse, ws.dqkv, ws.dsum, ws.dkv32, cu_seqlens, cu_seqlens_host, B,
-                                   n, nh, nkv, hd, h->base->attn_variant, st, ws.tok_pos, ws.rope, det));
+                                   n, nh, nkv, hd, attn_bwd_variant, st, ws.tok_pos, ws.rope, det));
     // adapters (side stream, next to the qkv data-gradient GEMM; both only read dqkv):
     // d B, d t = scaling * (d q B_q | d v B_v), d A
     LR_RUN(fork_side(h, st, &sd));

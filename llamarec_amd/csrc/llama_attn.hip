@@ -544,7 +544,7 @@ int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
     case 0:
       if (hd == 128) *kernel = (r.have_items_ws && !r.prefill) ? LR_ATTN_ROWS256 : LR_ATTN_MFMA128;
       else if (hd == 256 && r.prefill) *kernel = LR_ATTN_HD256;
-      else *kernel = (hd == 64 && r.prefill) ? LR_ATTN_HD64 : LR_ATTN_GENERIC;
+      else *kernel = (hd == 64 && (r.prefill || r.lora)) ? LR_ATTN_HD64 : LR_ATTN_GENERIC;
       return LR_OK;
     case 1: *kernel = LR_ATTN_GENERIC; return LR_OK;
     case 2: *kernel = LR_ATTN_MFMA128; return LR_OK;
@@ -565,9 +565,13 @@ int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
       if (hd != 64) LR_FAIL(LR_EUNSUPPORTED, "attention variant 5 needs head_dim 64 (got %d)", hd);
       *kernel = LR_ATTN_HD64;
       return LR_OK;
+    case 6:   // the training pair: variant 5's kernel, with lse when wanted; its backward is llama_attn_bwd_hd64.hip
+      if (hd != 64) LR_FAIL(LR_EUNSUPPORTED, "attention variant 6 needs head_dim 64 (got %d)", hd);
+      *kernel = LR_ATTN_HD64;
+      return LR_OK;
   }
   LR_FAIL(LR_EINVAL, "attention: unknown variant %d (0 auto, 1 generic, 2 = head_dim-128 MFMA, 3 = 256-row tiles, "
-          "4 = head_dim-256 MFMA, 5 = head_dim-64 MFMA)", r.variant);
+          "4 = head_dim-256 MFMA, 5 = head_dim-64 MFMA, 6 = head_dim-64 MFMA for training)", r.variant);
 }
 
 int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st) {
@@ -581,7 +585,7 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
     return lr_launch_attention_hd256(a, st);
   }
   if (kernel == LR_ATTN_HD64) {
-    if (prefix_len != 0 || a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-64 MFMA kernel takes no shared prefix, writes no lse");
+    if (prefix_len != 0) LR_FAIL(LR_EINVAL, "attention: the head_dim-64 MFMA kernel takes no shared prefix");
     return lr_launch_attention_hd64(a, st);
   }
   if (prefix_len < 0 || (prefix_len > 0 && (kernel != LR_ATTN_MFMA128 || cu_host[1] - cu_host[0] != prefix_len)))

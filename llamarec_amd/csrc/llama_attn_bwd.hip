@@ -18,6 +18,7 @@
 //      dKdV pass: a workgroup owns 64 keys of one kv head and walks the query blocks at or after them (and the query
 //                 heads of its group): S = Q K^T, dP = dO V^T put a key in the accumulator column; P and dS are the B
 //                 operands of dV^T += dO^T P and dK^T += Q^T dS (Q^T, dO^T through transposed LDS reads).
+//  variant 6 (head_dim 64): the same two passes narrowed to 64 dimensions, llama_attn_bwd_hd64.hip.
 #include <stdlib.h>
 
 #include "llama_train.h"
@@ -552,6 +553,7 @@ int lr_launch_attention_bwd(const u16* qkv, const u16* out, const u16* d_out, co
   if (nh % nkv != 0) LR_FAIL(LR_EINVAL, "attention backward: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
   if (hd > 256) LR_FAIL(LR_EUNSUPPORTED, "attention backward: head_dim %d > 256", hd);
   if (variant == 0 || variant == 3) variant = (hd == 128) ? 2 : 1;
+  if (variant == 6 && hd != 64) LR_FAIL(LR_EUNSUPPORTED, "attention backward variant 6 needs head_dim 64 (got %d)", hd);
   int rc = lr_launch_rowdot(out, d_out, n_tok, nh, hd, dsum, st);
   if (rc) return rc;
   double work = 0;  // 5 causal tile products of 2*T^2/2*hd flops each
@@ -602,8 +604,12 @@ int lr_launch_attention_bwd(const u16* qkv, const u16* out, const u16* d_out, co
       rc = lr_launch_rope_bwd(dqkv, n_tok, (nh + 2 * nkv) * hd, (nh + nkv) * hd, hd, tok_pos, rope_cs, st);
       if (rc) return rc;
     }
+  } else if (variant == 6) {   // one owner per element either way: `deterministic` changes nothing
+    if (rope_cs && !tok_pos) LR_FAIL(LR_EINVAL, "attention backward: rotary table without token positions");
+    return lr_launch_attention_bwd_hd64(qkv, d_out, lse, dsum, dqkv, cu, cu_host, B, n_tok, nh, nkv, hd, st, rope_cs);
   } else {
-    LR_FAIL(LR_EINVAL, "attention backward: unknown variant %d", variant);
+    LR_FAIL(LR_EINVAL, "attention backward: unknown variant %d (0 auto, 1 generic, 2 = head_dim-128 MFMA, 3 as 0, "
+            "6 = head_dim-64 MFMA; 4 and 5 have no backward)", variant);
   }
   return LR_OK;
 }

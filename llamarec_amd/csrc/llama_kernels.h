@@ -140,19 +140,21 @@ static inline int lr_check_segments(const int32_t* cu_host, int S, const char* w
 }
 
 // ---- varlen causal attention over packed qkv (RoPE applied) ----------------------------------------------------------------
-// The kernels (a requested variant 1 .. 5 asks for the kernel of the same number, 0 = auto):
+// The kernels (a requested variant 1 .. 5 asks for the kernel of the same number, 6 for HD64 with lse allowed, 0 = auto):
 //   GENERIC  any head_dim <= 256, scalar                                  (llama_attn.hip)
 //   MFMA128  head_dim 128, 128-row query tiles, reads a shared prefix     (llama_attn.hip)
 //   ROWS256  head_dim 128, 256-row query tiles over a device-built item list, shared prefix <= 64 (llama_attn256.hip)
 //   HD256    head_dim 256, no shared prefix, no lse                       (llama_attn_hd256.hip)
-//   HD64     head_dim 64, no shared prefix, no lse                        (llama_attn_hd64.hip)
+//   HD64     head_dim 64, no shared prefix, lse when asked for (variant 6) (llama_attn_hd64.hip, _lse.hip)
 enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 3, LR_ATTN_HD256 = 4, LR_ATTN_HD64 = 5 };
 
-// Which kernel a request runs on -- the one place that decides it, for the four routes
+// Which kernel a request runs on -- the one place that decides it, for the five routes
 //   prefill    run_body (api_llama.hip): lse never wanted, the handle's workspace always has room for an item list
 //   varlen     lr_attention_varlen: no lse, no workspace
 //   varlen_ws  lr_attention_varlen_ws: lse and workspace optional
-//   train      lr_attention_varlen_lse and the LoRA forward: lse wanted, no workspace
+//   train      lr_attention_varlen_lse: lse wanted, no workspace
+//   lora       the LoRA forward (api_llama_train.hip): lse wanted, no workspace; its backward follows the same choice
+//              (variant 0 at head_dim 64 -> lr_launch_attention_bwd variant 6)
 // prefix_len is 0 outside prefill. Prefill drops a shared prefix (runs every prompt whole) unless lr_attention_reads_prefix:
 // head_dim != 128 or variant 1 -- and with a single prompt. First matching row:
 //
@@ -163,8 +165,10 @@ enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 
 //                                                                   per CU are ahead of the 256-row kernel)
 //   0        256       0       no   yes      prefill      HD256
 //   0        64        0       no   yes      prefill      HD64     (faster than GENERIC on every shape of DESIGN 10)
+//   0        64        0       yes  no       lora         HD64     (with lse; the pair 6 / backward 6)
 //   0        any       0       any  any      any          GENERIC  (head_dim 256 and 64 too outside prefill: the entry points'
-//                                                                   auto is older than HD256 / HD64 and its results are kept)
+//                                                                   auto is older than HD256 / HD64 and its results are kept,
+//                                                                   lr_attention_varlen_lse / _bwd at head_dim 64 included)
 //   1        any       0       any  any      any          GENERIC
 //   2        any       any     any  any      any          MFMA128
 //   3        any       0       any  no       varlen, train  LR_EINVAL  (no item workspace exists on these routes)
@@ -179,14 +183,17 @@ enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 
 //   5        any       any     yes  any      any          LR_EINVAL  (HD64 writes no statistics)
 //   5        != 64     any     no   any      any          LR_EUNSUPPORTED
 //   5        64        0       no   any      any          HD64
+//   6        != 64     any     any  any      any          LR_EUNSUPPORTED
+//   6        64        0       any  any      any          HD64     (writes lse when wanted; without lse variant 5's bits; a
+//                                                                   shared prefix is dropped in prefill as for variant 5)
 //   other                                                 LR_EINVAL
 //
 // varlen_ws counts a variant-3 request as "item ws yes" whatever it was given: the item-list builder then reports a missing
 // or short workspace as LR_EWORKSPACE. lr_launch_attention still refuses what the resolved kernel cannot take: GENERIC above
 // head_dim 256 and MFMA128 off head_dim 128 (LR_EUNSUPPORTED; a one-layer pruned prefill launches neither, so these checks
-// cannot move up here), a shared prefix or lse on HD256 and HD64.
+// cannot move up here), a shared prefix or lse on HD256, a shared prefix on HD64.
 static inline bool lr_attention_reads_prefix(int variant, int hd) { return hd == 128 && variant != 1; }
-struct LrAttnRequest { int variant, hd, prefix_len = 0; bool want_lse = false, have_items_ws = false, prefill = false; };
+struct LrAttnRequest { int variant, hd, prefix_len = 0; bool want_lse = false, have_items_ws = false, prefill = false, lora = false; };
 int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel);
 
 // cu / cu_host = segment starts [S + 1] in packed rows; prefix_len = P > 0: segment 0 is the shared prefix (P rows) the
@@ -214,5 +221,6 @@ int lr_launch_attn256_items(const int32_t* cu, int S, int n_tok, int nh, int pre
 int lr_launch_attention256(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd256(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd64(const LrAttnArgs& a, hipStream_t st);
+int lr_launch_attention_hd64_lse(const LrAttnArgs& a, unsigned grid, int max_qblocks, int n_pairs, hipStream_t st);
 
 #endif

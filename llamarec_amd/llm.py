@@ -465,7 +465,9 @@ class LlamaRanker:
 
     def set_variants(self, gemm=0, attention=0):
         """Kernel selection (include/llamarec_mi355x.h): 0 = auto; gemm=5 = latency mode for the online
-        single-user path (split-K where a short prompt would leave most CUs idle)."""
+        single-user path (split-K where a short prompt would leave most CUs idle). attention: 1 generic, 2 / 3 head_dim 128,
+        4 head_dim 256, 5 head_dim 64 (scoring only: no lse), 6 = head_dim-64 MFMA attention for training (5's forward, writing
+        lse when a LoRA engine runs on this base, and the head_dim-64 MFMA backward; the LoRA step's auto at head_dim 64)."""
         check(lib().lr_llama_set_variants(self._h, gemm, attention), "lr_llama_set_variants")
         return self
 

@@ -11,7 +11,14 @@ beside the numbers.
   2. a random-weight Llama-3.2-1B prefill + verbalizer over a Beauty-sized token budget (prompts of 460 .. 1 125 tokens,
      packing.TOKEN_BUDGET rows): ms per step with attention auto (variant 5) and forced generic, and the kernel split from the
      library's LrProfScope records.
-Usage: python tools/bench_llama32.py [--reps 30] [--steps 5] [--layers 16] [--ab-lib qt4=path/to/lib.so]"""
+  3. --train (instead of 1 and 2): the training side, attention variant 6.
+     a. backward rows for the shapes of 1: variant 6 backward against variant 1 backward at head_dim 64 (same buffers), variant 2
+        backward at head_dim 128 with (nh / 2, nkv / 2), and the forward writing lse (variant 6) against variant 5. TF/s of the
+        backward as lr_launch_attention_bwd counts it (10 nh hd T (T + 1) / 2 per prompt), lr_launch_rowdot included.
+     b. a random-weight Llama-3.2-1B LoRA step (q_proj / v_proj, r = 8) over 16 prompts of 460 .. 1 125 tokens: fwd+bwd ms per
+        micro-batch with attention variant 1 and variant 6 ALTERNATING in one process on one engine (median, min .. max of
+        --steps >= 5), then one profiled pass per variant for the attention share (LrProfScope records).
+Usage: python tools/bench_llama32.py [--reps 30] [--steps 5] [--layers 16] [--ab-lib qt4=path/to/lib.so] [--train]"""
 from __future__ import annotations
 
 import argparse
@@ -144,6 +151,147 @@ def llama32_step(steps, layers, attention_variant):
                 kernels=split, attention_share=attn / step_ms), out.clone()
 
 
+def _timed(run, reps):
+    for _ in range(3):
+        run()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run()
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return float(np.median(times))
+
+
+def time_attention_train(nh, nkv, hd, T, B, reps, variants):
+    """{("fwd", v) / ("fwd_lse", v) / ("bwd", v): ms} on one set of buffers; the backward reads the out / lse of ITS forward."""
+    L = lib()
+    n = B * T
+    g = torch.Generator(device="cuda").manual_seed(T + nh)
+    qw = (nh + 2 * nkv) * hd
+    qkv = torch.randn(n, qw, generator=g, device="cuda").to(torch.bfloat16)
+    d_out = torch.randn(n, nh * hd, generator=g, device="cuda").to(torch.bfloat16)
+    out = torch.empty(n, nh * hd, dtype=torch.bfloat16, device="cuda")
+    lse = torch.empty(n, nh, dtype=torch.float32, device="cuda")
+    dqkv = torch.empty(n, qw, dtype=torch.bfloat16, device="cuda")
+    cu = np.arange(0, n + 1, T, dtype=np.int32)
+    cud = torch.from_numpy(cu).cuda()
+    sb = L.lr_attention_bwd_scratch_bytes(n, nh, nkv, hd)
+    scratch = torch.empty(sb, dtype=torch.uint8, device="cuda")
+    res, grads = {}, {}
+
+    def call(name, rc):
+        if rc:
+            raise RuntimeError(f"{name}: {rc} {L.lr_last_error()}")
+
+    for v in variants:
+        if v == 5:
+            res[("fwd", 5)] = _timed(lambda: call("fwd", L.lr_attention_varlen(
+                qkv.data_ptr(), out.data_ptr(), cud.data_ptr(), cu.ctypes.data, B, nh, nkv, hd, 5, stream_ptr())), reps)
+            continue
+        res[("fwd_lse", v)] = _timed(lambda: call("fwd_lse", L.lr_attention_varlen_lse(
+            qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), cud.data_ptr(), cu.ctypes.data, B, nh, nkv, hd, v, stream_ptr())), reps)
+        res[("bwd", v)] = _timed(lambda: call("bwd", L.lr_attention_varlen_bwd(
+            qkv.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), cud.data_ptr(), cu.ctypes.data, B,
+            nh, nkv, hd, v, scratch.data_ptr(), sb, stream_ptr())), reps)
+        grads[v] = dqkv.float().clone()
+    return res, grads
+
+
+def attention_train_table(reps):
+    rows = []
+    for nh, nkv in ((32, 8), (24, 8)):
+        for T in LENGTHS:
+            r64, g = time_attention_train(nh, nkv, 64, T, PROMPTS, reps, (5, 6, 1))
+            r128, _ = time_attention_train(nh // 2, nkv // 2, 128, T, PROMPTS, reps, (2,))
+            work = 10.0 * nh * 64 * PROMPTS * T * (T + 1) / 2
+            b6, b1, b2 = r64[("bwd", 6)], r64[("bwd", 1)], r128[("bwd", 2)]
+            diff = float((g[6] - g[1]).abs().max() / g[1].abs().max())
+            row = dict(nh=nh, nkv=nkv, T=T, B=PROMPTS, bwd_v6_ms=b6, bwd_v6_tflops=work / b6 / 1e9, bwd_generic_ms=b1,
+                       bwd_generic_tflops=work / b1 / 1e9, bwd_v2_hd128_ms=b2, bwd_v2_hd128_tflops=work / b2 / 1e9,
+                       bwd_v6_over_generic=b1 / b6, bwd_v6_over_v2=b2 / b6, fwd_v5_ms=r64[("fwd", 5)],
+                       fwd_lse_v6_ms=r64[("fwd_lse", 6)], fwd_lse_generic_ms=r64[("fwd_lse", 1)],
+                       max_rel_v6_minus_generic=diff)
+            rows.append(row)
+            print(f"attention bwd nh={nh:2d} nkv={nkv} {PROMPTS} x {T:4d}: v6 hd64 {b6:8.3f} ms {work / b6 / 1e9:6.1f} TF/s | generic hd64 "
+                  f"{b1:9.3f} ms {work / b1 / 1e9:6.2f} TF/s | v2 hd128 {b2:8.3f} ms {work / b2 / 1e9:6.1f} TF/s | v6/generic "
+                  f"{b1 / b6:6.1f}x v6/v2 {b2 / b6:4.2f} | fwd v5 {r64[('fwd', 5)]:7.3f} ms, fwd+lse v6 {r64[('fwd_lse', 6)]:7.3f} ms, "
+                  f"fwd+lse generic {r64[('fwd_lse', 1)]:8.3f} ms | max |v6 - generic| / max {diff:.4f}", flush=True)
+    return rows
+
+
+def llama32_lora_step(steps, layers):
+    from llamarec_amd.llm import LLAMA32_1B, LlamaRanker
+    from llamarec_amd.rank_train import LoraTrainEngine
+
+    cfg = dict(LLAMA32_1B, num_hidden_layers=layers)
+    ranker = LlamaRanker.random_init(cfg, seed=1)
+    eng = LoraTrainEngine(ranker, dropout=0.05)
+    init = eng.peft_init(3)
+    for k in init:                    # non-zero B so that every kernel of the backward sees real numbers
+        if k.endswith("lora_B"):
+            init[k] = torch.randn(init[k].shape) * 0.01
+    eng.load(init)
+    rng = np.random.default_rng(0)
+    lens = rng.integers(460, 1126, size=PROMPTS)
+    seqs = [np.concatenate([[1], rng.integers(3, cfg["vocab_size"], size=n - 2), [2]]).astype(np.int32) for n in lens]
+    labels = []
+    for s in seqs:
+        l = s.copy()
+        l[:-2] = -100
+        labels.append(l)
+    variants = (1, 6)
+    losses = {}
+    for v in variants:                # warm-up of both, sizes the workspace
+        ranker.set_variants(0, v)
+        losses[v] = float(eng.loss_and_grads(seqs, labels))
+    torch.cuda.synchronize()
+    times = {v: [] for v in variants}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(max(steps, 5)):
+        for v in variants:
+            ranker.set_variants(0, v)
+            e0.record()
+            eng.loss_and_grads(seqs, labels)
+            e1.record()
+            torch.cuda.synchronize()
+            times[v].append(e0.elapsed_time(e1))
+    L = lib()
+    res = dict(prompts=PROMPTS, tokens=int(lens.sum()), layers=layers, min_len=int(lens.min()), max_len=int(lens.max()))
+    for v in variants:                # one profiled pass per variant: the kernel split
+        ranker.set_variants(0, v)
+        check(L.lr_profile_start(3 * (layers * 64 + 64)), "lr_profile_start")
+        e0.record()
+        for _ in range(3):
+            eng.loss_and_grads(seqs, labels)
+        e1.record()
+        torch.cuda.synchronize()
+        check(L.lr_profile_stop(), "lr_profile_stop")
+        prof_ms = e0.elapsed_time(e1) / 3
+        split = {}
+        for kind, name in KINDS.items():
+            ms, work, n = C.c_double(), C.c_double(), C.c_int64()
+            L.lr_profile_collect(kind, C.byref(ms), C.byref(work), C.byref(n))
+            if n.value:
+                split[name] = dict(ms_per_step=ms.value / 3, tflops=work.value / max(ms.value, 1e-9) / 1e9, launches_per_step=n.value / 3)
+        attn = sum(x["ms_per_step"] for k, x in split.items() if k.startswith("attention"))
+        gemm = sum(x["ms_per_step"] for k, x in split.items() if k.startswith("gemm"))
+        t = times[v]
+        res[f"variant_{v}"] = dict(fwd_bwd_ms_median=float(np.median(t)), fwd_bwd_ms_min=min(t), fwd_bwd_ms_max=max(t), steps=len(t),
+                                   loss=losses[v], profiled_step_ms=prof_ms, kernels=split, attention_ms=attn, gemm_ms=gemm,
+                                   attention_share=attn / prof_ms, gemm_share=gemm / prof_ms)
+        print(f"llama-3.2-1b ({layers} layers, random weights) LoRA fwd+bwd, attention variant {v}: {PROMPTS} prompts of "
+              f"{lens.min()} .. {lens.max()}, {lens.sum()} tokens: median {np.median(t):.2f} ms per micro-batch (min {min(t):.2f}, max "
+              f"{max(t):.2f}, {len(t)} alternating steps); profiled pass {prof_ms:.2f} ms: attention {attn:.2f} ms "
+              f"({100 * attn / prof_ms:.1f} %), GEMMs {gemm:.2f} ms ({100 * gemm / prof_ms:.1f} %), loss {losses[v]:.4f}", flush=True)
+        for name, x in split.items():
+            print(f"  {name:18s} {x['ms_per_step']:8.2f} ms/step {x['tflops']:7.1f} TF/s {x['launches_per_step']:6.1f} launches", flush=True)
+    return res
+
+
 def clock_mhz():
     try:
         return int(torch.cuda.clock_rate(0))
@@ -157,6 +305,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--layers", type=int, default=16)
     ap.add_argument("--ab-lib", action="append", default=[], metavar="NAME=PATH")
+    ap.add_argument("--train", action="store_true", help="the training side instead: backward rows and the LoRA step")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     _lib.lib()
@@ -164,6 +313,12 @@ def main():
     box = dict(device=p.name, compute_units=p.multi_processor_count, clock_mhz=clock_mhz(),
                method=f"HIP events, one process, median of {args.reps}")
     print(f"box: {box['device']}, {box['compute_units']} CUs, clock {box['clock_mhz'] or 'not readable here'} MHz at start; {box['method']}", flush=True)
+    if args.train:
+        res = dict(box=box, attention_bwd=attention_train_table(args.reps))
+        res["llama32_1b_lora_step"] = llama32_lora_step(args.steps, args.layers)
+        box["clock_mhz_end"] = clock_mhz()
+        print(json.dumps(res))
+        return
     arms = {}
     for spec in args.ab_lib:
         name, path = spec.split("=", 1)
