@@ -238,10 +238,11 @@ int lr_llama_create_ex(const LrLlamaConfig* cfg, const LrLlamaArch* arch, const 
  * attention 3 = head_dim-128 flash attention on 256-row tiles, one wave per SIMD, persistent workgroups (shared prefix of at
  * most 64 tokens, falls back to 2 otherwise; ahead of 2 on long prompts -- thousands of tokens -- and behind it on this
  * path's 460 .. 1 125-token prompts, so auto keeps 2),
- * attention 4 = head_dim-256 MFMA flash attention (Gemma; 8 waves x 16 query rows per workgroup, K/V by LDS-DMA, no
- * shared prefix); auto takes it in the prefill for head_dim 256, and any other head_dim is LR_EUNSUPPORTED,
+ * attention 4 = head_dim-256 MFMA flash attention (Gemma; 8 waves x 16 query rows per workgroup, K/V by LDS-DMA; a
+ * shared prefix and the pruned last layer's one-query-row mode run on its kernels of llama_attn_hd256_prefix.hip, with the
+ * same bits); auto takes it in the prefill for head_dim 256, and any other head_dim is LR_EUNSUPPORTED,
  * attention 5 = head_dim-64 MFMA flash attention (Llama-3.2-1B; 4 waves x 32 query rows per workgroup, K/V by LDS-DMA, no
- * shared prefix, no lse); auto takes it in the prefill for head_dim 64, and any other head_dim is LR_EUNSUPPORTED,
+ * lse; a shared prefix and the one-query-row mode as for 4, llama_attn_hd64_prefix.hip); auto takes it in the prefill for head_dim 64, and any other head_dim is LR_EUNSUPPORTED,
  * attention 6 = head_dim-64 MFMA flash attention for training: variant 5's forward, optionally writing lse (without lse
  * the same bits as 5), and the head_dim-64 MFMA backward (two passes, one owner per gradient element, no atomics); the
  * LoRA step's auto takes the pair at head_dim 64, and any other head_dim is LR_EUNSUPPORTED. A LoRA engine on a base set to
@@ -319,7 +320,8 @@ int lr_llama_prefill_verbalize(lr_llama_t* h, const int32_t* packed_ids, const i
  * (lr_common_prefix_len computes the largest such value from host copies). The second precondition is VERIFIED on the
  * device: if any prompt's first prefix_len ids differ from prompt 0's, every score of the call is NaN (prefix rows, keys
  * and values come from prompt 0, so a stale prefix_len would otherwise score the other prompts silently wrong).
- * prefix_len = 0, B = 1, head_dim != 128 or the generic attention variant run the plain path. */
+ * prefix_len = 0, B = 1, a head_dim other than 64 / 128 / 256, the generic attention variant or a variant that does not
+ * belong to the head_dim run the plain path. */
 int lr_llama_prefill_verbalize_prefix(lr_llama_t* h, const int32_t* packed_ids, const int32_t* cu_seqlens,
                                       const int32_t* cu_seqlens_host, int32_t B, int32_t prefix_len,
                                       const int32_t* label_token_ids, int32_t C, float* out_scores,
@@ -417,6 +419,22 @@ size_t lr_attention_workspace_bytes(int32_t total_tokens, int32_t B, int32_t num
 int lr_attention_varlen_ws(const uint16_t* qkv, uint16_t* out, float* lse, const int32_t* cu_seqlens,
                            const int32_t* cu_seqlens_host, int32_t B, int32_t num_heads, int32_t num_kv_heads,
                            int32_t head_dim, int32_t variant, void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* The two modes of the prefill's MFMA attention kernels, stand-alone (exposed for parity tests). Both check on the host,
+ * before anything is launched (outputs untouched): seg_starts_host[0] == 0 and strictly increasing, segment 0 exactly
+ * prefix_len rows when prefix_len > 0 (and S >= 2), num_heads % num_kv_heads == 0 -- LR_EINVAL -- and the (variant, head_dim)
+ * pair: 0 / 2 at head_dim 128, 0 / 5 at 64, 0 / 4 at 256, anything else LR_EUNSUPPORTED.
+ * qkv rows laid out as the prefill lays them out: segment 0 = the prefix_len shared rows, segments 1.. continue it (their
+ * keys and values of positions < prefix_len are read from segment 0). out rows of every segment are written, each with the
+ * bits lr_attention_varlen (same variant; at 64 / 256 variant 5 / 4) writes for that row of the whole prompt. */
+int lr_attention_varlen_prefix(const uint16_t* qkv, uint16_t* out, const int32_t* seg_starts, const int32_t* seg_starts_host,
+                               int32_t S, int32_t prefix_len, int32_t num_heads, int32_t num_kv_heads, int32_t head_dim,
+                               int32_t variant, void* hip_stream);
+/* One query row per prompt: kv [n][2*nkv*hd] (K | V of every row), q_last / out_last [prompts][nh*hd] (the query at each
+ * prompt's last position); prefix_len as above (0: S prompts, no prefix segment; > 0: S - 1 prompts). */
+int lr_attention_last_rows(const uint16_t* kv, const uint16_t* q_last, uint16_t* out_last, const int32_t* seg_starts,
+                           const int32_t* seg_starts_host, int32_t S, int32_t prefix_len, int32_t num_heads,
+                           int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optional in-library kernel timing (HIP events on the caller's stream). Not part of the

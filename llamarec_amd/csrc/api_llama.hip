@@ -264,11 +264,11 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
     // weight already inside the projection matrix and rstd applied to the accumulator rows in the GEMM epilogue
     const bool folded = h->wqkv_folded != nullptr;
     const bool last_pruned = l == c.num_layers - 1 && h->prune_last;
-    // Pruned last layer, head_dim 128: only each prompt's last token is consumed after it (model/llm.py:131), so Q is
+    // Pruned last layer, on a kernel with a last-row mode (head_dim 64, 128, 256): only each prompt's last token is consumed after it (model/llm.py:131), so Q is
     // needed for B rows only -- K and V for all of them. The projection runs on the K | V rows of wqkv (2/3 of the
     // product) for every row and on its Q rows for the B last rows; the attention kernel then evaluates ONE query row
     // per (prompt, head) over the prompt's keys instead of every tile.
-    const bool last_q_only = last_pruned && !folded && hd == 128 && attn_mfma && gv != 1;
+    const bool last_q_only = last_pruned && !folded && lr_attention_has_last_row_mode(attn_kernel, hd) && gv != 1;
     if (folded && !EXP_SKIP_SWEEP) LR_RUN(lr_launch_rms_rstd(ws.x, ws.rstd, n, d, c.rms_eps, st));
     if (!folded && !input_normed) LR_RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st, ns));
     const int q_w = nh * hd, kv_w = 2 * nkv * hd;
@@ -493,6 +493,44 @@ extern "C" int lr_attention_varlen(const uint16_t* qkv, uint16_t* out, const int
   return lr_launch_attention({.qkv = qkv, .out = out, .cu = cu_seqlens, .cu_host = cu_seqlens_host, .S = B,
                               .n_tok = cu_seqlens_host[B], .nh = num_heads, .nkv = num_kv_heads, .hd = head_dim},
                              kernel, (hipStream_t)hip_stream);
+}
+
+// Host checks of the two shared-prefix entry points, before any launch: segments, segment 0 = the prefix, head shapes and
+// the (variant, head_dim) pairs whose kernel has the mode.
+static int check_prefix_request(const char* who, const int32_t* cu_host, int S, int prefix_len, int nh, int nkv, int hd,
+                                int variant) {
+  if (!cu_host || S < 1 || prefix_len < 0 || nh < 1 || nkv < 1) LR_FAIL(LR_EINVAL, "%s: bad argument", who);
+  if (int rc = lr_check_segments(cu_host, S, who)) return rc;
+  if (nh % nkv != 0) LR_FAIL(LR_EINVAL, "%s: num_heads %d not a multiple of num_kv_heads %d", who, nh, nkv);
+  if (prefix_len > 0 && (S < 2 || cu_host[1] != prefix_len))
+    LR_FAIL(LR_EINVAL, "%s: segment 0 has %d rows, the shared prefix %d (and a prompt must follow it)", who, cu_host[1], prefix_len);
+  const bool ok = (hd == 128 && (variant == 0 || variant == 2)) || (hd == 64 && (variant == 0 || variant == 5)) ||
+                  (hd == 256 && (variant == 0 || variant == 4));
+  if (!ok) LR_FAIL(LR_EUNSUPPORTED, "%s: variant %d at head_dim %d (0 / 2 at 128, 0 / 5 at 64, 0 / 4 at 256)", who, variant, hd);
+  return LR_OK;
+}
+
+extern "C" int lr_attention_varlen_prefix(const uint16_t* qkv, uint16_t* out, const int32_t* seg_starts,
+                                          const int32_t* seg_starts_host, int32_t S, int32_t prefix_len, int32_t num_heads,
+                                          int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* hip_stream) {
+  if (!qkv || !out || !seg_starts) LR_FAIL(LR_EINVAL, "lr_attention_varlen_prefix: null pointer");
+  LR_RUN(check_prefix_request("lr_attention_varlen_prefix", seg_starts_host, S, prefix_len, num_heads, num_kv_heads, head_dim,
+                              variant));
+  LrAttnKernel kernel;
+  LR_RUN(lr_resolve_attention({.variant = variant, .hd = head_dim, .prefix_len = prefix_len, .prefill = true}, &kernel));
+  return lr_launch_attention({.qkv = qkv, .out = out, .cu = seg_starts, .cu_host = seg_starts_host, .S = S,
+                              .n_tok = seg_starts_host[S], .nh = num_heads, .nkv = num_kv_heads, .hd = head_dim,
+                              .prefix_len = prefix_len}, kernel, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_attention_last_rows(const uint16_t* kv, const uint16_t* q_last, uint16_t* out_last, const int32_t* seg_starts,
+                                      const int32_t* seg_starts_host, int32_t S, int32_t prefix_len, int32_t num_heads,
+                                      int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* hip_stream) {
+  if (!kv || !q_last || !out_last || !seg_starts) LR_FAIL(LR_EINVAL, "lr_attention_last_rows: null pointer");
+  LR_RUN(check_prefix_request("lr_attention_last_rows", seg_starts_host, S, prefix_len, num_heads, num_kv_heads, head_dim,
+                              variant));
+  return lr_launch_attention_last(kv, q_last, out_last, seg_starts, seg_starts_host, S, seg_starts_host[S], num_heads,
+                                  num_kv_heads, head_dim, (hipStream_t)hip_stream, prefix_len);
 }
 
 extern "C" size_t lr_attention_workspace_bytes(int32_t total_tokens, int32_t B, int32_t num_heads) {

@@ -543,10 +543,17 @@ int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
   switch (r.variant) {
     case 0:
       if (hd == 128) *kernel = (r.have_items_ws && !r.prefill) ? LR_ATTN_ROWS256 : LR_ATTN_MFMA128;
-      else if (hd == 256 && r.prefill) *kernel = LR_ATTN_HD256;
-      else *kernel = (hd == 64 && (r.prefill || r.lora)) ? LR_ATTN_HD64 : LR_ATTN_GENERIC;
+      else if (hd == 256 && (r.prefill || r.prefix_len > 0)) *kernel = LR_ATTN_HD256;
+      else *kernel = (hd == 64 && (r.prefill || r.lora || r.prefix_len > 0)) ? LR_ATTN_HD64 : LR_ATTN_GENERIC;
+      if (r.prefix_len > 0 && *kernel == LR_ATTN_GENERIC)
+        LR_FAIL(LR_EUNSUPPORTED, "attention: no kernel reads a shared prefix at head_dim %d", hd);
+      if (r.prefix_len > 0 && r.want_lse && hd != 128)
+        LR_FAIL(LR_EINVAL, "attention: no lse with a shared prefix at head_dim %d", hd);
       return LR_OK;
-    case 1: *kernel = LR_ATTN_GENERIC; return LR_OK;
+    case 1:
+      if (r.prefix_len > 0) LR_FAIL(LR_EUNSUPPORTED, "attention variant 1 (generic) reads no shared prefix");
+      *kernel = LR_ATTN_GENERIC;
+      return LR_OK;
     case 2: *kernel = LR_ATTN_MFMA128; return LR_OK;
     case 3:
       if (!r.have_items_ws)
@@ -567,6 +574,7 @@ int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
       return LR_OK;
     case 6:   // the training pair: variant 5's kernel, with lse when wanted; its backward is llama_attn_bwd_hd64.hip
       if (hd != 64) LR_FAIL(LR_EUNSUPPORTED, "attention variant 6 needs head_dim 64 (got %d)", hd);
+      if (r.want_lse && r.prefix_len > 0) LR_FAIL(LR_EINVAL, "attention variant 6 writes no lse with a shared prefix");
       *kernel = LR_ATTN_HD64;
       return LR_OK;
   }
@@ -581,12 +589,12 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
   if (kernel == LR_ATTN_ROWS256) return lr_launch_attention256(a, st);
   if (nh % nkv != 0) LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
   if (kernel == LR_ATTN_HD256) {
-    if (prefix_len != 0 || a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-256 MFMA kernel takes no shared prefix, writes no lse");
-    return lr_launch_attention_hd256(a, st);
+    if (prefix_len < 0 || a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-256 MFMA kernel writes no lse (prefix %d)", prefix_len);
+    return prefix_len > 0 ? lr_launch_attention_hd256_prefix(a, st) : lr_launch_attention_hd256(a, st);
   }
   if (kernel == LR_ATTN_HD64) {
-    if (prefix_len != 0) LR_FAIL(LR_EINVAL, "attention: the head_dim-64 MFMA kernel takes no shared prefix");
-    return lr_launch_attention_hd64(a, st);
+    if (prefix_len < 0) LR_FAIL(LR_EINVAL, "attention: shared prefix of %d tokens", prefix_len);
+    return prefix_len > 0 ? lr_launch_attention_hd64_prefix(a, st) : lr_launch_attention_hd64(a, st);
   }
   if (prefix_len < 0 || (prefix_len > 0 && (kernel != LR_ATTN_MFMA128 || cu_host[1] - cu_host[0] != prefix_len)))
     LR_FAIL(LR_EINVAL, "attention: shared prefix of %d tokens needs the head_dim-128 MFMA kernel and segment 0 = the prefix",
@@ -639,12 +647,15 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
   return LR_OK;
 }
 
-// The pruned last layer: kv = [n_tok][2 * nkv * hd] (K | V of every row), q_last = [prompts][nh * hd] rotated query rows
+// The pruned last layer (head_dim 128 here, 64 and 256 in the _prefix files of their kernels): kv = [n_tok][2 * nkv * hd] (K | V of every row), q_last = [prompts][nh * hd] rotated query rows
 // of each prompt's last token, out_last = [prompts][nh * hd]. cu / cu_host / prefix_len as lr_launch_attention.
 int lr_launch_attention_last(const u16* kv, const u16* q_last, u16* out_last, const int32_t* cu, const int32_t* cu_host,
                              int S, int n_tok, int nh, int nkv, int hd, hipStream_t st, int prefix_len) {
   if (n_tok <= 0 || S <= 0) return LR_OK;
-  if (hd != 128 || nh % nkv != 0) LR_FAIL(LR_EUNSUPPORTED, "attention (last rows): head_dim 128 and nh %% nkv == 0 only");
+  if ((hd != 128 && hd != 64 && hd != 256) || nkv < 1 || nh % nkv != 0)
+    LR_FAIL(LR_EUNSUPPORTED, "attention (last rows): head_dim 64, 128 or 256 and nh %% nkv == 0 only");
+  if (hd == 64) return lr_launch_attention_hd64_last(kv, q_last, out_last, cu, cu_host, S, n_tok, nh, nkv, prefix_len, st);
+  if (hd == 256) return lr_launch_attention_hd256_last(kv, q_last, out_last, cu, cu_host, S, n_tok, nh, nkv, prefix_len, st);
   if (prefix_len < 0 || (prefix_len > 0 && cu_host[1] - cu_host[0] != prefix_len))
     LR_FAIL(LR_EINVAL, "attention (last rows): segment 0 must be the %d-token shared prefix", prefix_len);
   double work = 0;

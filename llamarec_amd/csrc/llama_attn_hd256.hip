@@ -17,7 +17,8 @@
 // when a score exceeds it by more than 2^FA4_DEFER), bf16 P into both the numerator and the row sum (an MFMA against a row
 // of ones), one bf16 rounding of O / l. A query row's bits depend only on its own prompt: tiles and key blocks are aligned
 // to positions inside the prompt, and the rescale decision is per row.
-// Forward only, no shared prefix, no log-sum-exp output (the LoRA path keeps its own kernels).
+// Forward only, no log-sum-exp output (the LoRA path keeps its own kernels). This kernel takes no shared prefix: with one, and
+// for the pruned last layer's one-query-row mode, lr_launch_attention runs the kernels of llama_attn_hd256_prefix.hip (same bits).
 #include "llama_kernels.h"
 #include "lr_attn_util.h"
 #include "lr_profile.h"

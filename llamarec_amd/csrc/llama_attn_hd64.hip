@@ -15,7 +15,8 @@
 // when a score exceeds it by more than 2^FA5_DEFER), bf16 P into both the numerator and the row sum (an MFMA against a row
 // of ones), one bf16 rounding of O / l. A query row's bits depend only on its own prompt: tiles and key blocks are aligned
 // to positions inside the prompt, and the rescale decision is per row.
-// No shared prefix. The LSE instantiation (attention variant 6, the training forward) also writes the natural-log log-sum-exp of
+// No shared prefix here: with one, and for the pruned last layer's one-query-row mode, the kernels of
+// llama_attn_hd64_prefix.hip run (same bits). The LSE instantiation (attention variant 6, the training forward) also writes the natural-log log-sum-exp of
 // the scaled scores per (token, head) from the deferred reference and the row sum, as variant 2 does; `out` has the same bits
 // in both instantiations. The kernel's text is llama_attn_hd64_body.h; this file instantiates variant 5 and holds the launcher,
 // llama_attn_hd64_lse.hip instantiates the lse-writing kernel. The backward is llama_attn_bwd_hd64.hip.

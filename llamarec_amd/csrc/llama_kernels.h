@@ -139,13 +139,27 @@ static inline int lr_check_segments(const int32_t* cu_host, int S, const char* w
   return LR_OK;
 }
 
+// Shared checks of the shared-prefix and last-row launchers at head_dim 64 / 256: segment 0 = the prefix with a prompt behind
+// it, and the packed rows fit what one buffer descriptor addresses with 64 rows to spare (the per-lane offsets of the block
+// that straddles the prefix's end reach up to 63 rows past the prompt's end and must not wrap back into range).
+static inline int lr_check_prefix_layout(const char* who, const int32_t* cu_host, int S, int n_tok, int row_elems,
+                                         int prefix_len) {
+  if (prefix_len < 0 || (prefix_len > 0 && (S < 2 || cu_host[1] - cu_host[0] != prefix_len)))
+    LR_FAIL(LR_EINVAL, "%s: segment 0 must be the %d-token shared prefix and a prompt must follow it", who, prefix_len);
+  if (((long long)n_tok + 64) * row_elems * 2 > 0xffffffffLL)
+    LR_FAIL(LR_EUNSUPPORTED, "%s: %d packed rows exceed the 4 GiB a buffer descriptor addresses", who, n_tok);
+  return LR_OK;
+}
+
 // ---- varlen causal attention over packed qkv (RoPE applied) ----------------------------------------------------------------
 // The kernels (a requested variant 1 .. 5 asks for the kernel of the same number, 6 for HD64 with lse allowed, 0 = auto):
 //   GENERIC  any head_dim <= 256, scalar                                  (llama_attn.hip)
 //   MFMA128  head_dim 128, 128-row query tiles, reads a shared prefix     (llama_attn.hip)
 //   ROWS256  head_dim 128, 256-row query tiles over a device-built item list, shared prefix <= 64 (llama_attn256.hip)
-//   HD256    head_dim 256, no shared prefix, no lse                       (llama_attn_hd256.hip)
-//   HD64     head_dim 64, no shared prefix, lse when asked for (variant 6) (llama_attn_hd64.hip, _lse.hip)
+//   HD256    head_dim 256, no lse; with a shared prefix the kernel of llama_attn_hd256_prefix.hip (llama_attn_hd256.hip)
+//   HD64     head_dim 64, lse when asked for (variant 6) and no prefix; with a shared prefix the kernel of
+//            llama_attn_hd64_prefix.hip                                    (llama_attn_hd64.hip, _lse.hip)
+// MFMA128, HD256 and HD64 also have a one-query-row mode (lr_launch_attention_last, the pruned last layer).
 enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 3, LR_ATTN_HD256 = 4, LR_ATTN_HD64 = 5 };
 
 // Which kernel a request runs on -- the one place that decides it, for the five routes
@@ -155,20 +169,25 @@ enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 
 //   train      lr_attention_varlen_lse: lse wanted, no workspace
 //   lora       the LoRA forward (api_llama_train.hip): lse wanted, no workspace; its backward follows the same choice
 //              (variant 0 at head_dim 64 -> lr_launch_attention_bwd variant 6)
-// prefix_len is 0 outside prefill. Prefill drops a shared prefix (runs every prompt whole) unless lr_attention_reads_prefix:
-// head_dim != 128 or variant 1 -- and with a single prompt. First matching row:
+// prefix_len is 0 outside prefill and lr_attention_varlen_prefix (which resolves as a prefill request without item workspace).
+// Prefill drops a shared prefix (runs every prompt whole) unless lr_attention_reads_prefix: variant 1, a head_dim other than
+// 64 / 128 / 256, variant 2 / 3 off head_dim 128 and the like -- and with a single prompt. First matching row:
 //
 //   variant  head_dim  prefix  lse  item ws  route        result
 //   0        128       0       any  yes      varlen_ws    ROWS256
 //   0        128       any     any  any      any          MFMA128  (prefill has the item workspace and still takes this one: on
 //                                                                   its prompts of 460 .. 1 125 tokens two 128-row workgroups
 //                                                                   per CU are ahead of the 256-row kernel)
-//   0        256       0       no   yes      prefill      HD256
-//   0        64        0       no   yes      prefill      HD64     (faster than GENERIC on every shape of DESIGN 10)
+//   0        256       any     no   any      prefill      HD256    (prefix > 0: its shared-prefix kernel)
+//   0        64        any     no   any      prefill      HD64     (faster than GENERIC on every shape of DESIGN 10; prefix > 0:
+//                                                                   its shared-prefix kernel)
+//   0        64, 256   > 0     yes  any      any          LR_EINVAL  (no lse with a shared prefix off head_dim 128)
 //   0        64        0       yes  no       lora         HD64     (with lse; the pair 6 / backward 6)
+//   0        other     > 0     any  any      any          LR_EUNSUPPORTED  (GENERIC reads no shared prefix)
 //   0        any       0       any  any      any          GENERIC  (head_dim 256 and 64 too outside prefill: the entry points'
 //                                                                   auto is older than HD256 / HD64 and its results are kept,
 //                                                                   lr_attention_varlen_lse / _bwd at head_dim 64 included)
+//   1        any       > 0     any  any      any          LR_EUNSUPPORTED
 //   1        any       0       any  any      any          GENERIC
 //   2        any       any     any  any      any          MFMA128
 //   3        any       0       any  no       varlen, train  LR_EINVAL  (no item workspace exists on these routes)
@@ -177,22 +196,33 @@ enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 
 //   3        128       > 64    no   yes      prefill      MFMA128  (only a 256-row tile's block 0 may hold shared-prefix keys)
 //   4        any       any     yes  any      any          LR_EINVAL  (HD256 writes no statistics)
 //   4        != 256    any     no   yes      prefill      LR_EUNSUPPORTED
+//   4        256       > 0     no   any      any          HD256    (its shared-prefix kernel)
 //   4        any       0       no   any      any          HD256    (outside prefill a head_dim other than 256 is refused by
 //                                                                   the launcher, LR_EUNSUPPORTED, behind its
 //                                                                   num_heads % num_kv_heads check, LR_EINVAL, as before)
 //   5        any       any     yes  any      any          LR_EINVAL  (HD64 writes no statistics)
 //   5        != 64     any     no   any      any          LR_EUNSUPPORTED
-//   5        64        0       no   any      any          HD64
+//   5        64        any     no   any      any          HD64     (prefix > 0: its shared-prefix kernel)
 //   6        != 64     any     any  any      any          LR_EUNSUPPORTED
-//   6        64        0       any  any      any          HD64     (writes lse when wanted; without lse variant 5's bits; a
-//                                                                   shared prefix is dropped in prefill as for variant 5)
+//   6        64        > 0     yes  any      any          LR_EINVAL  (no lse with a shared prefix)
+//   6        64        any     any  any      any          HD64     (writes lse when wanted; without lse variant 5's bits, with
+//                                                                   a shared prefix too)
 //   other                                                 LR_EINVAL
 //
 // varlen_ws counts a variant-3 request as "item ws yes" whatever it was given: the item-list builder then reports a missing
 // or short workspace as LR_EWORKSPACE. lr_launch_attention still refuses what the resolved kernel cannot take: GENERIC above
 // head_dim 256 and MFMA128 off head_dim 128 (LR_EUNSUPPORTED; a one-layer pruned prefill launches neither, so these checks
-// cannot move up here), a shared prefix or lse on HD256, a shared prefix on HD64.
-static inline bool lr_attention_reads_prefix(int variant, int hd) { return hd == 128 && variant != 1; }
+// cannot move up here), lse on HD256, lse with a shared prefix on HD64, a segment 0 that is not the prefix.
+static inline bool lr_attention_reads_prefix(int variant, int hd) {
+  if (hd == 128) return variant != 1;
+  if (hd == 64) return variant == 0 || variant == 5 || variant == 6;
+  if (hd == 256) return variant == 0 || variant == 4;
+  return false;
+}
+// The resolved kernel has a one-query-row (LASTQ) mode behind lr_launch_attention_last
+static inline bool lr_attention_has_last_row_mode(int kernel, int hd) {
+  return (hd == 128 && kernel != 1 /* LR_ATTN_GENERIC */) || kernel == 4 /* LR_ATTN_HD256 */ || kernel == 5 /* LR_ATTN_HD64 */;
+}
 struct LrAttnRequest { int variant, hd, prefix_len = 0; bool want_lse = false, have_items_ws = false, prefill = false, lora = false; };
 int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel);
 
@@ -208,7 +238,7 @@ struct LrAttnArgs {
   void* items_ws = nullptr;
 };
 int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st);
-// The pruned last layer (MFMA128's body): one query row per (prompt, head) over the prompt's keys
+// The pruned last layer (MFMA128's, HD64's or HD256's last-row kernel by head_dim): one query row per (prompt, head) over the prompt's keys
 int lr_launch_attention_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
                              const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int hd,
                              hipStream_t st, int prefix_len);
@@ -222,5 +252,14 @@ int lr_launch_attention256(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd256(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd64(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd64_lse(const LrAttnArgs& a, unsigned grid, int max_qblocks, int n_pairs, hipStream_t st);
+// HD64 / HD256 with a.prefix_len > 0 (llama_attn_hd64_prefix.hip, llama_attn_hd256_prefix.hip) and their last-row modes
+int lr_launch_attention_hd64_prefix(const LrAttnArgs& a, hipStream_t st);
+int lr_launch_attention_hd256_prefix(const LrAttnArgs& a, hipStream_t st);
+int lr_launch_attention_hd64_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
+                                  const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int prefix_len,
+                                  hipStream_t st);
+int lr_launch_attention_hd256_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
+                                   const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int prefix_len,
+                                   hipStream_t st);
 
 #endif

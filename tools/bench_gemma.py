@@ -4,7 +4,11 @@
      lr_launch_attention counts it (4 nh hd T (T + 1) / 2 per prompt), same process, median of the timed repeats.
   2. a random-weight Gemma-2B prefill + verbalizer over a Beauty-sized token budget (prompts of 460 .. 1 125 tokens,
      packing.TOKEN_BUDGET rows): ms per step and its kernel split from the library's LrProfScope records.
-Usage: python tools/bench_gemma.py [--reps 20] [--steps 5] [--layers 18]"""
+  3. --prefix-ab (instead of 1 and 2): the shared-prefix and last-row arms of tools/prefix_ab.py at head_dim 256 -- the prefix
+     kernel against variant 4 on the same whole prompts, the last-row launch against full attention + gather, and the Gemma-2B
+     step with the 36-token prefix shared against prefix_len = 0 and against every --ab-lib NAME=PATH build (the parent commit's
+     library: its step on the same prompts), arms alternating, median and min .. max of --reps.
+Usage: python tools/bench_gemma.py [--reps 20] [--steps 5] [--layers 18] [--prefix-ab] [--ab-lib parent=path/to/lib.so]"""
 from __future__ import annotations
 
 import argparse
@@ -120,9 +124,20 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--layers", type=int, default=18)
+    ap.add_argument("--prefix-ab", action="store_true", help="the shared-prefix / last-row arms instead (tools/prefix_ab.py)")
+    ap.add_argument("--ab-lib", action="append", default=[], metavar="NAME=PATH")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     _lib.lib()
+    if args.prefix_ab:
+        from llamarec_amd.llm import GEMMA_2B
+        from tools import prefix_ab
+
+        builds = {spec.split("=", 1)[0]: prefix_ab.load_build(spec.split("=", 1)[1]) for spec in args.ab_lib}
+        res = dict(attention_prefix=prefix_ab.attention_prefix_table(256, 4, ((8, 1), (16, 16)), args.reps))
+        res["gemma2b_prefix_ab"] = prefix_ab.step_ab(dict(GEMMA_2B, num_hidden_layers=args.layers), 2, args.reps, builds, "gemma-2b")
+        print(json.dumps(res))
+        return
     res = dict(attention=attention_table(args.reps), gemma2b=gemma2b_step(args.steps, args.layers))
     print(json.dumps(res))
 

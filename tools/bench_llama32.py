@@ -18,7 +18,11 @@ beside the numbers.
      b. a random-weight Llama-3.2-1B LoRA step (q_proj / v_proj, r = 8) over 16 prompts of 460 .. 1 125 tokens: fwd+bwd ms per
         micro-batch with attention variant 1 and variant 6 ALTERNATING in one process on one engine (median, min .. max of
         --steps >= 5), then one profiled pass per variant for the attention share (LrProfScope records).
-Usage: python tools/bench_llama32.py [--reps 30] [--steps 5] [--layers 16] [--ab-lib qt4=path/to/lib.so] [--train]"""
+  4. --prefix-ab (instead of 1 and 2): the shared-prefix and last-row arms of tools/prefix_ab.py at head_dim 64 -- the prefix
+     kernel against variant 5 on the same whole prompts, the last-row launch against full attention + gather, and the
+     Llama-3.2-1B step with the 36-token prefix shared against prefix_len = 0 and against every --ab-lib build (the parent
+     commit's library: its step on the same prompts), arms alternating, median and min .. max of --reps.
+Usage: python tools/bench_llama32.py [--reps 30] [--steps 5] [--layers 16] [--ab-lib qt4=path/to/lib.so] [--train] [--prefix-ab]"""
 from __future__ import annotations
 
 import argparse
@@ -306,6 +310,7 @@ def main():
     ap.add_argument("--layers", type=int, default=16)
     ap.add_argument("--ab-lib", action="append", default=[], metavar="NAME=PATH")
     ap.add_argument("--train", action="store_true", help="the training side instead: backward rows and the LoRA step")
+    ap.add_argument("--prefix-ab", action="store_true", help="the shared-prefix / last-row arms instead (tools/prefix_ab.py)")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     _lib.lib()
@@ -316,6 +321,17 @@ def main():
     if args.train:
         res = dict(box=box, attention_bwd=attention_train_table(args.reps))
         res["llama32_1b_lora_step"] = llama32_lora_step(args.steps, args.layers)
+        box["clock_mhz_end"] = clock_mhz()
+        print(json.dumps(res))
+        return
+    if args.prefix_ab:
+        from llamarec_amd.llm import LLAMA32_1B
+        from tools import prefix_ab
+
+        builds = {spec.split("=", 1)[0]: prefix_ab.load_build(spec.split("=", 1)[1]) for spec in args.ab_lib}
+        res = dict(box=box, attention_prefix=prefix_ab.attention_prefix_table(64, 5, ((32, 8), (24, 8)), args.reps))
+        res["llama32_1b_prefix_ab"] = prefix_ab.step_ab(dict(LLAMA32_1B, num_hidden_layers=args.layers), 1, args.reps, builds,
+                                                        "llama-3.2-1b")
         box["clock_mhz_end"] = clock_mhz()
         print(json.dumps(res))
         return
