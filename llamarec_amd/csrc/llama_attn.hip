@@ -599,25 +599,17 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
   if (prefix_len < 0 || (prefix_len > 0 && (kernel != LR_ATTN_MFMA128 || cu_host[1] - cu_host[0] != prefix_len)))
     LR_FAIL(LR_EINVAL, "attention: shared prefix of %d tokens needs the head_dim-128 MFMA kernel and segment 0 = the prefix",
             prefix_len);
-  double work = 0;  // causal QK^T + PV flops of the rows each segment owns
-  int maxT = 0;
-  for (int b = 0; b < B; ++b) {
-    const double P = (prefix_len > 0 && b > 0) ? prefix_len : 0;
-    const double T = P + cu_host[b + 1] - cu_host[b];
-    work += 4.0 * nh * hd * (T * (T + 1) / 2 - P * (P + 1) / 2);
-    maxT = max(maxT, (int)T);
-  }
-  LrProfScope prof(kernel == LR_ATTN_MFMA128 ? LR_PROF_ATTN_MFMA : LR_PROF_ATTN_GENERIC, work, st);
+  const LrAttnPlan pl = lr_attn_plan(cu_host, B, prefix_len, nh, hd, FA_QROWS, nh);   // the generic kernel takes its work sum only
+  LrProfScope prof(kernel == LR_ATTN_MFMA128 ? LR_PROF_ATTN_MFMA : LR_PROF_ATTN_GENERIC, pl.work, st);
   if (kernel == LR_ATTN_MFMA128) {
     if (hd != 128) LR_FAIL(LR_EUNSUPPORTED, "attention variant 2 needs head_dim 128 (got %d)", hd);
-    const int mq = (maxT + FA_QROWS - 1) / FA_QROWS;
+    const int mq = pl.mq;
     if (mq == 0) return LR_OK;
-    const long long n_pairs_ll = (long long)B * nh, grid_ll = 8 * ((n_pairs_ll + 7) / 8) * mq;
-    if (grid_ll > 0x7fffffffLL) LR_FAIL(LR_EUNSUPPORTED, "attention: %lld workgroups exceed the grid limit", grid_ll);
+    LR_RUN(lr_attn_check_grid(pl));
     if ((long long)n_tok * (nh + 2 * nkv) * hd * 2 > 0x7fffffffLL * 2)
       LR_FAIL(LR_EUNSUPPORTED, "attention: packed qkv of %d tokens exceeds the 4 GiB a buffer descriptor addresses", n_tok);
-    const int n_pairs = (int)n_pairs_ll;
-    const unsigned grid = (unsigned)grid_ll;
+    const int n_pairs = (int)pl.n_pairs;
+    const unsigned grid = (unsigned)pl.grid;
     static bool lds_set[LR_MAX_DEVICES] = {};
     if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_mfma128_kernel<false>), 2 * FA_STAGE_BYTES, lds_set))
       return rc;
@@ -658,21 +650,16 @@ int lr_launch_attention_last(const u16* kv, const u16* q_last, u16* out_last, co
   if (hd == 256) return lr_launch_attention_hd256_last(kv, q_last, out_last, cu, cu_host, S, n_tok, nh, nkv, prefix_len, st);
   if (prefix_len < 0 || (prefix_len > 0 && cu_host[1] - cu_host[0] != prefix_len))
     LR_FAIL(LR_EINVAL, "attention (last rows): segment 0 must be the %d-token shared prefix", prefix_len);
-  double work = 0;
-  for (int b = (prefix_len > 0 ? 1 : 0); b < S; ++b) {
-    const double T = (prefix_len > 0 ? prefix_len : 0) + cu_host[b + 1] - cu_host[b];
-    work += 4.0 * nh * hd * T;
-  }
-  LrProfScope prof(LR_PROF_ATTN_MFMA, work, st);
-  const long long n_pairs_ll = (long long)S * nh, grid_ll = 8 * ((n_pairs_ll + 7) / 8);
-  if (grid_ll > 0x7fffffffLL) LR_FAIL(LR_EUNSUPPORTED, "attention: %lld workgroups exceed the grid limit", grid_ll);
+  const LrAttnPlan pl = lr_attn_plan_last(cu_host, S, prefix_len, nh, hd, 8);
+  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
+  LR_RUN(lr_attn_check_grid(pl));
   if ((long long)n_tok * 2 * nkv * hd * 2 > 0x7fffffffLL * 2)
     LR_FAIL(LR_EUNSUPPORTED, "attention: packed kv of %d tokens exceeds the 4 GiB a buffer descriptor addresses", n_tok);
   static bool lds_set[LR_MAX_DEVICES] = {};
   if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_mfma128_kernel<false, true>), 2 * FA_STAGE_BYTES, lds_set))
     return rc;
-  hipLaunchKernelGGL((attn_mfma128_kernel<false, true>), dim3((unsigned)grid_ll), dim3(256), 2 * FA_STAGE_BYTES, st, kv, out_last,
-                     cu, prefix_len, nh, nkv, 0, (int)n_pairs_ll, (float*)nullptr, q_last);
+  hipLaunchKernelGGL((attn_mfma128_kernel<false, true>), dim3((unsigned)pl.grid), dim3(256), 2 * FA_STAGE_BYTES, st, kv, out_last,
+                     cu, prefix_len, nh, nkv, 0, (int)pl.n_pairs, (float*)nullptr, q_last);
   LR_CHECK_LAUNCH("attn_mfma128_kernel<last>");
   return LR_OK;
 }

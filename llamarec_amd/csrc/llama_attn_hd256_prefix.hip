@@ -1,296 +1,21 @@
-// llama_attn_hd256_prefix.hip -- the head_dim-256 MFMA attention (variant 4, llama_attn_hd256.hip: read its header first) with
-// the two modes attn_mfma128_kernel has in llama_attn.hip, as kernels of their own so that variant 4's code object stays what
-// it is. The body is a copy of attn_hd256_kernel<1> (8 waves x 16 query rows of one (prompt, head), 64-key blocks, 128 KiB LDS):
+// llama_attn_hd256_prefix.hip -- the head_dim-256 MFMA attention (variant 4; its text is attn_hd256_body in
+// llama_attn_hd256_body.h: read it first) instantiated in the two modes attn_mfma128_kernel has in llama_attn.hip, as kernels of
+// their own in a translation unit of their own, so that variant 4's code object holds variant 4 alone:
 //
-//   attn_hd256_prefix_kernel<false>  shared prompt prefix (prefix_len = P > 0). Segment 0 of the packed rows holds the P tokens
-//     every prompt starts with, segment s >= 1 the rest of prompt s - 1 at positions P.. . Keys and values of positions < P are
-//     read from segment 0's rows; query tiles and 64-key blocks stay aligned to positions inside the prompt, prefix included;
-//     rows of a tile at positions < P belong to segment 0 and are neither computed nor stored for segment s.
-//   attn_hd256_prefix_kernel<true>   LASTQ, the pruned last layer: `qkv` is the [rows][2 nkv hd] K | V projection, q_rows_last
-//     one rotated query row per prompt. A workgroup = one (prompt, head) walks the prompt's key blocks, all eight waves staging
-//     and wave 0 computing with every lane column holding the query at position T - 1; one output row per prompt.
+//   attn_hd256_prefix_kernel<false>  shared prompt prefix (prefix_len = P > 0): the body's PREFIX mode
+//   attn_hd256_prefix_kernel<true>   the pruned last layer, one query row per prompt: the body's LASTQ mode
 //
-// Contract: a row's bits are those variant 4 writes for the same row of the same whole prompt (block walk, masking, per-row
-// deferred maximum, bf16 P into both products, ones-MFMA row sum: variant 4's text). Only the home of a staged K / V row
-// differs, and the LDS image of a block is the same bytes either way (rows past the prompt's end are zero in both).
-// Staging: as llama_attn_hd64_prefix.hip. A block with one home (own rows, or segment 0) takes variant 4's per-block descriptor;
-// the block that straddles position P takes one descriptor over the packed rows [0, end of this segment] and a per-lane home
-// offset (a compare, a select and an add per piece). The hand-placed `s_waitcnt vmcnt(0)` stands in front of every barrier.
-// The swizzles depend on the row inside the block and the chunk only: the LDS side is variant 4's (derived, not measured).
-#include <type_traits>
-
-#include "llama_kernels.h"
-#include "lr_attn_util.h"
-#include "lr_profile.h"
-
-typedef unsigned short u16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-#define FA4_HD 256
-#define FA4_WAVES 8                       // 16 query rows each
-#define FA4_QR (16 * FA4_WAVES)           // query rows per workgroup
-#define FA4_KB 64                         // keys per block
-#define FA4_ROW_BYTES (FA4_HD * 2)        // one K or V row in LDS: 512 B = 32 chunks of 16 B
-#define FA4_TILE_BYTES (FA4_KB * FA4_ROW_BYTES)   // 32 KiB
-#define FA4_STAGE_BYTES (2 * FA4_TILE_BYTES)      // K tile + V tile
-#define FA4_LDS_BYTES (2 * FA4_STAGE_BYTES)       // two stages: 128 KiB
-#define FA4_DEFER 8.0f
-
-__device__ __forceinline__ int fa4_vswz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
+// Contract: a row's bits are those variant 4 writes for the same row of the same whole prompt. It holds because the block walk
+// and the softmax are the same lines of the body in every mode; only the home of a staged K / V row differs, and the LDS image
+// of a block is the same bytes either way (rows past the prompt's end are zero in both: the buffer descriptor's range check).
+// The hand-placed `s_waitcnt vmcnt(0)` in front of every barrier covers both staging forms (the DMA is inline asm).
+#include "llama_attn_hd256_body.h"
 
 template <bool LASTQ>
 __global__ __launch_bounds__(512, 1) void attn_hd256_prefix_kernel(const u16* __restrict__ qkv, u16* out, const int32_t* cu,
                                                                    int prefix_len, int nh, int nkv, int max_qblocks, int n_pairs,
                                                                    const u16* __restrict__ q_rows_last) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int hd = FA4_HD;
-  int seg, h, qb;
-  if (LASTQ) {
-    const int pair = blockIdx.x;
-    if (pair >= n_pairs) return;
-    seg = __builtin_amdgcn_readfirstlane(pair / nh);
-    h = __builtin_amdgcn_readfirstlane(pair - seg * nh);
-    if (prefix_len > 0 && seg == 0) return;   // segment 0 is the shared prefix, not a prompt
-    qb = 0;
-  } else {
-    const int id = blockIdx.x, stream = id & 7, j = id >> 3;
-    const int ppx = (n_pairs + 7) >> 3;
-    const int n_light = min(max_qblocks, 2), n_heavy = max_qblocks - n_light;
-    int pl;
-    if (j < ppx * n_heavy) {
-      pl = j / n_heavy;
-      qb = max_qblocks - 1 - j % n_heavy;
-    } else {
-      const int j2 = j - ppx * n_heavy;
-      pl = j2 / n_light;
-      qb = n_light - 1 - j2 % n_light;
-    }
-    const int pair = pl * 8 + stream;
-    if (pair >= n_pairs) return;
-    seg = __builtin_amdgcn_readfirstlane(pair / nh);
-    h = __builtin_amdgcn_readfirstlane(pair - seg * nh);
-    qb = __builtin_amdgcn_readfirstlane(qb);
-  }
-  const int tok0 = cu[seg];
-  const int P = (prefix_len > 0 && seg > 0) ? prefix_len : 0;   // keys [0, P) live in segment 0's rows [0, P)
-  const int T = P + cu[seg + 1] - tok0;                         // sequence length, prefix included
-  if (!LASTQ && (qb * FA4_QR >= T || (qb + 1) * FA4_QR <= P)) return;   // no query row of this segment in the tile
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int quad = lane >> 4, li = lane & 15;
-  const int kvh = __builtin_amdgcn_readfirstlane(h / (nh / nkv));
-  const int stride = LASTQ ? 2 * nkv * hd : (nh + 2 * nkv) * hd;
-  const int koff0 = LASTQ ? kvh * hd : (nh + kvh) * hd;
-  const int vtok0 = tok0 - P;   // the row of position p >= P is vtok0 + p (tok0 >= P: segment 0 precedes the segment)
-  const u16* pkbase = qkv + koff0;                           // prefix rows start at packed row 0
-  const u16* pvbase = pkbase + nkv * hd;
-  const u16* kbase = pkbase + (size_t)vtok0 * stride;
-  const u16* vbase = pvbase + (size_t)vtok0 * stride;
-  const int prompt = prefix_len > 0 ? seg - 1 : seg;         // LASTQ: row of q_rows_last / out
-
-  // ---- Q fragments (B operand of S^T = K Q^T): row q, d = 32 ks + 8 quad + 0..7
-  const int wave_q0 = LASTQ ? T - 1 : qb * FA4_QR + wave * 16;
-  const int qabs = LASTQ ? T - 1 : wave_q0 + li;
-  bf16x8 qf[8];
-  {
-    const int qr = min(max(qabs, P), T - 1);
-    const u16* qp = LASTQ ? q_rows_last + (size_t)prompt * nh * hd + h * hd + quad * 8
-                          : qkv + (size_t)(vtok0 + qr) * stride + h * hd + quad * 8;
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 32);
-  }
-  floatx4 ot[16];
-#pragma unroll
-  for (int dt = 0; dt < 16; ++dt) ot[dt] = floatx4{0.f, 0.f, 0.f, 0.f};
-  float m_run = -__builtin_inff(), mthr = -__builtin_inff();
-  floatx4 l_acc = floatx4{0.f, 0.f, 0.f, 0.f};
-  bf16x8 ones_f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) ones_f[i] = (__bf16)1.0f;
-
-  const int q_last = LASTQ ? T - 1 : min(qb * FA4_QR + FA4_QR - 1, T - 1);
-  const int kb_last = q_last / FA4_KB;
-  const int wave_q_last = LASTQ ? T - 1 : wave_q0 + 15;
-  // the wave owns at least one row of this segment (LASTQ: wave 0 computes, every wave stages)
-  const bool wave_live = LASTQ ? wave == 0 : (wave_q0 < T && wave_q_last >= P);
-  const float sl2 = 0.0625f * 1.4426950408889634f;  // 1/sqrt(256) * log2(e)
-  const float inv_sl2 = 1.0f / sl2;
-
-  // ---- DMA staging (variant 4's pieces: 2 rows x 512 B each; wave w moves pieces 4w..4w+3 of K and of V)
-  const int prow = lane >> 5, ppos = lane & 31;
-  unsigned koff[4], voff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = (wave * 4 + i) * 2 + prow;
-    koff[i] = (unsigned)(row * stride + (ppos ^ (row & 15)) * 8) * 2u;
-    voff[i] = (unsigned)(row * stride + (ppos ^ fa4_vswz(row)) * 8) * 2u;
-  }
-  auto stage = [&](int kb, int buf) {
-    char* base = smem + buf * FA4_STAGE_BYTES + wave * 4096;
-    const int k0 = kb * FA4_KB;
-    if (k0 >= P || k0 + FA4_KB <= P) {   // the whole block has one home: the segment's own rows, or segment 0
-      const bool own = k0 >= P;
-      const size_t blk_off = (size_t)k0 * stride * 2;
-      const int records = (((own ? T : P) - 1 - k0) * stride + hd) * 2;   // bytes from the block's first K (V) element
-      const fa_int4 rk = fa_make_rsrc(reinterpret_cast<const char*>(own ? kbase : pkbase) + blk_off, records);
-      const fa_int4 rv = fa_make_rsrc(reinterpret_cast<const char*>(own ? vbase : pvbase) + blk_off, records);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        fa_dma16(rk, base + i * 1024, koff[i]);
-        fa_dma16(rv, base + FA4_TILE_BYTES + i * 1024, voff[i]);
-      }
-    } else {   // the block straddles position P: one descriptor over the packed rows [0, end of this segment], per-lane home
-      const unsigned records = ((unsigned)(vtok0 + T - 1) * (unsigned)stride + hd) * 2u;
-      const fa_int4 rk = fa_make_rsrc(pkbase, (int)records);
-      const fa_int4 rv = fa_make_rsrc(pvbase, (int)records);
-      const unsigned home_pre = (unsigned)k0 * (unsigned)stride * 2u, home_own = (unsigned)(vtok0 + k0) * (unsigned)stride * 2u;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = (wave * 4 + i) * 2 + prow;
-        const unsigned home = (k0 + row < P) ? home_pre : home_own;
-        fa_dma16(rk, base + i * 1024, koff[i] + home);
-        fa_dma16(rv, base + FA4_TILE_BYTES + i * 1024, voff[i] + home);
-      }
-    }
-  };
-
-  typedef __attribute__((address_space(3))) char lds_char;
-  lds_char* const lds = (lds_char*)smem;
-  lds_char *kb_off[4], *vb_off[8];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) kb_off[ks] = lds + (li * FA4_ROW_BYTES + (((ks * 4 + quad) ^ li) << 4));
-  {
-    const int qp = li >> 2, p4 = li & 3, row = quad * 4 + qp;
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt)
-      vb_off[dt] = lds + (FA4_ROW_BYTES * row + 16 * ((dt * 2 + (p4 >> 1)) ^ fa4_vswz(row)) + 8 * (p4 & 1));
-  }
-
-  stage(0, 0);
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks) asm volatile("" ::"v"(qf[ks]));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the asm DMAs of block 0 (hipcc does not count them)
-  __syncthreads();
-
-  auto block = [&](const int kb, auto buf_c) {
-    constexpr int BUF = decltype(buf_c)::value;
-    constexpr int KS = BUF * FA4_STAGE_BYTES, VS = KS + FA4_TILE_BYTES;
-    if (kb < kb_last) stage(kb + 1, BUF ^ 1);
-    if (wave_live && kb * FA4_KB <= wave_q_last) {
-      // ---- S^T = K Q^T : st[nt] rows = keys nt*16 + 4*quad + r, col = query li
-      floatx4 st[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) st[nt] = floatx4{0.f, 0.f, 0.f, 0.f};
-      typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
-      bf16x8 kf[2][4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) kf[0][nt] = *reinterpret_cast<lds_bf16x8*>(kb_off[0] + (KS + nt * 16 * FA4_ROW_BYTES));
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        if (ks < 7) {
-          const int kn = ks + 1;
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt)
-            kf[kn & 1][nt] = *reinterpret_cast<lds_bf16x8*>(kb_off[kn & 3] + (KS + (kn >> 2) * 256 + nt * 16 * FA4_ROW_BYTES));
-        }
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) st[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[ks & 1][nt], qf[ks], st[nt], 0, 0, 0);
-      }
-      // ---- online softmax (lane-local row), P packed as the B operand of O^T = V^T P^T
-      bf16x8 pa[2];
-      const bool diag = (kb * FA4_KB + FA4_KB - 1) > wave_q0;
-      if (diag) {
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int key = kb * FA4_KB + nt * 16 + quad * 4 + r;
-            st[nt][r] = (key <= qabs) ? st[nt][r] : -__builtin_inff();
-          }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      float mx = fa_max3(st[0][0], st[0][1], st[0][2]);
-      mx = fa_max3(mx, st[0][3], st[1][0]);
-#pragma unroll
-      for (int nt = 1; nt < 4; ++nt) {
-        mx = fa_max3(mx, st[nt][1], st[nt][2]);
-        if (nt < 3) mx = fa_max3(mx, st[nt][3], st[nt + 1][0]);
-      }
-      mx = fa_max2(mx, st[3][3]);
-      // deferred maximum, decided per row (variant 2): a row that keeps its reference multiplies by exactly 1
-      if (__any(mx > mthr)) {
-        const float rmx = fa_max_xor16_32(mx);
-        const bool grew = rmx > mthr;
-        const float m_new = grew ? rmx * sl2 : m_run;
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) l_acc[r] *= alpha;
-#pragma unroll
-        for (int dt = 0; dt < 16; ++dt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) ot[dt][r] *= alpha;
-        m_run = m_new;
-        mthr = (m_new + FA4_DEFER) * inv_sl2;
-      }
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          pa[nt >> 1][(nt & 1) * 4 + r] = (__bf16)__builtin_amdgcn_exp2f(__builtin_fmaf(st[nt][r], sl2, -m_run));
-      // ---- O^T += V^T P^T (k index 8 quad + j <-> key 32 ks2 + 16 (j >> 2) + 4 quad + (j & 3), as the S^T layout gives it)
-#pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
-        l_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones_f, pa[ks2], l_acc, 0, 0, 0);
-#pragma unroll
-        for (int dt = 0; dt < 16; ++dt) {
-          const int o = VS + ks2 * 32 * FA4_ROW_BYTES + (dt >> 3) * 256;
-          const short4v t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) short4v*)(vb_off[dt & 7] + o));
-          const short4v t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) short4v*)(vb_off[dt & 7] + (o + 16 * FA4_ROW_BYTES)));
-          bf16x8 vf;
-          const bf16x4 b0 = __builtin_bit_cast(bf16x4, t0), b1 = __builtin_bit_cast(bf16x4, t1);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            vf[r] = b0[r];
-            vf[4 + r] = b1[r];
-          }
-          ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pa[ks2], ot[dt], 0, 0, 0);
-        }
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces of block kb + 1 have landed
-    __syncthreads();                                   // ... and every wave is done with block kb
-  };
-  for (int kb = 0; kb <= kb_last; kb += 2) {
-    block(kb, std::integral_constant<int, 0>{});
-    if (kb + 1 <= kb_last) block(kb + 1, std::integral_constant<int, 1>{});
-  }
-
-  // ---- normalise and store (variant 4's): every lane takes part in the swaps; only rows of this segment store.
-  // LASTQ: the 16 lane columns of wave 0 hold the same row; column 0's four quads store its 256 dims.
-  const float inv = 1.0f / l_acc[0];
-  const bool live = LASTQ ? (wave == 0 && li == 0) : (qabs < T && qabs >= P);
-  u16* op = out + (size_t)(LASTQ ? prompt : vtok0 + (live ? qabs : P)) * nh * hd + h * hd + (quad & 1) * 16 + (quad >> 1) * 8;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    unsigned a[2], b[2];
-#pragma unroll
-    for (int w = 0; w < 2; ++w) {
-      a[w] = (unsigned)f2bf(ot[2 * k][2 * w] * inv) | ((unsigned)f2bf(ot[2 * k][2 * w + 1] * inv) << 16);
-      b[w] = (unsigned)f2bf(ot[2 * k + 1][2 * w] * inv) | ((unsigned)f2bf(ot[2 * k + 1][2 * w + 1] * inv) << 16);
-      const auto sw = __builtin_amdgcn_permlane16_swap(a[w], b[w], false, false);
-      a[w] = sw[0];
-      b[w] = sw[1];
-    }
-    if (live) {
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-      *reinterpret_cast<u32x4*>(op + k * 32) = u32x4{a[0], a[1], b[0], b[1]};
-    }
-  }
+  attn_hd256_body<1, LASTQ, true>(qkv, out, cu, prefix_len, nh, nkv, max_qblocks, n_pairs, q_rows_last);
 }
 
 // cu / cu_host: segment starts [S + 1]; prefix_len = P > 0: segment 0 is the shared prefix the other segments continue
@@ -302,21 +27,13 @@ int lr_launch_attention_hd256_prefix(const LrAttnArgs& a, hipStream_t st) {
     LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
   if (a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-256 MFMA kernel writes no lse");
   LR_RUN(lr_check_prefix_layout("attention (head_dim 256)", a.cu_host, S, n_tok, (nh + 2 * nkv) * hd, P));
-  double work = 0;   // causal QK^T + PV flops of the rows each segment owns
-  int maxT = 0;
-  for (int b = 0; b < S; ++b) {
-    const double p = (P > 0 && b > 0) ? P : 0, T = p + a.cu_host[b + 1] - a.cu_host[b];
-    work += 4.0 * nh * hd * (T * (T + 1) / 2 - p * (p + 1) / 2);
-    maxT = max(maxT, (int)T);
-  }
-  LrProfScope prof(LR_PROF_ATTN_MFMA, work, st);
-  const int mq = (maxT + FA4_QR - 1) / FA4_QR;
-  const long long n_pairs_ll = (long long)S * nh, grid_ll = 8 * ((n_pairs_ll + 7) / 8) * mq;
-  if (grid_ll > 0x7fffffffLL) LR_FAIL(LR_EUNSUPPORTED, "attention: %lld workgroups exceed the grid limit", grid_ll);
+  const LrAttnPlan pl = lr_attn_plan(a.cu_host, S, P, nh, hd, FA4_QR, nh);
+  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
+  LR_RUN(lr_attn_check_grid(pl));
   static bool lds_set[LR_MAX_DEVICES] = {};
   if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_hd256_prefix_kernel<false>), FA4_LDS_BYTES, lds_set)) return rc;
-  hipLaunchKernelGGL(attn_hd256_prefix_kernel<false>, dim3((unsigned)grid_ll), dim3(512), FA4_LDS_BYTES, st, a.qkv, a.out, a.cu, P,
-                     nh, nkv, mq, (int)n_pairs_ll, (const u16*)nullptr);
+  hipLaunchKernelGGL(attn_hd256_prefix_kernel<false>, dim3((unsigned)pl.grid), dim3(512), FA4_LDS_BYTES, st, a.qkv, a.out, a.cu, P,
+                     nh, nkv, pl.mq, (int)pl.n_pairs, (const u16*)nullptr);
   LR_CHECK_LAUNCH("attn_hd256_prefix_kernel");
   return LR_OK;
 }
@@ -325,15 +42,13 @@ int lr_launch_attention_hd256_prefix(const LrAttnArgs& a, hipStream_t st) {
 int lr_launch_attention_hd256_last(const u16* kv, const u16* q_last, u16* out_last, const int32_t* cu, const int32_t* cu_host,
                                    int S, int n_tok, int nh, int nkv, int prefix_len, hipStream_t st) {
   LR_RUN(lr_check_prefix_layout("attention (last rows, head_dim 256)", cu_host, S, n_tok, 2 * nkv * FA4_HD, prefix_len));
-  double work = 0;
-  for (int b = (prefix_len > 0 ? 1 : 0); b < S; ++b) work += 4.0 * nh * FA4_HD * (double)(prefix_len + cu_host[b + 1] - cu_host[b]);
-  LrProfScope prof(LR_PROF_ATTN_MFMA, work, st);
-  const long long n_pairs_ll = (long long)S * nh;
-  if (n_pairs_ll > 0x7fffffffLL) LR_FAIL(LR_EUNSUPPORTED, "attention: %lld workgroups exceed the grid limit", n_pairs_ll);
+  const LrAttnPlan pl = lr_attn_plan_last(cu_host, S, prefix_len, nh, FA4_HD, 1);
+  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
+  LR_RUN(lr_attn_check_grid(pl));
   static bool lds_set[LR_MAX_DEVICES] = {};
   if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_hd256_prefix_kernel<true>), FA4_LDS_BYTES, lds_set)) return rc;
-  hipLaunchKernelGGL(attn_hd256_prefix_kernel<true>, dim3((unsigned)n_pairs_ll), dim3(512), FA4_LDS_BYTES, st, kv, out_last, cu,
-                     prefix_len, nh, nkv, 0, (int)n_pairs_ll, q_last);
+  hipLaunchKernelGGL(attn_hd256_prefix_kernel<true>, dim3((unsigned)pl.grid), dim3(512), FA4_LDS_BYTES, st, kv, out_last, cu,
+                     prefix_len, nh, nkv, 0, (int)pl.n_pairs, q_last);
   LR_CHECK_LAUNCH("attn_hd256_prefix_kernel<last>");
   return LR_OK;
 }

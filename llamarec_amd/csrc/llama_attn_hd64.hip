@@ -15,11 +15,12 @@
 // when a score exceeds it by more than 2^FA5_DEFER), bf16 P into both the numerator and the row sum (an MFMA against a row
 // of ones), one bf16 rounding of O / l. A query row's bits depend only on its own prompt: tiles and key blocks are aligned
 // to positions inside the prompt, and the rescale decision is per row.
-// No shared prefix here: with one, and for the pruned last layer's one-query-row mode, the kernels of
-// llama_attn_hd64_prefix.hip run (same bits). The LSE instantiation (attention variant 6, the training forward) also writes the natural-log log-sum-exp of
-// the scaled scores per (token, head) from the deferred reference and the row sum, as variant 2 does; `out` has the same bits
-// in both instantiations. The kernel's text is llama_attn_hd64_body.h; this file instantiates variant 5 and holds the launcher,
-// llama_attn_hd64_lse.hip instantiates the lse-writing kernel. The backward is llama_attn_bwd_hd64.hip.
+// The kernel's one text is attn_hd64_body in llama_attn_hd64_body.h, with its modes chosen at compile time. This file
+// instantiates variant 5 (no shared prefix, no lse) and holds its launcher. llama_attn_hd64_lse.hip instantiates the training
+// forward (attention variant 6), which also writes the natural-log log-sum-exp of the scaled scores per (token, head) from the
+// deferred reference and the row sum, as variant 2 does. llama_attn_hd64_prefix.hip instantiates the shared-prefix mode and the
+// pruned last layer's one-query-row mode. `out` has the same bits in every instantiation. The backward is
+// llama_attn_bwd_hd64.hip.
 #include "llama_attn_hd64_body.h"
 
 // cu / cu_host: prompt starts [B + 1] in packed rows (no shared prefix at head_dim 64)
@@ -29,25 +30,17 @@ int lr_launch_attention_hd64(const LrAttnArgs& a, hipStream_t st) {
   if (hd != FA5_HD) LR_FAIL(LR_EUNSUPPORTED, "attention variants 5 and 6 need head_dim 64 (got %d)", hd);
   if (nh < 1 || nkv < 1 || nh % nkv != 0)
     LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
-  double work = 0;
-  int maxT = 0;
-  for (int b = 0; b < B; ++b) {
-    const double T = a.cu_host[b + 1] - a.cu_host[b];
-    work += 4.0 * nh * hd * (T * (T + 1) / 2);
-    maxT = max(maxT, (int)T);
-  }
-  LrProfScope prof(LR_PROF_ATTN_MFMA, work, st);
-  const int mq = (maxT + FA5_QROWS - 1) / FA5_QROWS;
-  if (mq == 0) return LR_OK;
-  const long long n_pairs_ll = (long long)B * nh, grid_ll = 8 * ((n_pairs_ll + 7) / 8) * mq;
-  if (grid_ll > 0x7fffffffLL) LR_FAIL(LR_EUNSUPPORTED, "attention: %lld workgroups exceed the grid limit", grid_ll);
+  const LrAttnPlan pl = lr_attn_plan(a.cu_host, B, 0, nh, hd, FA5_QROWS, nh);
+  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
+  if (pl.mq == 0) return LR_OK;
+  LR_RUN(lr_attn_check_grid(pl));
   if ((long long)n_tok * (nh + 2 * nkv) * hd * 2 > 0x7fffffffLL * 2)
     LR_FAIL(LR_EUNSUPPORTED, "attention: packed qkv of %d tokens exceeds the 4 GiB a buffer descriptor addresses", n_tok);
-  if (a.lse) return lr_launch_attention_hd64_lse(a, (unsigned)grid_ll, mq, (int)n_pairs_ll, st);   // llama_attn_hd64_lse.hip
+  if (a.lse) return lr_launch_attention_hd64_lse(a, (unsigned)pl.grid, pl.mq, (int)pl.n_pairs, st);   // llama_attn_hd64_lse.hip
   static bool lds_set[LR_MAX_DEVICES] = {};
   if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_hd64_kernel<false>), FA5_LDS_BYTES, lds_set)) return rc;
-  hipLaunchKernelGGL(attn_hd64_kernel<false>, dim3((unsigned)grid_ll), dim3(256), FA5_LDS_BYTES, st, a.qkv, a.out, a.cu, nh, nkv,
-                     mq, (int)n_pairs_ll, (float*)nullptr);
+  hipLaunchKernelGGL(attn_hd64_kernel<false>, dim3((unsigned)pl.grid), dim3(256), FA5_LDS_BYTES, st, a.qkv, a.out, a.cu, nh, nkv,
+                     pl.mq, (int)pl.n_pairs, (float*)nullptr);
   LR_CHECK_LAUNCH("attn_hd64_kernel");
   return LR_OK;
 }

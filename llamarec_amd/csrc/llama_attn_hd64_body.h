@@ -1,7 +1,15 @@
-// llama_attn_hd64_body.h -- the kernel of llama_attn_hd64.hip (read its header first), as a template over LSE so that the
-// two instantiations live in two translation units: <false> = attention variant 5 in llama_attn_hd64.hip, the code it was
-// before the template; <true> = the training forward of variant 6 in llama_attn_hd64_lse.hip, the same code plus one lse
-// store per row and head.
+// llama_attn_hd64_body.h -- the one text of the head_dim-64 MFMA attention (llama_attn_hd64.hip: read its header first),
+// attn_hd64_body<LASTQ, PREFIX, LSE>, inlined into four kernels in three translation units:
+//   <false, false, false>  attn_hd64_kernel<false>, attention variant 5                          (llama_attn_hd64.hip)
+//   <false, false, true>   attn_hd64_kernel<true>, variant 6's training forward: one lse store per row and head more
+//                                                                                                (llama_attn_hd64_lse.hip)
+//   <false, true, false>   attn_hd64_prefix_kernel<false>, shared prompt prefix                  (llama_attn_hd64_prefix.hip)
+//   <true, true, false>    attn_hd64_prefix_kernel<true>, one query row per prompt               (llama_attn_hd64_prefix.hip)
+// The modes differ in where a K / V row and a query row live and in which rows a tile owns. Each such place picks its
+// expression at compile time (`if constexpr`, or a condition on the template parameters alone): without PREFIX no shared-prefix
+// length is ever computed, compared or added, so variant 5's instructions do not depend on the optimiser folding a zero away.
+// The block walk, the masking, the per-row deferred maximum, bf16 P into both products and the ones-MFMA row sum are common to
+// all four, which is what makes a row's bits the same in every mode.
 #ifndef LLAMA_ATTN_HD64_BODY_H
 #define LLAMA_ATTN_HD64_BODY_H
 
@@ -42,53 +50,82 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int fa5_kswz(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ int fa5_vswz(int row) { return ((row >> 1) & 3) << 1; }
 
-template <bool LSE>
-__global__ __launch_bounds__(256, FA5_MIN_WG) void attn_hd64_kernel(const u16* __restrict__ qkv, u16* out, const int32_t* cu, int nh,
-                                                           int nkv, int max_qblocks, int n_pairs, float* lse) {
-  constexpr int QT = FA5_QT;
+// PREFIX: prefix_len = P > 0 makes segment 0 of the packed rows the P tokens every prompt starts with and segment s >= 1 the
+//   rest of prompt s - 1 at positions P.. . Keys and values of positions < P are read from segment 0's rows; query tiles and
+//   64-key blocks stay aligned to positions inside the prompt, prefix included; rows of a tile at positions < P belong to
+//   segment 0 and are neither computed nor stored for segment s. Without PREFIX prefix_len is not read.
+// LASTQ (with PREFIX; prefix_len may be 0): `qkv` is the [rows][2 nkv hd] K | V projection, q_rows_last one rotated query row
+//   per prompt. A workgroup = one (prompt, head) walks the prompt's key blocks, all four waves staging and wave 0 computing with
+//   every lane column holding the query at position T - 1; one output row per prompt.
+// LSE (alone): lse[token][head] = natural-log log-sum-exp of the row's scaled scores.
+template <bool LASTQ, bool PREFIX, bool LSE>
+__device__ __forceinline__ void attn_hd64_body(const u16* qkv, u16* out, const int32_t* cu, int prefix_len, int nh, int nkv,
+                                               int max_qblocks, int n_pairs, float* lse, const u16* q_rows_last) {
+  static_assert(!LSE || (!PREFIX && !LASTQ), "the lse store exists without a shared prefix and for whole tiles only");
+  static_assert(!LASTQ || PREFIX, "the last-row mode reads a shared prefix");
+  constexpr int QT = LASTQ ? 1 : FA5_QT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int hd = FA5_HD;
-  // workgroup -> (prompt, head, query tile): variant 2's order (a (prompt, head) pair per dispatch stream, heavy tiles first,
-  // the two lightest tiles of every pair at the end of the launch)
   int seg, h, qb;
   {
-    const int id = blockIdx.x, stream = id & 7, j = id >> 3;
-    const int ppx = (n_pairs + 7) >> 3;
-    const int n_light = min(max_qblocks, 2), n_heavy = max_qblocks - n_light;
-    int pl;
-    if (j < ppx * n_heavy) {
-      pl = j / n_heavy;
-      qb = max_qblocks - 1 - j % n_heavy;
+    int pair;
+    if constexpr (LASTQ) {
+      pair = blockIdx.x;
+      qb = 0;
     } else {
-      const int j2 = j - ppx * n_heavy;
-      pl = j2 / n_light;
-      qb = n_light - 1 - j2 % n_light;
+      fa_tile_of_workgroup(n_pairs, max_qblocks, pair, qb);
     }
-    const int pair = pl * 8 + stream;
     if (pair >= n_pairs) return;
     seg = __builtin_amdgcn_readfirstlane(pair / nh);
     h = __builtin_amdgcn_readfirstlane(pair - seg * nh);
-    qb = __builtin_amdgcn_readfirstlane(qb);
+    if constexpr (LASTQ) {
+      if (prefix_len > 0 && seg == 0) return;   // segment 0 is the shared prefix, not a prompt
+    } else {
+      qb = __builtin_amdgcn_readfirstlane(qb);
+    }
   }
   const int tok0 = cu[seg];
-  const int T = cu[seg + 1] - tok0;
-  if (qb * FA5_QROWS >= T) return;
+  int P = 0, T, vtok0 = tok0;   // !PREFIX: P and vtok0 are named by no expression below
+  if constexpr (PREFIX) {
+    P = (prefix_len > 0 && seg > 0) ? prefix_len : 0;   // keys [0, P) live in segment 0's rows [0, P)
+    T = P + cu[seg + 1] - tok0;                         // sequence length, prefix included
+    vtok0 = tok0 - P;   // the row of position p >= P is vtok0 + p (tok0 >= P: segment 0 precedes the segment)
+  } else {
+    T = cu[seg + 1] - tok0;
+  }
+  // no query row of this segment in the tile
+  if (!LASTQ && (qb * FA5_QROWS >= T || (PREFIX && (qb + 1) * FA5_QROWS <= P))) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int quad = lane >> 4, li = lane & 15;
   const int kvh = __builtin_amdgcn_readfirstlane(h / (nh / nkv));
-  const int stride = (nh + 2 * nkv) * hd;
-  const u16* kbase = qkv + (size_t)tok0 * stride + (nh + kvh) * hd;
-  const u16* vbase = kbase + nkv * hd;
+  const int stride = LASTQ ? 2 * nkv * hd : (nh + 2 * nkv) * hd;
+  const u16 *kbase, *vbase, *pkbase = nullptr, *pvbase = nullptr;   // a position's K / V row: own rows, and (PREFIX) packed row 0
+  if constexpr (PREFIX) {
+    pkbase = qkv + (LASTQ ? kvh * hd : (nh + kvh) * hd);
+    pvbase = pkbase + nkv * hd;
+    kbase = pkbase + (size_t)vtok0 * stride;
+    vbase = pvbase + (size_t)vtok0 * stride;
+  } else {
+    kbase = qkv + (size_t)tok0 * stride + (nh + kvh) * hd;
+    vbase = kbase + nkv * hd;
+  }
+  const int prompt = prefix_len > 0 ? seg - 1 : seg;         // LASTQ: row of q_rows_last / out
 
   // ---- Q fragments (B operand of S^T = K Q^T): row q, d = 32 ks + 8 quad + 0..7
-  const int wave_q0 = qb * FA5_QROWS + wave * (16 * QT);
+  const int wave_q0 = LASTQ ? T - 1 : qb * FA5_QROWS + wave * (16 * QT);
   bf16x8 qf[QT][2];
   int qabs[QT];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    qabs[qt] = wave_q0 + qt * 16 + li;
-    const u16* qp = qkv + (size_t)(tok0 + min(qabs[qt], T - 1)) * stride + h * hd + quad * 8;
+    qabs[qt] = LASTQ ? T - 1 : wave_q0 + qt * 16 + li;
+    const u16* qp;
+    if constexpr (LASTQ)
+      qp = q_rows_last + (size_t)prompt * nh * hd + h * hd + quad * 8;
+    else if constexpr (PREFIX)
+      qp = qkv + (size_t)(vtok0 + min(max(qabs[qt], P), T - 1)) * stride + h * hd + quad * 8;
+    else
+      qp = qkv + (size_t)(tok0 + min(qabs[qt], T - 1)) * stride + h * hd + quad * 8;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) qf[qt][ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 32);
   }
@@ -107,10 +144,11 @@ __global__ __launch_bounds__(256, FA5_MIN_WG) void attn_hd64_kernel(const u16* _
 #pragma unroll
   for (int i = 0; i < 8; ++i) ones_f[i] = (__bf16)1.0f;
 
-  const int q_last = min(qb * FA5_QROWS + FA5_QROWS - 1, T - 1);
+  const int q_last = LASTQ ? T - 1 : min(qb * FA5_QROWS + FA5_QROWS - 1, T - 1);
   const int kb_last = q_last / FA5_KB;
-  const int wave_q_last = wave_q0 + 16 * QT - 1;
-  const bool wave_live = wave_q0 < T;              // the wave owns at least one row of the prompt
+  const int wave_q_last = LASTQ ? T - 1 : wave_q0 + 16 * QT - 1;
+  // the wave owns at least one row of this segment (LASTQ: wave 0 computes, every wave stages)
+  const bool wave_live = LASTQ ? wave == 0 : (wave_q0 < T && (!PREFIX || wave_q_last >= P));
   const float sl2 = 0.125f * 1.4426950408889634f;  // 1/sqrt(64) * log2(e)
   const float inv_sl2 = 1.0f / sl2;
 
@@ -125,16 +163,51 @@ __global__ __launch_bounds__(256, FA5_MIN_WG) void attn_hd64_kernel(const u16* _
     koff[i] = (unsigned)(row * stride + (ppos ^ fa5_kswz(row)) * 8) * 2u;
     voff[i] = (unsigned)(row * stride + (ppos ^ fa5_vswz(row)) * 8) * 2u;
   }
+  // Where a block's rows live is what the modes differ in, so each has its staging text. Without PREFIX every block takes a
+  // per-block descriptor (scalar work only). PREFIX: so does a block that lies wholly in the segment's own rows or wholly in
+  // segment 0. The one block that straddles position P is gathered from two places: its descriptor spans the packed rows from
+  // row 0 to the end of the segment's last row, and every lane adds the byte offset of ITS row's home (segment 0 for a key
+  // < P, the segment's own rows otherwise) to its block-invariant offset: one compare, one select and one add per piece in
+  // that block only. The LDS image of a block is the same bytes whatever the home of its rows, and the swizzle is a function
+  // of the row inside the block and the chunk, so the bank behaviour of the reads does not depend on the mode.
   auto stage = [&](int kb, int buf) {
     char* base = smem + buf * FA5_STAGE_BYTES + wave * 2048;
-    const size_t blk_off = (size_t)kb * FA5_KB * stride * 2;
-    const int records = ((T - 1 - kb * FA5_KB) * stride + hd) * 2;   // bytes from the block's first K (V) element
-    const fa_int4 rk = fa_make_rsrc(reinterpret_cast<const char*>(kbase) + blk_off, records);
-    const fa_int4 rv = fa_make_rsrc(reinterpret_cast<const char*>(vbase) + blk_off, records);
+    if constexpr (!PREFIX) {
+      const size_t blk_off = (size_t)kb * FA5_KB * stride * 2;
+      const int records = ((T - 1 - kb * FA5_KB) * stride + hd) * 2;   // bytes from the block's first K (V) element
+      const fa_int4 rk = fa_make_rsrc(reinterpret_cast<const char*>(kbase) + blk_off, records);
+      const fa_int4 rv = fa_make_rsrc(reinterpret_cast<const char*>(vbase) + blk_off, records);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      fa_dma16(rk, base + i * 1024, koff[i]);
-      fa_dma16(rv, base + FA5_TILE_BYTES + i * 1024, voff[i]);
+      for (int i = 0; i < 2; ++i) {
+        fa_dma16(rk, base + i * 1024, koff[i]);
+        fa_dma16(rv, base + FA5_TILE_BYTES + i * 1024, voff[i]);
+      }
+    } else {
+      const int k0 = kb * FA5_KB;
+      if (k0 >= P || k0 + FA5_KB <= P) {   // the whole block has one home: the segment's own rows, or segment 0
+        const bool own = k0 >= P;
+        const size_t blk_off = (size_t)k0 * stride * 2;
+        const int records = (((own ? T : P) - 1 - k0) * stride + hd) * 2;
+        const fa_int4 rk = fa_make_rsrc(reinterpret_cast<const char*>(own ? kbase : pkbase) + blk_off, records);
+        const fa_int4 rv = fa_make_rsrc(reinterpret_cast<const char*>(own ? vbase : pvbase) + blk_off, records);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          fa_dma16(rk, base + i * 1024, koff[i]);
+          fa_dma16(rv, base + FA5_TILE_BYTES + i * 1024, voff[i]);
+        }
+      } else {
+        const unsigned records = ((unsigned)(vtok0 + T - 1) * (unsigned)stride + hd) * 2u;
+        const fa_int4 rk = fa_make_rsrc(pkbase, (int)records);
+        const fa_int4 rv = fa_make_rsrc(pvbase, (int)records);
+        const unsigned home_pre = (unsigned)k0 * (unsigned)stride * 2u, home_own = (unsigned)(vtok0 + k0) * (unsigned)stride * 2u;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int row = (wave * 2 + i) * 8 + prow;
+          const unsigned home = (k0 + row < P) ? home_pre : home_own;
+          fa_dma16(rk, base + i * 1024, koff[i] + home);
+          fa_dma16(rv, base + FA5_TILE_BYTES + i * 1024, voff[i] + home);
+        }
+      }
     }
   };
 
@@ -267,14 +340,22 @@ __global__ __launch_bounds__(256, FA5_MIN_WG) void attn_hd64_kernel(const u16* _
 
   // ---- normalise and store: lane owns query row li, d = 16 dt + 4 quad + r. v_permlane16_swap on the packed tiles
   // (2k, 2k+1) gives even quads d = 32 k + 8 (quad / 2) .. +7 and odd quads the same + 16: 16-byte stores. Every lane
-  // takes part in the swaps; only rows of this prompt store.
+  // takes part in the swaps; only rows of this segment store. LASTQ: the 16 lane columns of wave 0 hold the same row;
+  // column 0's four quads store its 64 dims.
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
     const float inv = 1.0f / l_acc[qt][0];
-    const bool live = qabs[qt] < T;
+    const bool live = LASTQ ? (wave == 0 && li == 0) : (qabs[qt] < T && (!PREFIX || qabs[qt] >= P));
     if (LSE && live && quad == 0)   // the lane's row: m (log2 units) + log2 l, as natural log
       lse[(size_t)(tok0 + qabs[qt]) * nh + h] = (m_run[qt] + __builtin_amdgcn_logf(l_acc[qt][0])) * 0.6931471805599453f;
-    u16* op = out + (size_t)(tok0 + (live ? qabs[qt] : 0)) * nh * hd + h * hd + (quad & 1) * 16 + (quad >> 1) * 8;
+    int orow;
+    if constexpr (LASTQ)
+      orow = prompt;
+    else if constexpr (PREFIX)
+      orow = vtok0 + (live ? qabs[qt] : P);
+    else
+      orow = tok0 + (live ? qabs[qt] : 0);
+    u16* op = out + (size_t)orow * nh * hd + h * hd + (quad & 1) * 16 + (quad >> 1) * 8;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       unsigned a[2], b[2];
@@ -292,6 +373,12 @@ __global__ __launch_bounds__(256, FA5_MIN_WG) void attn_hd64_kernel(const u16* _
       }
     }
   }
+}
+
+template <bool LSE>
+__global__ __launch_bounds__(256, FA5_MIN_WG) void attn_hd64_kernel(const u16* __restrict__ qkv, u16* out, const int32_t* cu, int nh,
+                                                           int nkv, int max_qblocks, int n_pairs, float* lse) {
+  attn_hd64_body<false, false, LSE>(qkv, out, cu, 0, nh, nkv, max_qblocks, n_pairs, lse, nullptr);
 }
 
 #endif

@@ -151,15 +151,55 @@ static inline int lr_check_prefix_layout(const char* who, const int32_t* cu_host
   return LR_OK;
 }
 
+// The launch plan of the tiled MFMA attention kernels (MFMA128, HD64, HD256 and the shared-prefix forms) from the host copy of
+// the segment starts. prefix_len = P > 0: every segment but segment 0 continues the P keys of segment 0. A launcher hands
+// `work` to its LrProfScope and then asks lr_attn_check_grid; which 4 GiB test applies is the launcher's own business.
+struct LrAttnPlan {
+  double work = 0;                  // causal QK^T + PV flops of the rows each segment owns
+  int maxT = 0, mq = 0;             // longest sequence (prefix included) and the query tiles it needs
+  long long n_pairs = 0, grid = 0;  // (segment, head or head group) pairs and workgroups; both fit an int once the grid is checked
+};
+// q_rows = query rows per tile; pairs_per_prompt = nh, or nh / 2 with two heads per workgroup. The grid is that of
+// fa_tile_of_workgroup (lr_attn_util.h): a pair per dispatch stream, 8 * ceil(pairs / 8) * mq workgroups.
+static inline LrAttnPlan lr_attn_plan(const int32_t* cu_host, int S, int prefix_len, int nh, int hd, int q_rows,
+                                      int pairs_per_prompt) {
+  LrAttnPlan p;
+  for (int b = 0; b < S; ++b) {
+    const double P = (prefix_len > 0 && b > 0) ? prefix_len : 0, T = P + cu_host[b + 1] - cu_host[b];
+    p.work += 4.0 * nh * hd * (T * (T + 1) / 2 - P * (P + 1) / 2);
+    p.maxT = p.maxT > (int)T ? p.maxT : (int)T;
+  }
+  p.mq = (p.maxT + q_rows - 1) / q_rows;
+  p.n_pairs = (long long)S * pairs_per_prompt;
+  p.grid = 8 * ((p.n_pairs + 7) / 8) * p.mq;
+  return p;
+}
+// The last-row mode: one query row per prompt (segment 0 is no prompt when it is the prefix), one workgroup per (segment, head),
+// the grid rounded up to a multiple of grid_multiple
+static inline LrAttnPlan lr_attn_plan_last(const int32_t* cu_host, int S, int prefix_len, int nh, int hd, int grid_multiple) {
+  LrAttnPlan p;
+  for (int b = (prefix_len > 0 ? 1 : 0); b < S; ++b)
+    p.work += 4.0 * nh * hd * (double)((prefix_len > 0 ? prefix_len : 0) + cu_host[b + 1] - cu_host[b]);
+  p.n_pairs = (long long)S * nh;
+  p.grid = grid_multiple * ((p.n_pairs + grid_multiple - 1) / grid_multiple);
+  return p;
+}
+static inline int lr_attn_check_grid(const LrAttnPlan& p) {
+  if (p.grid > 0x7fffffffLL) LR_FAIL(LR_EUNSUPPORTED, "attention: %lld workgroups exceed the grid limit", p.grid);
+  return LR_OK;
+}
+
 // ---- varlen causal attention over packed qkv (RoPE applied) ----------------------------------------------------------------
 // The kernels (a requested variant 1 .. 5 asks for the kernel of the same number, 6 for HD64 with lse allowed, 0 = auto):
 //   GENERIC  any head_dim <= 256, scalar                                  (llama_attn.hip)
 //   MFMA128  head_dim 128, 128-row query tiles, reads a shared prefix     (llama_attn.hip)
 //   ROWS256  head_dim 128, 256-row query tiles over a device-built item list, shared prefix <= 64 (llama_attn256.hip)
-//   HD256    head_dim 256, no lse; with a shared prefix the kernel of llama_attn_hd256_prefix.hip (llama_attn_hd256.hip)
-//   HD64     head_dim 64, lse when asked for (variant 6) and no prefix; with a shared prefix the kernel of
-//            llama_attn_hd64_prefix.hip                                    (llama_attn_hd64.hip, _lse.hip)
-// MFMA128, HD256 and HD64 also have a one-query-row mode (lr_launch_attention_last, the pruned last layer).
+//   HD256    head_dim 256, no lse; one body (llama_attn_hd256_body.h) instantiated without a shared prefix in
+//            llama_attn_hd256.hip and with one in llama_attn_hd256_prefix.hip
+//   HD64     head_dim 64; one body (llama_attn_hd64_body.h) instantiated without a shared prefix in llama_attn_hd64.hip, with
+//            lse (variant 6, no prefix) in llama_attn_hd64_lse.hip and with a shared prefix in llama_attn_hd64_prefix.hip
+// MFMA128, HD256 and HD64 also have a one-query-row mode (lr_launch_attention_last, the pruned last layer); at HD256 and HD64
+// it is one more instantiation of the body, in the _prefix file.
 enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 3, LR_ATTN_HD256 = 4, LR_ATTN_HD64 = 5 };
 
 // Which kernel a request runs on -- the one place that decides it, for the five routes

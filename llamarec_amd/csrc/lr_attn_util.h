@@ -1,5 +1,6 @@
-// lr_attn_util.h -- device helpers shared by the MFMA flash-attention kernels (llama_attn.hip, llama_attn_hd256.hip):
-// LDS-DMA issued from inline asm, gfx950's lane-swap reductions, and max instructions on raw MFMA outputs.
+// lr_attn_util.h -- device helpers shared by the MFMA flash-attention kernels (llama_attn.hip, llama_attn_hd64_body.h,
+// llama_attn_hd256_body.h): LDS-DMA issued from inline asm, the workgroup-to-tile order, gfx950's lane-swap reductions, and
+// max instructions on raw MFMA outputs.
 #ifndef LR_ATTN_UTIL_H
 #define LR_ATTN_UTIL_H
 
@@ -31,6 +32,26 @@ __device__ __forceinline__ void fa_dma16(fa_int4 rsrc, const void* lds_wave_base
   const unsigned m0v = (unsigned)(size_t)((__attribute__((address_space(3))) const char*)lds_wave_base);
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(m0v), "v"(voff), "s"(rsrc)
                : "memory");
+}
+
+// workgroup -> ((prompt, head) pair, query tile) of the head_dim-64 and head_dim-256 kernels, variant 2's order: a pair per
+// dispatch stream (blockIdx.x & 7), heavy tiles first, the two lightest tiles of every pair at the end of the launch. The
+// launch holds 8 * ceil(n_pairs / 8) * max_qblocks workgroups; the caller returns when pair >= n_pairs. Neither result is
+// known to the compiler as wave-uniform yet.
+__device__ __forceinline__ void fa_tile_of_workgroup(int n_pairs, int max_qblocks, int& pair, int& qb) {
+  const int id = blockIdx.x, stream = id & 7, j = id >> 3;
+  const int ppx = (n_pairs + 7) >> 3;
+  const int n_light = min(max_qblocks, 2), n_heavy = max_qblocks - n_light;
+  int pl;
+  if (j < ppx * n_heavy) {
+    pl = j / n_heavy;
+    qb = max_qblocks - 1 - j % n_heavy;
+  } else {
+    const int j2 = j - ppx * n_heavy;
+    pl = j2 / n_light;
+    qb = n_light - 1 - j2 % n_light;
+  }
+  pair = pl * 8 + stream;
 }
 
 // x[lane] (op) x[lane ^ 16] and x[lane] (op) x[lane ^ 32] without the LDS crossbar: gfx950's row / half swaps

@@ -1,7 +1,9 @@
-"""Build-time checks on the gfx950 code objects of the shared-prefix and last-row attention kernels at head_dim 64 and 256
-(llama_attn_hd64_prefix.hip, llama_attn_hd256_prefix.hip; DESIGN.md sections 9 and 10), compiled with the Makefile's flags.
-From the code-object metadata: no scratch, no spilled register, and for the prefix kernels a VGPR count within the occupancy
-their pinned twins hold (three workgroups per CU at head_dim 64, two waves per SIMD at 256). From the instruction stream: the
+"""Build-time checks on the gfx950 code objects of the head_dim-64 and head_dim-256 attention kernels that share one body
+per head size (llama_attn_hd64_body.h, llama_attn_hd256_body.h; DESIGN.md sections 9 and 10): the pinned kernels
+(llama_attn_hd64.hip, llama_attn_hd256.hip) and the shared-prefix and last-row kernels (llama_attn_hd64_prefix.hip,
+llama_attn_hd256_prefix.hip), compiled with the Makefile's flags.
+From the code-object metadata: no scratch, no spilled register, and for the pinned and the prefix kernels a VGPR count within
+the occupancy they are built for (three workgroups per CU at head_dim 64, two waves per SIMD at 256). From the instruction stream: the
 LDS-DMA requests are inline asm that hipcc's counters do not see, so every s_barrier must have an `s_waitcnt vmcnt(0)` in front
 of it with no LDS-DMA between the two, and every write of M0 (the DMA's LDS base) must be followed by the DMA it was made for.
 Runs without a GPU (hipcc cross-compiles)."""
@@ -16,6 +18,8 @@ from tests.test_isa_checks import CSRC, FLAGS, HIPCC
 
 # kernel name fragment -> (source file, VGPR budget or None: spill-free is all the last-row kernels are held to)
 KERNELS = {
+    "attn_hd64_kernelILb0EE": ("llama_attn_hd64.hip", 168),                  # variant 5: 512 / 3 workgroups per CU
+    "attn_hd256_kernelILi1EE": ("llama_attn_hd256.hip", 256),                # variant 4: two waves per SIMD
     "attn_hd64_prefix_kernelILb0EE": ("llama_attn_hd64_prefix.hip", 168),    # 512 / 3 workgroups per CU, as variant 5
     "attn_hd64_prefix_kernelILb1EE": ("llama_attn_hd64_prefix.hip", None),
     "attn_hd256_prefix_kernelILb0EE": ("llama_attn_hd256_prefix.hip", 256),  # two waves per SIMD, as variant 4
@@ -38,9 +42,12 @@ def asm(tmp_path_factory):
 
 
 def test_each_file_holds_exactly_its_two_kernels(asm):
-    for src in sorted({s for s, _ in KERNELS.values()}):
+    """Each file holds the kernels the table gives it and no other: two in the prefix files, one in the pinned files."""
+    expected = {src: sorted(f for f, (s, _) in KERNELS.items() if s == src) for src in asm}
+    assert len(expected["llama_attn_hd64.hip"]) == 1 and len(expected["llama_attn_hd256.hip"]) == 1
+    for src, fragments in expected.items():
         names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", asm[src], flags=re.M)
-        assert len(names) == 2 and all(any(f in n for f in KERNELS) for n in names), (src, names)
+        assert len(names) == len(fragments) and all(any(f in n for n in names) for f in fragments), (src, names)
 
 
 @pytest.mark.parametrize("fragment", sorted(KERNELS))
