@@ -274,6 +274,38 @@ typedef struct LrRopeScaling {
  * these words from then on. NULL or kind 0: plain RoPE (the default). */
 int lr_llama_set_rope_scaling(lr_llama_t* h, const LrRopeScaling* s);
 
+/* Gemma-2 (model_type "gemma2") on a handle created with the Gemma arch (norm_style 1, mlp_act 1, embed_scale
+ * bf16(sqrt(hidden))). What it adds to Gemma v1's layer, per HF Gemma2Model:
+ *   attention   scores * attn_scale (query_pre_attn_scalar^-0.5: a config value, 1/16 for gemma-2-2b / 9b and 1/12 for 27b,
+ *               not derived from head_dim), then attn_softcap * tanh(. / attn_softcap) in fp32, then the causal mask and softmax
+ *   sandwich    h = attn(input_norm(x));  x = x + attn_out_norm(h);   h = mlp(post_norm(x));  x = x + mlp_out_norm(h)
+ *               -- all Gemma norms. NAMES: LrLlamaLayerWeights.post_norm stays the norm IN FRONT of the MLP, which is HF's
+ *               pre_feedforward_layernorm for Gemma-2; HF's post_attention_layernorm is attn_out_norm here and
+ *               post_feedforward_layernorm is mlp_out_norm.
+ *   head        final_softcap * tanh(logit / final_softcap) on the bf16 logit (HF's three bf16 steps), then fp32
+ * Sliding-window layers are NOT windowed: a caller keeps prompts within sliding_window tokens, where the window is the plain
+ * causal mask (llamarec_amd.llm refuses longer ones).
+ * Routing: with attn_softcap > 0, attention variants 0 and 4 at head_dim 256 run the soft-capped MFMA kernels (whole prompts,
+ * shared prefix, pruned last layer: same bits in all three); any other head_dim, or variant 1, runs the generic kernel with
+ * the cap (slow but correct: gemma-2-27b's head_dim 128); variants 2, 3, 5, 6 make the prefill return LR_EUNSUPPORTED.
+ * The MFMA kernels take caps up to 256 (their tanh has an ABSOLUTE error of about 1.7e-7 cap; Gemma-2's caps are 50 and 30); a
+ * larger attn_softcap runs the generic kernel at head_dim 256 too. With a cap, a shared prefix is kept only where the capped
+ * MFMA kernels run; everywhere else every prompt runs whole (same scores).
+ * LR_EINVAL, handle unchanged: a negative or non-finite cap or scale, a non-zero reserved word, one norm array without the
+ * other, a null layer pointer. LR_EUNSUPPORTED: any extension on a handle whose norm_style is not Gemma's (so no LoRA engine
+ * can exist on a handle that takes one); an attn_scale other
+ * than head_dim^-0.5 without an attn_softcap (the uncapped MFMA kernels have their scale compiled in). With an extension set,
+ * lr_llama_set_folded_norms (non-NULL) and lr_llama_lora_create return LR_EUNSUPPORTED. NULL: back to the plain layer. */
+typedef struct LrGemma2Ext {
+  float attn_softcap;        /* 0 = none */
+  float final_softcap;       /* 0 = none */
+  float attn_scale;          /* 0 = head_dim^-0.5 */
+  int32_t reserved[5];       /* must be zero */
+  const uint16_t* const* attn_out_norm;  /* HOST array [num_layers] of DEVICE bf16 [hidden], or NULL with mlp_out_norm */
+  const uint16_t* const* mlp_out_norm;   /* HOST array [num_layers] of DEVICE bf16 [hidden] */
+} LrGemma2Ext;
+int lr_llama_set_gemma2(lr_llama_t* h, const LrGemma2Ext* ext);
+
 /* Folded RMSNorm (optional, scoring path only). HF's layer computes  proj(norm_w * bf16(x * rstd))  with its own
  * read-and-write pass over the residual stream in front of q/k/v_proj and of gate/up_proj (LlamaRMSNorm, reached from
  * model/llm.py:89-100). Here the norm weight can be multiplied into the projection matrices once at load
@@ -436,12 +468,40 @@ int lr_attention_last_rows(const uint16_t* kv, const uint16_t* q_last, uint16_t*
                            const int32_t* seg_starts_host, int32_t S, int32_t prefix_len, int32_t num_heads,
                            int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* hip_stream);
 
+/* The same two with soft-capped scores, cap * tanh(q.k * scale / cap) (Gemma-2; exposed for parity tests). scale = 0 means
+ * head_dim^-0.5. cap = 0 (with scale 0 or head_dim^-0.5) routes to lr_attention_varlen_prefix / lr_attention_last_rows: same
+ * checks, same kernels, bit-identical results. cap > 0: the segment checks of those two, then variant 0 / 4 at head_dim 256
+ * with cap <= 256 run the soft-capped MFMA kernels, variant 1, a larger cap or any other head_dim (prefix_len must be 0
+ * there) the generic kernel, and
+ * variants 2, 3, 5, 6 return LR_EUNSUPPORTED; lr_attention_last_rows_softcap needs head_dim 256 and variant 0 / 4.
+ * A negative or non-finite scale or cap is LR_EINVAL. */
+int lr_attention_varlen_softcap(const uint16_t* qkv, uint16_t* out, const int32_t* seg_starts, const int32_t* seg_starts_host,
+                                int32_t S, int32_t prefix_len, int32_t num_heads, int32_t num_kv_heads, int32_t head_dim,
+                                float scale, float cap, int32_t variant, void* hip_stream);
+int lr_attention_last_rows_softcap(const uint16_t* kv, const uint16_t* q_last, uint16_t* out_last, const int32_t* seg_starts,
+                                   const int32_t* seg_starts_host, int32_t S, int32_t prefix_len, int32_t num_heads,
+                                   int32_t num_kv_heads, int32_t head_dim, float scale, float cap, int32_t variant,
+                                   void* hip_stream);
+/* Gemma-2's sandwich norm on [rows][d] bf16 DEVICE rows (exposed for parity tests), Gemma norms with fp32 statistics:
+ *   x  <- bf16( float(x) + float(bf16(h * rsqrt(mean(h^2) + eps) * (1 + w_out))) )       in place
+ *   xn  = bf16( x * rsqrt(mean(x^2) + eps) * (1 + w_next) )                               when w_next != NULL
+ * xn may alias h; w_next and xn are both NULL or both given. d: a multiple of 8, at most 8192 (LR_EUNSUPPORTED). */
+int lr_residual_postnorm_bf16(uint16_t* x, const uint16_t* h, const uint16_t* w_out, const uint16_t* w_next, uint16_t* xn,
+                              int32_t rows, int32_t d, float eps, void* hip_stream);
+/* The prefill's RMSNorm pass alone (exposed for parity tests and for timing the unfused form of the call above):
+ * out = norm(x) over [rows][d] bf16 DEVICE rows, norm_style 0 = Llama bf16(w * bf16(x * rstd)), 1 = Gemma
+ * bf16(x * rstd * (1 + w)); d a multiple of 8. lr_residual_postnorm_bf16 with w_next writes, bit for bit, what the same call
+ * without w_next followed by lr_rmsnorm_bf16(x, w_next, xn, ..., 1) writes. */
+int lr_rmsnorm_bf16(const uint16_t* x, const uint16_t* w, uint16_t* out, int32_t rows, int32_t d, float eps, int32_t norm_style,
+                    void* hip_stream);
+
 /* ------------------------------------------------------------------------------------------
  * Optional in-library kernel timing (HIP events on the caller's stream). Not part of the
  * reference's surface: it exists so a benchmark can report the measured duration and the
  * algorithmic work of each kernel family over its timed region.
  *   kinds: 0 gemm 256x256x64 (work = flops), 1 generic gemm (flops), 2 MFMA attention (flops),
- *          3 generic attention (flops), 4 LRU encoder (users), 5 item GEMM + top-K (flops)
+ *          3 generic attention (flops), 4 LRU encoder (users), 5 item GEMM + top-K (flops),
+ *          6 element-wise (work = bytes moved; Gemma-2's sandwich-norm kernel)
  * lr_profile_start/stop bracket the region (start allocates events: call it outside graph
  * capture); lr_profile_collect is valid after the stream has been synchronised.
  * ------------------------------------------------------------------------------------------ */

@@ -78,6 +78,18 @@ class LrRopeScaling(C.Structure):
     ]
 
 
+class LrGemma2Ext(C.Structure):
+    """include/llamarec_mi355x.h: LrGemma2Ext (lr_llama_set_gemma2)."""
+    _fields_ = [
+        ("attn_softcap", C.c_float),           # 0 = none
+        ("final_softcap", C.c_float),          # 0 = none
+        ("attn_scale", C.c_float),             # 0 = head_dim ** -0.5
+        ("reserved", C.c_int32 * 5),
+        ("attn_out_norm", C.POINTER(C.c_void_p)),   # host array [num_layers] of device pointers, or NULL with mlp_out_norm
+        ("mlp_out_norm", C.POINTER(C.c_void_p)),
+    ]
+
+
 class LrLlamaLayerWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("input_norm", "wqkv", "wo", "post_norm", "wgu", "wdown")]
 

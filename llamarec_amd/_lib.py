@@ -78,6 +78,7 @@ PROTOTYPES = {
     "lr_llama_set_variants": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "lr_llama_set_last_layer_pruning": (C.c_int, [C.c_void_p, C.c_int32]),
     "lr_llama_set_rope_scaling": (C.c_int, [C.c_void_p, C.POINTER(A.LrRopeScaling)]),
+    "lr_llama_set_gemma2": (C.c_int, [C.c_void_p, C.POINTER(A.LrGemma2Ext)]),
     "lr_fold_norm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "lr_llama_set_folded_norms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lr_llama_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
@@ -106,6 +107,14 @@ PROTOTYPES = {
                                              C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "lr_attention_last_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "lr_attention_varlen_softcap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p]),
+    "lr_attention_last_rows_softcap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32,
+                                                 C.c_void_p]),
+    "lr_residual_postnorm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_float, C.c_void_p]),
+    "lr_rmsnorm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),
     "lr_nf4_scratch_bytes": (C.c_size_t, [C.c_size_t]),
     "lr_nf4_roundtrip_bf16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.c_void_p]),

@@ -1,5 +1,6 @@
 // api_llama.hip -- C ABI entry points for stage 2 (declared in include/llamarec_mi355x.h):
 // one Llama prefill over packed prompts + verbalizer gather at each prompt's last token.
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -71,6 +72,58 @@ extern "C" int lr_llama_set_rope_scaling(lr_llama_t* h, const LrRopeScaling* s) 
   return LR_OK;
 }
 
+static bool finite_nonneg(float v) { return v >= 0.f && v < __builtin_inff(); }   // false for NaN too
+
+extern "C" int lr_llama_set_gemma2(lr_llama_t* h, const LrGemma2Ext* e) {
+  if (!h) LR_FAIL(LR_EINVAL, "lr_llama_set_gemma2: null handle");
+  const int L = h->cfg.num_layers;
+  const uint16_t **an = nullptr, **mn = nullptr;
+  float scale = 0.f;
+  if (e) {   // every check before the handle changes
+    if (!finite_nonneg(e->attn_softcap) || !finite_nonneg(e->final_softcap) || !finite_nonneg(e->attn_scale))
+      LR_FAIL(LR_EINVAL, "lr_llama_set_gemma2: attn_softcap=%g final_softcap=%g attn_scale=%g (finite and >= 0)",
+              (double)e->attn_softcap, (double)e->final_softcap, (double)e->attn_scale);
+    for (int i = 0; i < 5; ++i)
+      if (e->reserved[i]) LR_FAIL(LR_EINVAL, "lr_llama_set_gemma2: reserved word %d is not zero", i);
+    if ((e->attn_out_norm == nullptr) != (e->mlp_out_norm == nullptr))
+      LR_FAIL(LR_EINVAL, "lr_llama_set_gemma2: give both out-norm arrays or neither");
+    if (e->attn_out_norm)
+      for (int l = 0; l < L; ++l)
+        if (!e->attn_out_norm[l] || !e->mlp_out_norm[l]) LR_FAIL(LR_EINVAL, "lr_llama_set_gemma2: layer %d has a null out-norm", l);
+    // any extension: a Gemma handle. (Such a handle has no LoRA engine -- lr_llama_lora_create refuses it -- so no engine
+    // can be left running uncapped training attention beside a capped prefill.)
+    if (h->arch.norm_style != 1)
+      LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_gemma2: caps and out-norms need a handle with the Gemma norm (norm_style %d)",
+              h->arch.norm_style);
+    const float own = 1.0f / sqrtf((float)h->cfg.head_dim);
+    scale = e->attn_scale > 0.f ? e->attn_scale : own;
+    if (!(e->attn_softcap > 0.f) && scale != own)
+      LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_gemma2: attn_scale %g without a soft cap (the uncapped kernels scale by "
+              "head_dim^-0.5 = %g)", (double)scale, (double)own);
+    if (h->wqkv_folded) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_gemma2: the handle has folded norms");
+    if (e->attn_out_norm) {
+      an = (const uint16_t**)malloc(sizeof(void*) * L);
+      mn = (const uint16_t**)malloc(sizeof(void*) * L);
+      if (!an || !mn) {
+        free(an);
+        free(mn);
+        LR_FAIL(LR_EINVAL, "lr_llama_set_gemma2: out of host memory");
+      }
+      memcpy(an, e->attn_out_norm, sizeof(void*) * L);
+      memcpy(mn, e->mlp_out_norm, sizeof(void*) * L);
+    }
+  }
+  free(h->attn_out_norm);
+  free(h->mlp_out_norm);
+  h->attn_out_norm = an;
+  h->mlp_out_norm = mn;
+  h->gemma2 = e ? 1 : 0;
+  h->attn_softcap = e ? e->attn_softcap : 0.f;
+  h->final_softcap = e ? e->final_softcap : 0.f;
+  h->attn_scale = (e && e->attn_softcap > 0.f) ? scale : 0.f;
+  return LR_OK;
+}
+
 extern "C" int lr_llama_set_last_layer_pruning(lr_llama_t* h, int32_t enable) {
   if (!h) LR_FAIL(LR_EINVAL, "lr_llama_set_last_layer_pruning: null handle");
   h->prune_last = enable ? 1 : 0;
@@ -82,6 +135,8 @@ extern "C" void lr_llama_destroy(lr_llama_t* h) {
   free(h->layers);
   free(h->wqkv_folded);
   free(h->wgu_folded);
+  free(h->attn_out_norm);
+  free(h->mlp_out_norm);
   free(h);
 }
 
@@ -97,6 +152,8 @@ extern "C" int lr_llama_set_folded_norms(lr_llama_t* h, const uint16_t* const* w
   if ((h->arch.norm_style != 0 || h->arch.mlp_act != 0) && (wqkv_folded || wgu_folded))
     LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: Llama arch only (a Gemma norm (1 + w) cannot be folded into bf16 "
             "weights at HF's rounding, and the GeGLU epilogue takes no row scale)");
+  if (h->gemma2 && (wqkv_folded || wgu_folded))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: not with a Gemma-2 extension (lr_llama_set_gemma2)");
   free(h->wqkv_folded);
   free(h->wgu_folded);
   h->wqkv_folded = h->wgu_folded = nullptr;
@@ -194,7 +251,7 @@ static int plan_batch(const lr_llama_t* h, const int32_t* cu_host, int B, int P,
   if (P < 0 || (P > 0 && P >= minT))
     LR_FAIL(LR_EINVAL, "llama prefill: shared prefix of %d tokens, shortest prompt has %d (every prompt keeps >= 1 own token)",
             P, minT);
-  if (B == 1 || !lr_attention_reads_prefix(h->attn_variant, c.head_dim)) P = 0;
+  if (B == 1 || !lr_attention_reads_prefix(h->attn_variant, c.head_dim, h->attn_softcap)) P = 0;
   const int n_in = cu_host[B];
   out->ws = carve(c, n_in, B, (char*)workspace);
   if (out->ws.total > workspace_bytes)
@@ -232,14 +289,18 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
   const int epi_mlp = h->arch.mlp_act == 1 ? LR_EPI_GEGLU : LR_EPI_SWIGLU;
   const int gv = h->gemm_variant, pv = b_row_gemm_variant(h, B);
   LrAttnKernel attn_kernel;
-  LR_RUN(lr_resolve_attention({.variant = h->attn_variant, .hd = hd, .prefix_len = P, .have_items_ws = true, .prefill = true},
-                              &attn_kernel));
+  // Gemma-2 (lr_llama_set_gemma2): soft-capped scores, and o_proj / down_proj results normalised before they join the residual
+  const float a_scale = h->attn_scale, a_cap = h->attn_softcap;
+  const bool sandwich = h->attn_out_norm != nullptr;
+  LR_RUN(lr_resolve_attention({.variant = h->attn_variant, .hd = hd, .prefix_len = P, .have_items_ws = true, .prefill = true,
+                               .cap = a_cap}, &attn_kernel));
   // the MFMA kernels over ALL rows (188 us for 14.8 k tokens, 16 us for one prompt) beat the scalar kernel over the B last
   // rows (459 / 295 us), so a pruned last layer attends everything and keeps the last rows
   const bool attn_mfma = (hd == 128 && attn_kernel != LR_ATTN_GENERIC) || attn_kernel == LR_ATTN_HD256 ||
                          attn_kernel == LR_ATTN_HD64;
   const LrAttnArgs attn = {.qkv = ws.qkv, .out = ws.att, .cu = ws.seg_start, .cu_host = plan.seg_host.data(), .S = S,
-                           .n_tok = n, .nh = nh, .nkv = nkv, .hd = hd, .prefix_len = P, .items_ws = ws.attn_items};
+                           .n_tok = n, .nh = nh, .nkv = nkv, .hd = hd, .prefix_len = P, .items_ws = ws.attn_items,
+                           .scale = a_scale, .cap = a_cap};
   struct LayerRows { u16 *att, *x, *xn, *hmid; int M, gemm_variant; };   // what o_proj and the MLP run on
   const LayerRows full = {ws.att, ws.x, ws.xn, ws.hmid, n, gv}, last = {ws.att_last, ws.x_last, ws.xn_last, ws.h_last, B, pv};
   auto rope = [&](const int32_t* tok_pos, int rot_cols) {
@@ -278,7 +339,8 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
       LR_RUN(lr_launch_gather_rows(ws.xn, ws.last_rows, B, d, ws.xn_last, st));
       LR_RUN(lr_launch_gemm({.A = ws.xn_last, .B = w.wqkv, .C = ws.q_last, .M = B, .N = q_w, .K = d, .epi = LR_EPI_ROPE,
                              .variant = pv, .rope = rope(ws.last_pos, q_w), .splitk = ws.splitk}, st));
-      LR_RUN(lr_launch_attention_last(ws.qkv, ws.q_last, ws.att_last, attn.cu, attn.cu_host, S, n, nh, nkv, hd, st, P));
+      LR_RUN(lr_launch_attention_last(ws.qkv, ws.q_last, ws.att_last, attn.cu, attn.cu_host, S, n, nh, nkv, hd, st, P, a_scale,
+                                      a_cap));
     } else {
       LR_RUN(lr_launch_gemm({.A = folded ? ws.x : ws.xn, .B = folded ? h->wqkv_folded[l] : w.wqkv, .C = ws.qkv, .M = n,
                              .N = q_w + kv_w, .K = d, .epi = LR_EPI_ROPE, .variant = gv, .rope = rope(ws.tok_pos, q_w + kv_w / 2),
@@ -294,7 +356,7 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
         LR_RUN(lr_launch_attention(attn, attn_kernel, st));
         LR_RUN(lr_launch_gather_rows(ws.att, ws.last_rows, B, nh * hd, ws.att_last, st));
       } else if (!last_q_only) {
-        LR_RUN(lr_launch_attention_rows(ws.qkv, ws.att_last, cu, B, ws.last_rows, B, nh, nkv, hd, st));
+        LR_RUN(lr_launch_attention_rows(ws.qkv, ws.att_last, cu, B, ws.last_rows, B, nh, nkv, hd, st, a_scale, a_cap));
       }
       LR_RUN(lr_launch_gather_rows(ws.x, ws.last_rows, B, d, ws.x_last, st));
       ws.compact = true;   // and this was the last layer
@@ -302,6 +364,22 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
     // o_proj and the MLP: on every row, or -- pruned last layer -- on the B compact rows (b_row_gemm_variant, never folded)
     const LayerRows& r = last_pruned ? last : full;
     const bool fold_mlp = folded && !last_pruned;
+    if (sandwich) {
+      // Both products store plainly into r.xn, which is free by then (its last reader was the QKV, resp. the gate-up, product;
+      // the split-K form of the latency mode reduces without a residual), and one element-wise kernel per product normalises
+      // that row, adds it to r.x in place and writes the norm the next product reads back into r.xn. Never folded.
+      LR_RUN(lr_launch_gemm({.A = r.att, .B = w.wo, .C = r.xn, .M = r.M, .N = d, .K = nh * hd, .variant = r.gemm_variant,
+                             .splitk = ws.splitk}, st));
+      LR_RUN(lr_launch_residual_postnorm(r.x, r.xn, h->attn_out_norm[l], w.post_norm, r.xn, r.M, d, c.rms_eps, st));
+      LR_RUN(lr_launch_gemm({.A = r.xn, .B = w.wgu, .C = r.hmid, .M = r.M, .N = 2 * f, .K = d, .epi = epi_mlp,
+                             .variant = r.gemm_variant, .splitk = ws.splitk}, st));
+      LR_RUN(lr_launch_gemm({.A = r.hmid, .B = w.wdown, .C = r.xn, .M = r.M, .N = d, .K = f, .variant = r.gemm_variant,
+                             .splitk = ws.splitk}, st));
+      const u16* next_norm = l + 1 < c.num_layers ? h->layers[l + 1].input_norm : nullptr;
+      LR_RUN(lr_launch_residual_postnorm(r.x, r.xn, h->mlp_out_norm[l], next_norm, r.xn, r.M, d, c.rms_eps, st));
+      input_normed = next_norm != nullptr;
+      continue;
+    }
     bool post_normed = false;   // a split-K product's reduce pass also writes the RMSNorm that follows (same bits)
     LR_RUN(lr_launch_gemm({.A = r.att, .B = w.wo, .C = r.x, .R = r.x, .M = r.M, .N = d, .K = nh * hd, .epi = LR_EPI_RESIDUAL,
                            .variant = r.gemm_variant, .splitk = ws.splitk,
@@ -331,7 +409,7 @@ static int prefill_head(lr_llama_t* h, const int32_t* packed_ids, const int32_t*
   LR_RUN(run_body(h, packed_ids, cu_seqlens, cu_seqlens_host, B, prefix_len, workspace, workspace_bytes, st, &ws));
   return lr_launch_head(ws.compact ? ws.x_last : ws.x, ws.compact ? nullptr : ws.last_rows, h->final_norm, h->lm_head,
                         class_ids, B, C, h->cfg.hidden_size, h->cfg.rms_eps, out, h->cfg.vocab_size, st, ws.prefix_bad,
-                        h->arch.norm_style);
+                        h->arch.norm_style, h->final_softcap);
 }
 
 extern "C" int lr_llama_prefill_verbalize(lr_llama_t* h, const int32_t* packed_ids, const int32_t* cu_seqlens,
@@ -531,6 +609,86 @@ extern "C" int lr_attention_last_rows(const uint16_t* kv, const uint16_t* q_last
                               variant));
   return lr_launch_attention_last(kv, q_last, out_last, seg_starts, seg_starts_host, S, seg_starts_host[S], num_heads,
                                   num_kv_heads, head_dim, (hipStream_t)hip_stream, prefix_len);
+}
+
+// cap = 0: the uncapped entry point's own path (and bits); a scale other than head_dim^-0.5 then has no kernel
+static int check_softcap_request(const char* who, float scale, float cap, int hd, bool* capped) {
+  if (!finite_nonneg(scale) || !finite_nonneg(cap)) LR_FAIL(LR_EINVAL, "%s: scale %g cap %g (finite and >= 0)", who, (double)scale, (double)cap);
+  *capped = cap > 0.f;
+  if (!*capped && scale > 0.f && hd > 0 && scale != 1.0f / sqrtf((float)hd))
+    LR_FAIL(LR_EUNSUPPORTED, "%s: scale %g without a cap (the uncapped kernels scale by head_dim^-0.5)", who, (double)scale);
+  return LR_OK;
+}
+
+extern "C" int lr_attention_varlen_softcap(const uint16_t* qkv, uint16_t* out, const int32_t* seg_starts,
+                                           const int32_t* seg_starts_host, int32_t S, int32_t prefix_len, int32_t num_heads,
+                                           int32_t num_kv_heads, int32_t head_dim, float scale, float cap, int32_t variant,
+                                           void* hip_stream) {
+  const char* who = "lr_attention_varlen_softcap";
+  bool capped;
+  LR_RUN(check_softcap_request(who, scale, cap, head_dim, &capped));
+  if (!capped)
+    return lr_attention_varlen_prefix(qkv, out, seg_starts, seg_starts_host, S, prefix_len, num_heads, num_kv_heads, head_dim,
+                                      variant, hip_stream);
+  if (!qkv || !out || !seg_starts) LR_FAIL(LR_EINVAL, "%s: null pointer", who);
+  if (!seg_starts_host || S < 1 || prefix_len < 0 || num_heads < 1 || num_kv_heads < 1 || head_dim < 1 || head_dim > 256)
+    LR_FAIL(LR_EINVAL, "%s: bad argument", who);
+  LR_RUN(lr_check_segments(seg_starts_host, S, who));
+  if (num_heads % num_kv_heads != 0)
+    LR_FAIL(LR_EINVAL, "%s: num_heads %d not a multiple of num_kv_heads %d", who, num_heads, num_kv_heads);
+  if (prefix_len > 0 && (S < 2 || seg_starts_host[1] != prefix_len))
+    LR_FAIL(LR_EINVAL, "%s: segment 0 has %d rows, the shared prefix %d (and a prompt must follow it)", who, seg_starts_host[1],
+            prefix_len);
+  LrAttnKernel kernel;
+  LR_RUN(lr_resolve_attention({.variant = variant, .hd = head_dim, .prefix_len = prefix_len, .prefill = true, .cap = cap},
+                              &kernel));
+  const float sc = scale > 0.f ? scale : 1.0f / sqrtf((float)head_dim);
+  return lr_launch_attention({.qkv = qkv, .out = out, .cu = seg_starts, .cu_host = seg_starts_host, .S = S,
+                              .n_tok = seg_starts_host[S], .nh = num_heads, .nkv = num_kv_heads, .hd = head_dim,
+                              .prefix_len = prefix_len, .scale = sc, .cap = cap}, kernel, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_attention_last_rows_softcap(const uint16_t* kv, const uint16_t* q_last, uint16_t* out_last,
+                                              const int32_t* seg_starts, const int32_t* seg_starts_host, int32_t S,
+                                              int32_t prefix_len, int32_t num_heads, int32_t num_kv_heads, int32_t head_dim,
+                                              float scale, float cap, int32_t variant, void* hip_stream) {
+  const char* who = "lr_attention_last_rows_softcap";
+  bool capped;
+  LR_RUN(check_softcap_request(who, scale, cap, head_dim, &capped));
+  if (!capped)
+    return lr_attention_last_rows(kv, q_last, out_last, seg_starts, seg_starts_host, S, prefix_len, num_heads, num_kv_heads,
+                                  head_dim, variant, hip_stream);
+  if (!kv || !q_last || !out_last || !seg_starts) LR_FAIL(LR_EINVAL, "%s: null pointer", who);
+  if (!seg_starts_host || S < 1 || prefix_len < 0 || num_heads < 1 || num_kv_heads < 1) LR_FAIL(LR_EINVAL, "%s: bad argument", who);
+  LR_RUN(lr_check_segments(seg_starts_host, S, who));
+  if (num_heads % num_kv_heads != 0)
+    LR_FAIL(LR_EINVAL, "%s: num_heads %d not a multiple of num_kv_heads %d", who, num_heads, num_kv_heads);
+  if (prefix_len > 0 && (S < 2 || seg_starts_host[1] != prefix_len))
+    LR_FAIL(LR_EINVAL, "%s: segment 0 has %d rows, the shared prefix %d (and a prompt must follow it)", who, seg_starts_host[1],
+            prefix_len);
+  LrAttnKernel kernel;
+  LR_RUN(lr_resolve_attention({.variant = variant, .hd = head_dim, .prefix_len = prefix_len, .prefill = true, .cap = cap},
+                              &kernel));
+  if (kernel != LR_ATTN_HD256)
+    LR_FAIL(LR_EUNSUPPORTED, "%s: variant %d at head_dim %d has no one-row mode with a cap (0 / 4 at 256)", who, variant, head_dim);
+  return lr_launch_attention_last(kv, q_last, out_last, seg_starts, seg_starts_host, S, seg_starts_host[S], num_heads,
+                                  num_kv_heads, head_dim, (hipStream_t)hip_stream, prefix_len,
+                                  scale > 0.f ? scale : 1.0f / sqrtf((float)head_dim), cap);
+}
+
+extern "C" int lr_residual_postnorm_bf16(uint16_t* x, const uint16_t* hrows, const uint16_t* w_out, const uint16_t* w_next,
+                                         uint16_t* xn, int32_t rows, int32_t d, float eps, void* hip_stream) {
+  if (!x || !hrows || !w_out || rows < 1 || (w_next == nullptr) != (xn == nullptr) || !(eps >= 0.f) || !(eps < __builtin_inff()))
+    LR_FAIL(LR_EINVAL, "lr_residual_postnorm_bf16: bad argument (w_next and xn go together)");
+  return lr_launch_residual_postnorm(x, hrows, w_out, w_next, xn, rows, d, eps, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_rmsnorm_bf16(const uint16_t* x, const uint16_t* w, uint16_t* out, int32_t rows, int32_t d, float eps,
+                               int32_t norm_style, void* hip_stream) {
+  if (!x || !w || !out || rows < 1 || d < 8 || d % 8 != 0 || (norm_style != 0 && norm_style != 1) || !(eps >= 0.f) ||
+      !(eps < __builtin_inff()))
+    LR_FAIL(LR_EINVAL, "lr_rmsnorm_bf16: bad argument (rows %d, d %d a multiple of 8, norm_style %d)", rows, d, norm_style);
+  return lr_launch_rmsnorm(x, w, out, rows, d, eps, nullptr, (hipStream_t)hip_stream, norm_style);
 }
 
 extern "C" size_t lr_attention_workspace_bytes(int32_t total_tokens, int32_t B, int32_t num_heads) {

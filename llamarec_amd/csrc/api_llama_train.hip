@@ -183,6 +183,8 @@ extern "C" int lr_llama_lora_create_ex(lr_llama_t* base, const LrLlamaWeightsTDe
   if (rc) return rc;
   if (base->arch.norm_style != 0 || base->arch.mlp_act != 0 || base->arch.embed_scale != 1.0f)
     LR_FAIL(LR_EUNSUPPORTED, "lr_llama_lora_create: fine-tuning needs a Llama base (no GeGLU / Gemma-norm backward)");
+  if (base->gemma2)
+    LR_FAIL(LR_EUNSUPPORTED, "lr_llama_lora_create: fine-tuning needs a Llama base (no soft-cap / sandwich-norm backward)");
   if (!wt || !wt->layers || !wt->lm_head_t || !state || !out) LR_FAIL(LR_EINVAL, "lr_llama_lora_create: null argument");
   const LrLlamaConfig& c = base->cfg;
   for (int l = 0; l < c.num_layers; ++l) {

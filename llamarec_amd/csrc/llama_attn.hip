@@ -42,7 +42,7 @@ typedef u16 u16x8 __attribute__((ext_vector_type(8)));
 // =============================================================================================
 __global__ __launch_bounds__(256) void attn_generic_kernel(const u16* qkv, u16* out, const int32_t* cu, int B,
                                                            int n_tok, int nh, int nkv, int hd,
-                                                           const int32_t* q_rows, float* lse) {
+                                                           const int32_t* q_rows, float* lse, float scale_arg, float cap) {
   __shared__ float qs[4][256];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int item = blockIdx.x * 4 + wave;  // (token, head)
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void attn_generic_kernel(const u16* qkv, u16* 
   const u16* qp = qkv + (size_t)tok * stride + h * hd;
   for (int d = lane; d < hd; d += 64) qs[wave][d] = bf2f(qp[d]);
   __builtin_amdgcn_wave_barrier();
-  const float scale = 1.0f / sqrtf((float)hd);
+  const float scale = scale_arg > 0.f ? scale_arg : 1.0f / sqrtf((float)hd);   // 0: the head_dim's own
   float m = -__builtin_inff(), l = 0.f;
   float o[4] = {0.f, 0.f, 0.f, 0.f};  // dims lane, lane+64, lane+128, lane+192
   for (int k0 = 0; k0 <= pos; k0 += 64) {
@@ -73,6 +73,7 @@ __global__ __launch_bounds__(256) void attn_generic_kernel(const u16* qkv, u16* 
       float acc = 0.f;
       for (int d = 0; d < hd; ++d) acc = __builtin_fmaf(qs[wave][d], bf2f(kp[d]), acc);
       s = acc * scale;
+      if (cap > 0.f) s = cap * tanhf(s / cap);   // Gemma-2's soft cap, fp32, before masking and the maximum
     }
     float mx = s;
 #pragma unroll
@@ -526,12 +527,12 @@ extern "C" int lr_debug_attn_stamps(unsigned long long* out, int n) {
 
 // attention for a list of query tokens only (the last layer needs just each prompt's last token)
 int lr_launch_attention_rows(const u16* qkv, u16* out, const int32_t* cu, int B, const int32_t* q_rows,
-                             int n_rows, int nh, int nkv, int hd, hipStream_t st) {
+                             int n_rows, int nh, int nkv, int hd, hipStream_t st, float scale, float cap) {
   if (n_rows <= 0) return LR_OK;
   if (hd > 256) LR_FAIL(LR_EUNSUPPORTED, "attention: head_dim %d > 256", hd);
   const int items = n_rows * nh;
   hipLaunchKernelGGL(attn_generic_kernel, dim3((items + 3) / 4), dim3(256), 0, st, qkv, out, cu, B, n_rows,
-                     nh, nkv, hd, q_rows, (float*)nullptr);
+                     nh, nkv, hd, q_rows, (float*)nullptr, scale, cap);
   LR_CHECK_LAUNCH("attn_generic_kernel(rows)");
   return LR_OK;
 }
@@ -540,6 +541,19 @@ int lr_launch_attention_rows(const u16* qkv, u16* out, const int32_t* cu, int B,
 // the table in llama_kernels.h
 int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
   const int hd = r.hd;
+  if (r.cap > 0.f) {   // the short table of llama_kernels.h
+    if (r.want_lse) LR_FAIL(LR_EINVAL, "attention: no lse with a soft cap");
+    if (r.variant == 2 || r.variant == 3 || r.variant == 5 || r.variant == 6)
+      LR_FAIL(LR_EUNSUPPORTED, "attention variant %d has no soft-capped form (0 / 4 at head_dim 256, 1 generic)", r.variant);
+    if (r.variant != 0 && r.variant != 1 && r.variant != 4) LR_FAIL(LR_EINVAL, "attention: unknown variant %d", r.variant);
+    if (r.variant != 1 && hd == 256 && r.cap <= LR_SOFTCAP_MFMA_MAX) {
+      *kernel = LR_ATTN_HD256;
+      return LR_OK;
+    }
+    if (r.prefix_len > 0) LR_FAIL(LR_EUNSUPPORTED, "attention: the generic kernel reads no shared prefix (soft cap, head_dim %d)", hd);
+    *kernel = LR_ATTN_GENERIC;
+    return LR_OK;
+  }
   switch (r.variant) {
     case 0:
       if (hd == 128) *kernel = (r.have_items_ws && !r.prefill) ? LR_ATTN_ROWS256 : LR_ATTN_MFMA128;
@@ -586,10 +600,15 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
   const int32_t* cu_host = a.cu_host;
   const int B = a.S, n_tok = a.n_tok, nh = a.nh, nkv = a.nkv, hd = a.hd, prefix_len = a.prefix_len;
   if (n_tok <= 0 || B <= 0) return LR_OK;
+  if (a.cap < 0.f || a.scale < 0.f || a.cap != a.cap || a.scale != a.scale)
+    LR_FAIL(LR_EINVAL, "attention: scale %g cap %g", (double)a.scale, (double)a.cap);
+  if (a.cap > 0.f && kernel != LR_ATTN_HD256 && kernel != LR_ATTN_GENERIC)
+    LR_FAIL(LR_EUNSUPPORTED, "attention: kernel %d has no soft-capped form", (int)kernel);
   if (kernel == LR_ATTN_ROWS256) return lr_launch_attention256(a, st);
   if (nh % nkv != 0) LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
   if (kernel == LR_ATTN_HD256) {
     if (prefix_len < 0 || a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-256 MFMA kernel writes no lse (prefix %d)", prefix_len);
+    if (a.cap > 0.f) return lr_launch_attention_hd256_softcap(a, st);
     return prefix_len > 0 ? lr_launch_attention_hd256_prefix(a, st) : lr_launch_attention_hd256(a, st);
   }
   if (kernel == LR_ATTN_HD64) {
@@ -633,7 +652,7 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
     if (hd > 256) LR_FAIL(LR_EUNSUPPORTED, "attention: head_dim %d > 256", hd);
     const int items = n_tok * nh;
     hipLaunchKernelGGL(attn_generic_kernel, dim3((items + 3) / 4), dim3(256), 0, st, a.qkv, a.out, a.cu, B,
-                       n_tok, nh, nkv, hd, (const int32_t*)nullptr, a.lse);
+                       n_tok, nh, nkv, hd, (const int32_t*)nullptr, a.lse, a.scale, a.cap);
     LR_CHECK_LAUNCH("attn_generic_kernel");
   }
   return LR_OK;
@@ -642,8 +661,13 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
 // The pruned last layer (head_dim 128 here, 64 and 256 in the _prefix files of their kernels): kv = [n_tok][2 * nkv * hd] (K | V of every row), q_last = [prompts][nh * hd] rotated query rows
 // of each prompt's last token, out_last = [prompts][nh * hd]. cu / cu_host / prefix_len as lr_launch_attention.
 int lr_launch_attention_last(const u16* kv, const u16* q_last, u16* out_last, const int32_t* cu, const int32_t* cu_host,
-                             int S, int n_tok, int nh, int nkv, int hd, hipStream_t st, int prefix_len) {
+                             int S, int n_tok, int nh, int nkv, int hd, hipStream_t st, int prefix_len, float scale, float cap) {
   if (n_tok <= 0 || S <= 0) return LR_OK;
+  if (cap > 0.f) {
+    if (hd != 256 || nkv < 1 || nh % nkv != 0)
+      LR_FAIL(LR_EUNSUPPORTED, "attention (last rows, soft cap): head_dim 256 and nh %% nkv == 0 only");
+    return lr_launch_attention_hd256_softcap_last(kv, q_last, out_last, cu, cu_host, S, n_tok, nh, nkv, prefix_len, scale, cap, st);
+  }
   if ((hd != 128 && hd != 64 && hd != 256) || nkv < 1 || nh % nkv != 0)
     LR_FAIL(LR_EUNSUPPORTED, "attention (last rows): head_dim 64, 128 or 256 and nh %% nkv == 0 only");
   if (hd == 64) return lr_launch_attention_hd64_last(kv, q_last, out_last, cu, cu_host, S, n_tok, nh, nkv, prefix_len, st);

@@ -1,14 +1,15 @@
 // llama_attn_hd256_body.h -- the one text of the head_dim-256 MFMA attention (llama_attn_hd256.hip: read its header first),
-// attn_hd256_body<HPW, LASTQ, PREFIX>, inlined into four kernels in two translation units and one diagnostic build:
+// attn_hd256_body<HPW, LASTQ, PREFIX, SOFTCAP>, inlined into seven kernels in three translation units and one diagnostic build:
 //   <1, false, false>  attn_hd256_kernel<1>, attention variant 4                                 (llama_attn_hd256.hip)
 //   <2, false, false>  attn_hd256_kernel<2>, two heads of one KV head per workgroup: an A/B arm  (tools/diag/attn_hd256_mqa_ab.hip)
 //   <1, false, true>   attn_hd256_prefix_kernel<false>, shared prompt prefix                     (llama_attn_hd256_prefix.hip)
 //   <1, true, true>    attn_hd256_prefix_kernel<true>, one query row per prompt                  (llama_attn_hd256_prefix.hip)
+//   the same three <1, ., ., true> with soft-capped scores (Gemma-2)                             (llama_attn_hd256_softcap.hip)
 // The modes differ in where a K / V row and a query row live and in which rows a tile owns. Each such place picks its
 // expression at compile time (`if constexpr`, or a condition on the template parameters alone): without PREFIX no shared-prefix
 // length is ever computed, compared or added, so variant 4's instructions do not depend on the optimiser folding a zero away.
 // The block walk, the masking, the per-row deferred maximum, bf16 P into both products and the ones-MFMA row sum are common to
-// all four, which is what makes a row's bits the same in every mode.
+// all of them, which is what makes a row's bits the same in every mode of one SOFTCAP setting.
 #ifndef LLAMA_ATTN_HD256_BODY_H
 #define LLAMA_ATTN_HD256_BODY_H
 
@@ -49,9 +50,18 @@ __device__ __forceinline__ int fa4_vswz(int row) { return ((row & 3) << 2) | ((r
 // LASTQ (with PREFIX; prefix_len may be 0): `qkv` is the [rows][2 nkv hd] K | V projection, q_rows_last one rotated query row
 //   per prompt. A workgroup = one (prompt, head) walks the prompt's key blocks, all eight waves staging and wave 0 computing
 //   with every lane column holding the query at position T - 1; one output row per prompt.
-template <int HPW, bool LASTQ, bool PREFIX>
+// SOFTCAP (Gemma-2): the fp32 score s out of the MFMA becomes cap * tanh(s * scale / cap) before masking and the row maximum,
+//   with scale and cap run-time values (without SOFTCAP neither is read: the scale is the compile-time 1/16). The capped score
+//   is kept in the exp2 domain, y = cap log2(e) (1 - 2 / (1 + exp2(2 s scale log2(e) / cap))): a multiply, v_exp_f32, an add,
+//   v_rcp_f32 and an fma per score. exp2 overflowing to +inf gives rcp = 0 and y = +cap log2(e), underflowing to 0 gives
+//   -cap log2(e): no NaN at any finite s. The absolute error of the quotient form is ~1e-7 (one ulp of 1), times cap log2(e)
+//   <= 1e-5 for cap 50, against a bf16 step of P of 2^-8. The running maximum stays (|y| <= cap log2(e) would allow a fixed
+//   reference, but exp2(-2 cap log2(e)) is a denormal at cap 50 and can zero a row's sum).
+template <int HPW, bool LASTQ, bool PREFIX, bool SOFTCAP = false>
 __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const int32_t* cu, int prefix_len, int nh, int nkv,
-                                                int max_qblocks, int n_pairs, const u16* q_rows_last) {
+                                                int max_qblocks, int n_pairs, const u16* q_rows_last, float scale = 0.f,
+                                                float cap = 0.f) {
+  static_assert(!SOFTCAP || HPW == 1, "soft-capped scores: one head per workgroup");
   static_assert(HPW == 1 || (HPW == 2 && !PREFIX && !LASTQ), "two heads per workgroup: whole tiles without a shared prefix only");
   static_assert(!LASTQ || PREFIX, "the last-row mode reads a shared prefix");
   constexpr int WPH = FA4_WAVES / HPW;   // waves per head
@@ -137,6 +147,9 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
   const bool wave_live = LASTQ ? wave == 0 : (wave_q0 < T && (!PREFIX || wave_q_last >= P));
   const float sl2 = 0.0625f * 1.4426950408889634f;  // 1/sqrt(256) * log2(e)
   const float inv_sl2 = 1.0f / sl2;
+  // SOFTCAP: exp2 argument per raw score, and cap in the exp2 domain (wave-uniform; named by SOFTCAP expressions only)
+  const float cap_a = SOFTCAP ? 2.0f * 1.4426950408889634f * scale / cap : 0.f;
+  const float cap_l2 = SOFTCAP ? cap * 1.4426950408889634f : 0.f;
 
   // ---- DMA staging: a tile is 32 pieces of 1 KiB (2 rows x 512 B, lane-linear in LDS); wave w moves pieces 4w..4w+3 of
   // K and of V. Rows past the prompt's end are range-checked to zero by the per-block buffer descriptor (those keys are
@@ -240,6 +253,15 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) st[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[ks & 1][nt], qf[ks], st[nt], 0, 0, 0);
       }
+      if constexpr (SOFTCAP) {   // st <- cap log2(e) tanh(st scale / cap), every key of the block (masking follows)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float e = __builtin_amdgcn_exp2f(st[nt][r] * cap_a);
+            st[nt][r] = __builtin_fmaf(__builtin_amdgcn_rcpf(1.0f + e), -2.0f * cap_l2, cap_l2);
+          }
+      }
       // ---- online softmax (lane-local row), P packed as the B operand of O^T = V^T P^T
       bf16x8 pa[2];
       const bool diag = (kb * FA4_KB + FA4_KB - 1) > wave_q0;   // the block needs masking (wave-uniform)
@@ -265,7 +287,9 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
       if (__any(mx > mthr)) {
         const float rmx = fa_max_xor16_32(mx);
         const bool grew = rmx > mthr;
-        const float m_new = grew ? rmx * sl2 : m_run;
+        float m_new;   // SOFTCAP: the scores are in the exp2 domain already
+        if constexpr (SOFTCAP) m_new = grew ? rmx : m_run;
+        else m_new = grew ? rmx * sl2 : m_run;
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
 #pragma unroll
         for (int r = 0; r < 4; ++r) l_acc[r] *= alpha;
@@ -274,13 +298,16 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
 #pragma unroll
           for (int r = 0; r < 4; ++r) ot[dt][r] *= alpha;
         m_run = m_new;
-        mthr = (m_new + FA4_DEFER) * inv_sl2;
+        if constexpr (SOFTCAP) mthr = m_new + FA4_DEFER;
+        else mthr = (m_new + FA4_DEFER) * inv_sl2;
       }
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          pa[nt >> 1][(nt & 1) * 4 + r] = (__bf16)__builtin_amdgcn_exp2f(__builtin_fmaf(st[nt][r], sl2, -m_run));
+        for (int r = 0; r < 4; ++r) {
+          if constexpr (SOFTCAP) pa[nt >> 1][(nt & 1) * 4 + r] = (__bf16)__builtin_amdgcn_exp2f(st[nt][r] - m_run);
+          else pa[nt >> 1][(nt & 1) * 4 + r] = (__bf16)__builtin_amdgcn_exp2f(__builtin_fmaf(st[nt][r], sl2, -m_run));
+        }
       // ---- O^T += V^T P^T (k index 8 quad + j <-> key 32 ks2 + 16 (j >> 2) + 4 quad + (j & 3), as the S^T layout gives it)
 #pragma unroll
       for (int ks2 = 0; ks2 < 2; ++ks2) {

@@ -10,6 +10,7 @@
 //
 // All activations are bf16 with fp32 arithmetic inside a kernel; 16-byte vector accesses.
 #include "llama_kernels.h"
+#include "lr_profile.h"
 
 typedef unsigned short u16;
 typedef u16 u16x8 __attribute__((ext_vector_type(8)));
@@ -329,10 +330,14 @@ __global__ void rope_table_llama3_kernel(float* cs, unsigned* cs16, int T, int h
 
 // ---- final RMSNorm on each prompt's last token + dot with selected lm_head rows -------------
 // grid (B, ceil(C/32)); out[b][c] = float(bf16(sum_k xn[k] * W[row_c][k])), row_c = ids ? ids[c] : c
-template <int NS>
+// CAP (Gemma-2's final_logit_softcapping): HF runs logits / cap, tanh, * cap on the bf16 logits and then .float(), so each of
+// the three steps rounds to bf16: out = bf16(bf16(tanh(bf16(bf16(acc) / cap))) * cap). Without CAP `cap` is not read, and the
+// instructions of <0, false> and <1, false> are those of the kernel before it had the parameter ("What the
+// existing code objects became").
+template <int NS, bool CAP>
 __global__ __launch_bounds__(256) void head_kernel(const u16* x, const int32_t* rows, const u16* norm_w,
                                                    const u16* lm_head, const int32_t* class_ids, int C,
-                                                   int d, float eps, float* out, int vocab, const int32_t* poison) {
+                                                   int d, float eps, float* out, int vocab, const int32_t* poison, float cap) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   u16* xn = reinterpret_cast<u16*>(smem_raw);  // [d]
   __shared__ float red[4];
@@ -375,7 +380,11 @@ __global__ __launch_bounds__(256) void head_kernel(const u16* x, const int32_t* 
     }
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s, 64);
-    if (lane == 0) out[(size_t)b * C + c] = bf2f(f2bf(acc));
+    if constexpr (CAP) {
+      if (lane == 0) out[(size_t)b * C + c] = bf2f(f2bf(bf2f(f2bf(tanhf(bf2f(f2bf(bf2f(f2bf(acc)) / cap))))) * cap));
+    } else {
+      if (lane == 0) out[(size_t)b * C + c] = bf2f(f2bf(acc));
+    }
   }
 }
 
@@ -455,14 +464,99 @@ int lr_launch_rope_table(float* cs, int T, int hd, float theta, hipStream_t st, 
 
 int lr_launch_head(const u16* x, const int32_t* rows, const u16* norm_w, const u16* lm_head,
                    const int32_t* class_ids, int B, int C, int d, float eps, float* out, int vocab,
-                   hipStream_t st, const int32_t* poison, int norm_style) {
+                   hipStream_t st, const int32_t* poison, int norm_style, float final_softcap) {
   dim3 grid(B, (C + 31) / 32);
-  if (norm_style == 1)
-    hipLaunchKernelGGL(head_kernel<1>, grid, dim3(256), (size_t)d * sizeof(u16), st, x, rows, norm_w, lm_head,
-                       class_ids, C, d, eps, out, vocab, poison);
+  if (final_softcap > 0.f) {
+    if (norm_style != 1) LR_FAIL(LR_EUNSUPPORTED, "head: a final soft cap goes with the Gemma norm");
+    hipLaunchKernelGGL((head_kernel<1, true>), grid, dim3(256), (size_t)d * sizeof(u16), st, x, rows, norm_w, lm_head,
+                       class_ids, C, d, eps, out, vocab, poison, final_softcap);
+  } else if (norm_style == 1)
+    hipLaunchKernelGGL((head_kernel<1, false>), grid, dim3(256), (size_t)d * sizeof(u16), st, x, rows, norm_w, lm_head,
+                       class_ids, C, d, eps, out, vocab, poison, 0.f);
   else
-    hipLaunchKernelGGL(head_kernel<0>, grid, dim3(256), (size_t)d * sizeof(u16), st, x, rows, norm_w, lm_head,
-                       class_ids, C, d, eps, out, vocab, poison);
+    hipLaunchKernelGGL((head_kernel<0, false>), grid, dim3(256), (size_t)d * sizeof(u16), st, x, rows, norm_w, lm_head,
+                       class_ids, C, d, eps, out, vocab, poison, 0.f);
   LR_CHECK_LAUNCH("head_kernel");
+  return LR_OK;
+}
+
+// ---- Gemma-2's sandwich norm: the output h of attention (of the MLP) is normalised BEFORE it joins the residual ----------
+//   x'  = bf16( float(x) + float(bf16(h * rstd(h) * (1 + w_out))) )          written over x
+//   xn  = bf16( x' * rstd(x') * (1 + w_next) )                               NEXT only: the norm in front of the next product
+// One workgroup per row, rmsnorm_kernel's chunk assignment (thread t holds chunks t + 256 k of 8 columns in registers, so both
+// square sums are formed from the same values in the same order as two rmsnorm_kernel<1> launches around an add would form
+// them, and the bits are those), 16-byte loads and stores: three row reads (h, x, the weights come from cache) and one or two
+// row writes. xn may alias h: a thread reads its chunks of h before it writes the same chunks of xn, and no other thread
+// touches them. Rows longer than 256 * RMS_KEEP * 8 = 8192 columns are refused by the launcher.
+template <bool NEXT>
+__global__ __launch_bounds__(256) void residual_postnorm_kernel(u16* x, const u16* h, const u16* w_out, const u16* w_next,
+                                                                u16* xn, int d, float eps) {
+  __shared__ float red[4];
+  const size_t row_off = (size_t)blockIdx.x * d;
+  const int nv = d / 8;
+  u16x8 hb[RMS_KEEP], xb[RMS_KEEP], wb[RMS_KEEP], nb[RMS_KEEP];
+#pragma unroll
+  for (int k = 0; k < RMS_KEEP; ++k) {
+    const int i = threadIdx.x + 256 * k;
+    if (i < nv) {
+      hb[k] = reinterpret_cast<const u16x8*>(h + row_off)[i];
+      xb[k] = reinterpret_cast<const u16x8*>(x + row_off)[i];
+      wb[k] = reinterpret_cast<const u16x8*>(w_out)[i];
+      if (NEXT) nb[k] = reinterpret_cast<const u16x8*>(w_next)[i];
+    }
+  }
+  float ss = 0.f;
+#pragma unroll
+  for (int k = 0; k < RMS_KEEP; ++k) {
+    if (threadIdx.x + 256 * k < nv) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float f = bf2f(hb[k][j]);
+        ss = __builtin_fmaf(f, f, ss);
+      }
+    }
+  }
+  ss = block_sum_256(ss, red);
+  const float rstd_h = 1.0f / sqrtf(ss / (float)d + eps);
+  float ss2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < RMS_KEEP; ++k) {
+    const int i = threadIdx.x + 256 * k;
+    if (i < nv) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float f = bf2f(f2bf(bf2f(xb[k][j]) + bf2f(rms_apply<1>(wb[k][j], hb[k][j], rstd_h))));
+        xb[k][j] = f2bf(f);
+        ss2 = __builtin_fmaf(f, f, ss2);
+      }
+      reinterpret_cast<u16x8*>(x + row_off)[i] = xb[k];
+    }
+  }
+  if (!NEXT) return;
+  ss2 = block_sum_256(ss2, red);
+  const float rstd_x = 1.0f / sqrtf(ss2 / (float)d + eps);
+#pragma unroll
+  for (int k = 0; k < RMS_KEEP; ++k) {
+    const int i = threadIdx.x + 256 * k;
+    if (i < nv) {
+      u16x8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = rms_apply<1>(nb[k][j], xb[k][j], rstd_x);
+      reinterpret_cast<u16x8*>(xn + row_off)[i] = o;
+    }
+  }
+}
+
+int lr_launch_residual_postnorm(u16* x, const u16* h, const u16* w_out, const u16* w_next, u16* xn, int rows, int d, float eps,
+                                hipStream_t st) {
+  if (rows <= 0) return LR_OK;
+  if (d < 8 || d % 8 != 0 || d / 8 > 256 * RMS_KEEP)
+    LR_FAIL(LR_EUNSUPPORTED, "residual + out-norm: %d columns (a multiple of 8, at most %d)", d, 256 * RMS_KEEP * 8);
+  LrProfScope prof(LR_PROF_ELEMENTWISE, (w_next ? 5.0 : 3.0) * rows * d * 2, st);   // work = bytes the rows must move
+  if (w_next)
+    hipLaunchKernelGGL(residual_postnorm_kernel<true>, dim3(rows), dim3(256), 0, st, x, h, w_out, w_next, xn, d, eps);
+  else
+    hipLaunchKernelGGL(residual_postnorm_kernel<false>, dim3(rows), dim3(256), 0, st, x, h, w_out, w_next, xn, d, eps);
+  LR_CHECK_LAUNCH("residual_postnorm_kernel");
   return LR_OK;
 }

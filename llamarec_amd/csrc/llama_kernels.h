@@ -55,8 +55,10 @@ int lr_launch_token_meta(const int32_t* cu, int B, int prefix_len, int32_t* seg_
                          int32_t* prefix_bad = nullptr /* device word: zeroed, then set if a prompt's first P ids differ */);
 int lr_launch_gather_rows(const unsigned short* x, const int32_t* rows, int n_rows, int d, unsigned short* out,
                           hipStream_t st);
+// scale / cap: as LrAttnArgs below (0 / 0 = head_dim^-0.5 and no soft cap: the kernel's path is then what it was)
 int lr_launch_attention_rows(const unsigned short* qkv, unsigned short* out, const int32_t* cu, int B,
-                             const int32_t* q_rows, int n_rows, int nh, int nkv, int hd, hipStream_t st);
+                             const int32_t* q_rows, int n_rows, int nh, int nkv, int hd, hipStream_t st, float scale = 0.f,
+                             float cap = 0.f);
 int lr_launch_embed(const int32_t* ids, const int32_t* tok_src /*nullptr: identity*/, const unsigned short* table,
                     int vocab, int d, unsigned short* out, int n, hipStream_t st,
                     float scale = 1.0f /* != 1: rows bf16(e * scale) (Gemma's embedding scale) */);
@@ -73,7 +75,12 @@ int lr_launch_head(const unsigned short* x, const int32_t* rows /*[B]; nullptr: 
                    const unsigned short* lm_head, const int32_t* class_ids, int B, int C, int d, float eps,
                    float* out, int vocab, hipStream_t st,
                    const int32_t* poison = nullptr /* device word: non-zero -> every score of the call is NaN */,
-                   int norm_style = 0);
+                   int norm_style = 0,
+                   float final_softcap = 0.f /* > 0 (Gemma-2, norm_style 1): cap * tanh(logit / cap) at HF's bf16 steps */);
+// Gemma-2's sandwich norm, one workgroup per row (llama_elem.hip): x <- bf16(x + bf16(gemmanorm(h, w_out))) in place and,
+// with w_next, xn = bf16(gemmanorm(x, w_next)). xn may alias h (a workgroup reads its row of h before it writes any of xn).
+int lr_launch_residual_postnorm(unsigned short* x, const unsigned short* h, const unsigned short* w_out,
+                                const unsigned short* w_next, unsigned short* xn, int rows, int d, float eps, hipStream_t st);
 
 // C[M][N] (+epilogue) = A[M][K] * B[N][K]^T. Call sites name what they pass (designated initialisers); a member left
 // out is absent. variant: 0 auto, 1 generic, 4 = 256x256x64 MFMA tile, 5 = variant 4 with split-K when the tiles alone
@@ -249,11 +256,33 @@ enum LrAttnKernel { LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 
 //                                                                   a shared prefix too)
 //   other                                                 LR_EINVAL
 //
+// With a soft cap (LrAttnRequest.softcap: Gemma-2, lr_attention_varlen_softcap) the table is a short one. No lse anywhere
+// (LR_EINVAL), and first matching row:
+//
+//   variant        head_dim  cap                     prefix  result
+//   2, 3, 5, 6     any       any                     any     LR_EUNSUPPORTED  (those kernels have no capped form)
+//   0, 4           256       <= LR_SOFTCAP_MFMA_MAX  any     HD256    (the SOFTCAP instantiations of llama_attn_hd256_softcap.hip,
+//                                                                     on every route)
+//   0, 1, 4        any       any                     > 0     LR_EUNSUPPORTED  (GENERIC reads no shared prefix. The prefill never
+//                                                                     gets here: plan_batch asks lr_attention_reads_prefix WITH the
+//                                                                     cap, which answers true for the HD256 row above only, so a
+//                                                                     capped handle at head_dim 64 / 128 runs every prompt whole)
+//   0, 1, 4        any       any                     0       GENERIC  (slow but correct: gemma-2-27b's head_dim 128 lands here, and
+//                                                                     so does a cap above LR_SOFTCAP_MFMA_MAX at head_dim 256)
+//   other                                                    LR_EINVAL
+//
+// LR_SOFTCAP_MFMA_MAX: the MFMA kernels evaluate the capped score as c2 - 2 c2 rcp(1 + exp2(a s)) with c2 = cap log2(e), whose
+// absolute error is about two ulps of 1 times c2 (1.7e-7 cap in the exp2 domain, at small a s as well: there 1 + exp2(a s)
+// rounds a s to an ulp of 2). At cap 256 that is 4e-5, a hundredth of a bf16 step of P; the generic kernel's tanhf keeps a
+// RELATIVE error whatever the cap, so larger caps (where the cap hardly acts) go there. Gemma-2 uses 50.
+#define LR_SOFTCAP_MFMA_MAX 256.0f
 // varlen_ws counts a variant-3 request as "item ws yes" whatever it was given: the item-list builder then reports a missing
 // or short workspace as LR_EWORKSPACE. lr_launch_attention still refuses what the resolved kernel cannot take: GENERIC above
 // head_dim 256 and MFMA128 off head_dim 128 (LR_EUNSUPPORTED; a one-layer pruned prefill launches neither, so these checks
 // cannot move up here), lse on HD256, lse with a shared prefix on HD64, a segment 0 that is not the prefix.
-static inline bool lr_attention_reads_prefix(int variant, int hd) {
+// cap > 0 (soft-capped scores): only HD256's capped instantiations read a shared prefix (the short table above)
+static inline bool lr_attention_reads_prefix(int variant, int hd, float cap = 0.f) {
+  if (cap > 0.f) return hd == 256 && (variant == 0 || variant == 4) && cap <= LR_SOFTCAP_MFMA_MAX;
   if (hd == 128) return variant != 1;
   if (hd == 64) return variant == 0 || variant == 5 || variant == 6;
   if (hd == 256) return variant == 0 || variant == 4;
@@ -263,7 +292,11 @@ static inline bool lr_attention_reads_prefix(int variant, int hd) {
 static inline bool lr_attention_has_last_row_mode(int kernel, int hd) {
   return (hd == 128 && kernel != 1 /* LR_ATTN_GENERIC */) || kernel == 4 /* LR_ATTN_HD256 */ || kernel == 5 /* LR_ATTN_HD64 */;
 }
-struct LrAttnRequest { int variant, hd, prefix_len = 0; bool want_lse = false, have_items_ws = false, prefill = false, lora = false; };
+struct LrAttnRequest {
+  int variant, hd, prefix_len = 0;
+  bool want_lse = false, have_items_ws = false, prefill = false, lora = false;
+  float cap = 0.f;        // > 0: the scores are soft-capped (LrAttnArgs.cap): the short table
+};
 int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel);
 
 // cu / cu_host = segment starts [S + 1] in packed rows; prefix_len = P > 0: segment 0 is the shared prefix (P rows) the
@@ -276,12 +309,15 @@ struct LrAttnArgs {
   const int32_t *cu, *cu_host;
   int S, n_tok, nh, nkv, hd, prefix_len = 0;
   void* items_ws = nullptr;
+  // cap > 0: scores cap * tanh(q.k * scale / cap) (HD256's SOFTCAP instantiations and GENERIC only), scale > 0 then required
+  // by HD256; GENERIC takes scale = 0 as head_dim^-0.5. Both 0: the kernels' own head_dim^-0.5 and no cap.
+  float scale = 0.f, cap = 0.f;
 };
 int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st);
 // The pruned last layer (MFMA128's, HD64's or HD256's last-row kernel by head_dim): one query row per (prompt, head) over the prompt's keys
 int lr_launch_attention_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
                              const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int hd,
-                             hipStream_t st, int prefix_len);
+                             hipStream_t st, int prefix_len, float scale = 0.f, float cap = 0.f /* > 0: head_dim 256 only */);
 // ROWS256's item list for (cu, S, nh, prefix_len) into items_ws (lr_attn256_ws_bytes), built once per call; any number of
 // lr_launch_attention calls over the same segments may follow (one per layer)
 size_t lr_attn256_ws_bytes(int n_tok, int S, int nh);
@@ -301,5 +337,11 @@ int lr_launch_attention_hd64_last(const unsigned short* kv, const unsigned short
 int lr_launch_attention_hd256_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
                                    const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int prefix_len,
                                    hipStream_t st);
+// HD256 with soft-capped scores (llama_attn_hd256_softcap.hip): whole prompts or a shared prefix by a.prefix_len, and the
+// last-row mode
+int lr_launch_attention_hd256_softcap(const LrAttnArgs& a, hipStream_t st);
+int lr_launch_attention_hd256_softcap_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
+                                           const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv,
+                                           int prefix_len, float scale, float cap, hipStream_t st);
 
 #endif

@@ -159,6 +159,11 @@ struct lr_llama {
   const uint16_t** wqkv_folded;
   const uint16_t** wgu_folded;
   LrRopeScaling rope_scaling;  // kind 0 (calloc): plain RoPE (lr_llama_set_rope_scaling)
+  // Gemma-2 (lr_llama_set_gemma2); all zero / null (calloc): the plain layer
+  int gemma2;                        // an extension is set (refuses folded norms and LoRA engines)
+  float attn_softcap, final_softcap, attn_scale;   // attn_scale: the resolved value (> 0) whenever attn_softcap > 0
+  const uint16_t** attn_out_norm;    // [num_layers] owned copies of the caller's arrays, or null: no sandwich norms
+  const uint16_t** mlp_out_norm;
 };
 
 #endif  // LR_COMMON_H

@@ -40,11 +40,22 @@ GEMMA_2B = dict(model_type="gemma", vocab_size=256000, hidden_size=2048, interme
                 rms_norm_eps=1e-6, rope_theta=10000.0, hidden_activation="gelu_pytorch_tanh")
 GEMMA_7B = dict(GEMMA_2B, hidden_size=3072, intermediate_size=24576, num_hidden_layers=28, num_attention_heads=16,
                 num_key_value_heads=16)
+# google/gemma-2-2b and google/gemma-2-9b (config.json of the checkpoints; the reference's --llm gemma2 loads gemma-2-9b).
+# query_pre_attn_scalar is 256 = head_dim for both (144 for gemma-2-27b, whose head_dim is 128).
+GEMMA2_2B = dict(model_type="gemma2", vocab_size=256000, hidden_size=2304, intermediate_size=9216, num_hidden_layers=26,
+                 num_attention_heads=8, num_key_value_heads=4, head_dim=256, max_position_embeddings=8192,
+                 rms_norm_eps=1e-6, rope_theta=10000.0, hidden_activation="gelu_pytorch_tanh", query_pre_attn_scalar=256,
+                 attn_logit_softcapping=50.0, final_logit_softcapping=30.0, sliding_window=4096)
+GEMMA2_9B = dict(GEMMA2_2B, hidden_size=3584, intermediate_size=14336, num_hidden_layers=42, num_attention_heads=16,
+                 num_key_value_heads=8)
 
 # model_type -> backbone family of the kernels (LrLlamaArch). Llama-2 / Llama-3 and Mistral share Llama's arithmetic.
 LLAMA_FAMILY = ("llama", "mistral")
 GEMMA_FAMILY = ("gemma",)
-SUPPORTED_MODEL_TYPES = LLAMA_FAMILY + GEMMA_FAMILY
+GEMMA2_FAMILY = ("gemma2",)
+SUPPORTED_MODEL_TYPES = LLAMA_FAMILY + GEMMA_FAMILY + GEMMA2_FAMILY
+# what a gemma2 config must spell out (the two caps may be null): none of them has a default the kernels could assume
+GEMMA2_REQUIRED_KEYS = ("query_pre_attn_scalar", "attn_logit_softcapping", "final_logit_softcapping", "sliding_window", "head_dim")
 
 
 _LLAMA3_NUMBERS = ("factor", "low_freq_factor", "high_freq_factor", "original_max_position_embeddings")
@@ -75,9 +86,9 @@ def rope_parameters(config: dict):
 
 
 def model_family(config: dict) -> str:
-    """'llama' or 'gemma' for a HF config dict (a missing model_type means llama); anything else raises: the kernels
-    implement those two families' arithmetic only, and a checkpoint of another family would load (same tensor names)
-    and then score silently wrong."""
+    """'llama', 'gemma' or 'gemma2' for a HF config dict (a missing model_type means llama); anything else raises: the
+    kernels implement those families' arithmetic only, and a checkpoint of another family would load (same tensor names)
+    and then score silently wrong. A gemma2 config is accepted only when it is complete (GEMMA2_REQUIRED_KEYS)."""
     mt = config.get("model_type") or "llama"
     if mt in LLAMA_FAMILY:
         rope_parameters(config)   # plain RoPE or a complete llama3 rule; raises otherwise
@@ -90,6 +101,30 @@ def model_family(config: dict) -> str:
         if act not in ("gelu_pytorch_tanh", "gelu"):
             raise NotImplementedError(f"gemma with hidden_activation={act!r}: the kernels implement gelu_pytorch_tanh")
         return "gemma"
+    supported = f"supported families: {', '.join(SUPPORTED_MODEL_TYPES)}"
+    if mt in GEMMA2_FAMILY:
+        missing = [k for k in GEMMA2_REQUIRED_KEYS if k not in config or (config[k] is None and "softcapping" not in k)]
+        if missing:
+            raise NotImplementedError(f"model_type {mt!r} config lacks {', '.join(missing)}: soft caps, score scale, window "
+                                      f"and head_dim have no defaults the kernels could assume; {supported}")
+        act = config.get("hidden_activation") or config.get("hidden_act")
+        if act != "gelu_pytorch_tanh":
+            raise NotImplementedError(f"model_type {mt!r} with hidden_activation={act!r}: the kernels implement "
+                                      f"gelu_pytorch_tanh; {supported}")
+        if rope_parameters(config)[1] is not None:
+            raise NotImplementedError(f"model_type {mt!r} with rope_scaling="
+                                      f"{config.get('rope_scaling') or config.get('rope_parameters')!r}: scaled RoPE is "
+                                      f"implemented for the llama family only; {supported}")
+        for k in ("attn_logit_softcapping", "final_logit_softcapping", "query_pre_attn_scalar"):
+            v = config[k]
+            if v is not None and not (isinstance(v, (int, float)) and 0 < v < float("inf")):
+                raise NotImplementedError(f"model_type {mt!r} with {k}={v!r}: a positive finite number"
+                                          f"{' or null' if 'softcapping' in k else ''}; {supported}")
+        if config["attn_logit_softcapping"] is None and config["query_pre_attn_scalar"] != config["head_dim"]:
+            raise NotImplementedError(f"model_type {mt!r} with query_pre_attn_scalar={config['query_pre_attn_scalar']!r} != "
+                                      f"head_dim and no attn_logit_softcapping: the uncapped attention kernels scale by "
+                                      f"head_dim ** -0.5; {supported}")
+        return "gemma2"
     raise NotImplementedError(f"model_type {mt!r} is not supported by the ranker's kernels; supported families: "
                               f"{', '.join(SUPPORTED_MODEL_TYPES)}")
 
@@ -249,7 +284,9 @@ class LlamaRanker:
         self.rope_theta, self.rope_scaling = rope_parameters(c)   # scaling: None (plain RoPE) or the llama3 numbers
         self.hd = c.get("head_dim") or c["hidden_size"] // c["num_attention_heads"]
         # Mistral's sliding window: the kernels attend to the whole causal range, so a longer prompt is refused
-        self.max_prompt_len = c.get("sliding_window") if c.get("model_type") == "mistral" else None
+        # (Gemma-2: its even layers' window; within it the window is the plain causal mask)
+        self.max_prompt_len = c.get("sliding_window") if c.get("model_type") == "mistral" or self.family == "gemma2" else None
+        self._window_owner = "Gemma-2" if self.family == "gemma2" else "Mistral"
         self._h = C.c_void_p()
         self._tensors = {}
         self._ws = None
@@ -325,7 +362,14 @@ class LlamaRanker:
             T[f"{i}.wgu"] = self._interleave_gate_up(merged(p + "mlp.gate_proj.weight"), merged(p + "mlp.up_proj.weight"))
             T[f"{i}.wdown"] = merged(p + "mlp.down_proj.weight").to(torch.bfloat16).contiguous()
             T[f"{i}.input_norm"] = t(p + "input_layernorm.weight").to(torch.bfloat16).contiguous()
-            T[f"{i}.post_norm"] = t(p + "post_attention_layernorm.weight").to(torch.bfloat16).contiguous()
+            if self.family == "gemma2":
+                # LrLlamaLayerWeights.post_norm is the norm in FRONT of the MLP: Gemma-2's pre_feedforward_layernorm. HF's
+                # post_attention_layernorm acts on the attention output there (LrGemma2Ext.attn_out_norm).
+                T[f"{i}.post_norm"] = t(p + "pre_feedforward_layernorm.weight").to(torch.bfloat16).contiguous()
+                T[f"{i}.attn_out_norm"] = t(p + "post_attention_layernorm.weight").to(torch.bfloat16).contiguous()
+                T[f"{i}.mlp_out_norm"] = t(p + "post_feedforward_layernorm.weight").to(torch.bfloat16).contiguous()
+            else:
+                T[f"{i}.post_norm"] = t(p + "post_attention_layernorm.weight").to(torch.bfloat16).contiguous()
         self._create()
         return self
 
@@ -345,10 +389,11 @@ class LlamaRanker:
 
         T = self._tensors
         # unit norm scale: w = 1 for Llama, w = 0 for Gemma's (1 + w); Gemma's lm_head is the (tied) embedding
-        norm = torch.zeros if self.family == "gemma" else torch.ones
+        gemma = self.family in ("gemma", "gemma2")
+        norm = torch.zeros if gemma else torch.ones
         T["embed"] = rnd(v, d)
         T["final_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
-        T["lm_head"] = T["embed"] if self.family == "gemma" else rnd(v, d)
+        T["lm_head"] = T["embed"] if gemma else rnd(v, d)
         for i in range(c["num_hidden_layers"]):
             T[f"{i}.wqkv"] = rnd((nh + 2 * nkv) * hd, d)
             T[f"{i}.wo"] = rnd(d, nh * hd)
@@ -356,6 +401,9 @@ class LlamaRanker:
             T[f"{i}.wdown"] = rnd(d, f)
             T[f"{i}.input_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
             T[f"{i}.post_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
+            if self.family == "gemma2":
+                T[f"{i}.attn_out_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
+                T[f"{i}.mlp_out_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
         self._create()
         return self
 
@@ -396,8 +444,8 @@ class LlamaRanker:
 
     def arch(self):
         """The LrLlamaArch of this ranker's family (include/llamarec_mi355x.h)."""
-        if self.family == "gemma":
-            # HF GemmaModel: hidden * torch.tensor(hidden_size ** 0.5, dtype=bf16)
+        if self.family in ("gemma", "gemma2"):
+            # HF GemmaModel / Gemma2Model: hidden * torch.tensor(hidden_size ** 0.5, dtype=bf16)
             scale = float(torch.tensor(self.config["hidden_size"] ** 0.5, dtype=torch.bfloat16))
             return A.LrLlamaArch(norm_style=1, mlp_act=1, embed_scale=scale)
         return A.LrLlamaArch(norm_style=0, mlp_act=0, embed_scale=1.0)
@@ -428,8 +476,25 @@ class LlamaRanker:
                                     high_freq_factor=float(rs["high_freq_factor"]),
                                     original_max_positions=int(rs["original_max_position_embeddings"]))
             check(lib().lr_llama_set_rope_scaling(self._h, C.byref(words)), "lr_llama_set_rope_scaling")
+        if self.family == "gemma2":
+            ext, self._gemma2_arrs = self.gemma2_ext()
+            check(lib().lr_llama_set_gemma2(self._h, C.byref(ext)), "lr_llama_set_gemma2")
         if self.fold_norms:
             self.set_fold_norms(True)
+
+    def gemma2_ext(self):
+        """(LrGemma2Ext, the two pointer arrays it names) of a gemma2 ranker: caps, the score scale
+        query_pre_attn_scalar ** -0.5 and, once the weights are loaded, the out-norms of the sandwich."""
+        c, T, L = self.config, self._tensors, self.config["num_hidden_layers"]
+        ext = A.LrGemma2Ext(attn_softcap=float(c["attn_logit_softcapping"] or 0.0),
+                            final_softcap=float(c["final_logit_softcapping"] or 0.0),
+                            attn_scale=float(c["query_pre_attn_scalar"]) ** -0.5)
+        arrs = None
+        if "0.attn_out_norm" in T:
+            arrs = ((C.c_void_p * L)(*[T[f"{i}.attn_out_norm"].data_ptr() for i in range(L)]),
+                    (C.c_void_p * L)(*[T[f"{i}.mlp_out_norm"].data_ptr() for i in range(L)]))
+            ext.attn_out_norm, ext.mlp_out_norm = arrs
+        return ext, arrs
 
     def set_fold_norms(self, enable=True):
         """Fold the two RMSNorms of every layer into the following projection (include/llamarec_mi355x.h,
@@ -437,7 +502,7 @@ class LlamaRanker:
         kept beside the originals (+66 % of the q/k/v/gate/up bytes; the originals serve LoRA fine-tuning and the
         pruned last layer). Opt-in: see the note at LlamaRanker.fold_norms."""
         T, L = self._tensors, self.config["num_hidden_layers"]
-        if enable and self.family == "gemma":
+        if enable and self.family in ("gemma", "gemma2"):
             raise NotImplementedError("folded norms: Gemma's (1 + w) RMSNorm cannot be folded into bf16 weights at HF's rounding")
         if not enable:
             check(lib().lr_llama_set_folded_norms(self._h, None, None), "lr_llama_set_folded_norms")
@@ -488,7 +553,7 @@ class LlamaRanker:
     # -- scoring -----------------------------------------------------------------------------
     def _check_lengths(self, cu_host):
         if self.max_prompt_len is not None and int(np.diff(cu_host).max()) > self.max_prompt_len:
-            raise NotImplementedError(f"a prompt of {int(np.diff(cu_host).max())} tokens exceeds Mistral's sliding window of "
+            raise NotImplementedError(f"a prompt of {int(np.diff(cu_host).max())} tokens exceeds {self._window_owner}'s sliding window of "
                                       f"{self.max_prompt_len}: the kernels attend to the whole causal range")
 
     def _workspace(self, n_tokens, n_seqs):

@@ -110,6 +110,28 @@ def gemma_param_shapes(cfg: dict) -> list[tuple[str, tuple]]:
     return out
 
 
+def gemma2_param_shapes(cfg: dict) -> list[tuple[str, tuple]]:
+    """HF Gemma2ForCausalLM parameter names and shapes: Gemma's, plus the two norms per layer of the sandwich
+    (pre_feedforward_layernorm in front of the MLP, post_feedforward_layernorm on its output; post_attention_layernorm is
+    on the attention output here), in the order of HF's module tree per layer. No lm_head (tied)."""
+    d = cfg["hidden_size"]
+    out = []
+    for name, shape in gemma_param_shapes(cfg):
+        out.append((name, shape))
+        if name.endswith("post_attention_layernorm.weight"):
+            p = name[: -len("post_attention_layernorm.weight")]
+            out += [(p + "pre_feedforward_layernorm.weight", (d,)), (p + "post_feedforward_layernorm.weight", (d,))]
+    return out
+
+
+def synth_gemma2_state(cfg: dict, seed: int, std: float = 0.02, norm_std: float = 0.3) -> dict:
+    """As synth_gemma_state for a Gemma-2 config (four norms per layer). bf16 values."""
+    sd = {}
+    for i, (name, shape) in enumerate(gemma2_param_shapes(cfg)):
+        sd[name] = bf16_round(hash_uniform(seed * 1000 + i, shape, norm_std if len(shape) == 1 else std))
+    return sd
+
+
 def synth_gemma_state(cfg: dict, seed: int, std: float = 0.02, norm_std: float = 0.3) -> dict:
     """name -> float32 array for a Gemma config. Matrices ~ U(std); norm weights ~ U(norm_std) around 0 -- Gemma scales by
     (1 + w), so non-zero w exercises that form (w = 0 would make it indistinguishable from Llama's w = 1). bf16 values."""

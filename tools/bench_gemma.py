@@ -8,7 +8,11 @@
      kernel against variant 4 on the same whole prompts, the last-row launch against full attention + gather, and the Gemma-2B
      step with the 36-token prefix shared against prefix_len = 0 and against every --ab-lib NAME=PATH build (the parent commit's
      library: its step on the same prompts), arms alternating, median and min .. max of --reps.
-Usage: python tools/bench_gemma.py [--reps 20] [--steps 5] [--layers 18] [--prefix-ab] [--ab-lib parent=path/to/lib.so]"""
+  4. --gemma2 (instead of 1 and 2): Gemma-2. The soft-capped head_dim-256 kernel against variant 4 uncapped and against the
+     generic kernel with the cap on the same rows, arms alternating, median and min .. max of --reps (the generic arm: a
+     quarter of them); the sandwich-norm kernel's GB/s at the step's row count; a random-weight Gemma-2-2B step (26 layers) on
+     the Beauty token budget with its kernel split (the element-wise kernel from its own profile records).
+Usage: python tools/bench_gemma.py [--reps 20] [--steps 5] [--layers 18] [--prefix-ab] [--gemma2] [--ab-lib parent=path/to/lib.so]"""
 from __future__ import annotations
 
 import argparse
@@ -25,7 +29,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from llamarec_amd import _lib  # noqa: E402
 from llamarec_amd._lib import check, lib, stream_ptr  # noqa: E402
 
-KINDS = {0: "gemm 256-tile", 1: "gemm generic", 2: "attention MFMA", 3: "attention generic"}
+# kind 6's work is bytes, so its "TF/s" column reads TB/s
+KINDS = {0: "gemm 256-tile", 1: "gemm generic", 2: "attention MFMA", 3: "attention generic", 6: "sandwich norm (TB/s)"}
 
 
 def time_attention(nh, nkv, hd, T, B, variant, reps):
@@ -70,11 +75,113 @@ def attention_table(reps):
     return rows
 
 
-def gemma2b_step(steps, layers):
+def _event_ms(run):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    run()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def _stats(times):
+    return dict(ms=float(np.median(times)), min_ms=float(np.min(times)), max_ms=float(np.max(times)))
+
+
+def softcap_attention_table(reps, cap=50.0):
+    """Capped MFMA kernel | variant 4 uncapped | generic kernel with the cap, same rows, arms alternating."""
+    rows = []
+    for nh, nkv in ((8, 1), (16, 16), (8, 4), (16, 8)):
+        for T in (600, 1125):
+            B, hd = 16, 256
+            n = B * T
+            g = torch.Generator(device="cuda").manual_seed(T + nh)
+            qkv = torch.randn(n, (nh + 2 * nkv) * hd, generator=g, device="cuda").to(torch.bfloat16)
+            out = torch.empty(n, nh * hd, dtype=torch.bfloat16, device="cuda")
+            cu = np.arange(0, n + 1, T, dtype=np.int32)
+            cud = torch.from_numpy(cu).cuda()
+
+            def arm(c, variant):
+                return lambda: check(lib().lr_attention_varlen_softcap(qkv.data_ptr(), out.data_ptr(), cud.data_ptr(),
+                                                                       cu.ctypes.data, B, 0, nh, nkv, hd, 0.0, c, variant,
+                                                                       stream_ptr()), "attention")
+
+            arms = dict(capped=arm(cap, 4), v4=arm(0.0, 4), generic_capped=arm(cap, 1))
+            for run in arms.values():
+                run()
+            torch.cuda.synchronize()
+            times = {k: [] for k in arms}
+            for i in range(reps):
+                for k, run in arms.items():
+                    if k != "generic_capped" or i % 4 == 0:
+                        times[k].append(_event_ms(run))
+            work = 4.0 * nh * hd * B * T * (T + 1) / 2
+            st = {k: _stats(v) for k, v in times.items()}
+            row = dict(nh=nh, nkv=nkv, T=T, B=B, cap=cap, **{k: dict(v, tflops=work / v["ms"] / 1e9) for k, v in st.items()},
+                       capped_over_v4=st["capped"]["ms"] / st["v4"]["ms"],
+                       generic_over_capped=st["generic_capped"]["ms"] / st["capped"]["ms"])
+            rows.append(row)
+            print(f"softcap attention nh={nh:2d} nkv={nkv:2d} 16 x {T:4d}: capped {st['capped']['ms']:7.3f} ms "
+                  f"({st['capped']['min_ms']:.3f} .. {st['capped']['max_ms']:.3f}) {row['capped']['tflops']:6.1f} TF/s | v4 "
+                  f"{st['v4']['ms']:7.3f} ms ({st['v4']['min_ms']:.3f} .. {st['v4']['max_ms']:.3f}) {row['v4']['tflops']:6.1f} TF/s | "
+                  f"generic capped {st['generic_capped']['ms']:8.3f} ms | capped/v4 {row['capped_over_v4']:4.2f} "
+                  f"generic/capped {row['generic_over_capped']:5.1f}x", flush=True)
+    return rows
+
+
+def postnorm_table(reps, rows_n):
+    """The sandwich-norm kernel alone: with the next norm (3 row reads + 2 row writes of 2 d bytes) and without (2 + 1)."""
+    res = []
+    for d in (2304, 3584):
+        g = torch.Generator(device="cuda").manual_seed(d)
+        x = torch.randn(rows_n, d, generator=g, device="cuda").to(torch.bfloat16)
+        h = torch.randn(rows_n, d, generator=g, device="cuda").to(torch.bfloat16)
+        w = torch.zeros(2, d, dtype=torch.bfloat16, device="cuda")
+        arms = dict(
+            with_next=lambda: check(lib().lr_residual_postnorm_bf16(x.data_ptr(), h.data_ptr(), w[0].data_ptr(), w[1].data_ptr(),
+                                                                    h.data_ptr(), rows_n, d, 1e-6, stream_ptr()), "postnorm"),
+            without_next=lambda: check(lib().lr_residual_postnorm_bf16(x.data_ptr(), h.data_ptr(), w[0].data_ptr(), None, None,
+                                                                       rows_n, d, 1e-6, stream_ptr()), "postnorm"),
+            rmsnorm=lambda: check(lib().lr_rmsnorm_bf16(x.data_ptr(), w[1].data_ptr(), h.data_ptr(), rows_n, d, 1e-6, 1,
+                                                        stream_ptr()), "rmsnorm"))
+
+        def three_launches():      # the unfused form: norm(h) -> h, x += h (torch's add stands in: the library has none), norm(x)
+            check(lib().lr_rmsnorm_bf16(h.data_ptr(), w[0].data_ptr(), h.data_ptr(), rows_n, d, 1e-6, 1, stream_ptr()), "rmsnorm")
+            x.add_(h)
+            check(lib().lr_rmsnorm_bf16(x.data_ptr(), w[1].data_ptr(), h.data_ptr(), rows_n, d, 1e-6, 1, stream_ptr()), "rmsnorm")
+
+        def two_launches():        # norm + add fused, the next norm on its own
+            arms["without_next"]()
+            arms["rmsnorm"]()
+
+        arms["three_launches"], arms["two_launches"] = three_launches, two_launches
+        for run in arms.values():
+            run()
+        torch.cuda.synchronize()
+        times = {k: [] for k in arms}
+        for _ in range(reps):
+            for k, run in arms.items():
+                times[k].append(_event_ms(run))
+        row = dict(d=d, rows=rows_n)
+        for k, passes in (("with_next", 5), ("without_next", 3), ("rmsnorm", 2), ("two_launches", 5), ("three_launches", 7)):
+            st = _stats(times[k])
+            row[k] = dict(st, gbytes_per_s=passes * rows_n * d * 2 / st["ms"] / 1e6)
+        res.append(row)
+        print(f"sandwich norm {rows_n} x {d}: with the next norm {row['with_next']['ms'] * 1e3:7.1f} us "
+              f"({row['with_next']['min_ms'] * 1e3:.1f} .. {row['with_next']['max_ms'] * 1e3:.1f}) "
+              f"{row['with_next']['gbytes_per_s']:6.0f} GB/s | without {row['without_next']['ms'] * 1e3:7.1f} us "
+              f"{row['without_next']['gbytes_per_s']:6.0f} GB/s | rmsnorm alone {row['rmsnorm']['ms'] * 1e3:7.1f} us | "
+              f"without + rmsnorm {row['two_launches']['ms'] * 1e3:7.1f} us ({row['two_launches']['min_ms'] * 1e3:.1f} .. "
+              f"{row['two_launches']['max_ms'] * 1e3:.1f}) | rmsnorm, add, rmsnorm {row['three_launches']['ms'] * 1e3:7.1f} us "
+              f"({row['three_launches']['min_ms'] * 1e3:.1f} .. {row['three_launches']['max_ms'] * 1e3:.1f})", flush=True)
+    return res
+
+
+def gemma2b_step(steps, layers, base=None, name="gemma-2b"):
     from llamarec_amd.llm import GEMMA_2B, LlamaRanker, pack_prompts
     from llamarec_amd.packing import TOKEN_BUDGET
 
-    cfg = dict(GEMMA_2B, num_hidden_layers=layers)
+    cfg = dict(base or GEMMA_2B, num_hidden_layers=layers)
     model = LlamaRanker.random_init(cfg, seed=1)
     rng = np.random.default_rng(0)
     seqs, total = [], 0
@@ -102,17 +209,17 @@ def gemma2b_step(steps, layers):
     check(L.lr_profile_stop(), "lr_profile_stop")
     step_ms = e0.elapsed_time(e1) / steps
     split = {}
-    for kind, name in KINDS.items():
+    for kind, kname in KINDS.items():
         ms, work, n = C.c_double(), C.c_double(), C.c_int64()
         L.lr_profile_collect(kind, C.byref(ms), C.byref(work), C.byref(n))
         if n.value:
-            split[name] = dict(ms_per_step=ms.value / steps, tflops=work.value / max(ms.value, 1e-9) / 1e9,
+            split[kname] = dict(ms_per_step=ms.value / steps, tflops=work.value / max(ms.value, 1e-9) / 1e9,
                                launches_per_step=n.value / steps)
     assert torch.isfinite(out).all()
-    print(f"gemma-2b ({layers} layers, random weights) prefill + verbalizer: {len(seqs)} prompts, {total} tokens: "
+    print(f"{name} ({layers} layers, random weights) prefill + verbalizer: {len(seqs)} prompts, {total} tokens: "
           f"{step_ms:.2f} ms per step", flush=True)
-    for name, v in split.items():
-        print(f"  {name:18s} {v['ms_per_step']:8.2f} ms/step {v['tflops']:7.1f} TF/s {v['launches_per_step']:6.1f} launches",
+    for kname, v in split.items():
+        print(f"  {kname:18s} {v['ms_per_step']:8.2f} ms/step {v['tflops']:7.1f} TF/s {v['launches_per_step']:6.1f} launches",
               flush=True)
     attn = sum(v["ms_per_step"] for k, v in split.items() if k.startswith("attention"))
     return dict(prompts=len(seqs), tokens=total, layers=layers, step_ms=step_ms, kernels=split,
@@ -125,10 +232,30 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--layers", type=int, default=18)
     ap.add_argument("--prefix-ab", action="store_true", help="the shared-prefix / last-row arms instead (tools/prefix_ab.py)")
+    ap.add_argument("--gemma2", action="store_true", help="the Gemma-2 tables instead: capped attention, sandwich norm, 2B step")
     ap.add_argument("--ab-lib", action="append", default=[], metavar="NAME=PATH")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     _lib.lib()
+    if args.gemma2:
+        from llamarec_amd.llm import GEMMA2_2B
+        from llamarec_amd.packing import TOKEN_BUDGET
+
+        res = dict(softcap_attention=softcap_attention_table(args.reps))
+        res["sandwich_norm"] = postnorm_table(args.reps, TOKEN_BUDGET)
+        layers = 26 if args.layers == 18 else args.layers      # the default is Gemma-2B's 18; gemma-2-2b has 26
+        step = gemma2b_step(args.steps, layers, GEMMA2_2B, "gemma-2-2b")
+        # the element-wise kernel's own profile records (kind 6), inside the step
+        step["sandwich_norm_ms_per_step"] = sum(v["ms_per_step"] for k, v in step["kernels"].items() if k.startswith("sandwich"))
+        step["sandwich_norm_share"] = step["sandwich_norm_ms_per_step"] / step["step_ms"]
+        gemm = sum(v["ms_per_step"] for k, v in step["kernels"].items() if k.startswith("gemm"))
+        step["gemm_share"] = gemm / step["step_ms"]
+        step["rest_share"] = 1.0 - step["gemm_share"] - step["attention_share"] - step["sandwich_norm_share"]
+        print(f"  shares: GEMMs {step['gemm_share']:.3f}, attention {step['attention_share']:.3f}, sandwich norm "
+              f"{step['sandwich_norm_share']:.3f}, rest {step['rest_share']:.3f}")
+        res["gemma2_2b"] = step
+        print(json.dumps(res))
+        return
     if args.prefix_ab:
         from llamarec_amd.llm import GEMMA_2B
         from tools import prefix_ab

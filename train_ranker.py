@@ -40,7 +40,7 @@ def main(argv=None, export_root=None):
     args = cfg.parse(argv, model_code="llm")
     if not args.llm_retrieved_path:
         raise SystemExit("--llm_retrieved_path experiments/lru/<dataset> is required")
-    if args.llm == "gemma" and not args.eval_only:
+    if args.llm in ("gemma", "gemma2") and not args.eval_only:
         raise SystemExit(TRAIN_LLAMA_ONLY)
     if args.resume_from_checkpoint and (args.eval_only or args.llm_adapter_path):
         raise SystemExit("--resume_from_checkpoint continues a training run: it goes with neither --eval_only nor "
@@ -59,7 +59,7 @@ def main(argv=None, export_root=None):
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
     if args.synthetic:
-        from llamarec_amd.synth import FakeTokenizer, synth_gemma_state, synth_llama_state
+        from llamarec_amd.synth import FakeTokenizer, synth_gemma2_state, synth_gemma_state, synth_llama_state
 
         dataset = D.synthetic_dataset(num_users=300, num_items=1000, seed=args.seed)
         tokenizer = FakeTokenizer()
@@ -72,6 +72,12 @@ def main(argv=None, export_root=None):
         if args.llm == "gemma":   # a tiny Gemma: head_dim 256, MQA, (1 + w) norms, GeGLU, scaled embedding
             c = dict(c, model_type="gemma", num_key_value_heads=1, head_dim=256, rms_norm_eps=1e-6)
             model = LlamaRanker.from_state_dict(synth_gemma_state(c, args.seed), c, device=device, lora=lora,
+                                                nf4=args.llm_load_in_4bit)
+        elif args.llm == "gemma2":   # a tiny Gemma-2: the same plus soft caps that bite, sandwich norms, a 1/12 score scale
+            c = dict(c, model_type="gemma2", num_key_value_heads=1, head_dim=256, rms_norm_eps=1e-6, query_pre_attn_scalar=144,
+                     attn_logit_softcapping=2.0, final_logit_softcapping=1.0, sliding_window=4096,
+                     hidden_activation="gelu_pytorch_tanh")
+            model = LlamaRanker.from_state_dict(synth_gemma2_state(c, args.seed), c, device=device, lora=lora,
                                                 nf4=args.llm_load_in_4bit)
         else:
             model = LlamaRanker.from_state_dict(synth_llama_state(c, args.seed), c, device=device, lora=lora,
