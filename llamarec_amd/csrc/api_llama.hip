@@ -57,8 +57,8 @@ extern "C" int lr_llama_create(const LrLlamaConfig* cfg, const LrLlamaWeightsDes
 
 extern "C" int lr_llama_set_variants(lr_llama_t* h, int32_t gemm_variant, int32_t attention_variant) {
   if (!h || (gemm_variant != 0 && gemm_variant != 1 && gemm_variant != 4 && gemm_variant != 5) || attention_variant < 0 ||
-      attention_variant > 6)
-    LR_FAIL(LR_EINVAL, "lr_llama_set_variants: gemm in {0, 1, 4, 5}, attention in {0, 1, 2, 3, 4, 5, 6}");
+      attention_variant > 7)
+    LR_FAIL(LR_EINVAL, "lr_llama_set_variants: gemm in {0, 1, 4, 5}, attention in {0, 1, 2, 3, 4, 5, 6, 7}");
   h->gemm_variant = gemm_variant;
   h->attn_variant = attention_variant;
   return LR_OK;
@@ -297,7 +297,7 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
   // the MFMA kernels over ALL rows (188 us for 14.8 k tokens, 16 us for one prompt) beat the scalar kernel over the B last
   // rows (459 / 295 us), so a pruned last layer attends everything and keeps the last rows
   const bool attn_mfma = (hd == 128 && attn_kernel != LR_ATTN_GENERIC) || attn_kernel == LR_ATTN_HD256 ||
-                         attn_kernel == LR_ATTN_HD64;
+                         attn_kernel == LR_ATTN_HD64 || attn_kernel == LR_ATTN_HD96;
   const LrAttnArgs attn = {.qkv = ws.qkv, .out = ws.att, .cu = ws.seg_start, .cu_host = plan.seg_host.data(), .S = S,
                            .n_tok = n, .nh = nh, .nkv = nkv, .hd = hd, .prefix_len = P, .items_ws = ws.attn_items,
                            .scale = a_scale, .cap = a_cap};
@@ -325,7 +325,7 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
     // weight already inside the projection matrix and rstd applied to the accumulator rows in the GEMM epilogue
     const bool folded = h->wqkv_folded != nullptr;
     const bool last_pruned = l == c.num_layers - 1 && h->prune_last;
-    // Pruned last layer, on a kernel with a last-row mode (head_dim 64, 128, 256): only each prompt's last token is consumed after it (model/llm.py:131), so Q is
+    // Pruned last layer, on a kernel with a last-row mode (head_dim 64, 96, 128, 256): only each prompt's last token is consumed after it (model/llm.py:131), so Q is
     // needed for B rows only -- K and V for all of them. The projection runs on the K | V rows of wqkv (2/3 of the
     // product) for every row and on its Q rows for the B last rows; the attention kernel then evaluates ONE query row
     // per (prompt, head) over the prompt's keys instead of every tile.
@@ -583,8 +583,9 @@ static int check_prefix_request(const char* who, const int32_t* cu_host, int S, 
   if (prefix_len > 0 && (S < 2 || cu_host[1] != prefix_len))
     LR_FAIL(LR_EINVAL, "%s: segment 0 has %d rows, the shared prefix %d (and a prompt must follow it)", who, cu_host[1], prefix_len);
   const bool ok = (hd == 128 && (variant == 0 || variant == 2)) || (hd == 64 && (variant == 0 || variant == 5)) ||
-                  (hd == 256 && (variant == 0 || variant == 4));
-  if (!ok) LR_FAIL(LR_EUNSUPPORTED, "%s: variant %d at head_dim %d (0 / 2 at 128, 0 / 5 at 64, 0 / 4 at 256)", who, variant, hd);
+                  (hd == 96 && (variant == 0 || variant == 7)) || (hd == 256 && (variant == 0 || variant == 4));
+  if (!ok)
+    LR_FAIL(LR_EUNSUPPORTED, "%s: variant %d at head_dim %d (0 / 2 at 128, 0 / 5 at 64, 0 / 7 at 96, 0 / 4 at 256)", who, variant, hd);
   return LR_OK;
 }
 

@@ -543,7 +543,8 @@ int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
   const int hd = r.hd;
   if (r.cap > 0.f) {   // the short table of llama_kernels.h
     if (r.want_lse) LR_FAIL(LR_EINVAL, "attention: no lse with a soft cap");
-    if (r.variant == 2 || r.variant == 3 || r.variant == 5 || r.variant == 6)
+    // variant 7 is a kernel at head_dim 96 only: elsewhere a capped request for it stays the unknown variant it was (LR_EINVAL)
+    if (r.variant == 2 || r.variant == 3 || r.variant == 5 || r.variant == 6 || (r.variant == 7 && hd == 96))
       LR_FAIL(LR_EUNSUPPORTED, "attention variant %d has no soft-capped form (0 / 4 at head_dim 256, 1 generic)", r.variant);
     if (r.variant != 0 && r.variant != 1 && r.variant != 4) LR_FAIL(LR_EINVAL, "attention: unknown variant %d", r.variant);
     if (r.variant != 1 && hd == 256 && r.cap <= LR_SOFTCAP_MFMA_MAX) {
@@ -558,6 +559,7 @@ int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
     case 0:
       if (hd == 128) *kernel = (r.have_items_ws && !r.prefill) ? LR_ATTN_ROWS256 : LR_ATTN_MFMA128;
       else if (hd == 256 && (r.prefill || r.prefix_len > 0)) *kernel = LR_ATTN_HD256;
+      else if (hd == 96 && (r.prefill || r.prefix_len > 0)) *kernel = LR_ATTN_HD96;   // not r.lora: HD96 writes no lse
       else *kernel = (hd == 64 && (r.prefill || r.lora || r.prefix_len > 0)) ? LR_ATTN_HD64 : LR_ATTN_GENERIC;
       if (r.prefix_len > 0 && *kernel == LR_ATTN_GENERIC)
         LR_FAIL(LR_EUNSUPPORTED, "attention: no kernel reads a shared prefix at head_dim %d", hd);
@@ -591,9 +593,14 @@ int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
       if (r.want_lse && r.prefix_len > 0) LR_FAIL(LR_EINVAL, "attention variant 6 writes no lse with a shared prefix");
       *kernel = LR_ATTN_HD64;
       return LR_OK;
+    case 7:
+      if (r.want_lse) LR_FAIL(LR_EINVAL, "attention variant 7 (head_dim-96 MFMA) writes no lse");
+      if (hd != 96) LR_FAIL(LR_EUNSUPPORTED, "attention variant 7 needs head_dim 96 (got %d)", hd);
+      *kernel = LR_ATTN_HD96;
+      return LR_OK;
   }
   LR_FAIL(LR_EINVAL, "attention: unknown variant %d (0 auto, 1 generic, 2 = head_dim-128 MFMA, 3 = 256-row tiles, "
-          "4 = head_dim-256 MFMA, 5 = head_dim-64 MFMA, 6 = head_dim-64 MFMA for training)", r.variant);
+          "4 = head_dim-256 MFMA, 5 = head_dim-64 MFMA, 6 = head_dim-64 MFMA for training, 7 = head_dim-96 MFMA)", r.variant);
 }
 
 int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st) {
@@ -614,6 +621,10 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
   if (kernel == LR_ATTN_HD64) {
     if (prefix_len < 0) LR_FAIL(LR_EINVAL, "attention: shared prefix of %d tokens", prefix_len);
     return prefix_len > 0 ? lr_launch_attention_hd64_prefix(a, st) : lr_launch_attention_hd64(a, st);
+  }
+  if (kernel == LR_ATTN_HD96) {
+    if (prefix_len < 0 || a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-96 MFMA kernel writes no lse (prefix %d)", prefix_len);
+    return prefix_len > 0 ? lr_launch_attention_hd96_prefix(a, st) : lr_launch_attention_hd96(a, st);
   }
   if (prefix_len < 0 || (prefix_len > 0 && (kernel != LR_ATTN_MFMA128 || cu_host[1] - cu_host[0] != prefix_len)))
     LR_FAIL(LR_EINVAL, "attention: shared prefix of %d tokens needs the head_dim-128 MFMA kernel and segment 0 = the prefix",
@@ -658,7 +669,7 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
   return LR_OK;
 }
 
-// The pruned last layer (head_dim 128 here, 64 and 256 in the _prefix files of their kernels): kv = [n_tok][2 * nkv * hd] (K | V of every row), q_last = [prompts][nh * hd] rotated query rows
+// The pruned last layer (head_dim 128 here, 64, 96 and 256 in the _prefix files of their kernels): kv = [n_tok][2 * nkv * hd] (K | V of every row), q_last = [prompts][nh * hd] rotated query rows
 // of each prompt's last token, out_last = [prompts][nh * hd]. cu / cu_host / prefix_len as lr_launch_attention.
 int lr_launch_attention_last(const u16* kv, const u16* q_last, u16* out_last, const int32_t* cu, const int32_t* cu_host,
                              int S, int n_tok, int nh, int nkv, int hd, hipStream_t st, int prefix_len, float scale, float cap) {
@@ -668,8 +679,9 @@ int lr_launch_attention_last(const u16* kv, const u16* q_last, u16* out_last, co
       LR_FAIL(LR_EUNSUPPORTED, "attention (last rows, soft cap): head_dim 256 and nh %% nkv == 0 only");
     return lr_launch_attention_hd256_softcap_last(kv, q_last, out_last, cu, cu_host, S, n_tok, nh, nkv, prefix_len, scale, cap, st);
   }
-  if ((hd != 128 && hd != 64 && hd != 256) || nkv < 1 || nh % nkv != 0)
-    LR_FAIL(LR_EUNSUPPORTED, "attention (last rows): head_dim 64, 128 or 256 and nh %% nkv == 0 only");
+  if ((hd != 128 && hd != 64 && hd != 96 && hd != 256) || nkv < 1 || nh % nkv != 0)
+    LR_FAIL(LR_EUNSUPPORTED, "attention (last rows): head_dim 64, 96, 128 or 256 and nh %% nkv == 0 only");
+  if (hd == 96) return lr_launch_attention_hd96_last(kv, q_last, out_last, cu, cu_host, S, n_tok, nh, nkv, prefix_len, st);
   if (hd == 64) return lr_launch_attention_hd64_last(kv, q_last, out_last, cu, cu_host, S, n_tok, nh, nkv, prefix_len, st);
   if (hd == 256) return lr_launch_attention_hd256_last(kv, q_last, out_last, cu, cu_host, S, n_tok, nh, nkv, prefix_len, st);
   if (prefix_len < 0 || (prefix_len > 0 && cu_host[1] - cu_host[0] != prefix_len))

@@ -609,7 +609,7 @@ int lr_launch_attention_bwd(const u16* qkv, const u16* out, const u16* d_out, co
     return lr_launch_attention_bwd_hd64(qkv, d_out, lse, dsum, dqkv, cu, cu_host, B, n_tok, nh, nkv, hd, st, rope_cs);
   } else {
     LR_FAIL(LR_EINVAL, "attention backward: unknown variant %d (0 auto, 1 generic, 2 = head_dim-128 MFMA, 3 as 0, "
-            "6 = head_dim-64 MFMA; 4 and 5 have no backward)", variant);
+            "6 = head_dim-64 MFMA; 4, 5 and 7 have no backward)", variant);
   }
   return LR_OK;
 }

@@ -48,14 +48,25 @@ GEMMA2_2B = dict(model_type="gemma2", vocab_size=256000, hidden_size=2304, inter
                  attn_logit_softcapping=50.0, final_logit_softcapping=30.0, sliding_window=4096)
 GEMMA2_9B = dict(GEMMA2_2B, hidden_size=3584, intermediate_size=14336, num_hidden_layers=42, num_attention_heads=16,
                  num_key_value_heads=8)
+# microsoft/Phi-3-mini-4k-instruct and Phi-3-medium-4k-instruct (config.json of the checkpoints; the reference's --llm phi3).
+# Llama's arithmetic with fused qkv_proj / gate_up_proj Linears; mini's head_dim is 3072 / 32 = 96.
+PHI3_MINI = dict(model_type="phi3", vocab_size=32064, hidden_size=3072, intermediate_size=8192, num_hidden_layers=32,
+                 num_attention_heads=32, num_key_value_heads=32, max_position_embeddings=4096,
+                 original_max_position_embeddings=4096, rms_norm_eps=1e-5, rope_theta=10000.0, rope_scaling=None,
+                 hidden_act="silu", sliding_window=2047, tie_word_embeddings=False)
+PHI3_MEDIUM = dict(PHI3_MINI, hidden_size=5120, intermediate_size=17920, num_hidden_layers=40, num_attention_heads=40,
+                   num_key_value_heads=10)
 
 # model_type -> backbone family of the kernels (LrLlamaArch). Llama-2 / Llama-3 and Mistral share Llama's arithmetic.
 LLAMA_FAMILY = ("llama", "mistral")
 GEMMA_FAMILY = ("gemma",)
 GEMMA2_FAMILY = ("gemma2",)
-SUPPORTED_MODEL_TYPES = LLAMA_FAMILY + GEMMA_FAMILY + GEMMA2_FAMILY
+PHI3_FAMILY = ("phi3",)
+SUPPORTED_MODEL_TYPES = LLAMA_FAMILY + PHI3_FAMILY + GEMMA_FAMILY + GEMMA2_FAMILY
 # what a gemma2 config must spell out (the two caps may be null): none of them has a default the kernels could assume
 GEMMA2_REQUIRED_KEYS = ("query_pre_attn_scalar", "attn_logit_softcapping", "final_logit_softcapping", "sliding_window", "head_dim")
+# what a phi3 config must spell out (sliding_window may be null = none); every published Phi-3 config.json has all three
+PHI3_REQUIRED_KEYS = ("hidden_act", "original_max_position_embeddings", "sliding_window")
 
 
 _LLAMA3_NUMBERS = ("factor", "low_freq_factor", "high_freq_factor", "original_max_position_embeddings")
@@ -86,9 +97,10 @@ def rope_parameters(config: dict):
 
 
 def model_family(config: dict) -> str:
-    """'llama', 'gemma' or 'gemma2' for a HF config dict (a missing model_type means llama); anything else raises: the
-    kernels implement those families' arithmetic only, and a checkpoint of another family would load (same tensor names)
-    and then score silently wrong. A gemma2 config is accepted only when it is complete (GEMMA2_REQUIRED_KEYS)."""
+    """'llama', 'gemma', 'gemma2' or 'phi3' for a HF config dict (a missing model_type means llama); anything else raises:
+    the kernels implement those families' arithmetic only, and a checkpoint of another family would load (same tensor names)
+    and then score silently wrong. A gemma2 or phi3 config is accepted only when it is complete (GEMMA2_REQUIRED_KEYS,
+    PHI3_REQUIRED_KEYS). phi3 is Llama's arithmetic behind fused qkv_proj / gate_up_proj Linears (from_state_dict splits them)."""
     mt = config.get("model_type") or "llama"
     if mt in LLAMA_FAMILY:
         rope_parameters(config)   # plain RoPE or a complete llama3 rule; raises otherwise
@@ -125,6 +137,32 @@ def model_family(config: dict) -> str:
                                       f"head_dim and no attn_logit_softcapping: the uncapped attention kernels scale by "
                                       f"head_dim ** -0.5; {supported}")
         return "gemma2"
+    if mt in PHI3_FAMILY:
+        missing = [k for k in PHI3_REQUIRED_KEYS if k not in config or (config[k] is None and k != "sliding_window")]
+        if missing:
+            raise NotImplementedError(f"model_type {mt!r} config lacks {', '.join(missing)}: a Phi-3 config.json spells them "
+                                      f"out, and the kernels assume no defaults for them; {supported}")
+        if config["hidden_act"] != "silu":
+            raise NotImplementedError(f"model_type {mt!r} with hidden_act={config['hidden_act']!r}: the kernels implement "
+                                      f"silu (SwiGLU); {supported}")
+        try:
+            scaled = rope_parameters(config)[1] is not None   # longrope / su raise here
+        except NotImplementedError as e:
+            raise NotImplementedError(f"model_type {mt!r} with {e}; {supported}") from None
+        if scaled:
+            raise NotImplementedError(f"model_type {mt!r} with rope_scaling="
+                                      f"{config.get('rope_scaling') or config.get('rope_parameters')!r}: Phi-3 is served "
+                                      f"with plain RoPE only (no longrope / Phi-3-128k); {supported}")
+        prf = config.get("partial_rotary_factor")
+        if prf is None and isinstance(config.get("rope_parameters"), dict):
+            prf = config["rope_parameters"].get("partial_rotary_factor")
+        if prf is not None and prf != 1:
+            raise NotImplementedError(f"model_type {mt!r} with partial_rotary_factor={prf!r}: the rotary epilogue rotates the "
+                                      f"whole head; {supported}")
+        sw = config["sliding_window"]
+        if sw is not None and not (isinstance(sw, int) and sw > 0):
+            raise NotImplementedError(f"model_type {mt!r} with sliding_window={sw!r}: a positive integer or null; {supported}")
+        return "phi3"
     raise NotImplementedError(f"model_type {mt!r} is not supported by the ranker's kernels; supported families: "
                               f"{', '.join(SUPPORTED_MODEL_TYPES)}")
 
@@ -285,8 +323,10 @@ class LlamaRanker:
         self.hd = c.get("head_dim") or c["hidden_size"] // c["num_attention_heads"]
         # Mistral's sliding window: the kernels attend to the whole causal range, so a longer prompt is refused
         # (Gemma-2: its even layers' window; within it the window is the plain causal mask)
-        self.max_prompt_len = c.get("sliding_window") if c.get("model_type") == "mistral" or self.family == "gemma2" else None
-        self._window_owner = "Gemma-2" if self.family == "gemma2" else "Mistral"
+        # (Phi-3: every layer's window, 2047 for mini-4k; null means none)
+        windowed = c.get("model_type") == "mistral" or self.family in ("gemma2", "phi3")
+        self.max_prompt_len = c.get("sliding_window") if windowed else None
+        self._window_owner = {"gemma2": "Gemma-2", "phi3": "Phi-3"}.get(self.family, "Mistral")
         self._h = C.c_void_p()
         self._tensors = {}
         self._ws = None
@@ -349,17 +389,39 @@ class LlamaRanker:
             stray = sorted(set(lora["weights"]) - known)
             if stray:
                 raise NotImplementedError(f"adapter tensors that map to no Linear of this model's decoder layers: {stray[:4]}")
+        phi3 = self.family == "phi3"
+        if phi3:
+            if lora is not None and lora["weights"]:   # a Phi-3 checkpoint has no separate q_proj ... for an adapter to target
+                raise NotImplementedError("adapter tensors that map to no Linear of this model's decoder layers: a phi3 base "
+                                          f"stores fused qkv_proj / gate_up_proj Linears: {sorted(lora['weights'])[:4]}")
+            if config.get("tie_word_embeddings") and "lm_head.weight" not in state_dict:
+                raise NotImplementedError("model_type 'phi3' with tie_word_embeddings and no lm_head.weight: Phi-3's head is "
+                                          "untied")
+            nh, nkv = config["num_attention_heads"], config["num_key_value_heads"]
+
+            def split_rows(name, sizes):
+                """The fused Linear as stored (NF4 round trip included: bitsandbytes quantises it whole), cut into row blocks"""
+                w = merged(name)
+                if w.shape[0] != sum(sizes):
+                    raise ValueError(f"{name}: {w.shape[0]} rows, expected {' + '.join(map(str, sizes))}")
+                return torch.split(w, sizes, 0)
         T = self._tensors
         T["embed"] = t("model.embed_tokens.weight").to(torch.bfloat16).contiguous()
         T["final_norm"] = t("model.norm.weight").to(torch.bfloat16).contiguous()
         T["lm_head"] = (t("lm_head.weight") if "lm_head.weight" in state_dict else T["embed"]).to(torch.bfloat16).contiguous()
         for i in range(L):
             p = f"model.layers.{i}."
-            q, k, v = (merged(p + f"self_attn.{n}_proj.weight") for n in "qkv")
+            if phi3:
+                # q | k | v rows of qkv_proj; gate | up halves of gate_up_proj (HF: up * silu(gate) of chunk(2))
+                q, k, v = split_rows(p + "self_attn.qkv_proj.weight", [nh * self.hd, nkv * self.hd, nkv * self.hd])
+                gate, up = split_rows(p + "mlp.gate_up_proj.weight", [config["intermediate_size"]] * 2)
+            else:
+                q, k, v = (merged(p + f"self_attn.{n}_proj.weight") for n in "qkv")
+                gate, up = merged(p + "mlp.gate_proj.weight"), merged(p + "mlp.up_proj.weight")
             T[f"{i}.wqkv"] = torch.cat([self._interleave_rope_rows(q), self._interleave_rope_rows(k), v],
                                        0).to(torch.bfloat16).contiguous()
             T[f"{i}.wo"] = merged(p + "self_attn.o_proj.weight").to(torch.bfloat16).contiguous()
-            T[f"{i}.wgu"] = self._interleave_gate_up(merged(p + "mlp.gate_proj.weight"), merged(p + "mlp.up_proj.weight"))
+            T[f"{i}.wgu"] = self._interleave_gate_up(gate, up)
             T[f"{i}.wdown"] = merged(p + "mlp.down_proj.weight").to(torch.bfloat16).contiguous()
             T[f"{i}.input_norm"] = t(p + "input_layernorm.weight").to(torch.bfloat16).contiguous()
             if self.family == "gemma2":
@@ -531,7 +593,7 @@ class LlamaRanker:
     def set_variants(self, gemm=0, attention=0):
         """Kernel selection (include/llamarec_mi355x.h): 0 = auto; gemm=5 = latency mode for the online
         single-user path (split-K where a short prompt would leave most CUs idle). attention: 1 generic, 2 / 3 head_dim 128,
-        4 head_dim 256, 5 head_dim 64 (scoring only: no lse), 6 = head_dim-64 MFMA attention for training (5's forward, writing
+        4 head_dim 256, 5 head_dim 64 (scoring only: no lse), 7 head_dim 96 (scoring only: no lse), 6 = head_dim-64 MFMA attention for training (5's forward, writing
         lse when a LoRA engine runs on this base, and the head_dim-64 MFMA backward; the LoRA step's auto at head_dim 64)."""
         check(lib().lr_llama_set_variants(self._h, gemm, attention), "lr_llama_set_variants")
         return self

@@ -132,6 +132,46 @@ def synth_gemma2_state(cfg: dict, seed: int, std: float = 0.02, norm_std: float 
     return sd
 
 
+def phi3_param_shapes(cfg: dict) -> list[tuple[str, tuple]]:
+    """HF Phi3ForCausalLM parameter names and shapes: Llama's with the q | k | v Linears fused into self_attn.qkv_proj and
+    gate | up into mlp.gate_up_proj (no biases, untied lm_head)."""
+    d, f, v = cfg["hidden_size"], cfg["intermediate_size"], cfg["vocab_size"]
+    nh, nkv = cfg["num_attention_heads"], cfg["num_key_value_heads"]
+    hd = cfg.get("head_dim") or d // nh
+    out = [("model.embed_tokens.weight", (v, d))]
+    for i in range(cfg["num_hidden_layers"]):
+        p = f"model.layers.{i}."
+        out += [
+            (p + "self_attn.qkv_proj.weight", ((nh + 2 * nkv) * hd, d)),
+            (p + "self_attn.o_proj.weight", (d, nh * hd)),
+            (p + "mlp.gate_up_proj.weight", (2 * f, d)),
+            (p + "mlp.down_proj.weight", (d, f)),
+            (p + "input_layernorm.weight", (d,)),
+            (p + "post_attention_layernorm.weight", (d,)),
+        ]
+    out += [("model.norm.weight", (d,)), ("lm_head.weight", (v, d))]
+    return out
+
+
+# a tiny Phi-3 at head_dim 96 (train_ranker.py --synthetic --llm phi3; tests/gen_goldens_phi3.py's hd96_mha with another vocab)
+PHI3_TINY = dict(model_type="phi3", vocab_size=1000, hidden_size=768, intermediate_size=1024, num_hidden_layers=2,
+                 num_attention_heads=8, num_key_value_heads=8, max_position_embeddings=4096,
+                 original_max_position_embeddings=4096, rms_norm_eps=1e-5, rope_theta=10000.0, rope_scaling=None,
+                 hidden_act="silu", sliding_window=2047, tie_word_embeddings=False)
+
+
+def synth_phi3_state(cfg: dict, seed: int, std: float = 0.02, norm_jitter: float = 0.1) -> dict:
+    """As synth_llama_state under Phi-3's fused names. bf16 values."""
+    sd = {}
+    for i, (name, shape) in enumerate(phi3_param_shapes(cfg)):
+        if len(shape) == 1:
+            w = np.float32(1.0) + hash_uniform(seed * 1000 + i, shape, norm_jitter)
+        else:
+            w = hash_uniform(seed * 1000 + i, shape, std)
+        sd[name] = bf16_round(w)
+    return sd
+
+
 def synth_gemma_state(cfg: dict, seed: int, std: float = 0.02, norm_std: float = 0.3) -> dict:
     """name -> float32 array for a Gemma config. Matrices ~ U(std); norm weights ~ U(norm_std) around 0 -- Gemma scales by
     (1 + w), so non-zero w exercises that form (w = 0 would make it indistinguishable from Llama's w = 1). bf16 values."""
