@@ -255,7 +255,12 @@ int lr_llama_create_ex(const LrLlamaConfig* cfg, const LrLlamaArch* arch, const 
  * variant 4 plus split-K wherever the output tiles alone would leave most CUs idle (a 460-token prompt
  * gives o_proj / down_proj 32 tiles for 256 CUs); shapes that do not fit fall back as in auto. The
  * split-K summation order depends on the token count, so unlike the default a prompt's scores are
- * then reproducible only for the same packed batch size (bf16-level differences otherwise). */
+ * then reproducible only for the same packed batch size (bf16-level differences otherwise).
+ * gemm 6 = auto with a RAGGED LAST COLUMN TILE: a product with N % 64 == 0 but N % 256 != 0 (K % 64 == 0, at least 128 rows,
+ * store / residual / rope epilogue, no folded norm) runs variant 4's 256x256x64 body on ceil(N / 256) column tiles instead of
+ * the generic kernel -- same arithmetic, rows of B and columns of C past N never addressed. Every other product goes where
+ * auto sends it, with auto's bits. For models whose widths miss the tile (Qwen2-0.5B: hidden 896, qkv 1152);
+ * llamarec_amd.llm makes it the default of a qwen2 ranker. */
 int lr_llama_set_variants(lr_llama_t* h, int32_t gemm_variant, int32_t attention_variant);
 
 /* RoPE frequency scaling (Llama-3.1 / 3.2: rope_scaling.rope_type = "llama3" in config.json). Per frequency j of the rotary
@@ -308,6 +313,16 @@ typedef struct LrGemma2Ext {
   const uint16_t* const* mlp_out_norm;   /* HOST array [num_layers] of DEVICE bf16 [hidden] */
 } LrGemma2Ext;
 int lr_llama_set_gemma2(lr_llama_t* h, const LrGemma2Ext* ext);
+
+/* Qwen2 (model_type "qwen2"): Llama's layer with a bias on q_proj, k_proj and v_proj. bqkv: HOST array [num_layers] of DEVICE
+ * bf16 [(num_heads + 2 num_kv_heads) * head_dim], 8-byte aligned, in wqkv's row order (q and k pair-interleaved per head like
+ * lr_llama_pack_qkv's rows, v plain); the caller keeps the arrays alive. Every product of the prefill that reads wqkv -- the
+ * whole-prompt QKV product, the pruned last layer's K/V and Q products, the shared-prefix path, latency mode -- adds the
+ * matching slice in its epilogue: x = bf16(fp32 acc + fp32(bias[col])), one rounding, in front of the rotation.
+ * NULL: back to no bias. LR_EINVAL, handle unchanged: a null or misaligned entry. LR_EUNSUPPORTED: a handle with folded
+ * norms. With a bias set, lr_llama_set_folded_norms (non-NULL) and lr_llama_lora_create[_ex] return LR_EUNSUPPORTED (the
+ * live-adapter forward rotates in a kernel that knows no bias). */
+int lr_llama_set_qkv_bias(lr_llama_t* h, const uint16_t* const* bqkv);
 
 /* Folded RMSNorm (optional, scoring path only). HF's layer computes  proj(norm_w * bf16(x * rstd))  with its own
  * read-and-write pass over the residual stream in front of q/k/v_proj and of gate/up_proj (LlamaRMSNorm, reached from
@@ -395,7 +410,8 @@ int lr_nf4_dynamic_map(float* out256);
  * C[M][N] = A[M][K] * B[N][K]^T, bf16 in, fp32 accumulate, bf16 out; all DEVICE pointers,
  * row-major, leading dimensions = K, K, N. variant: 0 = auto, 1 = generic (any shape),
  * 4 = 256x256x64 MFMA tile, ping-pong pipeline with balanced fragment reads and region-recycling DMA prefetch
- * (default for N%256==0, K%64==0, M>=128; any M: rows are bounds-checked). */
+ * (default for N%256==0, K%64==0, M>=128; any M: rows are bounds-checked), 5 = 4 with split-K (lr_gemm_bf16_nt_ws),
+ * 6 = auto with a ragged last column tile for N%64==0, N%256!=0 (see lr_llama_set_variants). */
 int lr_gemm_bf16_nt(const uint16_t* A, const uint16_t* B, uint16_t* C, int32_t M, int32_t N,
                     int32_t K, int32_t variant, void* hip_stream);
 /* The same with a device workspace for variant 5 (split-K, see lr_llama_set_variants): fp32 partial
@@ -414,6 +430,13 @@ int lr_gemm_bf16_nt_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const
                         int32_t K, int32_t epilogue, int32_t variant, const int32_t* tok_pos, const float* rope_cs,
                         int32_t rope_positions, int32_t head_dim, int32_t rot_cols, void* workspace, size_t workspace_bytes,
                         void* hip_stream);
+/* The same with a bf16 bias[N] (DEVICE, 8-byte aligned, indexed by output column; NULL = none), epilogues 0 and 3 only:
+ * x = bf16(fp32 acc + fp32(bias[col])) -- one rounding, where lr_gemm_bf16_nt_epi rounds bf16(acc) -- then the rotation on
+ * [0, rot_cols) and the store as before. A bias with epilogue 1, 2 or 5 is LR_EINVAL (nothing is launched). */
+int lr_gemm_bf16_nt_bias_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const uint16_t* R, int32_t M, int32_t N,
+                             int32_t K, int32_t epilogue, int32_t variant, const int32_t* tok_pos, const float* rope_cs,
+                             int32_t rope_positions, int32_t head_dim, int32_t rot_cols, void* workspace,
+                             size_t workspace_bytes, const uint16_t* bias, void* hip_stream);
 /* o_proj / down_proj together with the RMSNorm that reads their result (exposed for parity tests):
  *   C = bf16(bf16(A B^T) + R),   norm_out = bf16(norm_w * bf16(C * rsqrt(mean(C^2) + eps)))     (C may alias R)
  * fuse != 0 lets a product that variant 5 splits over K write norm_out in its reduce pass (one launch less per product in

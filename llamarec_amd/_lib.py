@@ -47,6 +47,9 @@ PROTOTYPES = {
     "lr_gemm_bf16_nt_epi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lr_gemm_bf16_nt_bias_epi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "lr_gemm_bf16_nt_residual_rmsnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
                                                    C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -79,6 +82,7 @@ PROTOTYPES = {
     "lr_llama_set_last_layer_pruning": (C.c_int, [C.c_void_p, C.c_int32]),
     "lr_llama_set_rope_scaling": (C.c_int, [C.c_void_p, C.POINTER(A.LrRopeScaling)]),
     "lr_llama_set_gemma2": (C.c_int, [C.c_void_p, C.POINTER(A.LrGemma2Ext)]),
+    "lr_llama_set_qkv_bias": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lr_fold_norm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "lr_llama_set_folded_norms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lr_llama_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -14,8 +14,8 @@ EXPERIMENT_ROOT = "experiments"   # config.py:5-9
 STATE_DICT_KEY = "model_state_dict"
 RAW_DATASET_ROOT_FOLDER = "data"
 # --llm -> base model / tokenizer of the reference's set_template (config.py:29-55). The ranker's kernels serve the llama
-# (llama2, llama3, mistral), gemma, gemma2 and phi3 families (llm.model_family; phi3 for scoring only, plain RoPE); qwen2
-# parses like the reference's and is refused when its checkpoint is loaded.
+# (llama2, llama3, mistral), gemma, gemma2, phi3 and qwen2 families (llm.model_family; phi3 and qwen2 for scoring only, plain
+# RoPE).
 LLM_CHOICES = ["llama2", "llama3", "phi3", "gemma", "mistral", "gemma2", "qwen2"]
 LLM_BASE_MODELS = {
     "phi3": "microsoft/Phi-3-mini-4k-instruct",

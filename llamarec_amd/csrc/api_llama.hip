@@ -56,9 +56,9 @@ extern "C" int lr_llama_create(const LrLlamaConfig* cfg, const LrLlamaWeightsDes
 }
 
 extern "C" int lr_llama_set_variants(lr_llama_t* h, int32_t gemm_variant, int32_t attention_variant) {
-  if (!h || (gemm_variant != 0 && gemm_variant != 1 && gemm_variant != 4 && gemm_variant != 5) || attention_variant < 0 ||
-      attention_variant > 7)
-    LR_FAIL(LR_EINVAL, "lr_llama_set_variants: gemm in {0, 1, 4, 5}, attention in {0, 1, 2, 3, 4, 5, 6, 7}");
+  if (!h || (gemm_variant != 0 && gemm_variant != 1 && gemm_variant != 4 && gemm_variant != 5 && gemm_variant != 6) ||
+      attention_variant < 0 || attention_variant > 7)
+    LR_FAIL(LR_EINVAL, "lr_llama_set_variants: gemm in {0, 1, 4, 5, 6}, attention in {0, 1, 2, 3, 4, 5, 6, 7}");
   h->gemm_variant = gemm_variant;
   h->attn_variant = attention_variant;
   return LR_OK;
@@ -124,6 +124,26 @@ extern "C" int lr_llama_set_gemma2(lr_llama_t* h, const LrGemma2Ext* e) {
   return LR_OK;
 }
 
+extern "C" int lr_llama_set_qkv_bias(lr_llama_t* h, const uint16_t* const* bqkv) {
+  if (!h) LR_FAIL(LR_EINVAL, "lr_llama_set_qkv_bias: null handle");
+  const int L = h->cfg.num_layers;
+  const uint16_t** own = nullptr;
+  if (bqkv) {   // every check before the handle changes
+    for (int l = 0; l < L; ++l)
+      if (!bqkv[l]) LR_FAIL(LR_EINVAL, "lr_llama_set_qkv_bias: layer %d has a null bias", l);
+    for (int l = 0; l < L; ++l)   // the K | V slice starts nh head_dim elements in: both ends 8-byte aligned
+      if ((reinterpret_cast<uintptr_t>(bqkv[l]) & 7) || (h->cfg.num_heads * h->cfg.head_dim) % 4 != 0)
+        LR_FAIL(LR_EINVAL, "lr_llama_set_qkv_bias: layer %d's bias is not 8-byte aligned", l);
+    if (h->wqkv_folded) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_qkv_bias: the handle has folded norms");
+    own = (const uint16_t**)malloc(sizeof(void*) * L);
+    if (!own) LR_FAIL(LR_EINVAL, "lr_llama_set_qkv_bias: out of host memory");
+    memcpy(own, bqkv, sizeof(void*) * L);
+  }
+  free(h->bqkv);
+  h->bqkv = own;
+  return LR_OK;
+}
+
 extern "C" int lr_llama_set_last_layer_pruning(lr_llama_t* h, int32_t enable) {
   if (!h) LR_FAIL(LR_EINVAL, "lr_llama_set_last_layer_pruning: null handle");
   h->prune_last = enable ? 1 : 0;
@@ -137,6 +157,7 @@ extern "C" void lr_llama_destroy(lr_llama_t* h) {
   free(h->wgu_folded);
   free(h->attn_out_norm);
   free(h->mlp_out_norm);
+  free(h->bqkv);
   free(h);
 }
 
@@ -154,6 +175,8 @@ extern "C" int lr_llama_set_folded_norms(lr_llama_t* h, const uint16_t* const* w
             "weights at HF's rounding, and the GeGLU epilogue takes no row scale)");
   if (h->gemma2 && (wqkv_folded || wgu_folded))
     LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: not with a Gemma-2 extension (lr_llama_set_gemma2)");
+  if (h->bqkv && (wqkv_folded || wgu_folded))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: not with q/k/v biases (lr_llama_set_qkv_bias)");
   free(h->wqkv_folded);
   free(h->wgu_folded);
   h->wqkv_folded = h->wgu_folded = nullptr;
@@ -271,7 +294,7 @@ static int plan_batch(const lr_llama_t* h, const int32_t* cu_host, int B, int P,
 // else is in the batch; more prompts than that take the small-tile kernel as before. (Shapes the 256-tile kernel does not
 // take fall back to it inside lr_launch_gemm.)
 static int b_row_gemm_variant(const lr_llama_t* h, int B) {
-  return (h->gemm_variant == 5 || (h->gemm_variant == 0 && B <= 256)) ? 5 : 1;
+  return (h->gemm_variant == 5 || ((h->gemm_variant == 0 || h->gemm_variant == 6) && B <= 256)) ? 5 : 1;   // 6 routes as auto
 }
 
 // Runs the transformer body; leaves the residual stream (before the final norm) in ws.x (all internal rows) or,
@@ -333,18 +356,20 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
     if (folded && !EXP_SKIP_SWEEP) LR_RUN(lr_launch_rms_rstd(ws.x, ws.rstd, n, d, c.rms_eps, st));
     if (!folded && !input_normed) LR_RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st, ns));
     const int q_w = nh * hd, kv_w = 2 * nkv * hd;
+    const u16* const bias = h->bqkv ? h->bqkv[l] : nullptr;   // Qwen2: [q_w + kv_w] in wqkv's row order (never folded)
     if (last_q_only) {
       LR_RUN(lr_launch_gemm({.A = ws.xn, .B = w.wqkv + (size_t)q_w * d, .C = ws.qkv, .M = n, .N = kv_w, .K = d,
-                             .epi = LR_EPI_ROPE, .variant = gv, .rope = rope(ws.tok_pos, kv_w / 2), .splitk = ws.splitk}, st));
+                             .epi = LR_EPI_ROPE, .variant = gv, .rope = rope(ws.tok_pos, kv_w / 2), .bias = bias ? bias + q_w : nullptr,
+                             .splitk = ws.splitk}, st));
       LR_RUN(lr_launch_gather_rows(ws.xn, ws.last_rows, B, d, ws.xn_last, st));
       LR_RUN(lr_launch_gemm({.A = ws.xn_last, .B = w.wqkv, .C = ws.q_last, .M = B, .N = q_w, .K = d, .epi = LR_EPI_ROPE,
-                             .variant = pv, .rope = rope(ws.last_pos, q_w), .splitk = ws.splitk}, st));
+                             .variant = pv, .rope = rope(ws.last_pos, q_w), .bias = bias, .splitk = ws.splitk}, st));
       LR_RUN(lr_launch_attention_last(ws.qkv, ws.q_last, ws.att_last, attn.cu, attn.cu_host, S, n, nh, nkv, hd, st, P, a_scale,
                                       a_cap));
     } else {
       LR_RUN(lr_launch_gemm({.A = folded ? ws.x : ws.xn, .B = folded ? h->wqkv_folded[l] : w.wqkv, .C = ws.qkv, .M = n,
                              .N = q_w + kv_w, .K = d, .epi = LR_EPI_ROPE, .variant = gv, .rope = rope(ws.tok_pos, q_w + kv_w / 2),
-                             .row_scale = folded ? ws.rstd : nullptr, .splitk = ws.splitk}, st));
+                             .row_scale = folded ? ws.rstd : nullptr, .bias = bias, .splitk = ws.splitk}, st));
     }
     if (!last_pruned) {
       LR_RUN(lr_launch_attention(attn, attn_kernel, st));
@@ -515,6 +540,20 @@ extern "C" int lr_gemm_bf16_nt_epi(const uint16_t* A, const uint16_t* B, uint16_
   return lr_launch_gemm({.A = A, .B = B, .C = C, .R = R, .M = M, .N = N, .K = K, .epi = epilogue, .variant = variant,
                          .rope = {.tok_pos = tok_pos, .cs = rope_cs, .cs16 = cs16, .head_dim = head_dim, .rot_cols = rot_cols},
                          .splitk = {.ws = (float*)workspace, .bytes = workspace_bytes}}, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_gemm_bf16_nt_bias_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const uint16_t* R, int32_t M,
+                                        int32_t N, int32_t K, int32_t epilogue, int32_t variant, const int32_t* tok_pos,
+                                        const float* rope_cs, int32_t rope_positions, int32_t head_dim, int32_t rot_cols,
+                                        void* workspace, size_t workspace_bytes, const uint16_t* bias, void* hip_stream) {
+  if (!A || !B || !C) LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt_bias_epi: null pointer");
+  if (epilogue < LR_EPI_STORE || epilogue > LR_EPI_GEGLU || epilogue == LR_EPI_PARTIAL)
+    LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt_bias_epi: epilogue %d", epilogue);
+  const unsigned* cs16 = (rope_cs && rope_positions > 0 && head_dim >= 2)
+                             ? reinterpret_cast<const unsigned*>(rope_cs + (size_t)rope_positions * head_dim) : nullptr;
+  return lr_launch_gemm({.A = A, .B = B, .C = C, .R = R, .M = M, .N = N, .K = K, .epi = epilogue, .variant = variant,
+                         .rope = {.tok_pos = tok_pos, .cs = rope_cs, .cs16 = cs16, .head_dim = head_dim, .rot_cols = rot_cols},
+                         .bias = bias, .splitk = {.ws = (float*)workspace, .bytes = workspace_bytes}}, (hipStream_t)hip_stream);
 }
 
 extern "C" int lr_gemm_bf16_nt_residual_rmsnorm_ex(const uint16_t* A, const uint16_t* B, uint16_t* C, const uint16_t* R,

@@ -9,7 +9,8 @@
 // Two kernels:
 //  gemm_generic_kernel : 64x64x32 tile, any M/N/K (bounds-checked) -- tiny test models, odd shapes,
 //                        and the in-library reference for the fast kernel.
-//  gemm256rb_kernel    : 256x256x64 tile, 8 wave64 (2 x 4), each wave 128x64 = 8x4 MFMA tiles.
+//  gemm256rb_kernel    : 256x256x64 tile, 8 wave64 (2 x 4), each wave 128x64 = 8x4 MFMA tiles. RAGGED (variant 6): the last
+//                        column tile may end at any multiple of 64 (Qwen2-0.5B's 896 and 1152).
 //     * both operands stream global -> LDS with global_load_lds_dwordx4 (no VGPR staging): every
 //       wave-instruction moves 8 rows x 128 B = full cache lines; the LDS image is lane-linear
 //       (the DMA's constraint) and the 16-byte chunk a lane FETCHES is XOR-permuted
@@ -57,15 +58,19 @@ struct RopeArgs {
 // FOLD: -1 = scale by the folded-norm rstd when rope.row_scale is set (run-time check), 0 = never, 1 = always (the
 // 256-tile kernel is instantiated per case: as a run-time select the scaling cost a multiply and a v_cndmask per value
 // on the un-folded default path too).
-template <int EPI, int FOLD = -1>
+// BIAS (store and rope epilogues; Qwen2's q/k/v biases): bv = the fp32 values of bias[col .. col + 3], added to the fp32
+// accumulator in front of the one rounding to bf16 -- x = bf16(acc [* row scale] + bias) -- i.e. in front of the rotation.
+template <int EPI, int FOLD = -1, bool BIAS = false>
 __device__ __forceinline__ u16x4 epi_value4(floatx4 v, floatx4 up, u16x4 r, const RopeArgs& rope, int row, int col,
-                                            const float* pre_rs, const int* pre_pos, const float4* pre_cs = nullptr) {
+                                            const float* pre_rs, const int* pre_pos, const float4* pre_cs = nullptr,
+                                            floatx4 bv = floatx4{0.f, 0.f, 0.f, 0.f}) {
   u16x4 o;
   if ((EPI == LR_EPI_ROPE || LR_EPI_IS_GATED(EPI)) && (FOLD == 1 || (FOLD == -1 && rope.row_scale))) {
     const float rs = pre_rs ? *pre_rs : rope.row_scale[row];
     v *= rs;
     up *= rs;
   }
+  if (BIAS) v += bv;
   if (EPI == LR_EPI_ROPE) {
     float x[4];
 #pragma unroll
@@ -102,17 +107,27 @@ __device__ __forceinline__ u16x4 epi_value4(floatx4 v, floatx4 up, u16x4 r, cons
   return o;
 }
 
-template <int EPI>
+// The optional bias is the kernels' trailing parameter PACK (empty, or one const u16* = bf16 bias[N]): an instantiation
+// without a bias has the kernel arguments, and the instruction stream, it had before the bias existed.
+__device__ __forceinline__ const u16* bias_of() { return nullptr; }
+__device__ __forceinline__ const u16* bias_of(const u16* b) { return b; }
+__device__ __forceinline__ floatx4 bias4(const u16* bias, int col) {   // col a multiple of 4, col + 3 < N
+  const u16x4 b = *reinterpret_cast<const u16x4*>(bias + col);
+  return floatx4{bf2f(b[0]), bf2f(b[1]), bf2f(b[2]), bf2f(b[3])};
+}
+
+template <int EPI, bool BIAS = false>
 __device__ __forceinline__ void epi_store4(floatx4 v, floatx4 up, u16* C, const u16* R, size_t off,
                                            const RopeArgs& rope = RopeArgs{nullptr, nullptr, 0, 0, nullptr, nullptr}, int row = 0, int col = 0,
-                                           const float* pre_rs = nullptr, const int* pre_pos = nullptr) {
+                                           const float* pre_rs = nullptr, const int* pre_pos = nullptr,
+                                           floatx4 bv = floatx4{0.f, 0.f, 0.f, 0.f}) {
   if (EPI == LR_EPI_PARTIAL) {  // C is the fp32 partial plane of this split
     *reinterpret_cast<floatx4*>(reinterpret_cast<float*>(C) + off) = v;
     return;
   }
   u16x4 r = u16x4{0, 0, 0, 0};
   if (EPI == LR_EPI_RESIDUAL) r = *reinterpret_cast<const u16x4*>(R + off);
-  *reinterpret_cast<u16x4*>(C + off) = epi_value4<EPI>(v, up, r, rope, row, col, pre_rs, pre_pos);
+  *reinterpret_cast<u16x4*>(C + off) = epi_value4<EPI, -1, BIAS>(v, up, r, rope, row, col, pre_rs, pre_pos, nullptr, bv);
 }
 
 // =============================================================================================
@@ -123,10 +138,12 @@ __device__ __forceinline__ void epi_store4(floatx4 v, floatx4 up, u16* C, const 
 #define GG_BK 32
 #define GG_LD 40  // padded row length (elements): 80-byte rows keep 16-byte alignment
 
-template <int EPI>
+template <int EPI, typename... Bias>
 __global__ __launch_bounds__(256) void gemm_generic_kernel(const u16* __restrict__ A,
                                                            const u16* __restrict__ B, u16* C,
-                                                           const u16* R, int M, int N, int K, RopeArgs rope) {
+                                                           const u16* R, int M, int N, int K, RopeArgs rope, Bias... bias_arg) {
+  constexpr bool BIAS = sizeof...(Bias) == 1;
+  const u16* const bias = bias_of(bias_arg...);
   __shared__ __attribute__((aligned(16))) u16 As[GG_BM * GG_LD];
   __shared__ __attribute__((aligned(16))) u16 Bs[GG_BN * GG_LD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -186,10 +203,16 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(const u16* __restrict
       for (int nt = 0; nt < 2; ++nt) {
         const int col = n0 + wn * 32 + nt * 16 + (lane >> 4) * 4;
         if (col + 3 < N) {
-          epi_store4<EPI>(acc[mt][nt], acc[mt][nt], C, R, (size_t)row * N + col, rope, row, col);
+          floatx4 bv = floatx4{0.f, 0.f, 0.f, 0.f};
+          if (BIAS) bv = bias4(bias, col);
+          epi_store4<EPI, BIAS>(acc[mt][nt], acc[mt][nt], C, R, (size_t)row * N + col, rope, row, col, nullptr, nullptr, bv);
         } else {
           for (int j = 0; j < 4; ++j)  // only hit when N%4 != 0 (no rope cols there)
-            if (col + j < N) C[(size_t)row * N + col + j] = f2bf(acc[mt][nt][j] * (rope.row_scale ? rope.row_scale[row] : 1.0f));
+            if (col + j < N) {
+              float x = acc[mt][nt][j] * (rope.row_scale ? rope.row_scale[row] : 1.0f);
+              if (BIAS) x += bf2f(bias[col + j]);
+              C[(size_t)row * N + col + j] = f2bf(x);
+            }
         }
       }
     } else if (LR_EPI_IS_GATED(EPI)) {
@@ -210,7 +233,7 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(const u16* __restrict
           if (col < N) {
             size_t off = (size_t)row * N + col;
             float v = bf2f(f2bf(acc[mt][nt][j]));
-            C[off] = (EPI == LR_EPI_RESIDUAL) ? f2bf(v + bf2f(R[off])) : f2bf(acc[mt][nt][j]);
+            C[off] = (EPI == LR_EPI_RESIDUAL) ? f2bf(v + bf2f(R[off])) : f2bf(BIAS ? acc[mt][nt][j] + bf2f(bias[col]) : acc[mt][nt][j]);
           }
         }
     }
@@ -312,11 +335,19 @@ __device__ unsigned long long g_gemm_stamps[16384 * 2 * GEMM_STAMP_SLOTS];
   }
 #endif
 
-template <int EPI, bool FOLD = false, bool STAMP = false>
+// RAGGED (variant 6; store, residual and rope epilogues, N % 64 == 0): the last of ceil(N / 256) column tiles ends at N. Same
+// LDS image, K loop, MFMA order and barriers: the DMA source row of B is clamped to N - 1 as A's is to M - 1 (rows past N are
+// never addressed; what they feed is never stored), and a wave whose 64-column slab lies at or past N -- wave-uniform, the
+// slab is wholly inside or wholly outside -- takes part in every DMA and barrier and leaves in front of the epilogue's
+// loads and stores: no address at or past column N is formed for C, R, the bias or the rope table.
+template <int EPI, bool FOLD = false, bool STAMP = false, bool RAGGED = false, typename... Bias>
 __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ A,
                                                         const u16* __restrict__ B, u16* C,
                                                         const u16* R, int M, int N, int K, int group_m,
-                                                        RopeArgs rope) {
+                                                        RopeArgs rope, Bias... bias_arg) {
+  constexpr bool BIAS = sizeof...(Bias) == 1;
+  static_assert(!BIAS || EPI == LR_EPI_STORE || EPI == LR_EPI_ROPE, "a bias goes with the store and rope epilogues");
+  static_assert(!RAGGED || EPI == LR_EPI_STORE || EPI == LR_EPI_RESIDUAL || EPI == LR_EPI_ROPE, "ragged: no gated / split-K form");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -331,7 +362,7 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
     C = reinterpret_cast<u16*>(reinterpret_cast<float*>(C) + (size_t)s * M * N);
   }
 
-  const int tilesM = (M + 255) >> 8, tilesN = N >> 8;
+  const int tilesM = (M + 255) >> 8, tilesN = RAGGED ? (N + 255) >> 8 : N >> 8;
   const int nwg = tilesM * tilesN;
   int id;
   {
@@ -372,7 +403,8 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
         src[t][j] = reinterpret_cast<const char*>(A) + ((size_t)arow * K) * 2 + chunk * 16 + (size_t)kt_first * 128;
         ldsoff[t][j] = rows[t] * 128;
       } else {
-        src[t][j] = reinterpret_cast<const char*>(B) + ((size_t)(n0 + row) * K) * 2 + chunk * 16 + (size_t)kt_first * 128;
+        const int brow = RAGGED ? min(n0 + row, N - 1) : n0 + row;
+        src[t][j] = reinterpret_cast<const char*>(B) + ((size_t)brow * K) * 2 + chunk * 16 + (size_t)kt_first * 128;
         ldsoff[t][j] = 32768 + rows[t] * 128;
       }
     }
@@ -543,8 +575,9 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
       p1[i] = b_;
     }
   };
+  const bool slab_live = !RAGGED || n0 + wn * 64 < N;   // wave-uniform (N % 64 == 0)
   u32x4 rpre[8][2];
-  if (EPI == LR_EPI_RESIDUAL) {
+  if (EPI == LR_EPI_RESIDUAL && slab_live) {
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
 #pragma unroll
@@ -581,6 +614,10 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) ppre[mt] = rope.tok_pos[min(m0 + wm * 128 + mt * 16 + (lane & 15), M - 1)];
   }
+  if (RAGGED && !slab_live) return;   // behind the kernel's last barrier
+  floatx4 bpre[4];   // bias of my 4 columns in each of the 4 column tiles
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) bpre[nt] = BIAS ? bias4(bias_of(bias_arg...), n0 + wn * 64 + nt * 16 + quad * 4) : floatx4{0.f, 0.f, 0.f, 0.f};
   // LDS addresses of this lane's entries: row (wm 128 + mt 16 + li), pairs (wn & 1) 32 + nt 8 + 2 quad, + 1 = 8 bytes at
   // chunk ((wn & 1) 8 + 2 nt + (quad >> 1)) ^ li; the row tile mt is an immediate (4096 mt)
   int cs_off[4];
@@ -664,10 +701,10 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
           ra = u16x4{(u16)(x[0] & 0xffff), (u16)(x[0] >> 16), (u16)(x[1] & 0xffff), (u16)(x[1] >> 16)};
           rb = u16x4{(u16)(y[0] & 0xffff), (u16)(y[0] >> 16), (u16)(y[1] & 0xffff), (u16)(y[1] >> 16)};
         }
-        const u16x4 oa = epi_value4<EPI, has_rs ? 1 : 0>(acc[mt][2 * k], acc[mt][2 * k], ra, rope, rowc, cpair + quad * 4, prs, ppos,
-                                         EPI == LR_EPI_ROPE ? &tpre[mt & 3][2 * k] : nullptr);
-        const u16x4 ob = epi_value4<EPI, has_rs ? 1 : 0>(acc[mt][2 * k + 1], acc[mt][2 * k + 1], rb, rope, rowc, cpair + 16 + quad * 4, prs, ppos,
-                                         EPI == LR_EPI_ROPE ? &tpre[mt & 3][2 * k + 1] : nullptr);
+        const u16x4 oa = epi_value4<EPI, has_rs ? 1 : 0, BIAS>(acc[mt][2 * k], acc[mt][2 * k], ra, rope, rowc, cpair + quad * 4, prs, ppos,
+                                         EPI == LR_EPI_ROPE ? &tpre[mt & 3][2 * k] : nullptr, bpre[2 * k]);
+        const u16x4 ob = epi_value4<EPI, has_rs ? 1 : 0, BIAS>(acc[mt][2 * k + 1], acc[mt][2 * k + 1], rb, rope, rowc, cpair + 16 + quad * 4, prs, ppos,
+                                         EPI == LR_EPI_ROPE ? &tpre[mt & 3][2 * k + 1] : nullptr, bpre[2 * k + 1]);
         unsigned a[2] = {(unsigned)oa[0] | ((unsigned)oa[1] << 16), (unsigned)oa[2] | ((unsigned)oa[3] << 16)};
         unsigned b[2] = {(unsigned)ob[0] | ((unsigned)ob[1] << 16), (unsigned)ob[2] | ((unsigned)ob[3] << 16)};
 #pragma unroll
@@ -693,9 +730,10 @@ __global__ __launch_bounds__(512) void gemm256rb_kernel(const u16* __restrict__ 
 // =============================================================================================
 // split-K reduce: sum the S fp32 partial planes in split order, then the real epilogue
 // =============================================================================================
-template <int EPI>
+template <int EPI, typename... Bias>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int S, u16* C,
-                                                            const u16* R, int M, int N, RopeArgs rope) {
+                                                            const u16* R, int M, int N, RopeArgs rope, Bias... bias_arg) {
+  constexpr bool BIAS = sizeof...(Bias) == 1;
   const size_t plane = (size_t)M * N;
   if (LR_EPI_IS_GATED(EPI)) {
     // output column c of N/2: gate column (c/16)*32 + c%16, up column 16 further (16-row interleave of wgu)
@@ -716,7 +754,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     if (off >= plane) return;
     floatx4 v = *reinterpret_cast<const floatx4*>(part + off);
     for (int s = 1; s < S; ++s) v += *reinterpret_cast<const floatx4*>(part + s * plane + off);
-    epi_store4<EPI>(v, v, C, R, off, rope, (int)(off / N), (int)(off % N));
+    const int col = (int)(off % N);   // N % 4 == 0: a quad stays inside its row
+    floatx4 bv = floatx4{0.f, 0.f, 0.f, 0.f};
+    if (BIAS) bv = bias4(bias_of(bias_arg...), col);
+    epi_store4<EPI, BIAS>(v, v, C, R, off, rope, (int)(off / N), col, nullptr, nullptr, bv);
   }
 }
 
@@ -761,8 +802,21 @@ static int gemm256_prepare() {
   return lr_ensure_dynamic_lds(reinterpret_cast<const void*>(gemm256rb_kernel<EPI, FOLD>), 2 * G2_STAGE_BYTES + (FOLD ? 1024 : 0), done);
 }
 
-template <int EPI>
-static int launch_splitk(const LrGemmArgs& g, int S, RopeArgs rope, hipStream_t st) {
+// The 256-tile kernel with a bias (Bias = const u16*), a ragged last column tile (variant 6), or both
+template <int EPI, bool RAGGED, typename... Bias>
+static int launch256_ext(const LrGemmArgs& g, const RopeArgs& rope, hipStream_t st, Bias... bias) {
+  static bool done[LR_MAX_DEVICES] = {};
+  const auto kernel = gemm256rb_kernel<EPI, false, false, RAGGED, Bias...>;
+  if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), 2 * G2_STAGE_BYTES, done)) return rc;
+  const int nwg = ((g.M + 255) / 256) * ((g.N + 255) / 256);
+  hipLaunchKernelGGL(kernel, dim3(nwg), dim3(512), 2 * G2_STAGE_BYTES, st, g.A, g.B, g.C, g.R, g.M, g.N, g.K,
+                     gemm256_group_m(g.K), rope, bias...);
+  LR_CHECK_LAUNCH("gemm256rb_kernel");
+  return LR_OK;
+}
+
+template <int EPI, typename... Bias>
+static int launch_splitk(const LrGemmArgs& g, int S, RopeArgs rope, hipStream_t st, Bias... bias) {
   const int M = g.M, N = g.N, K = g.K;
   float* ws = g.splitk.ws;
   const LrGemmThenNorm& tn = g.then_norm;
@@ -777,18 +831,23 @@ static int launch_splitk(const LrGemmArgs& g, int S, RopeArgs rope, hipStream_t 
     return lr_launch_reduce_residual_rmsnorm(ws, S, g.C, g.R, M, N, tn.w, tn.out, tn.eps, st, tn.style);
   }
   const size_t quads = (LR_EPI_IS_GATED(EPI) ? (size_t)M * (N >> 1) : (size_t)M * N) / 4;
-  hipLaunchKernelGGL(splitk_reduce_kernel<EPI>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, ws, S, g.C, g.R, M,
-                     N, rope);
+  hipLaunchKernelGGL((splitk_reduce_kernel<EPI, Bias...>), dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, ws, S, g.C,
+                     g.R, M, N, rope, bias...);
   LR_CHECK_LAUNCH("splitk_reduce_kernel");
   return LR_OK;
 }
 
 // =============================================================================================
-template <int EPI>
-static int launch_epi(const LrGemmArgs& g, int variant, RopeArgs rope, hipStream_t st) {
+// variant: 1, 4 or 6 (6: the caller has checked that the product is a ragged one this kernel takes)
+template <int EPI, typename... Bias>
+static int launch_epi(const LrGemmArgs& g, int variant, RopeArgs rope, hipStream_t st, Bias... bias) {
   const int M = g.M, N = g.N, K = g.K;
   LrProfScope prof(variant >= 2 ? LR_PROF_GEMM256 : LR_PROF_GEMM_GENERIC, 2.0 * M * (double)N * K, st,
                    LR_PROF_GEMM_TAG(EPI, N, K));
+  if constexpr (EPI == LR_EPI_STORE || EPI == LR_EPI_RESIDUAL || EPI == LR_EPI_ROPE) {
+    if (variant == 6) return launch256_ext<EPI, true>(g, rope, st, bias...);
+    if (variant == 4 && sizeof...(Bias) == 1) return launch256_ext<EPI, false>(g, rope, st, bias...);
+  }
   if (variant == 4) {
     const int nwg = ((M + 255) / 256) * (N / 256);
     bool launched = false;
@@ -822,7 +881,7 @@ static int launch_epi(const LrGemmArgs& g, int variant, RopeArgs rope, hipStream
     LR_CHECK_LAUNCH("gemm256rb_kernel");
   } else {
     dim3 grid((N + GG_BN - 1) / GG_BN, (M + GG_BM - 1) / GG_BM);
-    hipLaunchKernelGGL(gemm_generic_kernel<EPI>, grid, dim3(256), 0, st, g.A, g.B, g.C, g.R, M, N, K, rope);
+    hipLaunchKernelGGL((gemm_generic_kernel<EPI, Bias...>), grid, dim3(256), 0, st, g.A, g.B, g.C, g.R, M, N, K, rope, bias...);
     LR_CHECK_LAUNCH("gemm_generic_kernel");
   }
   return LR_OK;
@@ -844,10 +903,19 @@ int lr_launch_gemm(const LrGemmArgs& g, hipStream_t st) {
   if (M <= 0) return LR_OK;
   if (N <= 0 || K <= 0) LR_FAIL(LR_EINVAL, "gemm: N=%d K=%d", N, K);
   const bool fast_ok = (N % 256 == 0) && (K % 64 == 0) && M >= 1;
+  // variant 6 = auto, except that a product whose N is a multiple of 64 but not of 256 (K % 64 == 0, M >= 128, store /
+  // residual / rope epilogue, no folded norm) runs the 256-tile body with a ragged last column tile instead of the generic
+  // kernel. Everything else -- N % 256 == 0, M < 128, gated epilogues, N % 64 != 0 -- goes where auto sends it, with auto's bits.
+  if (variant == 6) {
+    const bool ragged = (N % 256 != 0) && (N % 64 == 0) && (K % 64 == 0) && M >= 128 && !g.row_scale &&
+                        (epi == LR_EPI_STORE || epi == LR_EPI_RESIDUAL || epi == LR_EPI_ROPE);
+    if (!ragged) variant = 0;
+  }
   if (variant == 0) variant = (fast_ok && M >= 128) ? 4 : 1;
   if (variant == 5 && !fast_ok) variant = 1;  // latency mode: any row count (B last-token rows too), shapes as auto
-  if (variant != 1 && variant != 4 && variant != 5)
-    LR_FAIL(LR_EINVAL, "gemm: unknown variant %d (0 auto, 1 generic, 4 = 256x256x64 MFMA tile, 5 = 4 + split-K)", variant);
+  if (variant != 1 && variant != 4 && variant != 5 && variant != 6)
+    LR_FAIL(LR_EINVAL, "gemm: unknown variant %d (0 auto, 1 generic, 4 = 256x256x64 MFMA tile, 5 = 4 + split-K, 6 = auto + "
+            "ragged last column tile)", variant);
   if (variant == 4 && !fast_ok)
     LR_FAIL(LR_EUNSUPPORTED, "gemm variant 4 needs N%%256==0 and K%%64==0 (N=%d K=%d)", N, K);
   if (LR_EPI_IS_GATED(epi) && (N % 32 != 0)) LR_FAIL(LR_EINVAL, "gated-MLP epilogue needs N%%32==0 (N=%d)", N);
@@ -855,6 +923,10 @@ int lr_launch_gemm(const LrGemmArgs& g, hipStream_t st) {
   const RopeArgs rope{g.rope.tok_pos, g.rope.cs, g.rope.head_dim, g.rope.rot_cols, g.row_scale, g.rope.cs16};
   if (g.row_scale && epi != LR_EPI_ROPE && epi != LR_EPI_SWIGLU)
     LR_FAIL(LR_EINVAL, "gemm: a row scale (folded RMSNorm) is only applied by the rope and swiglu epilogues");
+  if (g.bias && epi != LR_EPI_STORE && epi != LR_EPI_ROPE)
+    LR_FAIL(LR_EINVAL, "gemm: a bias is only added by the store and rope epilogues (epilogue %d)", epi);
+  if (g.bias && g.row_scale) LR_FAIL(LR_EUNSUPPORTED, "gemm: a bias together with a row scale (folded RMSNorm)");
+  if (g.bias && (reinterpret_cast<uintptr_t>(g.bias) & 7)) LR_FAIL(LR_EINVAL, "gemm: the bias must be 8-byte aligned");
   if (epi == LR_EPI_ROPE) {
     if (!rope.tok_pos || !rope.cs || rope.head_dim < 2 || rope.head_dim % 4 != 0 || rope.rot_cols % 4 != 0 || rope.rot_cols > N)
       LR_FAIL(LR_EINVAL, "rope epilogue: bad arguments (head_dim=%d rot_cols=%d)", rope.head_dim, rope.rot_cols);
@@ -866,22 +938,22 @@ int lr_launch_gemm(const LrGemmArgs& g, hipStream_t st) {
         LR_FAIL(LR_EWORKSPACE, "gemm variant 5: split-K x%d of %dx%d needs %zu workspace bytes, have %zu", S, M, N,
                 (size_t)S * M * N * sizeof(float), g.splitk.ws ? g.splitk.bytes : (size_t)0);
       switch (epi) {
-        case LR_EPI_STORE: return launch_splitk<LR_EPI_STORE>(g, S, rope, st);
+        case LR_EPI_STORE: return g.bias ? launch_splitk<LR_EPI_STORE>(g, S, rope, st, g.bias) : launch_splitk<LR_EPI_STORE>(g, S, rope, st);
         case LR_EPI_RESIDUAL: return launch_splitk<LR_EPI_RESIDUAL>(g, S, rope, st);
         case LR_EPI_SWIGLU: return launch_splitk<LR_EPI_SWIGLU>(g, S, rope, st);
         case LR_EPI_GEGLU: return launch_splitk<LR_EPI_GEGLU>(g, S, rope, st);
-        case LR_EPI_ROPE: return launch_splitk<LR_EPI_ROPE>(g, S, rope, st);
+        case LR_EPI_ROPE: return g.bias ? launch_splitk<LR_EPI_ROPE>(g, S, rope, st, g.bias) : launch_splitk<LR_EPI_ROPE>(g, S, rope, st);
       }
       LR_FAIL(LR_EINVAL, "gemm: unknown epilogue %d", epi);
     }
     variant = 4;
   }
   switch (epi) {
-    case LR_EPI_STORE: return launch_epi<LR_EPI_STORE>(g, variant, rope, st);
+    case LR_EPI_STORE: return g.bias ? launch_epi<LR_EPI_STORE>(g, variant, rope, st, g.bias) : launch_epi<LR_EPI_STORE>(g, variant, rope, st);
     case LR_EPI_RESIDUAL: return launch_epi<LR_EPI_RESIDUAL>(g, variant, rope, st);
     case LR_EPI_SWIGLU: return launch_epi<LR_EPI_SWIGLU>(g, variant, rope, st);
     case LR_EPI_GEGLU: return launch_epi<LR_EPI_GEGLU>(g, variant, rope, st);
-    case LR_EPI_ROPE: return launch_epi<LR_EPI_ROPE>(g, variant, rope, st);
+    case LR_EPI_ROPE: return g.bias ? launch_epi<LR_EPI_ROPE>(g, variant, rope, st, g.bias) : launch_epi<LR_EPI_ROPE>(g, variant, rope, st);
   }
   LR_FAIL(LR_EINVAL, "gemm: unknown epilogue %d", epi);
 }

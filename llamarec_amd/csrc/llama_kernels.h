@@ -84,7 +84,8 @@ int lr_launch_residual_postnorm(unsigned short* x, const unsigned short* h, cons
 
 // C[M][N] (+epilogue) = A[M][K] * B[N][K]^T. Call sites name what they pass (designated initialisers); a member left
 // out is absent. variant: 0 auto, 1 generic, 4 = 256x256x64 MFMA tile, 5 = variant 4 with split-K when the tiles alone
-// would leave most CUs idle (needs splitk).
+// would leave most CUs idle (needs splitk), 6 = auto, with the 256-tile body on a ragged last column tile where N % 64 == 0
+// but N % 256 != 0 (llama_gemm.hip, lr_launch_gemm).
 struct LrGemmRope {                 // LR_EPI_ROPE only
   const int32_t* tok_pos = nullptr; // [M] position of each row inside its prompt
   const float* cs = nullptr;        // lr_launch_rope_table's fp32 table
@@ -111,6 +112,8 @@ struct LrGemmArgs {
   int epi = LR_EPI_STORE, variant = 0;
   LrGemmRope rope;
   const float* row_scale = nullptr;  // rope / swiglu epilogues: accumulator row m times row_scale[m] (folded RMSNorm)
+  // store / rope epilogues: bf16 bias[N] by output column (8-byte aligned), x = bf16(acc + bias) in front of the rotation
+  const unsigned short* bias = nullptr;
   LrGemmSplitK splitk;
   LrGemmThenNorm then_norm;
 };

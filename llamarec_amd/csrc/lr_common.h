@@ -152,7 +152,7 @@ struct lr_llama {
   const uint16_t* lm_head;
   LrLlamaLayerWeights* layers;  // host array
   int device;
-  int gemm_variant;  // 0 auto, 1 generic, 4 256x256x64 MFMA tile, 5 = 4 + split-K (latency mode)
+  int gemm_variant;  // 0 auto, 1 generic, 4 256x256x64 MFMA tile, 5 = 4 + split-K (latency mode), 6 = auto + ragged column tile
   int attn_variant;  // 0 auto, 1 generic, 2 MFMA head_dim 128, 3 256-row tiles, 4 MFMA head_dim 256, 5 MFMA head_dim 64
   int prune_last;    // last layer: attention output / o_proj / MLP only for each prompt's last token
   // folded RMSNorm (lr_llama_set_folded_norms): per layer wqkv * diag(input_norm) and wgu * diag(post_norm), or null
@@ -164,6 +164,9 @@ struct lr_llama {
   float attn_softcap, final_softcap, attn_scale;   // attn_scale: the resolved value (> 0) whenever attn_softcap > 0
   const uint16_t** attn_out_norm;    // [num_layers] owned copies of the caller's arrays, or null: no sandwich norms
   const uint16_t** mlp_out_norm;
+  // Qwen2 (lr_llama_set_qkv_bias): [num_layers] owned copy of the caller's array of bf16 [(nh + 2 nkv) head_dim] biases in
+  // wqkv's row order, or null (calloc): no bias (refuses folded norms and LoRA engines)
+  const uint16_t** bqkv;
 };
 
 #endif  // LR_COMMON_H

@@ -56,17 +56,30 @@ PHI3_MINI = dict(model_type="phi3", vocab_size=32064, hidden_size=3072, intermed
                  hidden_act="silu", sliding_window=2047, tie_word_embeddings=False)
 PHI3_MEDIUM = dict(PHI3_MINI, hidden_size=5120, intermediate_size=17920, num_hidden_layers=40, num_attention_heads=40,
                    num_key_value_heads=10)
+# Qwen/Qwen2-0.5B, Qwen2-1.5B and Qwen2-7B (config.json of the checkpoints; the reference's --llm qwen2 loads Qwen2-0.5B).
+# Llama's arithmetic with a bias on q_proj / k_proj / v_proj. 0.5B's widths (896, qkv 1152) miss the 256-column GEMM tile.
+QWEN2_0_5B = dict(model_type="qwen2", vocab_size=151936, hidden_size=896, intermediate_size=4864, num_hidden_layers=24,
+                  num_attention_heads=14, num_key_value_heads=2, max_position_embeddings=131072, rms_norm_eps=1e-6,
+                  rope_theta=1000000.0, hidden_act="silu", use_sliding_window=False, sliding_window=131072,
+                  max_window_layers=24, tie_word_embeddings=True)
+QWEN2_1_5B = dict(QWEN2_0_5B, hidden_size=1536, intermediate_size=8960, num_hidden_layers=28, num_attention_heads=12,
+                  max_window_layers=28)
+QWEN2_7B = dict(QWEN2_1_5B, vocab_size=152064, hidden_size=3584, intermediate_size=18944, num_attention_heads=28,
+                num_key_value_heads=4, tie_word_embeddings=False)
 
 # model_type -> backbone family of the kernels (LrLlamaArch). Llama-2 / Llama-3 and Mistral share Llama's arithmetic.
 LLAMA_FAMILY = ("llama", "mistral")
 GEMMA_FAMILY = ("gemma",)
 GEMMA2_FAMILY = ("gemma2",)
 PHI3_FAMILY = ("phi3",)
-SUPPORTED_MODEL_TYPES = LLAMA_FAMILY + PHI3_FAMILY + GEMMA_FAMILY + GEMMA2_FAMILY
+QWEN2_FAMILY = ("qwen2",)
+SUPPORTED_MODEL_TYPES = LLAMA_FAMILY + PHI3_FAMILY + QWEN2_FAMILY + GEMMA_FAMILY + GEMMA2_FAMILY
 # what a gemma2 config must spell out (the two caps may be null): none of them has a default the kernels could assume
 GEMMA2_REQUIRED_KEYS = ("query_pre_attn_scalar", "attn_logit_softcapping", "final_logit_softcapping", "sliding_window", "head_dim")
 # what a phi3 config must spell out (sliding_window may be null = none); every published Phi-3 config.json has all three
 PHI3_REQUIRED_KEYS = ("hidden_act", "original_max_position_embeddings", "sliding_window")
+# what a qwen2 config must spell out (sliding_window may be null); every published Qwen2 config.json has all four
+QWEN2_REQUIRED_KEYS = ("hidden_act", "use_sliding_window", "sliding_window", "max_window_layers")
 
 
 _LLAMA3_NUMBERS = ("factor", "low_freq_factor", "high_freq_factor", "original_max_position_embeddings")
@@ -97,10 +110,11 @@ def rope_parameters(config: dict):
 
 
 def model_family(config: dict) -> str:
-    """'llama', 'gemma', 'gemma2' or 'phi3' for a HF config dict (a missing model_type means llama); anything else raises:
+    """'llama', 'gemma', 'gemma2', 'phi3' or 'qwen2' for a HF config dict (a missing model_type means llama); anything else raises:
     the kernels implement those families' arithmetic only, and a checkpoint of another family would load (same tensor names)
-    and then score silently wrong. A gemma2 or phi3 config is accepted only when it is complete (GEMMA2_REQUIRED_KEYS,
-    PHI3_REQUIRED_KEYS). phi3 is Llama's arithmetic behind fused qkv_proj / gate_up_proj Linears (from_state_dict splits them)."""
+    and then score silently wrong. A gemma2, phi3 or qwen2 config is accepted only when it is complete (GEMMA2_REQUIRED_KEYS,
+    PHI3_REQUIRED_KEYS, QWEN2_REQUIRED_KEYS). phi3 is Llama's arithmetic behind fused qkv_proj / gate_up_proj Linears
+    (from_state_dict splits them); qwen2 is Llama's arithmetic with q/k/v biases (lr_llama_set_qkv_bias)."""
     mt = config.get("model_type") or "llama"
     if mt in LLAMA_FAMILY:
         rope_parameters(config)   # plain RoPE or a complete llama3 rule; raises otherwise
@@ -163,6 +177,34 @@ def model_family(config: dict) -> str:
         if sw is not None and not (isinstance(sw, int) and sw > 0):
             raise NotImplementedError(f"model_type {mt!r} with sliding_window={sw!r}: a positive integer or null; {supported}")
         return "phi3"
+    if mt in QWEN2_FAMILY:
+        missing = [k for k in QWEN2_REQUIRED_KEYS if k not in config or (config[k] is None and k != "sliding_window")]
+        if missing:
+            raise NotImplementedError(f"model_type {mt!r} config lacks {', '.join(missing)}: a Qwen2 config.json spells them "
+                                      f"out, and the kernels assume no defaults for them; {supported}")
+        if config["hidden_act"] != "silu":
+            raise NotImplementedError(f"model_type {mt!r} with hidden_act={config['hidden_act']!r}: the kernels implement "
+                                      f"silu (SwiGLU); {supported}")
+        try:
+            scaled = rope_parameters(config)[1] is not None   # yarn, dynamic, ... raise here
+        except NotImplementedError as e:
+            raise NotImplementedError(f"model_type {mt!r} with {e}; {supported}") from None
+        if scaled:
+            raise NotImplementedError(f"model_type {mt!r} with rope_scaling="
+                                      f"{config.get('rope_scaling') or config.get('rope_parameters')!r}: Qwen2 is served "
+                                      f"with plain RoPE only; {supported}")
+        hd = config.get("head_dim")
+        if hd is not None and hd != config["hidden_size"] // config["num_attention_heads"]:
+            raise NotImplementedError(f"model_type {mt!r} with head_dim={hd!r} != hidden_size / num_attention_heads = "
+                                      f"{config['hidden_size'] // config['num_attention_heads']}; {supported}")
+        if not isinstance(config["use_sliding_window"], bool):
+            raise NotImplementedError(f"model_type {mt!r} with use_sliding_window={config['use_sliding_window']!r}: true or "
+                                      f"false; {supported}")
+        sw = config["sliding_window"]
+        if config["use_sliding_window"] and not (isinstance(sw, int) and not isinstance(sw, bool) and sw > 0):
+            raise NotImplementedError(f"model_type {mt!r} with use_sliding_window and sliding_window={sw!r}: a positive "
+                                      f"integer; {supported}")
+        return "qwen2"
     raise NotImplementedError(f"model_type {mt!r} is not supported by the ranker's kernels; supported families: "
                               f"{', '.join(SUPPORTED_MODEL_TYPES)}")
 
@@ -324,9 +366,11 @@ class LlamaRanker:
         # Mistral's sliding window: the kernels attend to the whole causal range, so a longer prompt is refused
         # (Gemma-2: its even layers' window; within it the window is the plain causal mask)
         # (Phi-3: every layer's window, 2047 for mini-4k; null means none)
-        windowed = c.get("model_type") == "mistral" or self.family in ("gemma2", "phi3")
+        # (Qwen2: only with use_sliding_window, then on the layers from max_window_layers on; false: the window is ignored)
+        windowed = (c.get("model_type") == "mistral" or self.family in ("gemma2", "phi3")
+                    or (self.family == "qwen2" and c["use_sliding_window"]))
         self.max_prompt_len = c.get("sliding_window") if windowed else None
-        self._window_owner = {"gemma2": "Gemma-2", "phi3": "Phi-3"}.get(self.family, "Mistral")
+        self._window_owner = {"gemma2": "Gemma-2", "phi3": "Phi-3", "qwen2": "Qwen2"}.get(self.family, "Mistral")
         self._h = C.c_void_p()
         self._tensors = {}
         self._ws = None
@@ -339,6 +383,9 @@ class LlamaRanker:
         # 164.2 vs 163.5 ms per step in a same-box A/B
         self.fold_norms = False
         self.training = False
+        # Qwen2's widths may miss the 256-column GEMM tile (0.5B: 896 and 1152): its default GEMM variant is 6, auto with a
+        # ragged last column tile (set_variants overrides it; no other family's default changes)
+        self.default_gemm_variant = 6 if self.family == "qwen2" else 0
 
     # -- construction ------------------------------------------------------------------------
     @classmethod
@@ -406,6 +453,12 @@ class LlamaRanker:
                     raise ValueError(f"{name}: {w.shape[0]} rows, expected {' + '.join(map(str, sizes))}")
                 return torch.split(w, sizes, 0)
         T = self._tensors
+        if self.family == "qwen2":
+            for i in range(L):
+                for n in "qkv":
+                    if f"model.layers.{i}.self_attn.{n}_proj.bias" not in state_dict:
+                        raise KeyError(f"model_type 'qwen2': model.layers.{i}.self_attn.{n}_proj.bias is missing (Qwen2's "
+                                       "q/k/v Linears have biases)")
         T["embed"] = t("model.embed_tokens.weight").to(torch.bfloat16).contiguous()
         T["final_norm"] = t("model.norm.weight").to(torch.bfloat16).contiguous()
         T["lm_head"] = (t("lm_head.weight") if "lm_head.weight" in state_dict else T["embed"]).to(torch.bfloat16).contiguous()
@@ -420,6 +473,12 @@ class LlamaRanker:
                 gate, up = merged(p + "mlp.gate_proj.weight"), merged(p + "mlp.up_proj.weight")
             T[f"{i}.wqkv"] = torch.cat([self._interleave_rope_rows(q), self._interleave_rope_rows(k), v],
                                        0).to(torch.bfloat16).contiguous()
+            if self.family == "qwen2":
+                # the biases in wqkv's row order: q and k through the same pair interleave as the weight rows, v plain. They
+                # stay out of the NF4 round trip (bitsandbytes quantises weights only) and no adapter touches them.
+                bq, bk, bv = (t(p + f"self_attn.{n}_proj.bias").float().reshape(-1, 1) for n in "qkv")
+                T[f"{i}.bqkv"] = torch.cat([self._interleave_rope_rows(bq), self._interleave_rope_rows(bk), bv],
+                                           0).reshape(-1).to(torch.bfloat16).contiguous()
             T[f"{i}.wo"] = merged(p + "self_attn.o_proj.weight").to(torch.bfloat16).contiguous()
             T[f"{i}.wgu"] = self._interleave_gate_up(gate, up)
             T[f"{i}.wdown"] = merged(p + "mlp.down_proj.weight").to(torch.bfloat16).contiguous()
@@ -458,6 +517,8 @@ class LlamaRanker:
         T["lm_head"] = T["embed"] if gemma else rnd(v, d)
         for i in range(c["num_hidden_layers"]):
             T[f"{i}.wqkv"] = rnd((nh + 2 * nkv) * hd, d)
+            if self.family == "qwen2":
+                T[f"{i}.bqkv"] = rnd((nh + 2 * nkv) * hd)
             T[f"{i}.wo"] = rnd(d, nh * hd)
             T[f"{i}.wgu"] = rnd(2 * f, d)  # already in the interleaved gate/up layout (random anyway)
             T[f"{i}.wdown"] = rnd(d, f)
@@ -541,6 +602,11 @@ class LlamaRanker:
         if self.family == "gemma2":
             ext, self._gemma2_arrs = self.gemma2_ext()
             check(lib().lr_llama_set_gemma2(self._h, C.byref(ext)), "lr_llama_set_gemma2")
+        if "0.bqkv" in T:
+            self._bqkv_arr = (C.c_void_p * L)(*[T[f"{i}.bqkv"].data_ptr() for i in range(L)])
+            check(lib().lr_llama_set_qkv_bias(self._h, self._bqkv_arr), "lr_llama_set_qkv_bias")
+        if self.default_gemm_variant:
+            self.set_variants(gemm=self.default_gemm_variant)
         if self.fold_norms:
             self.set_fold_norms(True)
 
@@ -566,6 +632,8 @@ class LlamaRanker:
         T, L = self._tensors, self.config["num_hidden_layers"]
         if enable and self.family in ("gemma", "gemma2"):
             raise NotImplementedError("folded norms: Gemma's (1 + w) RMSNorm cannot be folded into bf16 weights at HF's rounding")
+        if enable and self.family == "qwen2":
+            raise NotImplementedError("folded norms: not with Qwen2's q/k/v biases (lr_llama_set_qkv_bias)")
         if not enable:
             check(lib().lr_llama_set_folded_norms(self._h, None, None), "lr_llama_set_folded_norms")
             for i in range(L):
@@ -592,7 +660,8 @@ class LlamaRanker:
 
     def set_variants(self, gemm=0, attention=0):
         """Kernel selection (include/llamarec_mi355x.h): 0 = auto; gemm=5 = latency mode for the online
-        single-user path (split-K where a short prompt would leave most CUs idle). attention: 1 generic, 2 / 3 head_dim 128,
+        single-user path (split-K where a short prompt would leave most CUs idle); gemm=6 = auto with the MFMA tile on a ragged
+        last column tile (widths that are multiples of 64 but not of 256: a qwen2 ranker's default). attention: 1 generic, 2 / 3 head_dim 128,
         4 head_dim 256, 5 head_dim 64 (scoring only: no lse), 7 head_dim 96 (scoring only: no lse), 6 = head_dim-64 MFMA attention for training (5's forward, writing
         lse when a LoRA engine runs on this base, and the head_dim-64 MFMA backward; the LoRA step's auto at head_dim 64)."""
         check(lib().lr_llama_set_variants(self._h, gemm, attention), "lr_llama_set_variants")

@@ -172,6 +172,45 @@ def synth_phi3_state(cfg: dict, seed: int, std: float = 0.02, norm_jitter: float
     return sd
 
 
+def qwen2_param_shapes(cfg: dict) -> list[tuple[str, tuple]]:
+    """HF Qwen2ForCausalLM parameter names and shapes: Llama's with a bias behind each of q_proj, k_proj and v_proj (in HF's
+    module order: weight, then bias), and no lm_head.weight when the embeddings are tied."""
+    out = []
+    for name, shape in llama_param_shapes(cfg):
+        if name == "lm_head.weight" and cfg.get("tie_word_embeddings"):
+            continue
+        out.append((name, shape))
+        if name.endswith(("q_proj.weight", "k_proj.weight", "v_proj.weight")):
+            out.append((name[: -len("weight")] + "bias", (shape[0],)))
+    return out
+
+
+# a tiny Qwen2 at Qwen2-0.5B's widths (train_ranker.py --synthetic --llm qwen2; tests/gen_goldens_qwen2.py's hd64_ragged with
+# another vocab): hidden 896 and qkv 1152 miss the 256-column GEMM tile, 14 query heads share 2 KV heads, tied head
+QWEN2_TINY = dict(model_type="qwen2", vocab_size=1000, hidden_size=896, intermediate_size=1280, num_hidden_layers=2,
+                  num_attention_heads=14, num_key_value_heads=2, max_position_embeddings=4096, rms_norm_eps=1e-6,
+                  rope_theta=1000000.0, hidden_act="silu", use_sliding_window=False, sliding_window=4096, max_window_layers=2,
+                  tie_word_embeddings=True)
+
+
+def synth_qwen2_state(cfg: dict, seed: int, std: float = 0.02, bias_std: float = 0.5, norm_jitter: float = 0.1,
+                      v_bias_std: float | None = None) -> dict:
+    """As synth_llama_state under Qwen2's names: matrices ~ U(std), q/k/v biases ~ U(bias_std) (the published checkpoints'
+    q and k biases reach several units), norm weights 1 + U(norm_jitter). v_bias_std: another width for v_proj's bias (the
+    checkpoints' are small; a v bias far wider than v itself makes every position's value the same vector, and the attention
+    weights -- all that the q and k biases act on -- then hardly reach the logits). bf16 values."""
+    sd = {}
+    for i, (name, shape) in enumerate(qwen2_param_shapes(cfg)):
+        if name.endswith(".bias"):
+            w = hash_uniform(seed * 1000 + i, shape, v_bias_std if v_bias_std is not None and "v_proj" in name else bias_std)
+        elif len(shape) == 1:
+            w = np.float32(1.0) + hash_uniform(seed * 1000 + i, shape, norm_jitter)
+        else:
+            w = hash_uniform(seed * 1000 + i, shape, std)
+        sd[name] = bf16_round(w)
+    return sd
+
+
 def synth_gemma_state(cfg: dict, seed: int, std: float = 0.02, norm_std: float = 0.3) -> dict:
     """name -> float32 array for a Gemma config. Matrices ~ U(std); norm weights ~ U(norm_std) around 0 -- Gemma scales by
     (1 + w), so non-zero w exercises that form (w = 0 would make it indistinguishable from Llama's w = 1). bf16 values."""

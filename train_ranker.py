@@ -25,7 +25,8 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 TRAIN_LLAMA_ONLY = ("LoRA fine-tuning needs a Llama-family base (the training step has no GeGLU, Gemma-norm or head_dim-256 "
                     "attention backward, and for Phi-3 no head_dim-96 attention backward and no adapter on the fused qkv_proj): "
-                    "score a Gemma ranker with --eval_only [--llm_adapter_path <peft dir>], a Phi-3 ranker with --eval_only")
+                    "score a Gemma ranker with --eval_only [--llm_adapter_path <peft dir>], a Phi-3 ranker with --eval_only; "
+                    "for Qwen2 the live-adapter forward has no q/k/v bias: score it with --eval_only [--llm_adapter_path <peft dir>]")
 
 
 def main(argv=None, export_root=None):
@@ -41,7 +42,7 @@ def main(argv=None, export_root=None):
     args = cfg.parse(argv, model_code="llm")
     if not args.llm_retrieved_path:
         raise SystemExit("--llm_retrieved_path experiments/lru/<dataset> is required")
-    if args.llm in ("gemma", "gemma2", "phi3") and not args.eval_only:
+    if args.llm in ("gemma", "gemma2", "phi3", "qwen2") and not args.eval_only:
         raise SystemExit(TRAIN_LLAMA_ONLY)
     if args.resume_from_checkpoint and (args.eval_only or args.llm_adapter_path):
         raise SystemExit("--resume_from_checkpoint continues a training run: it goes with neither --eval_only nor "
@@ -60,8 +61,8 @@ def main(argv=None, export_root=None):
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
     if args.synthetic:
-        from llamarec_amd.synth import (PHI3_TINY, FakeTokenizer, synth_gemma2_state, synth_gemma_state, synth_llama_state,
-                                        synth_phi3_state)
+        from llamarec_amd.synth import (PHI3_TINY, QWEN2_TINY, FakeTokenizer, synth_gemma2_state, synth_gemma_state,
+                                        synth_llama_state, synth_phi3_state, synth_qwen2_state)
 
         dataset = D.synthetic_dataset(num_users=300, num_items=1000, seed=args.seed)
         tokenizer = FakeTokenizer()
@@ -84,6 +85,10 @@ def main(argv=None, export_root=None):
         elif args.llm == "phi3":   # a tiny Phi-3: fused qkv_proj / gate_up_proj, 8 heads of head_dim 96
             c = dict(PHI3_TINY, vocab_size=c["vocab_size"])
             model = LlamaRanker.from_state_dict(synth_phi3_state(c, args.seed), c, device=device, lora=lora,
+                                                nf4=args.llm_load_in_4bit)
+        elif args.llm == "qwen2":   # a tiny Qwen2 at 0.5B's widths: q/k/v biases, 14 heads on 2 KV heads, ragged GEMM tiles
+            c = dict(QWEN2_TINY, vocab_size=c["vocab_size"])
+            model = LlamaRanker.from_state_dict(synth_qwen2_state(c, args.seed), c, device=device, lora=lora,
                                                 nf4=args.llm_load_in_4bit)
         else:
             model = LlamaRanker.from_state_dict(synth_llama_state(c, args.seed), c, device=device, lora=lora,
