@@ -14,7 +14,7 @@
 // (256 B/clk) serves for four SIMDs at their full MFMA rate -- the kernel is bound by the softmax and the barriers long
 // before that.
 // Rounding points are variant 2's: fp32 scores and online softmax with the deferred maximum (a row's reference moves only
-// when a score exceeds it by more than 2^FA4_DEFER), bf16 P into both the numerator and the row sum (an MFMA against a row
+// when a score exceeds it by more than 2^FA_DEFER), bf16 P into both the numerator and the row sum (an MFMA against a row
 // of ones), one bf16 rounding of O / l. A query row's bits depend only on its own prompt: tiles and key blocks are aligned
 // to positions inside the prompt, and the rescale decision is per row.
 // Forward only, no log-sum-exp output (the LoRA path keeps its own kernels). The kernel's one text is attn_hd256_body in
@@ -32,28 +32,10 @@ __global__ __launch_bounds__(512, 1) void attn_hd256_kernel(const u16* __restric
 }
 
 template <int HPW>
-static int launch_hd256(const u16* qkv, u16* out, const int32_t* cu, const int32_t* cu_host, int B, int n_tok, int nh,
-                        int nkv, int hd, hipStream_t st) {
-  if (n_tok <= 0 || B <= 0) return LR_OK;
-  if (hd != FA4_HD) LR_FAIL(LR_EUNSUPPORTED, "attention variant 4 needs head_dim 256 (got %d)", hd);
-  if (nh < 1 || nkv < 1 || nh % nkv != 0)
-    LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
-  const LrAttnPlan pl = lr_attn_plan(cu_host, B, 0, nh, hd, FA4_QR / HPW, nh / HPW);
-  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
-  if (HPW == 2 && (nh / nkv) % 2 != 0) LR_FAIL(LR_EINVAL, "attention: two heads per workgroup need an even nh / nkv");
-  if (pl.mq == 0) return LR_OK;
-  LR_RUN(lr_attn_check_grid(pl));
-  if ((long long)n_tok * (nh + 2 * nkv) * hd * 2 > 0x7fffffffLL * 2)
-    LR_FAIL(LR_EUNSUPPORTED, "attention: packed qkv of %d tokens exceeds the 4 GiB a buffer descriptor addresses", n_tok);
-  static bool lds_set[LR_MAX_DEVICES] = {};
-  if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_hd256_kernel<HPW>), FA4_LDS_BYTES, lds_set)) return rc;
-  hipLaunchKernelGGL(attn_hd256_kernel<HPW>, dim3((unsigned)pl.grid), dim3(512), FA4_LDS_BYTES, st, qkv, out, cu, nh, nkv, pl.mq,
-                     (int)pl.n_pairs);
-  LR_CHECK_LAUNCH("attn_hd256_kernel");
-  return LR_OK;
+static int launch_hd256(const LrAttnArgs& a, hipStream_t st) {
+  return lr_attn_launch_tiles<attn_hd256_kernel<HPW>, FA4_HD, FA4_QR, 512, FA4_LDS_BYTES, false, HPW>(
+      "attn_hd256_kernel", "attention variant 4 needs head_dim 256", nullptr, nullptr, nullptr, a, st);
 }
 
-// cu / cu_host: prompt starts [B + 1] in packed rows (no shared prefix at head_dim 256)
-int lr_launch_attention_hd256(const LrAttnArgs& a, hipStream_t st) {
-  return launch_hd256<1>(a.qkv, a.out, a.cu, a.cu_host, a.S, a.n_tok, a.nh, a.nkv, a.hd, st);
-}
+// cu / cu_host: prompt starts [B + 1] in packed rows (no shared prefix at head_dim 256; a.lse is lr_launch_attention's to refuse)
+int lr_launch_attention_hd256(const LrAttnArgs& a, hipStream_t st) { return launch_hd256<1>(a, st); }

@@ -5,25 +5,13 @@
 //   <1, false, true>   attn_hd256_prefix_kernel<false>, shared prompt prefix                     (llama_attn_hd256_prefix.hip)
 //   <1, true, true>    attn_hd256_prefix_kernel<true>, one query row per prompt                  (llama_attn_hd256_prefix.hip)
 //   the same three <1, ., ., true> with soft-capped scores (Gemma-2)                             (llama_attn_hd256_softcap.hip)
-// The modes differ in where a K / V row and a query row live and in which rows a tile owns. Each such place picks its
-// expression at compile time (`if constexpr`, or a condition on the template parameters alone): without PREFIX no shared-prefix
-// length is ever computed, compared or added, so variant 4's instructions do not depend on the optimiser folding a zero away.
-// The block walk, the masking, the per-row deferred maximum, bf16 P into both products and the ones-MFMA row sum are common to
-// all of them, which is what makes a row's bits the same in every mode of one SOFTCAP setting.
+// Here stand the constants, the LDS layout with its swizzles and staging offsets, the QK product and the mask. The prologue,
+// the staging of a block, the softmax steps and the store are lr_attn_body.h's, shared with head_dim 64 and 96; the PREFIX and
+// LASTQ modes are described there, HPW and SOFTCAP below. A row's bits are the same in every mode of one SOFTCAP setting.
 #ifndef LLAMA_ATTN_HD256_BODY_H
 #define LLAMA_ATTN_HD256_BODY_H
 
-#include <type_traits>
-
-#include "llama_kernels.h"
-#include "lr_attn_util.h"
-#include "lr_profile.h"
-
-typedef unsigned short u16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
+#include "lr_attn_body.h"
 
 #define FA4_HD 256
 #define FA4_WAVES 8                       // 16 query rows each
@@ -33,30 +21,26 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 #define FA4_TILE_BYTES (FA4_KB * FA4_ROW_BYTES)   // 32 KiB
 #define FA4_STAGE_BYTES (2 * FA4_TILE_BYTES)      // K tile + V tile
 #define FA4_LDS_BYTES (2 * FA4_STAGE_BYTES)       // two stages: 128 KiB
-#define FA4_DEFER 8.0f
 
 // K tile: chunk c of row r sits at position c ^ (r & 15) (conflict-free ds_read_b128 of 16 rows at one chunk).
 // V tile: the dual-use swizzle of variant 2, c ^ (((r & 3) << 2) | ((r >> 2) & 3)) (conflict-free transposed reads).
-// Both flip the low 4 bits of the chunk index only, so a chunk stays in its 256-byte half of the row.
+// Both flip the low 4 bits of the chunk index only, so a chunk stays in its 256-byte half of the row; both depend on the row
+// inside the block and the chunk only (derived, not measured with the conflict counter).
 __device__ __forceinline__ int fa4_vswz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
 // HPW = heads per workgroup. 1: the 8 waves are 128 query rows of one head. 2 (MQA / GQA, two heads of one KV head): waves
 //   0-3 are 64 rows of head 2p, waves 4-7 the same rows of head 2p + 1, both fed by one staged K/V tile (same reuse of the LDS
 //   tile per stage, half-height causal tiles). A row's arithmetic is the same in both.
-// PREFIX: prefix_len = P > 0 makes segment 0 of the packed rows the P tokens every prompt starts with and segment s >= 1 the
-//   rest of prompt s - 1 at positions P.. . Keys and values of positions < P are read from segment 0's rows; query tiles and
-//   64-key blocks stay aligned to positions inside the prompt, prefix included; rows of a tile at positions < P belong to
-//   segment 0 and are neither computed nor stored for segment s. Without PREFIX prefix_len is not read.
-// LASTQ (with PREFIX; prefix_len may be 0): `qkv` is the [rows][2 nkv hd] K | V projection, q_rows_last one rotated query row
-//   per prompt. A workgroup = one (prompt, head) walks the prompt's key blocks, all eight waves staging and wave 0 computing
-//   with every lane column holding the query at position T - 1; one output row per prompt.
 // SOFTCAP (Gemma-2): the fp32 score s out of the MFMA becomes cap * tanh(s * scale / cap) before masking and the row maximum,
 //   with scale and cap run-time values (without SOFTCAP neither is read: the scale is the compile-time 1/16). The capped score
 //   is kept in the exp2 domain, y = cap log2(e) (1 - 2 / (1 + exp2(2 s scale log2(e) / cap))): a multiply, v_exp_f32, an add,
 //   v_rcp_f32 and an fma per score. exp2 overflowing to +inf gives rcp = 0 and y = +cap log2(e), underflowing to 0 gives
 //   -cap log2(e): no NaN at any finite s. The absolute error of the quotient form is ~1e-7 (one ulp of 1), times cap log2(e)
 //   <= 1e-5 for cap 50, against a bf16 step of P of 2^-8. The running maximum stays (|y| <= cap log2(e) would allow a fixed
-//   reference, but exp2(-2 cap log2(e)) is a denormal at cap 50 and can zero a row's sum).
+//   reference, but exp2(-2 cap log2(e)) is a denormal at cap 50 and can zero a row's sum). Scores in the exp2 domain take no
+//   scale, so the capped rescale and P packing are fa_rescale and fa_pack_p without sl2, written out in the block loop: through
+//   the helpers (with a SOFTCAP parameter, or with a scale of 1) attn_hd256_softcap_kernel orders two register moves in the
+//   loop's preheader the other way round, and the whole-prompt kernels are held to the instruction stream they had.
 template <int HPW, bool LASTQ, bool PREFIX, bool SOFTCAP = false>
 __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const int32_t* cu, int prefix_len, int nh, int nkv,
                                                 int max_qblocks, int n_pairs, const u16* q_rows_last, float scale = 0.f,
@@ -67,35 +51,22 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
   constexpr int WPH = FA4_WAVES / HPW;   // waves per head
   constexpr int QR = 16 * WPH;           // query rows per head and workgroup
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int hd = FA4_HD;
   int seg, h, qb;
-  {
+  {   // (`pair` in a scope of its own, seg and h assigned: lr_attn_body.h on what keeps the whole-prompt kernels' code)
     int pair;
-    if constexpr (LASTQ) {
-      pair = blockIdx.x;
-      qb = 0;
-    } else {
-      fa_tile_of_workgroup(n_pairs, max_qblocks, pair, qb);
-    }
+    fa_pair_of_workgroup<LASTQ>(n_pairs, max_qblocks, pair, qb);
     if (pair >= n_pairs) return;
-    const int hg = nh / HPW;   // head groups per prompt
-    seg = __builtin_amdgcn_readfirstlane(pair / hg);
-    h = __builtin_amdgcn_readfirstlane((pair - seg * hg) * HPW);   // first head of the group
+    const FaSegHead sh = fa_segment_and_head(pair, nh / HPW);   // head groups per prompt
+    seg = sh.seg;
+    h = sh.h * HPW;   // first head of the group
     if constexpr (LASTQ) {
       if (prefix_len > 0 && seg == 0) return;   // segment 0 is the shared prefix, not a prompt
     } else {
       qb = __builtin_amdgcn_readfirstlane(qb);
     }
   }
-  const int tok0 = cu[seg];
-  int P = 0, T, vtok0 = tok0;   // !PREFIX: P and vtok0 are named by no expression below
-  if constexpr (PREFIX) {
-    P = (prefix_len > 0 && seg > 0) ? prefix_len : 0;   // keys [0, P) live in segment 0's rows [0, P)
-    T = P + cu[seg + 1] - tok0;                         // sequence length, prefix included
-    vtok0 = tok0 - P;   // the row of position p >= P is vtok0 + p (tok0 >= P: segment 0 precedes the segment)
-  } else {
-    T = cu[seg + 1] - tok0;
-  }
+  const FaSeg sg = fa_segment_rows<PREFIX>(cu, seg, prefix_len);
+  const int P = sg.P, T = sg.T;
   // no query row of this segment in the tile
   if (!LASTQ && (qb * QR >= T || (PREFIX && (qb + 1) * QR <= P))) return;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -103,17 +74,8 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
   const int quad = lane >> 4, li = lane & 15;
   const int kvh = __builtin_amdgcn_readfirstlane(h / (nh / nkv));   // (HPW = 2: both heads' KV head)
   h += wave / WPH;                                                      // this wave's head
-  const int stride = LASTQ ? 2 * nkv * hd : (nh + 2 * nkv) * hd;
-  const u16 *kbase, *vbase, *pkbase = nullptr, *pvbase = nullptr;   // a position's K / V row: own rows, and (PREFIX) packed row 0
-  if constexpr (PREFIX) {
-    pkbase = qkv + (LASTQ ? kvh * hd : (nh + kvh) * hd);
-    pvbase = pkbase + nkv * hd;
-    kbase = pkbase + (size_t)vtok0 * stride;
-    vbase = pvbase + (size_t)vtok0 * stride;
-  } else {
-    kbase = qkv + (size_t)tok0 * stride + (nh + kvh) * hd;
-    vbase = kbase + nkv * hd;
-  }
+  const FaKV kv = fa_kv_bases<LASTQ, PREFIX, FA4_HD>(qkv, nh, nkv, kvh, sg);
+  const int stride = kv.stride;
   const int prompt = prefix_len > 0 ? seg - 1 : seg;         // LASTQ: row of q_rows_last / out
 
   // ---- Q fragments (B operand of S^T = K Q^T): row q, d = 32 ks + 8 quad + 0..7
@@ -121,13 +83,7 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
   const int qabs = LASTQ ? T - 1 : wave_q0 + li;
   bf16x8 qf[8];
   {
-    const u16* qp;
-    if constexpr (LASTQ)
-      qp = q_rows_last + (size_t)prompt * nh * hd + h * hd + quad * 8;
-    else if constexpr (PREFIX)
-      qp = qkv + (size_t)(vtok0 + min(max(qabs, P), T - 1)) * stride + h * hd + quad * 8;
-    else
-      qp = qkv + (size_t)(tok0 + min(qabs, T - 1)) * stride + h * hd + quad * 8;
+    const u16* qp = fa_q_ptr<LASTQ, PREFIX, FA4_HD>(qkv, q_rows_last, sg, stride, prompt, qabs, nh, h, quad);
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 32);
   }
@@ -136,7 +92,7 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
   for (int dt = 0; dt < 16; ++dt) ot[dt] = floatx4{0.f, 0.f, 0.f, 0.f};
   float m_run = -__builtin_inff(), mthr = -__builtin_inff();
   floatx4 l_acc = floatx4{0.f, 0.f, 0.f, 0.f};
-  bf16x8 ones_f;
+  bf16x8 ones_f;   // (built here, not in a helper: attn_hd256_kernel<1> schedules one instruction elsewhere otherwise)
 #pragma unroll
   for (int i = 0; i < 8; ++i) ones_f[i] = (__bf16)1.0f;
 
@@ -151,9 +107,8 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
   const float cap_a = SOFTCAP ? 2.0f * 1.4426950408889634f * scale / cap : 0.f;
   const float cap_l2 = SOFTCAP ? cap * 1.4426950408889634f : 0.f;
 
-  // ---- DMA staging: a tile is 32 pieces of 1 KiB (2 rows x 512 B, lane-linear in LDS); wave w moves pieces 4w..4w+3 of
-  // K and of V. Rows past the prompt's end are range-checked to zero by the per-block buffer descriptor (those keys are
-  // masked for every stored query row).
+  // ---- DMA staging (fa_stage_block): a tile is 32 pieces of 1 KiB (2 rows x 512 B); wave w moves pieces 4w..4w+3 of K and
+  // of V.
   const int prow = lane >> 5, ppos = lane & 31;
   unsigned koff[4], voff[4];
 #pragma unroll
@@ -162,56 +117,13 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
     koff[i] = (unsigned)(row * stride + (ppos ^ (row & 15)) * 8) * 2u;
     voff[i] = (unsigned)(row * stride + (ppos ^ fa4_vswz(row)) * 8) * 2u;
   }
-  // Where a block's rows live is what the modes differ in, so each has its staging text (as llama_attn_hd64_body.h). Without
-  // PREFIX every block takes a per-block descriptor (scalar work only). PREFIX: so does a block that lies wholly in the
-  // segment's own rows or wholly in segment 0; the one block that straddles position P takes one descriptor over the packed
-  // rows [0, end of this segment] and a per-lane home offset (a compare, a select and an add per piece). The LDS image of a
-  // block is the same bytes whatever the home of its rows, and the swizzles depend on the row inside the block and the chunk
-  // only (derived, not measured with the conflict counter).
   auto stage = [&](int kb, int buf) {
-    char* base = smem + buf * FA4_STAGE_BYTES + wave * 4096;
-    if constexpr (!PREFIX) {
-      const size_t blk_off = (size_t)kb * FA4_KB * stride * 2;
-      const int records = ((T - 1 - kb * FA4_KB) * stride + hd) * 2;   // bytes from the block's first K (V) element
-      const fa_int4 rk = fa_make_rsrc(reinterpret_cast<const char*>(kbase) + blk_off, records);
-      const fa_int4 rv = fa_make_rsrc(reinterpret_cast<const char*>(vbase) + blk_off, records);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        fa_dma16(rk, base + i * 1024, koff[i]);
-        fa_dma16(rv, base + FA4_TILE_BYTES + i * 1024, voff[i]);
-      }
-    } else {
-      const int k0 = kb * FA4_KB;
-      if (k0 >= P || k0 + FA4_KB <= P) {   // the whole block has one home: the segment's own rows, or segment 0
-        const bool own = k0 >= P;
-        const size_t blk_off = (size_t)k0 * stride * 2;
-        const int records = (((own ? T : P) - 1 - k0) * stride + hd) * 2;
-        const fa_int4 rk = fa_make_rsrc(reinterpret_cast<const char*>(own ? kbase : pkbase) + blk_off, records);
-        const fa_int4 rv = fa_make_rsrc(reinterpret_cast<const char*>(own ? vbase : pvbase) + blk_off, records);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          fa_dma16(rk, base + i * 1024, koff[i]);
-          fa_dma16(rv, base + FA4_TILE_BYTES + i * 1024, voff[i]);
-        }
-      } else {
-        const unsigned records = ((unsigned)(vtok0 + T - 1) * (unsigned)stride + hd) * 2u;
-        const fa_int4 rk = fa_make_rsrc(pkbase, (int)records);
-        const fa_int4 rv = fa_make_rsrc(pvbase, (int)records);
-        const unsigned home_pre = (unsigned)k0 * (unsigned)stride * 2u, home_own = (unsigned)(vtok0 + k0) * (unsigned)stride * 2u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int row = (wave * 4 + i) * 2 + prow;
-          const unsigned home = (k0 + row < P) ? home_pre : home_own;
-          fa_dma16(rk, base + i * 1024, koff[i] + home);
-          fa_dma16(rv, base + FA4_TILE_BYTES + i * 1024, voff[i] + home);
-        }
-      }
-    }
+    fa_stage_block<PREFIX, FA4_HD, FA4_KB, 4, FA4_TILE_BYTES>(smem + buf * FA4_STAGE_BYTES + wave * 4096, kv, sg, kb, koff, voff,
+                                                              [=](int i) { return (wave * 4 + i) * 2 + prow; });
   };
 
   // LDS read addresses. K: row nt*16 + li, chunk 4 ks + quad (ks >= 4: the same position + 256 B). V^T (transposed reads):
   // row quad*4 + (li >> 2) (+16, +32, +48 per key sub-block), dims 16 dt + 4 (li & 3) (dt >= 8: + 256 B).
-  typedef __attribute__((address_space(3))) char lds_char;
   lds_char* const lds = (lds_char*)smem;
   lds_char *kb_off[4], *vb_off[8];
 #pragma unroll
@@ -234,7 +146,7 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
     constexpr int KS = BUF * FA4_STAGE_BYTES, VS = KS + FA4_TILE_BYTES;
     if (kb < kb_last) stage(kb + 1, BUF ^ 1);
     if (wave_live && kb * FA4_KB <= wave_q_last) {   // otherwise every key of the block is masked for this wave
-      // ---- S^T = K Q^T : st[nt] rows = keys nt*16 + 4*quad + r, col = query li
+      // ---- S^T = K Q^T : st[nt] rows = keys nt*16 + 4*quad + r, col = query li. The K fragments are double-buffered.
       floatx4 st[4];
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) st[nt] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -262,7 +174,7 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
             st[nt][r] = __builtin_fmaf(__builtin_amdgcn_rcpf(1.0f + e), -2.0f * cap_l2, cap_l2);
           }
       }
-      // ---- online softmax (lane-local row), P packed as the B operand of O^T = V^T P^T
+      // ---- online softmax (lane-local row)
       bf16x8 pa[2];
       const bool diag = (kb * FA4_KB + FA4_KB - 1) > wave_q0;   // the block needs masking (wave-uniform)
       if (diag) {
@@ -275,57 +187,36 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
           }
         __builtin_amdgcn_sched_barrier(0);
       }
-      float mx = fa_max3(st[0][0], st[0][1], st[0][2]);
-      mx = fa_max3(mx, st[0][3], st[1][0]);
+      if constexpr (!SOFTCAP) {
+        fa_rescale<16>(fa_max16(st), sl2, inv_sl2, m_run, mthr, l_acc, ot);
+        fa_pack_p(st, sl2, m_run, pa);
+      } else {
+        const float mx = fa_max16(st);
+        if (__any(mx > mthr)) {
+          const float rmx = fa_max_xor16_32(mx);
+          const float m_new = rmx > mthr ? rmx : m_run;
+          const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
 #pragma unroll
-      for (int nt = 1; nt < 4; ++nt) {
-        mx = fa_max3(mx, st[nt][1], st[nt][2]);
-        if (nt < 3) mx = fa_max3(mx, st[nt][3], st[nt + 1][0]);
-      }
-      mx = fa_max2(mx, st[3][3]);
-      // deferred maximum, decided per row (variant 2): a row that keeps its reference multiplies by exactly 1
-      if (__any(mx > mthr)) {
-        const float rmx = fa_max_xor16_32(mx);
-        const bool grew = rmx > mthr;
-        float m_new;   // SOFTCAP: the scores are in the exp2 domain already
-        if constexpr (SOFTCAP) m_new = grew ? rmx : m_run;
-        else m_new = grew ? rmx * sl2 : m_run;
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+          for (int r = 0; r < 4; ++r) l_acc[r] *= alpha;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) l_acc[r] *= alpha;
+          for (int dt = 0; dt < 16; ++dt)
 #pragma unroll
-        for (int dt = 0; dt < 16; ++dt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) ot[dt][r] *= alpha;
-        m_run = m_new;
-        if constexpr (SOFTCAP) mthr = m_new + FA4_DEFER;
-        else mthr = (m_new + FA4_DEFER) * inv_sl2;
-      }
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if constexpr (SOFTCAP) pa[nt >> 1][(nt & 1) * 4 + r] = (__bf16)__builtin_amdgcn_exp2f(st[nt][r] - m_run);
-          else pa[nt >> 1][(nt & 1) * 4 + r] = (__bf16)__builtin_amdgcn_exp2f(__builtin_fmaf(st[nt][r], sl2, -m_run));
+            for (int r = 0; r < 4; ++r) ot[dt][r] *= alpha;
+          m_run = m_new;
+          mthr = m_new + FA_DEFER;
         }
-      // ---- O^T += V^T P^T (k index 8 quad + j <-> key 32 ks2 + 16 (j >> 2) + 4 quad + (j & 3), as the S^T layout gives it)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) pa[nt >> 1][(nt & 1) * 4 + r] = (__bf16)__builtin_amdgcn_exp2f(st[nt][r] - m_run);
+      }
+      // ---- O^T += V^T P^T
 #pragma unroll
       for (int ks2 = 0; ks2 < 2; ++ks2) {
-        l_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones_f, pa[ks2], l_acc, 0, 0, 0);
+        fa_row_sum(ones_f, pa[ks2], l_acc);
 #pragma unroll
         for (int dt = 0; dt < 16; ++dt) {
-          const int o = VS + ks2 * 32 * FA4_ROW_BYTES + (dt >> 3) * 256;
-          const short4v t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) short4v*)(vb_off[dt & 7] + o));
-          const short4v t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) short4v*)(vb_off[dt & 7] + (o + 16 * FA4_ROW_BYTES)));
-          bf16x8 vf;
-          const bf16x4 b0 = __builtin_bit_cast(bf16x4, t0), b1 = __builtin_bit_cast(bf16x4, t1);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            vf[r] = b0[r];
-            vf[4 + r] = b1[r];
-          }
+          const bf16x8 vf = fa_read_vt<FA4_ROW_BYTES>(vb_off[dt & 7] + (VS + ks2 * 32 * FA4_ROW_BYTES + (dt >> 3) * 256));
           ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pa[ks2], ot[dt], 0, 0, 0);
         }
       }
@@ -338,36 +229,11 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
     if (kb + 1 <= kb_last) block(kb + 1, std::integral_constant<int, 1>{});
   }
 
-  // ---- normalise and store: lane owns query row li, d = 16 dt + 4 quad + r. v_permlane16_swap on the packed tiles
-  // (2k, 2k+1) gives even quads d = 32 k + 8 (quad / 2) .. +7 and odd quads the same + 16: 16-byte stores. Every lane
-  // takes part in the swaps; only rows of this segment store. LASTQ: the 16 lane columns of wave 0 hold the same row;
-  // column 0's four quads store its 256 dims.
+  // ---- normalise and store (fa_store_row)
   const float inv = 1.0f / l_acc[0];
-  const bool live = LASTQ ? (wave == 0 && li == 0) : (qabs < T && (!PREFIX || qabs >= P));
-  int orow;
-  if constexpr (LASTQ)
-    orow = prompt;
-  else if constexpr (PREFIX)
-    orow = vtok0 + (live ? qabs : P);
-  else
-    orow = tok0 + (live ? qabs : 0);
-  u16* op = out + (size_t)orow * nh * hd + h * hd + (quad & 1) * 16 + (quad >> 1) * 8;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    unsigned a[2], b[2];
-#pragma unroll
-    for (int w = 0; w < 2; ++w) {
-      a[w] = (unsigned)f2bf(ot[2 * k][2 * w] * inv) | ((unsigned)f2bf(ot[2 * k][2 * w + 1] * inv) << 16);
-      b[w] = (unsigned)f2bf(ot[2 * k + 1][2 * w] * inv) | ((unsigned)f2bf(ot[2 * k + 1][2 * w + 1] * inv) << 16);
-      const auto sw = __builtin_amdgcn_permlane16_swap(a[w], b[w], false, false);
-      a[w] = sw[0];
-      b[w] = sw[1];
-    }
-    if (live) {
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-      *reinterpret_cast<u32x4*>(op + k * 32) = u32x4{a[0], a[1], b[0], b[1]};
-    }
-  }
+  const bool live = fa_row_live<LASTQ, PREFIX>(sg, qabs, wave, li);
+  const int orow = fa_out_row<LASTQ, PREFIX>(sg, prompt, live, qabs);
+  fa_store_row<16>(ot, inv, live, out + (size_t)orow * nh * FA4_HD + h * FA4_HD + (quad & 1) * 16 + (quad >> 1) * 8);
 }
 
 #endif

@@ -20,35 +20,14 @@ __global__ __launch_bounds__(512, 1) void attn_hd256_prefix_kernel(const u16* __
 
 // cu / cu_host: segment starts [S + 1]; prefix_len = P > 0: segment 0 is the shared prefix the other segments continue
 int lr_launch_attention_hd256_prefix(const LrAttnArgs& a, hipStream_t st) {
-  const int S = a.S, n_tok = a.n_tok, nh = a.nh, nkv = a.nkv, hd = a.hd, P = a.prefix_len;
-  if (n_tok <= 0 || S <= 0) return LR_OK;
-  if (hd != FA4_HD) LR_FAIL(LR_EUNSUPPORTED, "attention variant 4 needs head_dim 256 (got %d)", hd);
-  if (nh < 1 || nkv < 1 || nh % nkv != 0)
-    LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
-  if (a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-256 MFMA kernel writes no lse");
-  LR_RUN(lr_check_prefix_layout("attention (head_dim 256)", a.cu_host, S, n_tok, (nh + 2 * nkv) * hd, P));
-  const LrAttnPlan pl = lr_attn_plan(a.cu_host, S, P, nh, hd, FA4_QR, nh);
-  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
-  LR_RUN(lr_attn_check_grid(pl));
-  static bool lds_set[LR_MAX_DEVICES] = {};
-  if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_hd256_prefix_kernel<false>), FA4_LDS_BYTES, lds_set)) return rc;
-  hipLaunchKernelGGL(attn_hd256_prefix_kernel<false>, dim3((unsigned)pl.grid), dim3(512), FA4_LDS_BYTES, st, a.qkv, a.out, a.cu, P,
-                     nh, nkv, pl.mq, (int)pl.n_pairs, (const u16*)nullptr);
-  LR_CHECK_LAUNCH("attn_hd256_prefix_kernel");
-  return LR_OK;
+  return lr_attn_launch_tiles<attn_hd256_prefix_kernel<false>, FA4_HD, FA4_QR, 512, FA4_LDS_BYTES, true>(
+      "attn_hd256_prefix_kernel", "attention variant 4 needs head_dim 256", "attention: the head_dim-256 MFMA kernel writes no lse",
+      nullptr, "attention (head_dim 256)", a, st, (const u16*)nullptr);
 }
 
-// The pruned last layer at head_dim 256 (lr_launch_attention_last): kv = [n_tok][2 nkv hd], q_last / out_last = [prompts][nh hd]
 int lr_launch_attention_hd256_last(const u16* kv, const u16* q_last, u16* out_last, const int32_t* cu, const int32_t* cu_host,
                                    int S, int n_tok, int nh, int nkv, int prefix_len, hipStream_t st) {
-  LR_RUN(lr_check_prefix_layout("attention (last rows, head_dim 256)", cu_host, S, n_tok, 2 * nkv * FA4_HD, prefix_len));
-  const LrAttnPlan pl = lr_attn_plan_last(cu_host, S, prefix_len, nh, FA4_HD, 1);
-  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
-  LR_RUN(lr_attn_check_grid(pl));
-  static bool lds_set[LR_MAX_DEVICES] = {};
-  if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_hd256_prefix_kernel<true>), FA4_LDS_BYTES, lds_set)) return rc;
-  hipLaunchKernelGGL(attn_hd256_prefix_kernel<true>, dim3((unsigned)pl.grid), dim3(512), FA4_LDS_BYTES, st, kv, out_last, cu,
-                     prefix_len, nh, nkv, 0, (int)pl.n_pairs, q_last);
-  LR_CHECK_LAUNCH("attn_hd256_prefix_kernel<last>");
-  return LR_OK;
+  return lr_attn_launch_last<attn_hd256_prefix_kernel<true>, FA4_HD, 512, FA4_LDS_BYTES>(
+      "attn_hd256_prefix_kernel<last>", "attention (last rows, head_dim 256)", kv, q_last, out_last, cu, cu_host, S, n_tok, nh,
+      nkv, prefix_len, st);
 }

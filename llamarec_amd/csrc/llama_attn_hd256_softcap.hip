@@ -37,46 +37,22 @@ static int check_cap(float scale, float cap) {
 
 // a.cap > 0, a.scale > 0; a.prefix_len = P > 0: segment 0 is the shared prefix the other segments continue
 int lr_launch_attention_hd256_softcap(const LrAttnArgs& a, hipStream_t st) {
-  const int S = a.S, n_tok = a.n_tok, nh = a.nh, nkv = a.nkv, hd = a.hd, P = a.prefix_len;
-  if (n_tok <= 0 || S <= 0) return LR_OK;
-  if (hd != FA4_HD) LR_FAIL(LR_EUNSUPPORTED, "soft-capped MFMA attention needs head_dim 256 (got %d)", hd);
-  if (nh < 1 || nkv < 1 || nh % nkv != 0)
-    LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
-  if (a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-256 MFMA kernel writes no lse");
-  LR_RUN(check_cap(a.scale, a.cap));
-  LR_RUN(lr_check_prefix_layout("attention (soft cap, head_dim 256)", a.cu_host, S, n_tok, (nh + 2 * nkv) * hd, P));
-  const LrAttnPlan pl = lr_attn_plan(a.cu_host, S, P, nh, hd, FA4_QR, nh);
-  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
-  if (pl.mq == 0) return LR_OK;
-  LR_RUN(lr_attn_check_grid(pl));
-  if (P > 0) {
-    static bool lds_set[LR_MAX_DEVICES] = {};
-    LR_RUN(lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_hd256_softcap_prefix_kernel<false>), FA4_LDS_BYTES, lds_set));
-    hipLaunchKernelGGL(attn_hd256_softcap_prefix_kernel<false>, dim3((unsigned)pl.grid), dim3(512), FA4_LDS_BYTES, st, a.qkv,
-                       a.out, a.cu, P, nh, nkv, pl.mq, (int)pl.n_pairs, (const u16*)nullptr, a.scale, a.cap);
-  } else {
-    static bool lds_set[LR_MAX_DEVICES] = {};
-    LR_RUN(lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_hd256_softcap_kernel), FA4_LDS_BYTES, lds_set));
-    hipLaunchKernelGGL(attn_hd256_softcap_kernel, dim3((unsigned)pl.grid), dim3(512), FA4_LDS_BYTES, st, a.qkv, a.out, a.cu, nh,
-                       nkv, pl.mq, (int)pl.n_pairs, a.scale, a.cap);
-  }
-  LR_CHECK_LAUNCH("attn_hd256_softcap_kernel");
-  return LR_OK;
+  const char *needs = "soft-capped MFMA attention needs head_dim 256", *no_lse = "attention: the head_dim-256 MFMA kernel writes no lse",
+             *layout = "attention (soft cap, head_dim 256)";
+  const auto cap_ok = [](const LrAttnArgs& a) { return check_cap(a.scale, a.cap); };
+  if (a.prefix_len > 0)
+    return lr_attn_launch_tiles<attn_hd256_softcap_prefix_kernel<false>, FA4_HD, FA4_QR, 512, FA4_LDS_BYTES, true>(
+        "attn_hd256_softcap_kernel", needs, no_lse, cap_ok, layout, a, st, (const u16*)nullptr, a.scale, a.cap);
+  return lr_attn_launch_tiles<attn_hd256_softcap_kernel, FA4_HD, FA4_QR, 512, FA4_LDS_BYTES, false>(
+      "attn_hd256_softcap_kernel", needs, no_lse, cap_ok, layout, a, st, a.scale, a.cap);
 }
 
-// The pruned last layer with a cap: kv = [n_tok][2 nkv hd], q_last / out_last = [prompts][nh hd]
+// The pruned last layer with a cap
 int lr_launch_attention_hd256_softcap_last(const u16* kv, const u16* q_last, u16* out_last, const int32_t* cu,
                                            const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int prefix_len, float scale,
                                            float cap, hipStream_t st) {
   LR_RUN(check_cap(scale, cap));
-  LR_RUN(lr_check_prefix_layout("attention (soft cap, last rows, head_dim 256)", cu_host, S, n_tok, 2 * nkv * FA4_HD, prefix_len));
-  const LrAttnPlan pl = lr_attn_plan_last(cu_host, S, prefix_len, nh, FA4_HD, 1);
-  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
-  LR_RUN(lr_attn_check_grid(pl));
-  static bool lds_set[LR_MAX_DEVICES] = {};
-  LR_RUN(lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_hd256_softcap_prefix_kernel<true>), FA4_LDS_BYTES, lds_set));
-  hipLaunchKernelGGL(attn_hd256_softcap_prefix_kernel<true>, dim3((unsigned)pl.grid), dim3(512), FA4_LDS_BYTES, st, kv, out_last,
-                     cu, prefix_len, nh, nkv, 0, (int)pl.n_pairs, q_last, scale, cap);
-  LR_CHECK_LAUNCH("attn_hd256_softcap_prefix_kernel<last>");
-  return LR_OK;
+  return lr_attn_launch_last<attn_hd256_softcap_prefix_kernel<true>, FA4_HD, 512, FA4_LDS_BYTES>(
+      "attn_hd256_softcap_prefix_kernel<last>", "attention (soft cap, last rows, head_dim 256)", kv, q_last, out_last, cu, cu_host,
+      S, n_tok, nh, nkv, prefix_len, st, scale, cap);
 }

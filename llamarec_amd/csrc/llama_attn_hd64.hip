@@ -12,7 +12,7 @@
 // per lane: the softmax binds, so what counts is how many waves a SIMD holds to overlap one wave's exponentials with
 // another's MFMAs.
 // Rounding points are variant 2's: fp32 scores and online softmax with the deferred maximum (a row's reference moves only
-// when a score exceeds it by more than 2^FA5_DEFER), bf16 P into both the numerator and the row sum (an MFMA against a row
+// when a score exceeds it by more than 2^FA_DEFER), bf16 P into both the numerator and the row sum (an MFMA against a row
 // of ones), one bf16 rounding of O / l. A query row's bits depend only on its own prompt: tiles and key blocks are aligned
 // to positions inside the prompt, and the rescale decision is per row.
 // The kernel's one text is attn_hd64_body in llama_attn_hd64_body.h, with its modes chosen at compile time. This file
@@ -25,22 +25,7 @@
 
 // cu / cu_host: prompt starts [B + 1] in packed rows (no shared prefix at head_dim 64)
 int lr_launch_attention_hd64(const LrAttnArgs& a, hipStream_t st) {
-  const int B = a.S, n_tok = a.n_tok, nh = a.nh, nkv = a.nkv, hd = a.hd;
-  if (n_tok <= 0 || B <= 0) return LR_OK;
-  if (hd != FA5_HD) LR_FAIL(LR_EUNSUPPORTED, "attention variants 5 and 6 need head_dim 64 (got %d)", hd);
-  if (nh < 1 || nkv < 1 || nh % nkv != 0)
-    LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
-  const LrAttnPlan pl = lr_attn_plan(a.cu_host, B, 0, nh, hd, FA5_QROWS, nh);
-  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
-  if (pl.mq == 0) return LR_OK;
-  LR_RUN(lr_attn_check_grid(pl));
-  if ((long long)n_tok * (nh + 2 * nkv) * hd * 2 > 0x7fffffffLL * 2)
-    LR_FAIL(LR_EUNSUPPORTED, "attention: packed qkv of %d tokens exceeds the 4 GiB a buffer descriptor addresses", n_tok);
-  if (a.lse) return lr_launch_attention_hd64_lse(a, (unsigned)pl.grid, pl.mq, (int)pl.n_pairs, st);   // llama_attn_hd64_lse.hip
-  static bool lds_set[LR_MAX_DEVICES] = {};
-  if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_hd64_kernel<false>), FA5_LDS_BYTES, lds_set)) return rc;
-  hipLaunchKernelGGL(attn_hd64_kernel<false>, dim3((unsigned)pl.grid), dim3(256), FA5_LDS_BYTES, st, a.qkv, a.out, a.cu, nh, nkv,
-                     pl.mq, (int)pl.n_pairs, (float*)nullptr);
-  LR_CHECK_LAUNCH("attn_hd64_kernel");
-  return LR_OK;
+  if (a.lse) return lr_launch_attention_hd64_lse(a, st);   // llama_attn_hd64_lse.hip
+  return lr_attn_launch_tiles<attn_hd64_kernel<false>, FA5_HD, FA5_QROWS, 256, FA5_LDS_BYTES, false>(
+      "attn_hd64_kernel", "attention variants 5 and 6 need head_dim 64", nullptr, nullptr, nullptr, a, st, (float*)nullptr);
 }

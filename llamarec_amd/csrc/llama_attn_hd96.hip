@@ -10,7 +10,7 @@
 // of one (prompt, head); 64-key blocks, K and V tiles of 64 x 192 B = 12 KiB each, double-buffered: 48 KiB of LDS, three
 // workgroups per CU. Per 64-key block and 16-row tile a wave issues 12 + 12 + 2 MFMAs beside the same 16 exponentials per lane.
 // Rounding points are variant 5's: fp32 scores and online softmax with the deferred maximum (a row's reference moves only
-// when a score exceeds it by more than 2^FA7_DEFER), bf16 P into both the numerator and the row sum (an MFMA against a row
+// when a score exceeds it by more than 2^FA_DEFER), bf16 P into both the numerator and the row sum (an MFMA against a row
 // of ones), one bf16 rounding of O / l. A query row's bits depend only on its own prompt: tiles and key blocks are aligned
 // to positions inside the prompt, and the rescale decision is per row.
 // The kernel's one text is attn_hd96_body in llama_attn_hd96_body.h (the LDS layout and its swizzles are derived there), with
@@ -26,22 +26,7 @@ __global__ __launch_bounds__(256, FA7_MIN_WG) void attn_hd96_kernel(const u16* _
 
 // cu / cu_host: prompt starts [B + 1] in packed rows (no shared prefix)
 int lr_launch_attention_hd96(const LrAttnArgs& a, hipStream_t st) {
-  const int B = a.S, n_tok = a.n_tok, nh = a.nh, nkv = a.nkv, hd = a.hd;
-  if (n_tok <= 0 || B <= 0) return LR_OK;
-  if (hd != FA7_HD) LR_FAIL(LR_EUNSUPPORTED, "attention variant 7 needs head_dim 96 (got %d)", hd);
-  if (nh < 1 || nkv < 1 || nh % nkv != 0)
-    LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
-  if (a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-96 MFMA kernel writes no lse");
-  const LrAttnPlan pl = lr_attn_plan(a.cu_host, B, 0, nh, hd, FA7_QROWS, nh);
-  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
-  if (pl.mq == 0) return LR_OK;
-  LR_RUN(lr_attn_check_grid(pl));
-  if ((long long)n_tok * (nh + 2 * nkv) * hd * 2 > 0x7fffffffLL * 2)
-    LR_FAIL(LR_EUNSUPPORTED, "attention: packed qkv of %d tokens exceeds the 4 GiB a buffer descriptor addresses", n_tok);
-  static bool lds_set[LR_MAX_DEVICES] = {};
-  if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_hd96_kernel), FA7_LDS_BYTES, lds_set)) return rc;
-  hipLaunchKernelGGL(attn_hd96_kernel, dim3((unsigned)pl.grid), dim3(256), FA7_LDS_BYTES, st, a.qkv, a.out, a.cu, nh, nkv, pl.mq,
-                     (int)pl.n_pairs);
-  LR_CHECK_LAUNCH("attn_hd96_kernel");
-  return LR_OK;
+  return lr_attn_launch_tiles<attn_hd96_kernel, FA7_HD, FA7_QROWS, 256, FA7_LDS_BYTES, false>(
+      "attn_hd96_kernel", "attention variant 7 needs head_dim 96", "attention: the head_dim-96 MFMA kernel writes no lse", nullptr,
+      nullptr, a, st);
 }

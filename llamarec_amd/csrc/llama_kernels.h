@@ -3,6 +3,7 @@
 #define LLAMA_KERNELS_H
 
 #include "lr_common.h"
+#include "lr_profile.h"
 
 __device__ __forceinline__ float bf2f(unsigned short b) {
   return __builtin_bit_cast(float, (unsigned int)b << 16);
@@ -212,7 +213,8 @@ static inline int lr_attn_check_grid(const LrAttnPlan& p) {
 //   HD96     head_dim 96, no lse (variant 7); one body (llama_attn_hd96_body.h) instantiated without a shared prefix in
 //            llama_attn_hd96.hip and with one in llama_attn_hd96_prefix.hip
 // MFMA128, HD256, HD64 and HD96 also have a one-query-row mode (lr_launch_attention_last, the pruned last layer); at HD256,
-// HD64 and HD96 it is one more instantiation of the body, in the _prefix file.
+// HD64 and HD96 it is one more instantiation of the body, in the _prefix file. The three bodies hold what differs per head
+// size; what they share is lr_attn_body.h on the device side and lr_attn_launch_tiles / _last (below) on the host side.
 enum LrAttnKernel {
   LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 3, LR_ATTN_HD256 = 4, LR_ATTN_HD64 = 5, LR_ATTN_HD96 = 7
 };
@@ -345,7 +347,7 @@ int lr_launch_attn256_items(const int32_t* cu, int S, int n_tok, int nh, int pre
 int lr_launch_attention256(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd256(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd64(const LrAttnArgs& a, hipStream_t st);
-int lr_launch_attention_hd64_lse(const LrAttnArgs& a, unsigned grid, int max_qblocks, int n_pairs, hipStream_t st);
+int lr_launch_attention_hd64_lse(const LrAttnArgs& a, hipStream_t st);   // a.lse != nullptr: lr_launch_attention_hd64 sends it here
 // HD64 / HD256 with a.prefix_len > 0 (llama_attn_hd64_prefix.hip, llama_attn_hd256_prefix.hip) and their last-row modes
 int lr_launch_attention_hd64_prefix(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd256_prefix(const LrAttnArgs& a, hipStream_t st);
@@ -367,5 +369,62 @@ int lr_launch_attention_hd256_softcap(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd256_softcap_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
                                            const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv,
                                            int prefix_len, float scale, float cap, hipStream_t st);
+
+// ---- the launch sequence of the HD64 / HD96 / HD256 kernels, once ------------------------------------------------------------
+// Every lr_launch_attention_hd* above is one call of lr_attn_launch_tiles or lr_attn_launch_last with its kernel (a template
+// argument: the dynamic-LDS flag is per kernel), head_dim, threads and dynamic LDS bytes per workgroup. The kernels' argument
+// lists are (qkv, out, cu, [prefix_len,] nh, nkv, max_qblocks, n_pairs, tail...): `tail` is passed through.
+template <auto KERNEL, int BLOCK, int LDS_BYTES, class... Args>
+static inline int lr_attn_launch_kernel(const LrAttnPlan& pl, const char* kernel_name, hipStream_t st, Args... args) {
+  static bool lds_set[LR_MAX_DEVICES] = {};
+  LR_RUN(lr_ensure_dynamic_lds(reinterpret_cast<const void*>(KERNEL), LDS_BYTES, lds_set));
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)pl.grid), dim3(BLOCK), LDS_BYTES, st, args...);
+  LR_CHECK_LAUNCH(kernel_name);
+  return LR_OK;
+}
+// Whole query tiles of QROWS rows, HPW heads per workgroup. needs = "<who> needs head_dim <HD>" for the head_dim refusal;
+// no_lse = the refusal of a.lse (nullptr: the kernel writes it, or the caller has dealt with it); extra = a check of the
+// caller's own behind those (the soft cap's). layout = the name lr_check_prefix_layout reports under: the kernel takes
+// a.prefix_len and reads a shared prefix; nullptr: whole prompts, which must fit one buffer descriptor. No rows, no launch.
+template <auto KERNEL, int HD, int QROWS, int BLOCK, int LDS_BYTES, bool PREFIX_ARG, int HPW = 1, class... Tail>
+static inline int lr_attn_launch_tiles(const char* kernel_name, const char* needs, const char* no_lse,
+                                       int (*extra)(const LrAttnArgs&), const char* layout, const LrAttnArgs& a, hipStream_t st,
+                                       Tail... tail) {
+  const int S = a.S, n_tok = a.n_tok, nh = a.nh, nkv = a.nkv, hd = a.hd, P = a.prefix_len;
+  if (n_tok <= 0 || S <= 0) return LR_OK;
+  if (hd != HD) LR_FAIL(LR_EUNSUPPORTED, "%s (got %d)", needs, hd);
+  if (nh < 1 || nkv < 1 || nh % nkv != 0)
+    LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
+  if (no_lse && a.lse) LR_FAIL(LR_EINVAL, "%s", no_lse);
+  if (extra) LR_RUN(extra(a));
+  if (layout) LR_RUN(lr_check_prefix_layout(layout, a.cu_host, S, n_tok, (nh + 2 * nkv) * hd, P));
+  const LrAttnPlan pl = lr_attn_plan(a.cu_host, S, layout ? P : 0, nh, hd, QROWS / HPW, nh / HPW);
+  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
+  if (HPW == 2 && (nh / nkv) % 2 != 0) LR_FAIL(LR_EINVAL, "attention: two heads per workgroup need an even nh / nkv");
+  if (pl.mq == 0) return LR_OK;
+  LR_RUN(lr_attn_check_grid(pl));
+  if (!layout && (long long)n_tok * (nh + 2 * nkv) * hd * 2 > 0x7fffffffLL * 2)
+    LR_FAIL(LR_EUNSUPPORTED, "attention: packed qkv of %d tokens exceeds the 4 GiB a buffer descriptor addresses", n_tok);
+  if constexpr (PREFIX_ARG)
+    return lr_attn_launch_kernel<KERNEL, BLOCK, LDS_BYTES>(pl, kernel_name, st, a.qkv, a.out, a.cu, P, nh, nkv, pl.mq,
+                                                            (int)pl.n_pairs, tail...);
+  else
+    return lr_attn_launch_kernel<KERNEL, BLOCK, LDS_BYTES>(pl, kernel_name, st, a.qkv, a.out, a.cu, nh, nkv, pl.mq,
+                                                            (int)pl.n_pairs, tail...);
+}
+// The pruned last layer (lr_launch_attention_last): kv = [n_tok][2 nkv hd], q_last / out_last = [prompts][nh hd], one workgroup
+// per (segment, head)
+template <auto KERNEL, int HD, int BLOCK, int LDS_BYTES, class... Tail>
+static inline int lr_attn_launch_last(const char* kernel_name, const char* layout, const unsigned short* kv,
+                                      const unsigned short* q_last, unsigned short* out_last, const int32_t* cu,
+                                      const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int prefix_len, hipStream_t st,
+                                      Tail... tail) {
+  LR_RUN(lr_check_prefix_layout(layout, cu_host, S, n_tok, 2 * nkv * HD, prefix_len));
+  const LrAttnPlan pl = lr_attn_plan_last(cu_host, S, prefix_len, nh, HD, 1);
+  LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
+  LR_RUN(lr_attn_check_grid(pl));
+  return lr_attn_launch_kernel<KERNEL, BLOCK, LDS_BYTES>(pl, kernel_name, st, kv, out_last, cu, prefix_len, nh, nkv, 0,
+                                                          (int)pl.n_pairs, q_last, tail...);
+}
 
 #endif

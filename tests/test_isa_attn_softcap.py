@@ -59,11 +59,18 @@ def test_capped_kernels_fit_256_vgprs_without_scratch_and_with_variant_4s_lds(as
 
 
 def test_both_launchers_ask_for_the_same_dynamic_lds():
-    """The 128 KiB are dynamic LDS: both files name the one macro of the shared body in every launch."""
+    """The 128 KiB are dynamic LDS: both files name the one macro of the shared body in every launch. A launch is a call of
+    llama_kernels.h's launcher templates, which hand their BLOCK and LDS_BYTES arguments to the one hipLaunchKernelGGL."""
     body = open(os.path.join(CSRC, "llama_attn_hd256_body.h")).read()
     assert len(re.findall(r"^#define FA4_LDS_BYTES\b", body, flags=re.M)) == 1
+    header = open(os.path.join(CSRC, "llama_kernels.h")).read()
+    assert "hipLaunchKernelGGL(KERNEL, dim3((unsigned)pl.grid), dim3(BLOCK), LDS_BYTES, st, args...);" in header
+    n = 0
     for src in ("llama_attn_hd256_softcap.hip", "llama_attn_hd256.hip", "llama_attn_hd256_prefix.hip"):
         text = open(os.path.join(CSRC, src)).read()
-        launches = re.findall(r"hipLaunchKernelGGL\((.*?)\);", text, flags=re.S)
-        assert launches and all("dim3(512), FA4_LDS_BYTES" in l for l in launches), src
+        assert "hipLaunchKernelGGL" not in text and "lr_attn_launch_kernel" not in text, src
+        launches = re.findall(r"lr_attn_launch_(?:tiles|last)<(.*?)>\(", text, flags=re.S)
+        assert launches and all(re.search(r"\b512, FA4_LDS_BYTES\b", l) for l in launches), src
         assert "#define FA4_LDS_BYTES" not in text, src
+        n += len(launches)
+    assert n == 6, n   # variant 4's three forms and the capped three: one launch per kernel

@@ -5,6 +5,8 @@
 
 extern "C" int diag_attn_hd256(const unsigned short* qkv, unsigned short* out, const int32_t* cu, const int32_t* cu_host, int B,
                                int n_tok, int nh, int nkv, int heads_per_wg, void* stream) {
-  if (heads_per_wg == 2) return launch_hd256<2>(qkv, out, cu, cu_host, B, n_tok, nh, nkv, 256, (hipStream_t)stream);
-  return launch_hd256<1>(qkv, out, cu, cu_host, B, n_tok, nh, nkv, 256, (hipStream_t)stream);
+  LrAttnArgs a = {};
+  a.qkv = qkv, a.out = out, a.cu = cu, a.cu_host = cu_host;
+  a.S = B, a.n_tok = n_tok, a.nh = nh, a.nkv = nkv, a.hd = 256;
+  return heads_per_wg == 2 ? launch_hd256<2>(a, (hipStream_t)stream) : launch_hd256<1>(a, (hipStream_t)stream);
 }
