@@ -16,17 +16,19 @@
 // The kernel's one text is attn_hd96_body in llama_attn_hd96_body.h (the LDS layout and its swizzles are derived there), with
 // its modes chosen at compile time. This file instantiates variant 7 (no shared prefix) and holds its launcher;
 // llama_attn_hd96_prefix.hip instantiates the shared-prefix mode and the pruned last layer's one-query-row mode. `out` has
-// the same bits in every instantiation. There is no lse and no backward at this head size.
+// the same bits in every instantiation. llama_attn_hd96_lse.hip instantiates the training forward (attention variant 8), which
+// also writes the natural-log log-sum-exp per (token, head); the backward is llama_attn_bwd_hd96.hip.
 #include "llama_attn_hd96_body.h"
 
 __global__ __launch_bounds__(256, FA7_MIN_WG) void attn_hd96_kernel(const u16* __restrict__ qkv, u16* out, const int32_t* cu, int nh,
                                                            int nkv, int max_qblocks, int n_pairs) {
-  attn_hd96_body<false, false>(qkv, out, cu, 0, nh, nkv, max_qblocks, n_pairs, nullptr);
+  attn_hd96_body<false, false, false>(qkv, out, cu, 0, nh, nkv, max_qblocks, n_pairs, nullptr, nullptr);
 }
 
-// cu / cu_host: prompt starts [B + 1] in packed rows (no shared prefix)
+// cu / cu_host: prompt starts [B + 1] in packed rows (no shared prefix). a.lse reaches this launcher only where the resolver
+// allowed it (variant 8, or the LoRA route's auto): lr_resolve_attention refuses variant 7 with lse.
 int lr_launch_attention_hd96(const LrAttnArgs& a, hipStream_t st) {
+  if (a.lse) return lr_launch_attention_hd96_lse(a, st);   // llama_attn_hd96_lse.hip
   return lr_attn_launch_tiles<attn_hd96_kernel, FA7_HD, FA7_QROWS, 256, FA7_LDS_BYTES, false>(
-      "attn_hd96_kernel", "attention variant 7 needs head_dim 96", "attention: the head_dim-96 MFMA kernel writes no lse", nullptr,
-      nullptr, a, st);
+      "attn_hd96_kernel", "attention variants 7 and 8 need head_dim 96", nullptr, nullptr, nullptr, a, st);
 }

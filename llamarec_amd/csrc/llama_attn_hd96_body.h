@@ -1,11 +1,13 @@
 // llama_attn_hd96_body.h -- the one text of the head_dim-96 MFMA attention (llama_attn_hd96.hip: read its header first),
-// attn_hd96_body<LASTQ, PREFIX>, inlined into three kernels in two translation units:
-//   <false, false>  attn_hd96_kernel, attention variant 7                        (llama_attn_hd96.hip)
-//   <false, true>   attn_hd96_prefix_kernel<false>, shared prompt prefix          (llama_attn_hd96_prefix.hip)
-//   <true, true>    attn_hd96_prefix_kernel<true>, one query row per prompt       (llama_attn_hd96_prefix.hip)
+// attn_hd96_body<LASTQ, PREFIX, LSE>, inlined into four kernels in three translation units:
+//   <false, false, false>  attn_hd96_kernel, attention variant 7                        (llama_attn_hd96.hip)
+//   <false, false, true>   attn_hd96_lse_kernel, variant 8's training forward: one lse store per row and head more
+//                                                                                       (llama_attn_hd96_lse.hip)
+//   <false, true, false>   attn_hd96_prefix_kernel<false>, shared prompt prefix          (llama_attn_hd96_prefix.hip)
+//   <true, true, false>    attn_hd96_prefix_kernel<true>, one query row per prompt       (llama_attn_hd96_prefix.hip)
 // Here stand the constants, the LDS layout with its swizzle and staging offsets, the QK product and the mask. The prologue,
 // the staging of a block, the softmax steps and the store are lr_attn_body.h's, shared with head_dim 64 and 256; the PREFIX and
-// LASTQ modes are described there. No lse and no backward exist at this head size.
+// LASTQ modes are described there. The backward is llama_attn_bwd_hd96.hip, which stages and reads its tiles by this layout.
 //
 // What differs at 96: a K or V row is 192 B = 12 chunks of 16 B (not a power of two), the QK product has 3 k-steps of 32 and
 // O has 6 d-tiles of 16.
@@ -51,9 +53,11 @@
 
 __device__ __forceinline__ int fa7_swz(int row) { return (0 - (row >> 2)) & 3; }
 
-template <bool LASTQ, bool PREFIX>
+// LSE (alone): lse[token][head] = natural-log log-sum-exp of the row's scaled scores.
+template <bool LASTQ, bool PREFIX, bool LSE>
 __device__ __forceinline__ void attn_hd96_body(const u16* qkv, u16* out, const int32_t* cu, int prefix_len, int nh, int nkv,
-                                               int max_qblocks, int n_pairs, const u16* q_rows_last) {
+                                               int max_qblocks, int n_pairs, float* lse, const u16* q_rows_last) {
+  static_assert(!LSE || (!PREFIX && !LASTQ), "the lse store exists without a shared prefix and for whole tiles only");
   static_assert(!LASTQ || PREFIX, "the last-row mode reads a shared prefix");
   constexpr int QT = LASTQ ? 1 : FA7_QT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -229,6 +233,10 @@ __device__ __forceinline__ void attn_hd96_body(const u16* qkv, u16* out, const i
     const float inv = 1.0f / l_acc[qt][0];
     const int qabs = qabs_of(qt);
     const bool live = fa_row_live<LASTQ, PREFIX>(sg, qabs, wave, li);
+    if constexpr (LSE) {   // the lane's row: m (log2 units) + log2 l, as natural log; quad 0 of the row's lanes writes it
+      if (live && quad == 0)
+        lse[(size_t)(sg.tok0 + qabs) * nh + h] = (m_run[qt] + __builtin_amdgcn_logf(l_acc[qt][0])) * 0.6931471805599453f;
+    }
     const int orow = fa_out_row<LASTQ, PREFIX>(sg, prompt, live, qabs);
     fa_store_row<FA7_DT>(ot[qt], inv, live, out + (size_t)orow * nh * FA7_HD + h * FA7_HD + (quad & 1) * 16 + (quad >> 1) * 8);
   }

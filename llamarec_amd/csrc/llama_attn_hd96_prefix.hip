@@ -15,7 +15,7 @@ template <bool LASTQ>
 __global__ __launch_bounds__(256, FA7_MIN_WG) void attn_hd96_prefix_kernel(const u16* __restrict__ qkv, u16* out, const int32_t* cu,
                                                                   int prefix_len, int nh, int nkv, int max_qblocks, int n_pairs,
                                                                   const u16* __restrict__ q_rows_last) {
-  attn_hd96_body<LASTQ, true>(qkv, out, cu, prefix_len, nh, nkv, max_qblocks, n_pairs, q_rows_last);
+  attn_hd96_body<LASTQ, true, false>(qkv, out, cu, prefix_len, nh, nkv, max_qblocks, n_pairs, nullptr, q_rows_last);
 }
 
 // cu / cu_host: segment starts [S + 1]; prefix_len = P > 0: segment 0 is the shared prefix the other segments continue

@@ -202,7 +202,7 @@ static inline int lr_attn_check_grid(const LrAttnPlan& p) {
 
 // ---- varlen causal attention over packed qkv (RoPE applied) ----------------------------------------------------------------
 // The kernels (a requested variant 1 .. 5 asks for the kernel of the same number, 6 for HD64 with lse allowed, 7 for HD96,
-// 0 = auto):
+// 8 for HD96 with lse allowed, 0 = auto):
 //   GENERIC  any head_dim <= 256, scalar                                  (llama_attn.hip)
 //   MFMA128  head_dim 128, 128-row query tiles, reads a shared prefix     (llama_attn.hip)
 //   ROWS256  head_dim 128, 256-row query tiles over a device-built item list, shared prefix <= 64 (llama_attn256.hip)
@@ -210,8 +210,8 @@ static inline int lr_attn_check_grid(const LrAttnPlan& p) {
 //            llama_attn_hd256.hip and with one in llama_attn_hd256_prefix.hip
 //   HD64     head_dim 64; one body (llama_attn_hd64_body.h) instantiated without a shared prefix in llama_attn_hd64.hip, with
 //            lse (variant 6, no prefix) in llama_attn_hd64_lse.hip and with a shared prefix in llama_attn_hd64_prefix.hip
-//   HD96     head_dim 96, no lse (variant 7); one body (llama_attn_hd96_body.h) instantiated without a shared prefix in
-//            llama_attn_hd96.hip and with one in llama_attn_hd96_prefix.hip
+//   HD96     head_dim 96; one body (llama_attn_hd96_body.h) instantiated without a shared prefix in llama_attn_hd96.hip, with
+//            lse (variant 8, no prefix) in llama_attn_hd96_lse.hip and with a shared prefix in llama_attn_hd96_prefix.hip
 // MFMA128, HD256, HD64 and HD96 also have a one-query-row mode (lr_launch_attention_last, the pruned last layer); at HD256,
 // HD64 and HD96 it is one more instantiation of the body, in the _prefix file. The three bodies hold what differs per head
 // size; what they share is lr_attn_body.h on the device side and lr_attn_launch_tiles / _last (below) on the host side.
@@ -225,7 +225,7 @@ enum LrAttnKernel {
 //   varlen_ws  lr_attention_varlen_ws: lse and workspace optional
 //   train      lr_attention_varlen_lse: lse wanted, no workspace
 //   lora       the LoRA forward (api_llama_train.hip): lse wanted, no workspace; its backward follows the same choice
-//              (variant 0 at head_dim 64 -> lr_launch_attention_bwd variant 6)
+//              (variant 0 at head_dim 64 -> lr_launch_attention_bwd variant 6, at head_dim 96 -> variant 8)
 // prefix_len is 0 outside prefill and lr_attention_varlen_prefix (which resolves as a prefill request without item workspace).
 // Prefill drops a shared prefix (runs every prompt whole) unless lr_attention_reads_prefix: variant 1, a head_dim other than
 // 64 / 96 / 128 / 256, variant 2 / 3 off head_dim 128 and the like -- and with a single prompt. First matching row:
@@ -242,11 +242,12 @@ enum LrAttnKernel {
 //                                                                   prefix > 0: its shared-prefix kernel)
 //   0        64, 96, 256  > 0  yes  any      any          LR_EINVAL  (no lse with a shared prefix off head_dim 128)
 //   0        64        0       yes  no       lora         HD64     (with lse; the pair 6 / backward 6)
+//   0        96        0       yes  no       lora         HD96     (with lse; the pair 8 / backward 8)
 //   0        other     > 0     any  any      any          LR_EUNSUPPORTED  (GENERIC reads no shared prefix)
-//   0        any       0       any  any      any          GENERIC  (head_dim 256, 96 and 64 too outside prefill -- at 96 the
-//                                                                   LoRA forward as well, which wants lse: the entry points'
-//                                                                   auto is older than HD256 / HD64 and its results are kept,
-//                                                                   lr_attention_varlen_lse / _bwd at head_dim 64 included)
+//   0        any       0       any  any      any          GENERIC  (head_dim 256, 96 and 64 too outside prefill and the LoRA
+//                                                                   route: the entry points' auto is older than HD256 / HD64 /
+//                                                                   HD96 and its results are kept, lr_attention_varlen_lse /
+//                                                                   _bwd at head_dim 64 and 96 included)
 //   1        any       > 0     any  any      any          LR_EUNSUPPORTED
 //   1        any       0       any  any      any          GENERIC
 //   2        any       any     any  any      any          MFMA128
@@ -267,9 +268,13 @@ enum LrAttnKernel {
 //   6        64        > 0     yes  any      any          LR_EINVAL  (no lse with a shared prefix)
 //   6        64        any     any  any      any          HD64     (writes lse when wanted; without lse variant 5's bits, with
 //                                                                   a shared prefix too)
-//   7        any       any     yes  any      any          LR_EINVAL  (HD96 writes no statistics)
+//   7        any       any     yes  any      any          LR_EINVAL  (variant 7 writes no statistics: 8 does)
 //   7        != 96     any     no   any      any          LR_EUNSUPPORTED
 //   7        96        any     no   any      any          HD96     (prefix > 0: its shared-prefix kernel)
+//   8        != 96     any     any  any      any          LR_EUNSUPPORTED
+//   8        96        > 0     yes  any      any          LR_EINVAL  (no lse with a shared prefix)
+//   8        96        any     any  any      any          HD96     (writes lse when wanted; without lse variant 7's bits, with
+//                                                                   a shared prefix too)
 //   other                                                 LR_EINVAL
 //
 // With a soft cap (LrAttnRequest.softcap: Gemma-2, lr_attention_varlen_softcap) the table is a short one. No lse anywhere
@@ -277,8 +282,8 @@ enum LrAttnKernel {
 //
 //   variant        head_dim  cap                     prefix  result
 //   2, 3, 5, 6     any       any                     any     LR_EUNSUPPORTED  (those kernels have no capped form)
-//   7              96        any                     any     LR_EUNSUPPORTED  (nor has HD96; off head_dim 96 a capped variant 7
-//                                                                     stays LR_EINVAL, the last row, as before HD96 existed)
+//   7, 8           96        any                     any     LR_EUNSUPPORTED  (nor has HD96; off head_dim 96 a capped variant 7
+//                                                                     or 8 stays LR_EINVAL, the last row, as before HD96 existed)
 //   0, 4           256       <= LR_SOFTCAP_MFMA_MAX  any     HD256    (the SOFTCAP instantiations of llama_attn_hd256_softcap.hip,
 //                                                                     on every route)
 //   0, 1, 4        any       any                     > 0     LR_EUNSUPPORTED  (GENERIC reads no shared prefix. The prefill never
@@ -297,13 +302,13 @@ enum LrAttnKernel {
 // varlen_ws counts a variant-3 request as "item ws yes" whatever it was given: the item-list builder then reports a missing
 // or short workspace as LR_EWORKSPACE. lr_launch_attention still refuses what the resolved kernel cannot take: GENERIC above
 // head_dim 256 and MFMA128 off head_dim 128 (LR_EUNSUPPORTED; a one-layer pruned prefill launches neither, so these checks
-// cannot move up here), lse on HD256 and HD96, lse with a shared prefix on HD64, a segment 0 that is not the prefix.
+// cannot move up here), lse on HD256, lse with a shared prefix on HD64 and HD96, a segment 0 that is not the prefix.
 // cap > 0 (soft-capped scores): only HD256's capped instantiations read a shared prefix (the short table above)
 static inline bool lr_attention_reads_prefix(int variant, int hd, float cap = 0.f) {
   if (cap > 0.f) return hd == 256 && (variant == 0 || variant == 4) && cap <= LR_SOFTCAP_MFMA_MAX;
   if (hd == 128) return variant != 1;
   if (hd == 64) return variant == 0 || variant == 5 || variant == 6;
-  if (hd == 96) return variant == 0 || variant == 7;
+  if (hd == 96) return variant == 0 || variant == 7 || variant == 8;
   if (hd == 256) return variant == 0 || variant == 4;
   return false;
 }
@@ -359,6 +364,7 @@ int lr_launch_attention_hd256_last(const unsigned short* kv, const unsigned shor
                                    hipStream_t st);
 // HD96 (llama_attn_hd96.hip), with a.prefix_len > 0 and its last-row mode (llama_attn_hd96_prefix.hip)
 int lr_launch_attention_hd96(const LrAttnArgs& a, hipStream_t st);
+int lr_launch_attention_hd96_lse(const LrAttnArgs& a, hipStream_t st);   // a.lse != nullptr: lr_launch_attention_hd96 sends it here
 int lr_launch_attention_hd96_prefix(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd96_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
                                   const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int prefix_len,

@@ -663,7 +663,9 @@ class LlamaRanker:
         single-user path (split-K where a short prompt would leave most CUs idle); gemm=6 = auto with the MFMA tile on a ragged
         last column tile (widths that are multiples of 64 but not of 256: a qwen2 ranker's default). attention: 1 generic, 2 / 3 head_dim 128,
         4 head_dim 256, 5 head_dim 64 (scoring only: no lse), 7 head_dim 96 (scoring only: no lse), 6 = head_dim-64 MFMA attention for training (5's forward, writing
-        lse when a LoRA engine runs on this base, and the head_dim-64 MFMA backward; the LoRA step's auto at head_dim 64)."""
+        lse when a LoRA engine runs on this base, and the head_dim-64 MFMA backward; the LoRA step's auto at head_dim 64),
+        8 = the same pair at head_dim 96 (7's forward writing lse, the head_dim-96 MFMA backward; the LoRA step's auto at
+        head_dim 96)."""
         check(lib().lr_llama_set_variants(self._h, gemm, attention), "lr_llama_set_variants")
         return self
 

@@ -227,11 +227,13 @@ def attention_train_table(reps):
     return rows
 
 
-def llama32_lora_step(steps, layers):
-    from llamarec_amd.llm import LLAMA32_1B, LlamaRanker
+def lora_step(cfg, label, variants, steps):
+    """The LoRA fwd+bwd of a random-weight Llama-format model `cfg` (printed as `label`) with the attention `variants`
+    alternating on one engine; tools/bench_phi3.py --train runs it at Phi-3-mini's shape."""
+    from llamarec_amd.llm import LlamaRanker
     from llamarec_amd.rank_train import LoraTrainEngine
 
-    cfg = dict(LLAMA32_1B, num_hidden_layers=layers)
+    layers = cfg["num_hidden_layers"]
     ranker = LlamaRanker.random_init(cfg, seed=1)
     eng = LoraTrainEngine(ranker, dropout=0.05)
     init = eng.peft_init(3)
@@ -247,7 +249,6 @@ def llama32_lora_step(steps, layers):
         l = s.copy()
         l[:-2] = -100
         labels.append(l)
-    variants = (1, 6)
     losses = {}
     for v in variants:                # warm-up of both, sizes the workspace
         ranker.set_variants(0, v)
@@ -287,7 +288,7 @@ def llama32_lora_step(steps, layers):
         res[f"variant_{v}"] = dict(fwd_bwd_ms_median=float(np.median(t)), fwd_bwd_ms_min=min(t), fwd_bwd_ms_max=max(t), steps=len(t),
                                    loss=losses[v], profiled_step_ms=prof_ms, kernels=split, attention_ms=attn, gemm_ms=gemm,
                                    attention_share=attn / prof_ms, gemm_share=gemm / prof_ms)
-        print(f"llama-3.2-1b ({layers} layers, random weights) LoRA fwd+bwd, attention variant {v}: {PROMPTS} prompts of "
+        print(f"{label} ({layers} layers, random weights) LoRA fwd+bwd, attention variant {v}: {PROMPTS} prompts of "
               f"{lens.min()} .. {lens.max()}, {lens.sum()} tokens: median {np.median(t):.2f} ms per micro-batch (min {min(t):.2f}, max "
               f"{max(t):.2f}, {len(t)} alternating steps); profiled pass {prof_ms:.2f} ms: attention {attn:.2f} ms "
               f"({100 * attn / prof_ms:.1f} %), GEMMs {gemm:.2f} ms ({100 * gemm / prof_ms:.1f} %), loss {losses[v]:.4f}", flush=True)
@@ -320,7 +321,9 @@ def main():
     print(f"box: {box['device']}, {box['compute_units']} CUs, clock {box['clock_mhz'] or 'not readable here'} MHz at start; {box['method']}", flush=True)
     if args.train:
         res = dict(box=box, attention_bwd=attention_train_table(args.reps))
-        res["llama32_1b_lora_step"] = llama32_lora_step(args.steps, args.layers)
+        from llamarec_amd.llm import LLAMA32_1B
+
+        res["llama32_1b_lora_step"] = lora_step(dict(LLAMA32_1B, num_hidden_layers=args.layers), "llama-3.2-1b", (1, 6), args.steps)
         box["clock_mhz_end"] = clock_mhz()
         print(json.dumps(res))
         return
