@@ -254,6 +254,10 @@ int lr_llama_create_ex(const LrLlamaConfig* cfg, const LrLlamaArch* arch, const 
  * the same bits as 7, with a shared prefix and in the one-query-row mode too), and the head_dim-96 MFMA backward (two passes,
  * one owner per gradient element, no atomics); the LoRA step's auto takes the pair at head_dim 96, and any other head_dim is
  * LR_EUNSUPPORTED,
+ * attention 9 = head_dim-256 MFMA flash attention for training: variant 4's forward, optionally writing lse (without lse
+ * the same bits as 4, with a shared prefix and in the one-query-row mode too; no soft-capped form: LR_EUNSUPPORTED on a handle
+ * with attn_logit_softcapping), and the head_dim-256 MFMA backward (two passes, one owner per gradient element, no atomics);
+ * the LoRA step's auto takes the pair at head_dim 256, and any other head_dim is LR_EUNSUPPORTED,
  * gemm 4 = the ping-pong pipelined 256x256x64 MFMA GEMM (an error if a shape does not fit).
  * gemm 5 = LATENCY MODE for the online single-user path (demo/inference.py:56-76):
  * variant 4 plus split-K wherever the output tiles alone would leave most CUs idle (a 460-token prompt
@@ -468,7 +472,7 @@ int lr_rope_table_ex(float* cs, int32_t max_positions, int32_t head_dim, float t
  * dims inside q and k heads), out: bf16 [total][nh*hd]. variant 0 = auto (2 at head_dim 128, else 1), 1 generic,
  * 2 = head_dim-128 MFMA, 4 = head_dim-256 MFMA, 5 = head_dim-64 MFMA, 6 = the same kernel, which also serves _lse and has a
  * backward (_bwd), 7 = head_dim-96 MFMA (no lse, no backward), 8 = the same kernel, which also serves _lse and has a backward
- * (_bwd). auto keeps the generic kernels at head_dim 64, 96 and 256
+ * (_bwd), 9 = variant 4's kernel, which also serves _lse and has a backward (_bwd; LR_EUNSUPPORTED off head_dim 256). auto keeps the generic kernels at head_dim 64, 96 and 256
  * here: these entry points' results are kept.
  * cu_seqlens_host (HOST int32 [B+1], the values of cu_seqlens): cu_seqlens_host[0] == 0 and strictly increasing, so that
  * every segment holds at least one row. lr_attention_varlen, _ws, _lse and _bwd check this on the host and return LR_EINVAL
@@ -487,7 +491,7 @@ int lr_attention_varlen_ws(const uint16_t* qkv, uint16_t* out, float* lse, const
 /* The two modes of the prefill's MFMA attention kernels, stand-alone (exposed for parity tests). Both check on the host,
  * before anything is launched (outputs untouched): seg_starts_host[0] == 0 and strictly increasing, segment 0 exactly
  * prefix_len rows when prefix_len > 0 (and S >= 2), num_heads % num_kv_heads == 0 -- LR_EINVAL -- and the (variant, head_dim)
- * pair: 0 / 2 at head_dim 128, 0 / 5 at 64, 0 / 7 / 8 at 96, 0 / 4 at 256, anything else LR_EUNSUPPORTED.
+ * pair: 0 / 2 at head_dim 128, 0 / 5 at 64, 0 / 7 / 8 at 96, 0 / 4 / 9 at 256, anything else LR_EUNSUPPORTED.
  * qkv rows laid out as the prefill lays them out: segment 0 = the prefix_len shared rows, segments 1.. continue it (their
  * keys and values of positions < prefix_len are read from segment 0). out rows of every segment are written, each with the
  * bits lr_attention_varlen (same variant; at 64 / 96 / 256 variant 5 / 7 / 4) writes for that row of the whole prompt. */
@@ -505,7 +509,7 @@ int lr_attention_last_rows(const uint16_t* kv, const uint16_t* q_last, uint16_t*
  * checks, same kernels, bit-identical results. cap > 0: the segment checks of those two, then variant 0 / 4 at head_dim 256
  * with cap <= 256 run the soft-capped MFMA kernels, variant 1, a larger cap or any other head_dim (prefix_len must be 0
  * there) the generic kernel, and
- * variants 2, 3, 5, 6 (and 7 / 8 at their head_dim 96) return LR_EUNSUPPORTED; lr_attention_last_rows_softcap needs head_dim 256 and variant 0 / 4.
+ * variants 2, 3, 5, 6 (and 7 / 8 at their head_dim 96, 9 at its head_dim 256) return LR_EUNSUPPORTED; lr_attention_last_rows_softcap needs head_dim 256 and variant 0 / 4.
  * A negative or non-finite scale or cap is LR_EINVAL. */
 int lr_attention_varlen_softcap(const uint16_t* qkv, uint16_t* out, const int32_t* seg_starts, const int32_t* seg_starts_host,
                                 int32_t S, int32_t prefix_len, int32_t num_heads, int32_t num_kv_heads, int32_t head_dim,
@@ -731,7 +735,8 @@ int lr_llama_lora_prefill_verbalize(lr_llama_lora_t* h, const int32_t* packed_id
  * bf16 [total][nh*hd]; lse fp32 [total][nh] from lr_attention_varlen_lse; dqkv bf16 like qkv.
  * scratch: DEVICE, lr_attention_bwd_scratch_bytes. variant: 0 / 1 / 2 as lr_attention_varlen, 6 = the head_dim-64 MFMA pair
  * (LR_EUNSUPPORTED at any other head_dim; its backward uses only the first, per-(token, head) part of the scratch, whose size
- * is the same for every variant), 8 = the head_dim-96 MFMA pair likewise (LR_EUNSUPPORTED off head_dim 96); 4, 5 and 7 write no lse and have no backward: LR_EINVAL. */
+ * is the same for every variant), 8 = the head_dim-96 MFMA pair likewise (LR_EUNSUPPORTED off head_dim 96),
+ * 9 = the head_dim-256 MFMA pair likewise (LR_EUNSUPPORTED off head_dim 256); 4, 5 and 7 write no lse and have no backward: LR_EINVAL. */
 int lr_attention_varlen_lse(const uint16_t* qkv, uint16_t* out, float* lse, const int32_t* cu_seqlens,
                             const int32_t* cu_seqlens_host, int32_t B, int32_t num_heads, int32_t num_kv_heads,
                             int32_t head_dim, int32_t variant, void* hip_stream);
@@ -744,10 +749,10 @@ int lr_attention_varlen_bwd(const uint16_t* qkv, const uint16_t* out, const uint
  * rope_cs: DEVICE, the table lr_rope_table wrote for head_dim with rope_positions positions; when given, dqkv is the
  * gradient w.r.t. the UNROTATED q and k (v as before). tok_pos: DEVICE int32[total], required with rope_cs, and must hold
  * each row's position INSIDE ITS PROMPT (row - cu_seqlens[b]): the head_dim-128 MFMA passes index the table by that
- * position directly (so do variant 6's head_dim-64 and variant 8's head_dim-96 passes) and the generic path reads tok_pos, so any other content makes the two disagree. LR_EINVAL (with a
+ * position directly (so do variant 6's head_dim-64, variant 8's head_dim-96 and variant 9's head_dim-256 passes) and the generic path reads tok_pos, so any other content makes the two disagree. LR_EINVAL (with a
  * message, nothing launched) for rope_cs without tok_pos and for a segment longer than rope_positions.
  * deterministic != 0: the generic path (variant 1) computes dK / dV per owner instead of with fp32 atomics -- the same
- * bits on every run; the MFMA passes (variants 2, 6 and 8) have no atomics either way and ignore the flag. */
+ * bits on every run; the MFMA passes (variants 2, 6, 8 and 9) have no atomics either way and ignore the flag. */
 int lr_attention_varlen_bwd_ex(const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out, const float* lse,
                                uint16_t* dqkv, const int32_t* cu_seqlens, const int32_t* cu_seqlens_host, int32_t B,
                                int32_t num_heads, int32_t num_kv_heads, int32_t head_dim, int32_t variant,

@@ -57,8 +57,8 @@ extern "C" int lr_llama_create(const LrLlamaConfig* cfg, const LrLlamaWeightsDes
 
 extern "C" int lr_llama_set_variants(lr_llama_t* h, int32_t gemm_variant, int32_t attention_variant) {
   if (!h || (gemm_variant != 0 && gemm_variant != 1 && gemm_variant != 4 && gemm_variant != 5 && gemm_variant != 6) ||
-      attention_variant < 0 || attention_variant > 8)
-    LR_FAIL(LR_EINVAL, "lr_llama_set_variants: gemm in {0, 1, 4, 5, 6}, attention in {0, 1, 2, 3, 4, 5, 6, 7, 8}");
+      attention_variant < 0 || attention_variant > 9)
+    LR_FAIL(LR_EINVAL, "lr_llama_set_variants: gemm in {0, 1, 4, 5, 6}, attention in {0, 1, 2, 3, 4, 5, 6, 7, 8, 9}");
   h->gemm_variant = gemm_variant;
   h->attn_variant = attention_variant;
   return LR_OK;
@@ -622,9 +622,9 @@ static int check_prefix_request(const char* who, const int32_t* cu_host, int S, 
   if (prefix_len > 0 && (S < 2 || cu_host[1] != prefix_len))
     LR_FAIL(LR_EINVAL, "%s: segment 0 has %d rows, the shared prefix %d (and a prompt must follow it)", who, cu_host[1], prefix_len);
   const bool ok = (hd == 128 && (variant == 0 || variant == 2)) || (hd == 64 && (variant == 0 || variant == 5)) ||
-                  (hd == 96 && (variant == 0 || variant == 7 || variant == 8)) || (hd == 256 && (variant == 0 || variant == 4));
+                  (hd == 96 && (variant == 0 || variant == 7 || variant == 8)) || (hd == 256 && (variant == 0 || variant == 4 || variant == 9));
   if (!ok)
-    LR_FAIL(LR_EUNSUPPORTED, "%s: variant %d at head_dim %d (0 / 2 at 128, 0 / 5 at 64, 0 / 7 / 8 at 96, 0 / 4 at 256)", who, variant, hd);
+    LR_FAIL(LR_EUNSUPPORTED, "%s: variant %d at head_dim %d (0 / 2 at 128, 0 / 5 at 64, 0 / 7 / 8 at 96, 0 / 4 / 9 at 256)", who, variant, hd);
   return LR_OK;
 }
 

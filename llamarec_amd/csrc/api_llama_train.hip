@@ -603,10 +603,13 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
   const int gv = h->base->gemm_variant == 5 ? 0 : h->base->gemm_variant;
   const int tw = md.tw, L = c.num_layers;
   // the backward follows the forward's kernel (lr_resolve_attention's lora route): the head_dim-64 MFMA pair is variant 6,
-  // the head_dim-96 one variant 8
+  // the head_dim-96 one variant 8, the head_dim-256 one variant 9
   LrAttnKernel fwd_kernel;
   LR_RUN(lr_resolve_attention({.variant = h->base->attn_variant, .hd = hd, .want_lse = true, .lora = true}, &fwd_kernel));
-  const int attn_bwd_variant = fwd_kernel == LR_ATTN_HD64 ? 6 : fwd_kernel == LR_ATTN_HD96 ? 8 : h->base->attn_variant;
+  const int attn_bwd_variant = fwd_kernel == LR_ATTN_HD64    ? 6
+                               : fwd_kernel == LR_ATTN_HD96  ? 8
+                               : fwd_kernel == LR_ATTN_HD256 ? 9
+                                                             : h->base->attn_variant;
   h->pass += 1;
   if (!accumulate) LR_CHECK_HIP(hipMemsetAsync(h->grads, 0, h->n_params * sizeof(float), st));
   float* const scal = det ? ws.det_loss : h->scratch;  // loss sum / per-row losses, rows without a token id

@@ -543,9 +543,10 @@ int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
   const int hd = r.hd;
   if (r.cap > 0.f) {   // the short table of llama_kernels.h
     if (r.want_lse) LR_FAIL(LR_EINVAL, "attention: no lse with a soft cap");
-    // variants 7 and 8 are a kernel at head_dim 96 only: elsewhere a capped request for them stays the unknown variant it was
-    // (LR_EINVAL)
-    if (r.variant == 2 || r.variant == 3 || r.variant == 5 || r.variant == 6 || ((r.variant == 7 || r.variant == 8) && hd == 96))
+    // variants 7 and 8 are a kernel at head_dim 96 only, variant 9 at head_dim 256 only: elsewhere a capped request for them
+    // stays the unknown variant it was (LR_EINVAL)
+    if (r.variant == 2 || r.variant == 3 || r.variant == 5 || r.variant == 6 || ((r.variant == 7 || r.variant == 8) && hd == 96) ||
+        (r.variant == 9 && hd == 256))
       LR_FAIL(LR_EUNSUPPORTED, "attention variant %d has no soft-capped form (0 / 4 at head_dim 256, 1 generic)", r.variant);
     if (r.variant != 0 && r.variant != 1 && r.variant != 4) LR_FAIL(LR_EINVAL, "attention: unknown variant %d", r.variant);
     if (r.variant != 1 && hd == 256 && r.cap <= LR_SOFTCAP_MFMA_MAX) {
@@ -559,7 +560,7 @@ int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
   switch (r.variant) {
     case 0:
       if (hd == 128) *kernel = (r.have_items_ws && !r.prefill) ? LR_ATTN_ROWS256 : LR_ATTN_MFMA128;
-      else if (hd == 256 && (r.prefill || r.prefix_len > 0)) *kernel = LR_ATTN_HD256;
+      else if (hd == 256 && (r.prefill || r.lora || r.prefix_len > 0)) *kernel = LR_ATTN_HD256;   // lora: with lse, the pair 9 / 9
       else if (hd == 96 && (r.prefill || r.lora || r.prefix_len > 0)) *kernel = LR_ATTN_HD96;   // lora: with lse, the pair 8 / 8
       else *kernel = (hd == 64 && (r.prefill || r.lora || r.prefix_len > 0)) ? LR_ATTN_HD64 : LR_ATTN_GENERIC;
       if (r.prefix_len > 0 && *kernel == LR_ATTN_GENERIC)
@@ -604,10 +605,15 @@ int lr_resolve_attention(const LrAttnRequest& r, LrAttnKernel* kernel) {
       if (r.want_lse && r.prefix_len > 0) LR_FAIL(LR_EINVAL, "attention variant 8 writes no lse with a shared prefix");
       *kernel = LR_ATTN_HD96;
       return LR_OK;
+    case 9:   // the training pair: variant 4's kernel, with lse when wanted; its backward is llama_attn_bwd_hd256.hip
+      if (hd != 256) LR_FAIL(LR_EUNSUPPORTED, "attention variant 9 needs head_dim 256 (got %d)", hd);
+      if (r.want_lse && r.prefix_len > 0) LR_FAIL(LR_EINVAL, "attention variant 9 writes no lse with a shared prefix");
+      *kernel = LR_ATTN_HD256;
+      return LR_OK;
   }
   LR_FAIL(LR_EINVAL, "attention: unknown variant %d (0 auto, 1 generic, 2 = head_dim-128 MFMA, 3 = 256-row tiles, "
           "4 = head_dim-256 MFMA, 5 = head_dim-64 MFMA, 6 = head_dim-64 MFMA for training, 7 = head_dim-96 MFMA, "
-          "8 = head_dim-96 MFMA for training)", r.variant);
+          "8 = head_dim-96 MFMA for training, 9 = head_dim-256 MFMA for training)", r.variant);
 }
 
 int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st) {
@@ -621,7 +627,9 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
   if (kernel == LR_ATTN_ROWS256) return lr_launch_attention256(a, st);
   if (nh % nkv != 0) LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
   if (kernel == LR_ATTN_HD256) {
-    if (prefix_len < 0 || a.lse) LR_FAIL(LR_EINVAL, "attention: the head_dim-256 MFMA kernel writes no lse (prefix %d)", prefix_len);
+    if (prefix_len < 0 || (a.lse && (prefix_len > 0 || a.cap > 0.f)))
+      LR_FAIL(LR_EINVAL, "attention: the head_dim-256 MFMA kernel writes no lse with a shared prefix or a soft cap (prefix %d)",
+              prefix_len);
     if (a.cap > 0.f) return lr_launch_attention_hd256_softcap(a, st);
     return prefix_len > 0 ? lr_launch_attention_hd256_prefix(a, st) : lr_launch_attention_hd256(a, st);
   }

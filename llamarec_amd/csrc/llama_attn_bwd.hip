@@ -20,6 +20,7 @@
 //                 operands of dV^T += dO^T P and dK^T += Q^T dS (Q^T, dO^T through transposed LDS reads).
 //  variant 6 (head_dim 64): the same two passes narrowed to 64 dimensions, llama_attn_bwd_hd64.hip.
 //  variant 8 (head_dim 96): the same two passes at 96 dimensions, llama_attn_bwd_hd96.hip.
+//  variant 9 (head_dim 256): the same two passes at 256 dimensions, llama_attn_bwd_hd256.hip.
 #include <stdlib.h>
 
 #include "llama_train.h"
@@ -556,6 +557,7 @@ int lr_launch_attention_bwd(const u16* qkv, const u16* out, const u16* d_out, co
   if (variant == 0 || variant == 3) variant = (hd == 128) ? 2 : 1;
   if (variant == 6 && hd != 64) LR_FAIL(LR_EUNSUPPORTED, "attention backward variant 6 needs head_dim 64 (got %d)", hd);
   if (variant == 8 && hd != 96) LR_FAIL(LR_EUNSUPPORTED, "attention backward variant 8 needs head_dim 96 (got %d)", hd);
+  if (variant == 9 && hd != 256) LR_FAIL(LR_EUNSUPPORTED, "attention backward variant 9 needs head_dim 256 (got %d)", hd);
   int rc = lr_launch_rowdot(out, d_out, n_tok, nh, hd, dsum, st);
   if (rc) return rc;
   double work = 0;  // 5 causal tile products of 2*T^2/2*hd flops each
@@ -612,9 +614,12 @@ int lr_launch_attention_bwd(const u16* qkv, const u16* out, const u16* d_out, co
   } else if (variant == 8) {   // as variant 6
     if (rope_cs && !tok_pos) LR_FAIL(LR_EINVAL, "attention backward: rotary table without token positions");
     return lr_launch_attention_bwd_hd96(qkv, d_out, lse, dsum, dqkv, cu, cu_host, B, n_tok, nh, nkv, hd, st, rope_cs);
+  } else if (variant == 9) {   // as variant 6
+    if (rope_cs && !tok_pos) LR_FAIL(LR_EINVAL, "attention backward: rotary table without token positions");
+    return lr_launch_attention_bwd_hd256(qkv, d_out, lse, dsum, dqkv, cu, cu_host, B, n_tok, nh, nkv, hd, st, rope_cs);
   } else {
     LR_FAIL(LR_EINVAL, "attention backward: unknown variant %d (0 auto, 1 generic, 2 = head_dim-128 MFMA, 3 as 0, "
-            "6 = head_dim-64 MFMA, 8 = head_dim-96 MFMA; 4, 5 and 7 have no backward)", variant);
+            "6 = head_dim-64 MFMA, 8 = head_dim-96 MFMA, 9 = head_dim-256 MFMA; 4, 5 and 7 have no backward)", variant);
   }
   return LR_OK;
 }

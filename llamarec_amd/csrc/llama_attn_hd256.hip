@@ -17,10 +17,11 @@
 // when a score exceeds it by more than 2^FA_DEFER), bf16 P into both the numerator and the row sum (an MFMA against a row
 // of ones), one bf16 rounding of O / l. A query row's bits depend only on its own prompt: tiles and key blocks are aligned
 // to positions inside the prompt, and the rescale decision is per row.
-// Forward only, no log-sum-exp output (the LoRA path keeps its own kernels). The kernel's one text is attn_hd256_body in
-// llama_attn_hd256_body.h, with its modes chosen at compile time. This file instantiates variant 4 (no shared prefix) and holds
-// its launcher; with a shared prefix, and for the pruned last layer's one-query-row mode, lr_launch_attention runs the
-// instantiations of llama_attn_hd256_prefix.hip (same bits).
+// The kernel's one text is attn_hd256_body in llama_attn_hd256_body.h, with its modes chosen at compile time. This file
+// instantiates variant 4 (no shared prefix, no log-sum-exp output) and holds its launcher; with a shared prefix, and for the
+// pruned last layer's one-query-row mode, lr_launch_attention runs the instantiations of llama_attn_hd256_prefix.hip (same
+// bits). llama_attn_hd256_lse.hip instantiates the training forward (attention variant 9), which also writes the natural-log
+// log-sum-exp per (token, head); the backward is llama_attn_bwd_hd256.hip.
 #include "llama_attn_hd256_body.h"
 
 // HPW = heads per workgroup (llama_attn_hd256_body.h): 1 is the product, selected by lr_launch_attention_hd256; 2 is an A/B arm
@@ -37,5 +38,9 @@ static int launch_hd256(const LrAttnArgs& a, hipStream_t st) {
       "attn_hd256_kernel", "attention variant 4 needs head_dim 256", nullptr, nullptr, nullptr, a, st);
 }
 
-// cu / cu_host: prompt starts [B + 1] in packed rows (no shared prefix at head_dim 256; a.lse is lr_launch_attention's to refuse)
-int lr_launch_attention_hd256(const LrAttnArgs& a, hipStream_t st) { return launch_hd256<1>(a, st); }
+// cu / cu_host: prompt starts [B + 1] in packed rows (no shared prefix). a.lse reaches this launcher only where the resolver
+// allowed it (variant 9, or the LoRA route's auto): lr_resolve_attention refuses variant 4 with lse.
+int lr_launch_attention_hd256(const LrAttnArgs& a, hipStream_t st) {
+  if (a.lse) return lr_launch_attention_hd256_lse(a, st);   // llama_attn_hd256_lse.hip
+  return launch_hd256<1>(a, st);
+}

@@ -1,6 +1,9 @@
 // llama_attn_hd256_body.h -- the one text of the head_dim-256 MFMA attention (llama_attn_hd256.hip: read its header first),
-// attn_hd256_body<HPW, LASTQ, PREFIX, SOFTCAP>, inlined into seven kernels in three translation units and one diagnostic build:
+// attn_hd256_body<HPW, LASTQ, PREFIX, SOFTCAP, LSE>, inlined into eight kernels in four translation units and one diagnostic
+// build:
 //   <1, false, false>  attn_hd256_kernel<1>, attention variant 4                                 (llama_attn_hd256.hip)
+//   <1, false, false, false, true>  attn_hd256_lse_kernel, variant 9's training forward: one lse store per row and head more
+//                                                                                                (llama_attn_hd256_lse.hip)
 //   <2, false, false>  attn_hd256_kernel<2>, two heads of one KV head per workgroup: an A/B arm  (tools/diag/attn_hd256_mqa_ab.hip)
 //   <1, false, true>   attn_hd256_prefix_kernel<false>, shared prompt prefix                     (llama_attn_hd256_prefix.hip)
 //   <1, true, true>    attn_hd256_prefix_kernel<true>, one query row per prompt                  (llama_attn_hd256_prefix.hip)
@@ -8,6 +11,7 @@
 // Here stand the constants, the LDS layout with its swizzles and staging offsets, the QK product and the mask. The prologue,
 // the staging of a block, the softmax steps and the store are lr_attn_body.h's, shared with head_dim 64 and 96; the PREFIX and
 // LASTQ modes are described there, HPW and SOFTCAP below. A row's bits are the same in every mode of one SOFTCAP setting.
+// The backward is llama_attn_bwd_hd256.hip, which has an LDS layout of its own (one swizzle for both kinds of read).
 #ifndef LLAMA_ATTN_HD256_BODY_H
 #define LLAMA_ATTN_HD256_BODY_H
 
@@ -25,7 +29,11 @@
 // K tile: chunk c of row r sits at position c ^ (r & 15) (conflict-free ds_read_b128 of 16 rows at one chunk).
 // V tile: the dual-use swizzle of variant 2, c ^ (((r & 3) << 2) | ((r >> 2) & 3)) (conflict-free transposed reads).
 // Both flip the low 4 bits of the chunk index only, so a chunk stays in its 256-byte half of the row; both depend on the row
-// inside the block and the chunk only (derived, not measured with the conflict counter).
+// inside the block and the chunk only. Derived, and since measured with the conflict counter ("Training at
+// head_dim 256"): SQ_LDS_BANK_CONFLICT is a third of SQ_LDS_IDX_ACTIVE in variant 4, which is the transposed V read being 2-way
+// (a 32-lane half takes rows 8 m .. 8 m + 7, and rows r and r + 4 share a 32-byte slot under fa4_vswz); the K read is
+// conflict-free. The backward's one swizzle ab9_swz (llama_attn_bwd_hd256.hip) measures 0 for both kinds of read; moving this
+// V tile to it would change variant 4's instruction stream and has not been done.
 __device__ __forceinline__ int fa4_vswz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
 // HPW = heads per workgroup. 1: the 8 waves are 128 query rows of one head. 2 (MQA / GQA, two heads of one KV head): waves
@@ -41,10 +49,13 @@ __device__ __forceinline__ int fa4_vswz(int row) { return ((row & 3) << 2) | ((r
 //   scale, so the capped rescale and P packing are fa_rescale and fa_pack_p without sl2, written out in the block loop: through
 //   the helpers (with a SOFTCAP parameter, or with a scale of 1) attn_hd256_softcap_kernel orders two register moves in the
 //   loop's preheader the other way round, and the whole-prompt kernels are held to the instruction stream they had.
-template <int HPW, bool LASTQ, bool PREFIX, bool SOFTCAP = false>
+// LSE (alone): lse[token][head] = natural-log log-sum-exp of the row's scaled scores; `lse` is read by no other mode.
+template <int HPW, bool LASTQ, bool PREFIX, bool SOFTCAP = false, bool LSE = false>
 __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const int32_t* cu, int prefix_len, int nh, int nkv,
                                                 int max_qblocks, int n_pairs, const u16* q_rows_last, float scale = 0.f,
-                                                float cap = 0.f) {
+                                                float cap = 0.f, float* lse = nullptr) {
+  static_assert(!LSE || (HPW == 1 && !PREFIX && !LASTQ && !SOFTCAP),
+                "the lse store exists for whole tiles of one head without a shared prefix and without a soft cap only");
   static_assert(!SOFTCAP || HPW == 1, "soft-capped scores: one head per workgroup");
   static_assert(HPW == 1 || (HPW == 2 && !PREFIX && !LASTQ), "two heads per workgroup: whole tiles without a shared prefix only");
   static_assert(!LASTQ || PREFIX, "the last-row mode reads a shared prefix");
@@ -232,6 +243,9 @@ __device__ __forceinline__ void attn_hd256_body(const u16* qkv, u16* out, const 
   // ---- normalise and store (fa_store_row)
   const float inv = 1.0f / l_acc[0];
   const bool live = fa_row_live<LASTQ, PREFIX>(sg, qabs, wave, li);
+  if constexpr (LSE) {   // the lane's row: m (log2 units) + log2 l, as natural log; quad 0 of the row's lanes writes it
+    if (live && quad == 0) lse[(size_t)(sg.tok0 + qabs) * nh + h] = (m_run + __builtin_amdgcn_logf(l_acc[0])) * 0.6931471805599453f;
+  }
   const int orow = fa_out_row<LASTQ, PREFIX>(sg, prompt, live, qabs);
   fa_store_row<16>(ot, inv, live, out + (size_t)orow * nh * FA4_HD + h * FA4_HD + (quad & 1) * 16 + (quad >> 1) * 8);
 }

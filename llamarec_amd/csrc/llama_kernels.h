@@ -202,12 +202,13 @@ static inline int lr_attn_check_grid(const LrAttnPlan& p) {
 
 // ---- varlen causal attention over packed qkv (RoPE applied) ----------------------------------------------------------------
 // The kernels (a requested variant 1 .. 5 asks for the kernel of the same number, 6 for HD64 with lse allowed, 7 for HD96,
-// 8 for HD96 with lse allowed, 0 = auto):
+// 8 for HD96 with lse allowed, 9 for HD256 with lse allowed, 0 = auto):
 //   GENERIC  any head_dim <= 256, scalar                                  (llama_attn.hip)
 //   MFMA128  head_dim 128, 128-row query tiles, reads a shared prefix     (llama_attn.hip)
 //   ROWS256  head_dim 128, 256-row query tiles over a device-built item list, shared prefix <= 64 (llama_attn256.hip)
-//   HD256    head_dim 256, no lse; one body (llama_attn_hd256_body.h) instantiated without a shared prefix in
-//            llama_attn_hd256.hip and with one in llama_attn_hd256_prefix.hip
+//   HD256    head_dim 256; one body (llama_attn_hd256_body.h) instantiated without a shared prefix in llama_attn_hd256.hip,
+//            with lse (variant 9, no prefix) in llama_attn_hd256_lse.hip, with a shared prefix in llama_attn_hd256_prefix.hip
+//            and with soft-capped scores in llama_attn_hd256_softcap.hip
 //   HD64     head_dim 64; one body (llama_attn_hd64_body.h) instantiated without a shared prefix in llama_attn_hd64.hip, with
 //            lse (variant 6, no prefix) in llama_attn_hd64_lse.hip and with a shared prefix in llama_attn_hd64_prefix.hip
 //   HD96     head_dim 96; one body (llama_attn_hd96_body.h) instantiated without a shared prefix in llama_attn_hd96.hip, with
@@ -225,7 +226,8 @@ enum LrAttnKernel {
 //   varlen_ws  lr_attention_varlen_ws: lse and workspace optional
 //   train      lr_attention_varlen_lse: lse wanted, no workspace
 //   lora       the LoRA forward (api_llama_train.hip): lse wanted, no workspace; its backward follows the same choice
-//              (variant 0 at head_dim 64 -> lr_launch_attention_bwd variant 6, at head_dim 96 -> variant 8)
+//              (variant 0 at head_dim 64 -> lr_launch_attention_bwd variant 6, at head_dim 96 -> variant 8, at head_dim 256
+//              -> variant 9)
 // prefix_len is 0 outside prefill and lr_attention_varlen_prefix (which resolves as a prefill request without item workspace).
 // Prefill drops a shared prefix (runs every prompt whole) unless lr_attention_reads_prefix: variant 1, a head_dim other than
 // 64 / 96 / 128 / 256, variant 2 / 3 off head_dim 128 and the like -- and with a single prompt. First matching row:
@@ -243,11 +245,12 @@ enum LrAttnKernel {
 //   0        64, 96, 256  > 0  yes  any      any          LR_EINVAL  (no lse with a shared prefix off head_dim 128)
 //   0        64        0       yes  no       lora         HD64     (with lse; the pair 6 / backward 6)
 //   0        96        0       yes  no       lora         HD96     (with lse; the pair 8 / backward 8)
+//   0        256       0       yes  no       lora         HD256    (with lse; the pair 9 / backward 9)
 //   0        other     > 0     any  any      any          LR_EUNSUPPORTED  (GENERIC reads no shared prefix)
 //   0        any       0       any  any      any          GENERIC  (head_dim 256, 96 and 64 too outside prefill and the LoRA
 //                                                                   route: the entry points' auto is older than HD256 / HD64 /
 //                                                                   HD96 and its results are kept, lr_attention_varlen_lse /
-//                                                                   _bwd at head_dim 64 and 96 included)
+//                                                                   _bwd at head_dim 64, 96 and 256 included)
 //   1        any       > 0     any  any      any          LR_EUNSUPPORTED
 //   1        any       0       any  any      any          GENERIC
 //   2        any       any     any  any      any          MFMA128
@@ -255,7 +258,7 @@ enum LrAttnKernel {
 //   3        != 128    any     any  yes      any          LR_EUNSUPPORTED
 //   3        128       <= 64   any  yes      any          ROWS256
 //   3        128       > 64    no   yes      prefill      MFMA128  (only a 256-row tile's block 0 may hold shared-prefix keys)
-//   4        any       any     yes  any      any          LR_EINVAL  (HD256 writes no statistics)
+//   4        any       any     yes  any      any          LR_EINVAL  (variant 4 writes no statistics: 9 does)
 //   4        != 256    any     no   yes      prefill      LR_EUNSUPPORTED
 //   4        256       > 0     no   any      any          HD256    (its shared-prefix kernel)
 //   4        any       0       no   any      any          HD256    (outside prefill a head_dim other than 256 is refused by
@@ -275,6 +278,10 @@ enum LrAttnKernel {
 //   8        96        > 0     yes  any      any          LR_EINVAL  (no lse with a shared prefix)
 //   8        96        any     any  any      any          HD96     (writes lse when wanted; without lse variant 7's bits, with
 //                                                                   a shared prefix too)
+//   9        != 256    any     any  any      any          LR_EUNSUPPORTED
+//   9        256       > 0     yes  any      any          LR_EINVAL  (no lse with a shared prefix)
+//   9        256       any     any  any      any          HD256    (writes lse when wanted; without lse variant 4's bits, with
+//                                                                   a shared prefix too)
 //   other                                                 LR_EINVAL
 //
 // With a soft cap (LrAttnRequest.softcap: Gemma-2, lr_attention_varlen_softcap) the table is a short one. No lse anywhere
@@ -284,6 +291,8 @@ enum LrAttnKernel {
 //   2, 3, 5, 6     any       any                     any     LR_EUNSUPPORTED  (those kernels have no capped form)
 //   7, 8           96        any                     any     LR_EUNSUPPORTED  (nor has HD96; off head_dim 96 a capped variant 7
 //                                                                     or 8 stays LR_EINVAL, the last row, as before HD96 existed)
+//   9              256       any                     any     LR_EUNSUPPORTED  (the training pair has no capped form; off head_dim
+//                                                                     256 a capped variant 9 stays LR_EINVAL, the last row)
 //   0, 4           256       <= LR_SOFTCAP_MFMA_MAX  any     HD256    (the SOFTCAP instantiations of llama_attn_hd256_softcap.hip,
 //                                                                     on every route)
 //   0, 1, 4        any       any                     > 0     LR_EUNSUPPORTED  (GENERIC reads no shared prefix. The prefill never
@@ -302,14 +311,15 @@ enum LrAttnKernel {
 // varlen_ws counts a variant-3 request as "item ws yes" whatever it was given: the item-list builder then reports a missing
 // or short workspace as LR_EWORKSPACE. lr_launch_attention still refuses what the resolved kernel cannot take: GENERIC above
 // head_dim 256 and MFMA128 off head_dim 128 (LR_EUNSUPPORTED; a one-layer pruned prefill launches neither, so these checks
-// cannot move up here), lse on HD256, lse with a shared prefix on HD64 and HD96, a segment 0 that is not the prefix.
+// cannot move up here), lse with a shared prefix on HD64, HD96 and HD256, lse with a soft cap, a segment 0 that is not the
+// prefix.
 // cap > 0 (soft-capped scores): only HD256's capped instantiations read a shared prefix (the short table above)
 static inline bool lr_attention_reads_prefix(int variant, int hd, float cap = 0.f) {
   if (cap > 0.f) return hd == 256 && (variant == 0 || variant == 4) && cap <= LR_SOFTCAP_MFMA_MAX;
   if (hd == 128) return variant != 1;
   if (hd == 64) return variant == 0 || variant == 5 || variant == 6;
   if (hd == 96) return variant == 0 || variant == 7 || variant == 8;
-  if (hd == 256) return variant == 0 || variant == 4;
+  if (hd == 256) return variant == 0 || variant == 4 || variant == 9;
   return false;
 }
 // The resolved kernel has a one-query-row (LASTQ) mode behind lr_launch_attention_last
@@ -351,6 +361,7 @@ int lr_launch_attn256_items(const int32_t* cu, int S, int n_tok, int nh, int pre
 // the per-file launchers behind lr_launch_attention
 int lr_launch_attention256(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd256(const LrAttnArgs& a, hipStream_t st);
+int lr_launch_attention_hd256_lse(const LrAttnArgs& a, hipStream_t st);   // a.lse != nullptr: lr_launch_attention_hd256 sends it here
 int lr_launch_attention_hd64(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd64_lse(const LrAttnArgs& a, hipStream_t st);   // a.lse != nullptr: lr_launch_attention_hd64 sends it here
 // HD64 / HD256 with a.prefix_len > 0 (llama_attn_hd64_prefix.hip, llama_attn_hd256_prefix.hip) and their last-row modes

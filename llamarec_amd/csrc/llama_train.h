@@ -60,10 +60,11 @@ uint32_t lr_lora_drop_stream(uint64_t seed, uint32_t pass, uint32_t layer);
 // given, w.r.t. the UNROTATED ones (the inverse rotation is pair-local in the packed layout and rides in the MFMA
 // passes' epilogues). dsum: [n][nh] fp32 scratch, dkv32: [n][2*nkv*hd] fp32 scratch (generic path only).
 // deterministic: the generic path computes dK / dV per owner instead of adding them atomically (dkv32 unused); the head_dim-128
-// passes have no atomics either way, nor have variant 6's head_dim-64 and variant 8's head_dim-96 passes.
+// passes have no atomics either way, nor have variant 6's head_dim-64, variant 8's head_dim-96 and variant 9's head_dim-256
+// passes.
 // variant: 0 / 3 = auto (2 at head_dim 128, else 1), 1 generic, 2 = head_dim-128 MFMA passes, 6 = head_dim-64 MFMA passes
-// (LR_EUNSUPPORTED off head_dim 64), 8 = head_dim-96 MFMA passes (LR_EUNSUPPORTED off head_dim 96); 4, 5 and 7 are
-// forward-only kernels: LR_EINVAL.
+// (LR_EUNSUPPORTED off head_dim 64), 8 = head_dim-96 MFMA passes (LR_EUNSUPPORTED off head_dim 96), 9 = head_dim-256 MFMA
+// passes (LR_EUNSUPPORTED off head_dim 256); 4, 5 and 7 are forward-only kernels: LR_EINVAL.
 int lr_launch_attention_bwd(const unsigned short* qkv, const unsigned short* out, const unsigned short* d_out,
                             const float* lse, unsigned short* dqkv, float* dsum, float* dkv32, const int32_t* cu,
                             const int32_t* cu_host, int B, int n_tok, int nh, int nkv, int hd, int variant,
@@ -78,5 +79,9 @@ int lr_launch_attention_bwd_hd64(const unsigned short* qkv, const unsigned short
 int lr_launch_attention_bwd_hd96(const unsigned short* qkv, const unsigned short* d_out, const float* lse, const float* dsum,
                                  unsigned short* dqkv, const int32_t* cu, const int32_t* cu_host, int B, int n_tok, int nh,
                                  int nkv, int hd, hipStream_t st, const float* rope_cs);
+// variant 9's two passes (llama_attn_bwd_hd256.hip): the same at head_dim 256
+int lr_launch_attention_bwd_hd256(const unsigned short* qkv, const unsigned short* d_out, const float* lse, const float* dsum,
+                                  unsigned short* dqkv, const int32_t* cu, const int32_t* cu_host, int B, int n_tok, int nh,
+                                  int nkv, int hd, hipStream_t st, const float* rope_cs);
 
 #endif

@@ -153,7 +153,8 @@ struct lr_llama {
   LrLlamaLayerWeights* layers;  // host array
   int device;
   int gemm_variant;  // 0 auto, 1 generic, 4 256x256x64 MFMA tile, 5 = 4 + split-K (latency mode), 6 = auto + ragged column tile
-  int attn_variant;  // 0 auto, 1 generic, 2 MFMA head_dim 128, 3 256-row tiles, 4 MFMA head_dim 256, 5 MFMA head_dim 64
+  int attn_variant;  // 0 auto, 1 generic, 2 MFMA head_dim 128, 3 256-row tiles, 4 MFMA head_dim 256, 5 MFMA head_dim 64,
+                     // 6 = 5 with lse and a backward, 7 MFMA head_dim 96, 8 = 7 with lse and a backward, 9 = 4 with lse and a backward
   int prune_last;    // last layer: attention output / o_proj / MLP only for each prompt's last token
   // folded RMSNorm (lr_llama_set_folded_norms): per layer wqkv * diag(input_norm) and wgu * diag(post_norm), or null
   const uint16_t** wqkv_folded;

@@ -665,7 +665,8 @@ class LlamaRanker:
         4 head_dim 256, 5 head_dim 64 (scoring only: no lse), 7 head_dim 96 (scoring only: no lse), 6 = head_dim-64 MFMA attention for training (5's forward, writing
         lse when a LoRA engine runs on this base, and the head_dim-64 MFMA backward; the LoRA step's auto at head_dim 64),
         8 = the same pair at head_dim 96 (7's forward writing lse, the head_dim-96 MFMA backward; the LoRA step's auto at
-        head_dim 96)."""
+        head_dim 96), 9 = the same pair at head_dim 256 (4's forward writing lse, the head_dim-256 MFMA backward; the LoRA
+        step's auto at head_dim 256; no soft-capped form)."""
         check(lib().lr_llama_set_variants(self._h, gemm, attention), "lr_llama_set_variants")
         return self
 

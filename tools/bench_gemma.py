@@ -12,7 +12,19 @@
      generic kernel with the cap on the same rows, arms alternating, median and min .. max of --reps (the generic arm: a
      quarter of them); the sandwich-norm kernel's GB/s at the step's row count; a random-weight Gemma-2-2B step (26 layers) on
      the Beauty token budget with its kernel split (the element-wise kernel from its own profile records).
-Usage: python tools/bench_gemma.py [--reps 20] [--steps 5] [--layers 18] [--prefix-ab] [--gemma2] [--ab-lib parent=path/to/lib.so]"""
+  5. --train (instead of 1 and 2): the training side at head_dim 256, attention variant 9.
+     a. over 16 prompts of 5, 64, 129, 600 and 1 125 tokens, one process, HIP events, the arms of a shape ALTERNATING inside
+        every repeat, median and min .. max of --reps: the backward of variant 9 at (8, 1) x 256 and (16, 16) x 256 against the
+        generic backward on the same buffers (what this route ran before variant 9; every fourth repeat, being slow), and at
+        equal width nh hd = 2048 variant 9 at (8, 8) x 256 against variant 2 at (16, 16) x 128; the forward of variant 4 against
+        variant 9 writing lse and the generic kernel writing lse. Each backward reads the out / lse of its own forward. TF/s of
+        the backward as lr_launch_attention_bwd counts it (10 nh hd T (T + 1) / 2 per prompt), lr_launch_rowdot included.
+     b. a random-weight Llama-format model of Gemma-2B's shape (hidden 2048, 8 x 256 heads on 1 KV head, intermediate 16384,
+        --layers 18): LoRA fwd+bwd (q_proj / v_proj, r = 8) over 16 prompts of 460 .. 1 125 tokens with attention variant 1 and
+        auto (variant 9) alternating on one engine, then one profiled pass per arm for the attention / GEMM split
+        (tools/bench_llama32.py's lora_step).
+Usage: python tools/bench_gemma.py [--reps 20] [--steps 5] [--layers 18] [--prefix-ab] [--gemma2] [--train] [--no-step]
+       [--ab-lib parent=path/to/lib.so]"""
 from __future__ import annotations
 
 import argparse
@@ -226,6 +238,103 @@ def gemma2b_step(steps, layers, base=None, name="gemma-2b"):
                 attention_share=attn / step_ms)
 
 
+TRAIN_LENGTHS = (5, 64, 129, 600, 1125)
+TRAIN_PROMPTS = 16
+# group -> arm -> (nh, nkv, hd, variant, take every n-th repeat, what it times); the arms of a group share one qkv / d_out
+TRAIN_GROUPS = {
+    "(8, 1) x 256": {"bwd_v9": (8, 1, 256, 9, 1, "bwd"), "bwd_generic": (8, 1, 256, 1, 4, "bwd"),
+                     "fwd_v4": (8, 1, 256, 4, 1, "fwd"), "fwd_lse_v9": (8, 1, 256, 9, 1, "fwd_lse"),
+                     "fwd_lse_generic": (8, 1, 256, 1, 4, "fwd_lse")},
+    "(16, 16) x 256": {"bwd_v9": (16, 16, 256, 9, 1, "bwd"), "bwd_generic": (16, 16, 256, 1, 4, "bwd"),
+                       "fwd_v4": (16, 16, 256, 4, 1, "fwd"), "fwd_lse_v9": (16, 16, 256, 9, 1, "fwd_lse"),
+                       "fwd_lse_generic": (16, 16, 256, 1, 4, "fwd_lse")},
+    "width 2048": {"bwd_v9_hd256": (8, 8, 256, 9, 1, "bwd"), "bwd_v2_hd128": (16, 16, 128, 2, 1, "bwd"),
+                   "fwd_lse_v9_hd256": (8, 8, 256, 9, 1, "fwd_lse"), "fwd_lse_v2_hd128": (16, 16, 128, 2, 1, "fwd_lse")},
+}
+# Llama-format: what train_ranker.py --llm_base_model loads; Gemma-2B's shape with Llama's arithmetic
+GEMMA2B_SHAPE_LLAMA = dict(model_type="llama", vocab_size=32000, hidden_size=2048, intermediate_size=16384, num_hidden_layers=18,
+                           num_attention_heads=8, num_key_value_heads=1, head_dim=256, max_position_embeddings=4096,
+                           rms_norm_eps=1e-6, rope_theta=10000.0, tie_word_embeddings=False)
+
+
+def attention_train_table(reps):
+    L = lib()
+    rows = []
+    B = TRAIN_PROMPTS
+
+    def call(name, rc):
+        if rc:
+            raise RuntimeError(f"{name}: {rc} {L.lr_last_error()}")
+
+    for group, arms in TRAIN_GROUPS.items():
+        for T in TRAIN_LENGTHS:
+            n = B * T
+            cu = np.arange(0, n + 1, T, dtype=np.int32)
+            cud = torch.from_numpy(cu).cuda()
+            g = torch.Generator(device="cuda").manual_seed(T)
+            qw = max((nh + 2 * nkv) * hd for nh, nkv, hd, *_ in arms.values())
+            ow = max(nh * hd for nh, nkv, hd, *_ in arms.values())
+            assert all((nh + 2 * nkv) * hd == qw and nh * hd == ow for nh, nkv, hd, *_ in arms.values())
+            qkv = torch.randn(n, qw, generator=g, device="cuda").to(torch.bfloat16)
+            d_out = torch.randn(n, ow, generator=g, device="cuda").to(torch.bfloat16)
+            runs, grads = {}, {}
+            for name, (nh, nkv, hd, v, _, what) in arms.items():
+                out = torch.empty(n, ow, dtype=torch.bfloat16, device="cuda")
+                lse = torch.empty(n, nh, dtype=torch.float32, device="cuda")
+                head = (cud.data_ptr(), cu.ctypes.data, B, nh, nkv, hd, v)
+
+                def fwd_lse(out=out, lse=lse, head=head):
+                    call("lr_attention_varlen_lse", L.lr_attention_varlen_lse(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), *head,
+                                                                              stream_ptr()))
+
+                if what == "fwd":
+                    runs[name] = lambda out=out, head=head: call("lr_attention_varlen", L.lr_attention_varlen(
+                        qkv.data_ptr(), out.data_ptr(), *head, stream_ptr()))
+                elif what == "fwd_lse":
+                    runs[name] = fwd_lse
+                else:
+                    fwd_lse()                                   # the backward reads the out / lse of ITS forward
+                    dqkv = torch.empty(n, qw, dtype=torch.bfloat16, device="cuda")
+                    sb = L.lr_attention_bwd_scratch_bytes(n, nh, nkv, hd)
+                    scratch = torch.empty(sb, dtype=torch.uint8, device="cuda")
+                    grads[name] = dqkv
+                    runs[name] = lambda out=out, lse=lse, head=head, dqkv=dqkv, scratch=scratch, sb=sb: call(
+                        "lr_attention_varlen_bwd", L.lr_attention_varlen_bwd(qkv.data_ptr(), out.data_ptr(), d_out.data_ptr(),
+                                                                             lse.data_ptr(), dqkv.data_ptr(), *head,
+                                                                             scratch.data_ptr(), sb, stream_ptr()))
+            for name, r in runs.items():
+                for _ in range(1 if "generic" in name else 3):
+                    r()
+            torch.cuda.synchronize()
+            times = {k: [] for k in runs}
+            for i in range(reps):
+                for name, r in runs.items():
+                    if i % arms[name][4] == 0:
+                        times[name].append(_event_ms(r))
+            pairs = float(ow) * B * T * (T + 1) / 2
+            row = dict(group=group, T=T, B=B)
+            print(f"attention training {group}, {B} x {T:4d}:", flush=True)
+            for name, t in times.items():
+                work = (10.0 if arms[name][5] == "bwd" else 4.0) * pairs
+                med = float(np.median(t))
+                row[name] = dict(ms_median=med, ms_min=min(t), ms_max=max(t), reps=len(t), tflops=work / med / 1e9)
+                print(f"  {name:20s} {med:9.3f} ms ({min(t):.3f} .. {max(t):.3f}, n={len(t)}) {work / med / 1e9:8.2f} TF/s", flush=True)
+            if "bwd_generic" in row:
+                g9, g1 = grads["bwd_v9"].float(), grads["bwd_generic"].float()
+                row["bwd_v9_over_generic"] = row["bwd_generic"]["ms_median"] / row["bwd_v9"]["ms_median"]
+                row["bwd_ranges_disjoint"] = row["bwd_v9"]["ms_max"] < row["bwd_generic"]["ms_min"]
+                row["fwd_lse_inside_v4_range"] = row["fwd_v4"]["ms_min"] <= row["fwd_lse_v9"]["ms_median"] <= row["fwd_v4"]["ms_max"]
+                row["max_rel_v9_minus_generic"] = float((g9 - g1).abs().max() / g1.abs().max())
+                print(f"  v9 / generic backward {row['bwd_v9_over_generic']:.1f}x (ranges disjoint: {row['bwd_ranges_disjoint']}), "
+                      f"fwd+lse median inside variant 4's min .. max: {row['fwd_lse_inside_v4_range']}, "
+                      f"max |v9 - generic| / max {row['max_rel_v9_minus_generic']:.4f}", flush=True)
+            else:
+                row["bwd_v9_over_v2_tflops"] = row["bwd_v9_hd256"]["tflops"] / row["bwd_v2_hd128"]["tflops"]
+                print(f"  v9 hd256 / v2 hd128 backward TF/s {row['bwd_v9_over_v2_tflops']:.2f}", flush=True)
+            rows.append(row)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -233,10 +342,25 @@ def main():
     ap.add_argument("--layers", type=int, default=18)
     ap.add_argument("--prefix-ab", action="store_true", help="the shared-prefix / last-row arms instead (tools/prefix_ab.py)")
     ap.add_argument("--gemma2", action="store_true", help="the Gemma-2 tables instead: capped attention, sandwich norm, 2B step")
+    ap.add_argument("--train", action="store_true", help="the training side instead: variant 9's backward rows and the LoRA step")
+    ap.add_argument("--no-step", action="store_true", help="--train: skip the LoRA step")
     ap.add_argument("--ab-lib", action="append", default=[], metavar="NAME=PATH")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     _lib.lib()
+    if args.train:
+        from tools import bench_llama32
+
+        p = torch.cuda.get_device_properties(0)
+        res = dict(box=dict(device=p.name, compute_units=p.multi_processor_count,
+                            method=f"HIP events, one process, arms alternating, median of {args.reps}"))
+        print(f"box: {p.name}, {p.multi_processor_count} CUs; {res['box']['method']}", flush=True)
+        res["attention_train"] = attention_train_table(args.reps)
+        if not args.no_step:
+            res["gemma2b_shape_lora_step"] = bench_llama32.lora_step(dict(GEMMA2B_SHAPE_LLAMA, num_hidden_layers=args.layers),
+                                                                     "llama-format model of gemma-2b's shape", (1, 0), args.steps)
+        print(json.dumps(res))
+        return
     if args.gemma2:
         from llamarec_amd.llm import GEMMA2_2B
         from llamarec_amd.packing import TOKEN_BUDGET

@@ -23,8 +23,8 @@ import sys
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
-TRAIN_LLAMA_ONLY = ("LoRA fine-tuning needs a Llama-family base (the training step has no GeGLU, Gemma-norm or head_dim-256 "
-                    "attention backward, and for Phi-3 no adapter on the fused qkv_proj): "
+TRAIN_LLAMA_ONLY = ("LoRA fine-tuning needs a Llama-family base (the training step has no GeGLU or Gemma-norm "
+                    "backward, and for Phi-3 no adapter on the fused qkv_proj): "
                     "score a Gemma ranker with --eval_only [--llm_adapter_path <peft dir>], a Phi-3 ranker with --eval_only; "
                     "for Qwen2 the live-adapter forward has no q/k/v bias: score it with --eval_only [--llm_adapter_path <peft dir>]")
 
