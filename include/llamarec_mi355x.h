@@ -332,6 +332,20 @@ int lr_llama_set_gemma2(lr_llama_t* h, const LrGemma2Ext* ext);
  * live-adapter forward rotates in a kernel that knows no bias). */
 int lr_llama_set_qkv_bias(lr_llama_t* h, const uint16_t* const* bqkv);
 
+/* Qwen3 (model_type "qwen3"): Llama's layer with an RMSNorm over head_dim on every q head and every k head, between the
+ * projection and the rotation (HF's Qwen3RMSNorm: bf16(w * bf16(x * rsqrt(mean(x^2) + rms_eps))), fp32 statistics). q_norm /
+ * k_norm: HOST arrays [num_layers] of DEVICE bf16 [head_dim], 16-byte aligned, permuted like a head's rows of wq / wk
+ * (entry 2i = HF's weight i, 2i + 1 = HF's weight i + head_dim / 2); the caller keeps the arrays alive. With norms set every
+ * product of the prefill that reads wqkv -- the whole-prompt QKV product, the pruned last layer's K/V and Q products, the
+ * shared-prefix path, latency mode -- stores plainly, and one sweep (lr_qk_norm_rope_bf16's kernel) norms and rotates its q / k
+ * columns in place; the LoRA step (lr_llama_lora_create[_ex] accepts such a handle) norms in its own forward sweep and
+ * differentiates through the norm (lr_qk_norm_bwd_bf16's kernel; the norm weights are frozen).
+ * NULL, NULL: back to Llama's layer. LR_EINVAL, handle unchanged: one array without the other, a null or misaligned entry.
+ * LR_EUNSUPPORTED: a handle with folded norms, a Gemma-2 extension or q/k/v biases (lr_llama_set_folded_norms (non-NULL),
+ * lr_llama_set_gemma2 (non-NULL) and lr_llama_set_qkv_bias (non-NULL) refuse a handle with q/k norms likewise), or a head_dim
+ * that is not a power of two from 16 to 256. */
+int lr_llama_set_qk_norm(lr_llama_t* h, const uint16_t* const* q_norm, const uint16_t* const* k_norm);
+
 /* Folded RMSNorm (optional, scoring path only). HF's layer computes  proj(norm_w * bf16(x * rstd))  with its own
  * read-and-write pass over the residual stream in front of q/k/v_proj and of gate/up_proj (LlamaRMSNorm, reached from
  * model/llm.py:89-100). Here the norm weight can be multiplied into the projection matrices once at load
@@ -530,6 +544,16 @@ int lr_residual_postnorm_bf16(uint16_t* x, const uint16_t* h, const uint16_t* w_
  * without w_next followed by lr_rmsnorm_bf16(x, w_next, xn, ..., 1) writes. */
 int lr_rmsnorm_bf16(const uint16_t* x, const uint16_t* w, uint16_t* out, int32_t rows, int32_t d, float eps, int32_t norm_style,
                     void* hip_stream);
+/* Qwen3's q/k norm + rotation sweep alone (exposed for parity tests and timing), in place on buf [rows][ld] bf16 DEVICE rows:
+ * columns [col0, col0 + (nq + nk) head_dim) hold nq + nk heads in the packed pair-interleaved order the rope epilogue writes;
+ * per (row, head) y = bf16(w * bf16(x * rsqrt(mean(x^2) + eps))) with w = q_norm for the first nq heads and k_norm for the
+ * rest (bf16 [head_dim] in the packed order, 16-byte aligned; either group may be empty and its pointer NULL), then the
+ * rotation of y by (cos, sin)[tok_pos[row]] of lr_rope_table's fp32 table, rounded once. Columns outside the range are neither
+ * read nor written. head_dim: a power of two from 16 to 256, else LR_EUNSUPPORTED and nothing is launched; col0 and ld
+ * multiples of 8. */
+int lr_qk_norm_rope_bf16(uint16_t* buf, int32_t rows, int32_t ld, int32_t col0, int32_t nq, int32_t nk, int32_t head_dim,
+                         const uint16_t* q_norm, const uint16_t* k_norm, float eps, const int32_t* tok_pos, const float* rope_cs,
+                         void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optional in-library kernel timing (HIP events on the caller's stream). Not part of the
@@ -661,6 +685,16 @@ typedef struct lr_llama_lora lr_llama_lora_t;
 
 /* dst[c][r] = src[r][c], bf16, DEVICE pointers. */
 int lr_transpose_bf16(const uint16_t* src, int32_t rows, int32_t cols, uint16_t* dst, void* hip_stream);
+
+/* Backward of Qwen3's q/k norm alone (exposed for parity tests), in place on dqk [rows][ld] bf16 DEVICE rows: columns
+ * [col0, col0 + (nq + nk) head_dim) hold d loss / d y of the normed, unrotated heads (lr_attention_varlen_bwd_ex's output with a
+ * rotary table) and receive d loss / d x. x [rows][ldx]: the pre-norm values of the same heads from column 0 on. Per (row,
+ * head), with g = w .* dy and xh = x * rstd: dx = rstd * (g - xh * mean(xh .* g)), fp32 with one rounding; the norm weights are
+ * frozen (no weight gradient). One owner per element and no atomics: two runs write the same bits. Arguments as for
+ * lr_qk_norm_rope_bf16. */
+int lr_qk_norm_bwd_bf16(uint16_t* dqk, int32_t rows, int32_t ld, int32_t col0, const uint16_t* x, int32_t ldx, int32_t nq,
+                        int32_t nk, int32_t head_dim, const uint16_t* q_norm, const uint16_t* k_norm, float eps,
+                        void* hip_stream);
 
 /* DEVICE bytes for the adapters: fp32 parameters, gradients, Adam moments, bf16 working copies. */
 size_t lr_llama_lora_state_bytes(const lr_llama_t* base, const LrLoraTrainConfig* cfg);

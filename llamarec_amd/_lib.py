@@ -83,6 +83,11 @@ PROTOTYPES = {
     "lr_llama_set_rope_scaling": (C.c_int, [C.c_void_p, C.POINTER(A.LrRopeScaling)]),
     "lr_llama_set_gemma2": (C.c_int, [C.c_void_p, C.POINTER(A.LrGemma2Ext)]),
     "lr_llama_set_qkv_bias": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lr_llama_set_qk_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lr_qk_norm_rope_bf16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lr_qk_norm_bwd_bf16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "lr_fold_norm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "lr_llama_set_folded_norms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lr_llama_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -14,9 +14,9 @@ EXPERIMENT_ROOT = "experiments"   # config.py:5-9
 STATE_DICT_KEY = "model_state_dict"
 RAW_DATASET_ROOT_FOLDER = "data"
 # --llm -> base model / tokenizer of the reference's set_template (config.py:29-55). The ranker's kernels serve the llama
-# (llama2, llama3, mistral), gemma, gemma2, phi3 and qwen2 families (llm.model_family; phi3 and qwen2 for scoring only, plain
-# RoPE).
-LLM_CHOICES = ["llama2", "llama3", "phi3", "gemma", "mistral", "gemma2", "qwen2"]
+# (llama2, llama3, mistral), gemma, gemma2, phi3, qwen2 and qwen3 families (llm.model_family; phi3 and qwen2 for scoring only,
+# plain RoPE; qwen3 -- not a choice of the reference's -- scores and trains, with Llama-2's batch sizes).
+LLM_CHOICES = ["llama2", "llama3", "phi3", "gemma", "mistral", "gemma2", "qwen2", "qwen3"]
 LLM_BASE_MODELS = {
     "phi3": "microsoft/Phi-3-mini-4k-instruct",
     "llama2": "meta-llama/Llama-2-7b-hf",
@@ -25,6 +25,7 @@ LLM_BASE_MODELS = {
     "mistral": "mistralai/Mistral-7B-v0.3",
     "gemma2": "google/gemma-2-9b",
     "qwen2": "Qwen/Qwen2-0.5B",
+    "qwen3": "Qwen/Qwen3-0.6B",
 }
 DEFAULT_LLM_BASE = "meta-llama/Llama-2-7b-hf"
 

@@ -101,6 +101,7 @@ extern "C" int lr_llama_set_gemma2(lr_llama_t* h, const LrGemma2Ext* e) {
       LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_gemma2: attn_scale %g without a soft cap (the uncapped kernels scale by "
               "head_dim^-0.5 = %g)", (double)scale, (double)own);
     if (h->wqkv_folded) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_gemma2: the handle has folded norms");
+    if (h->q_norm) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_gemma2: the handle has q/k norms (lr_llama_set_qk_norm)");
     if (e->attn_out_norm) {
       an = (const uint16_t**)malloc(sizeof(void*) * L);
       mn = (const uint16_t**)malloc(sizeof(void*) * L);
@@ -135,12 +136,46 @@ extern "C" int lr_llama_set_qkv_bias(lr_llama_t* h, const uint16_t* const* bqkv)
       if ((reinterpret_cast<uintptr_t>(bqkv[l]) & 7) || (h->cfg.num_heads * h->cfg.head_dim) % 4 != 0)
         LR_FAIL(LR_EINVAL, "lr_llama_set_qkv_bias: layer %d's bias is not 8-byte aligned", l);
     if (h->wqkv_folded) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_qkv_bias: the handle has folded norms");
+    if (h->q_norm) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_qkv_bias: the handle has q/k norms (lr_llama_set_qk_norm)");
     own = (const uint16_t**)malloc(sizeof(void*) * L);
     if (!own) LR_FAIL(LR_EINVAL, "lr_llama_set_qkv_bias: out of host memory");
     memcpy(own, bqkv, sizeof(void*) * L);
   }
   free(h->bqkv);
   h->bqkv = own;
+  return LR_OK;
+}
+
+extern "C" int lr_llama_set_qk_norm(lr_llama_t* h, const uint16_t* const* q_norm, const uint16_t* const* k_norm) {
+  if (!h) LR_FAIL(LR_EINVAL, "lr_llama_set_qk_norm: null handle");
+  const int L = h->cfg.num_layers;
+  const uint16_t **qn = nullptr, **kn = nullptr;
+  if ((q_norm == nullptr) != (k_norm == nullptr)) LR_FAIL(LR_EINVAL, "lr_llama_set_qk_norm: give both arrays or neither");
+  if (q_norm) {   // every check before the handle changes
+    for (int l = 0; l < L; ++l)
+      if (!q_norm[l] || !k_norm[l]) LR_FAIL(LR_EINVAL, "lr_llama_set_qk_norm: layer %d has a null norm weight", l);
+    for (int l = 0; l < L; ++l)   // the sweeps load the weights 16 bytes at a time
+      if ((reinterpret_cast<uintptr_t>(q_norm[l]) | reinterpret_cast<uintptr_t>(k_norm[l])) & 15)
+        LR_FAIL(LR_EINVAL, "lr_llama_set_qk_norm: layer %d's norm weights are not 16-byte aligned", l);
+    if (h->wqkv_folded) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_qk_norm: the handle has folded norms");
+    if (h->gemma2) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_qk_norm: the handle has a Gemma-2 extension (lr_llama_set_gemma2)");
+    if (h->bqkv) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_qk_norm: the handle has q/k/v biases (lr_llama_set_qkv_bias)");
+    if (!lr_qk_norm_head_dim_ok(h->cfg.head_dim))
+      LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_qk_norm: head_dim %d (a power of two from 16 to 256)", h->cfg.head_dim);
+    qn = (const uint16_t**)malloc(sizeof(void*) * L);
+    kn = (const uint16_t**)malloc(sizeof(void*) * L);
+    if (!qn || !kn) {
+      free(qn);
+      free(kn);
+      LR_FAIL(LR_EINVAL, "lr_llama_set_qk_norm: out of host memory");
+    }
+    memcpy(qn, q_norm, sizeof(void*) * L);
+    memcpy(kn, k_norm, sizeof(void*) * L);
+  }
+  free(h->q_norm);
+  free(h->k_norm);
+  h->q_norm = qn;
+  h->k_norm = kn;
   return LR_OK;
 }
 
@@ -158,6 +193,8 @@ extern "C" void lr_llama_destroy(lr_llama_t* h) {
   free(h->attn_out_norm);
   free(h->mlp_out_norm);
   free(h->bqkv);
+  free(h->q_norm);
+  free(h->k_norm);
   free(h);
 }
 
@@ -177,6 +214,8 @@ extern "C" int lr_llama_set_folded_norms(lr_llama_t* h, const uint16_t* const* w
     LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: not with a Gemma-2 extension (lr_llama_set_gemma2)");
   if (h->bqkv && (wqkv_folded || wgu_folded))
     LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: not with q/k/v biases (lr_llama_set_qkv_bias)");
+  if (h->q_norm && (wqkv_folded || wgu_folded))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: not with q/k norms (lr_llama_set_qk_norm)");
   free(h->wqkv_folded);
   free(h->wgu_folded);
   h->wqkv_folded = h->wgu_folded = nullptr;
@@ -357,19 +396,28 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
     if (!folded && !input_normed) LR_RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st, ns));
     const int q_w = nh * hd, kv_w = 2 * nkv * hd;
     const u16* const bias = h->bqkv ? h->bqkv[l] : nullptr;   // Qwen2: [q_w + kv_w] in wqkv's row order (never folded)
+    // Qwen3 (lr_llama_set_qk_norm; never folded, never with a bias): each QKV product stores plainly -- in latency mode the
+    // split-K reduce does -- and one sweep per product norms every q / k head and rotates it (lr_launch_qk_norm_rope)
+    const u16 *const qn = h->q_norm ? h->q_norm[l] : nullptr, *const kn = h->k_norm ? h->k_norm[l] : nullptr;
+    const int epi_qkv = qn ? LR_EPI_STORE : LR_EPI_ROPE;
     if (last_q_only) {
       LR_RUN(lr_launch_gemm({.A = ws.xn, .B = w.wqkv + (size_t)q_w * d, .C = ws.qkv, .M = n, .N = kv_w, .K = d,
-                             .epi = LR_EPI_ROPE, .variant = gv, .rope = rope(ws.tok_pos, kv_w / 2), .bias = bias ? bias + q_w : nullptr,
-                             .splitk = ws.splitk}, st));
+                             .epi = epi_qkv, .variant = gv, .rope = qn ? LrGemmRope{} : rope(ws.tok_pos, kv_w / 2),
+                             .bias = bias ? bias + q_w : nullptr, .splitk = ws.splitk}, st));
+      if (qn) LR_RUN(lr_launch_qk_norm_rope(ws.qkv, n, kv_w, 0, nkv, hd, nullptr, kn, c.rms_eps, ws.tok_pos, ws.rope, st));
       LR_RUN(lr_launch_gather_rows(ws.xn, ws.last_rows, B, d, ws.xn_last, st));
-      LR_RUN(lr_launch_gemm({.A = ws.xn_last, .B = w.wqkv, .C = ws.q_last, .M = B, .N = q_w, .K = d, .epi = LR_EPI_ROPE,
-                             .variant = pv, .rope = rope(ws.last_pos, q_w), .bias = bias, .splitk = ws.splitk}, st));
+      LR_RUN(lr_launch_gemm({.A = ws.xn_last, .B = w.wqkv, .C = ws.q_last, .M = B, .N = q_w, .K = d, .epi = epi_qkv,
+                             .variant = pv, .rope = qn ? LrGemmRope{} : rope(ws.last_pos, q_w), .bias = bias,
+                             .splitk = ws.splitk}, st));
+      if (qn) LR_RUN(lr_launch_qk_norm_rope(ws.q_last, B, q_w, nh, 0, hd, qn, nullptr, c.rms_eps, ws.last_pos, ws.rope, st));
       LR_RUN(lr_launch_attention_last(ws.qkv, ws.q_last, ws.att_last, attn.cu, attn.cu_host, S, n, nh, nkv, hd, st, P, a_scale,
                                       a_cap));
     } else {
       LR_RUN(lr_launch_gemm({.A = folded ? ws.x : ws.xn, .B = folded ? h->wqkv_folded[l] : w.wqkv, .C = ws.qkv, .M = n,
-                             .N = q_w + kv_w, .K = d, .epi = LR_EPI_ROPE, .variant = gv, .rope = rope(ws.tok_pos, q_w + kv_w / 2),
+                             .N = q_w + kv_w, .K = d, .epi = epi_qkv, .variant = gv,
+                             .rope = qn ? LrGemmRope{} : rope(ws.tok_pos, q_w + kv_w / 2),
                              .row_scale = folded ? ws.rstd : nullptr, .bias = bias, .splitk = ws.splitk}, st));
+      if (qn) LR_RUN(lr_launch_qk_norm_rope(ws.qkv, n, q_w + kv_w, nh, nkv, hd, qn, kn, c.rms_eps, ws.tok_pos, ws.rope, st));
     }
     if (!last_pruned) {
       LR_RUN(lr_launch_attention(attn, attn_kernel, st));
@@ -729,6 +777,19 @@ extern "C" int lr_rmsnorm_bf16(const uint16_t* x, const uint16_t* w, uint16_t* o
       !(eps < __builtin_inff()))
     LR_FAIL(LR_EINVAL, "lr_rmsnorm_bf16: bad argument (rows %d, d %d a multiple of 8, norm_style %d)", rows, d, norm_style);
   return lr_launch_rmsnorm(x, w, out, rows, d, eps, nullptr, (hipStream_t)hip_stream, norm_style);
+}
+
+extern "C" int lr_qk_norm_rope_bf16(uint16_t* buf, int32_t rows, int32_t ld, int32_t col0, int32_t nq, int32_t nk,
+                                    int32_t head_dim, const uint16_t* q_norm, const uint16_t* k_norm, float eps,
+                                    const int32_t* tok_pos, const float* rope_cs, void* hip_stream) {
+  if (!lr_qk_norm_head_dim_ok(head_dim))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_qk_norm_rope_bf16: head_dim %d (a power of two from 16 to 256)", head_dim);
+  if (!buf || rows < 1 || ld < 8 || col0 < 0 || col0 % 8 != 0 || nq < 0 || nk < 0 || nq + nk < 1 ||
+      (long long)col0 + (long long)(nq + nk) * head_dim > ld || !tok_pos || !rope_cs || !(eps >= 0.f) || !(eps < __builtin_inff()))
+    LR_FAIL(LR_EINVAL, "lr_qk_norm_rope_bf16: bad argument (rows %d, ld %d, col0 %d a multiple of 8, %d + %d heads of %d)", rows,
+            ld, col0, nq, nk, head_dim);
+  return lr_launch_qk_norm_rope(buf + col0, rows, ld, nq, nk, head_dim, q_norm, k_norm, eps, tok_pos, rope_cs,
+                                (hipStream_t)hip_stream);
 }
 
 extern "C" size_t lr_attention_workspace_bytes(int32_t total_tokens, int32_t B, int32_t num_heads) {

@@ -291,6 +291,7 @@ struct LoraLayerSave {
   u16 *x, *xn, *qkv, *att, *xmid, *gu, *t;
   float* lse;
   u16* t2;  // [n][tw]: drop(input) A^T of the extra modules
+  u16* xqk; // [n][(nh + nkv) hd]: the pre-norm q | k values, delta included (a base with q/k norms only, else null)
 };
 struct LoraWs {
   int32_t *tok_pos, *last_rows;
@@ -305,14 +306,15 @@ struct LoraWs {
   // call is issued on one stream (the side stream, or the caller's without one), which runs partials, fold, next partials in
   // order; the main stream never touches the region.
   float *det_loss, *det_part;
-  size_t o_t2;
+  size_t o_t2, o_xqk;
+  bool qk_norm;
   size_t save0, save_stride;              // per-layer saved activations: base + l * save_stride
   size_t o_x, o_xn, o_qkv, o_att, o_xmid, o_gu, o_t, o_lse;
   char* base;
   size_t total;
 };
 static LoraWs carve(const LrLlamaConfig& c, const LoraMods& md, int n_tok, int B, int m, int slots, bool training,
-                    char* base, int r = 0, bool deterministic = false) {
+                    char* base, int r = 0, bool deterministic = false, bool qk_norm = false) {
   LoraWs w;
   memset(&w, 0, sizeof(w));
   w.base = base;
@@ -346,6 +348,9 @@ static LoraWs carve(const LrLlamaConfig& c, const LoraMods& md, int n_tok, int B
   w.o_t = stake(n * 2 * LT_RP * 2);
   w.o_lse = stake(n * c.num_heads * 4);
   w.o_t2 = stake(n * md.tw * 2);
+  // behind everything else and empty without q/k norms: such a handle keeps its layout and sizes to the byte
+  w.qk_norm = qk_norm;
+  w.o_xqk = stake(qk_norm ? n * (qcols + kv) * 2 : 0);
   w.save_stride = so;
   w.save0 = take(so * (size_t)slots);
   // transients: forward's (xn2, hmid) share memory with backward's (dxn, dh)
@@ -399,6 +404,7 @@ static LoraLayerSave slot(const LoraWs& w, int l) {
   s.t = (u16*)(b + w.o_t);
   s.lse = (float*)(b + w.o_lse);
   s.t2 = (u16*)(b + w.o_t2);
+  s.xqk = w.qk_norm ? (u16*)(b + w.o_xqk) : nullptr;
   return s;
 }
 
@@ -408,7 +414,7 @@ extern "C" size_t lr_llama_lora_workspace_bytes(const lr_llama_lora_t* h, int32_
   if (max_seqs < 1) max_seqs = 1;
   const LrLlamaConfig& c = h->base->cfg;
   return carve(c, lora_mods(c, h->cfg.r, h->mods), max_tokens, max_seqs, max_loss_rows, c.num_layers, true, nullptr, h->cfg.r,
-               h->deterministic != 0).total;
+               h->deterministic != 0, h->base->q_norm != nullptr).total;
 }
 extern "C" int lr_llama_lora_set_deterministic(lr_llama_lora_t* h, int32_t enable) {
   if (!h) LR_FAIL(LR_EINVAL, "lr_llama_lora_set_deterministic: null handle");
@@ -455,7 +461,8 @@ extern "C" size_t lr_llama_lora_eval_workspace_bytes(const lr_llama_lora_t* h, i
   if (!h || max_tokens < 1) return 0;
   if (max_seqs < 1) max_seqs = 1;
   const LrLlamaConfig& c = h->base->cfg;
-  return carve(c, lora_mods(c, h->cfg.r, h->mods), max_tokens, max_seqs, 0, 1, false, nullptr).total;
+  return carve(c, lora_mods(c, h->cfg.r, h->mods), max_tokens, max_seqs, 0, 1, false, nullptr, 0, false,
+               h->base->q_norm != nullptr).total;
 }
 
 static u16* work_of(const lr_llama_lora* h, int l) { return h->work + (size_t)l * h->work_per_layer; }
@@ -533,7 +540,9 @@ static int forward(lr_llama_lora* h, const int32_t* ids, const int32_t* cu, cons
     LR_RUN(join_side(h, st));
     // k's delta rides in the same sweep, before the rotation like q's
     LR_RUN(lr_launch_lora_rope_fwd(s.qkv, n, qw, h->qcols, h->kcols, hd, s.t, bq_t, bv_t, h->cfg.r, scaling, ws.tok_pos,
-                                   ws.rope, st, s.t2, tw, md.tk, md.has(MK) ? wk + md.wk_b : nullptr));
+                                   ws.rope, st, s.t2, tw, md.tk, md.has(MK) ? wk + md.wk_b : nullptr,
+                                   h->base->q_norm ? LrQkNormFwd{h->base->q_norm[l], h->base->k_norm[l], c.rms_eps, s.xqk}
+                                                   : LrQkNormFwd{}));
     LR_RUN(lr_launch_attention({.qkv = s.qkv, .out = s.att, .lse = s.lse, .cu = cu, .cu_host = cu_host, .S = B, .n_tok = n,
                                 .nh = nh, .nkv = nkv, .hd = hd}, attn_kernel, st));
     // the extra modules: t = drop(input) A^T on the side stream next to the GEMM that reads the same input, the delta
@@ -592,7 +601,7 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
   if (m > n) LR_FAIL(LR_EINVAL, "lr_llama_lora_loss_grad: %d labelled rows for %d tokens", m, n);
   const LoraMods md = lora_mods(c, h->cfg.r, h->mods);
   const bool det = h->deterministic != 0;
-  const LoraWs ws = carve(c, md, n, B, m, c.num_layers, true, (char*)workspace, h->cfg.r, det);
+  const LoraWs ws = carve(c, md, n, B, m, c.num_layers, true, (char*)workspace, h->cfg.r, det, h->base->q_norm != nullptr);
   if (ws.total > workspace_bytes)
     LR_FAIL(LR_EWORKSPACE, "lr_llama_lora_loss_grad: workspace needs %zu bytes for %d tokens, have %zu", ws.total, n,
             workspace_bytes);
@@ -696,6 +705,10 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
     // ... down to the gradient of the UNROTATED q, k, v (the inverse rotation rides in the attention passes)
     LR_RUN(lr_launch_attention_bwd(s.qkv, s.att, ws.datt, s.lse, ws.dqkv, ws.dsum, ws.dkv32, cu_seqlens, cu_seqlens_host, B,
                                    n, nh, nkv, hd, attn_bwd_variant, st, ws.tok_pos, ws.rope, det));
+    // Qwen3: ... and through the per-head norms to the gradient of the projections' outputs, before anything reads dqkv
+    if (h->base->q_norm)
+      LR_RUN(lr_launch_qk_norm_bwd(ws.dqkv, n, qw, s.xqk, h->qcols + h->kcols, nh, nkv, hd, h->base->q_norm[l],
+                                   h->base->k_norm[l], c.rms_eps, st));
     // adapters (side stream, next to the qkv data-gradient GEMM; both only read dqkv):
     // d B, d t = scaling * (d q B_q | d v B_v), d A
     LR_RUN(fork_side(h, st, &sd));
@@ -753,7 +766,8 @@ extern "C" int lr_llama_lora_prefill_verbalize(lr_llama_lora_t* h, const int32_t
   const LrLlamaConfig& c = h->base->cfg;
   int n, maxT;
   LR_RUN(validate_batch(h, cu_seqlens_host, B, &n, &maxT));
-  const LoraWs ws = carve(c, lora_mods(c, h->cfg.r, h->mods), n, B, 0, 1, false, (char*)workspace);
+  const LoraWs ws = carve(c, lora_mods(c, h->cfg.r, h->mods), n, B, 0, 1, false, (char*)workspace, 0, false,
+                          h->base->q_norm != nullptr);
   if (ws.total > workspace_bytes)
     LR_FAIL(LR_EWORKSPACE, "lr_llama_lora_prefill_verbalize: workspace needs %zu bytes for %d tokens, have %zu",
             ws.total, n, workspace_bytes);
@@ -761,6 +775,18 @@ extern "C" int lr_llama_lora_prefill_verbalize(lr_llama_lora_t* h, const int32_t
   LR_RUN(forward(h, packed_ids, cu_seqlens, cu_seqlens_host, B, n, maxT, ws, false, 0.f, st));
   return lr_launch_head(ws.x_final, ws.last_rows, h->base->final_norm, h->base->lm_head, label_token_ids, B, C,
                         c.hidden_size, c.rms_eps, out_scores, c.vocab_size, st);
+}
+
+extern "C" int lr_qk_norm_bwd_bf16(uint16_t* dqk, int32_t rows, int32_t ld, int32_t col0, const uint16_t* x, int32_t ldx,
+                                   int32_t nq, int32_t nk, int32_t head_dim, const uint16_t* q_norm, const uint16_t* k_norm,
+                                   float eps, void* hip_stream) {
+  if (!lr_qk_norm_head_dim_ok(head_dim))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_qk_norm_bwd_bf16: head_dim %d (a power of two from 16 to 256)", head_dim);
+  if (!dqk || !x || rows < 1 || ld < 8 || ldx < 8 || col0 < 0 || col0 % 8 != 0 || nq < 0 || nk < 0 || nq + nk < 1 ||
+      (long long)col0 + (long long)(nq + nk) * head_dim > ld || !(eps >= 0.f) || !(eps < __builtin_inff()))
+    LR_FAIL(LR_EINVAL, "lr_qk_norm_bwd_bf16: bad argument (rows %d, ld %d, col0 %d a multiple of 8, %d + %d heads of %d)", rows,
+            ld, col0, nq, nk, head_dim);
+  return lr_launch_qk_norm_bwd(dqk + col0, rows, ld, x, ldx, nq, nk, head_dim, q_norm, k_norm, eps, (hipStream_t)hip_stream);
 }
 
 extern "C" int lr_transpose_bf16(const uint16_t* src, int32_t rows, int32_t cols, uint16_t* dst, void* hip_stream) {

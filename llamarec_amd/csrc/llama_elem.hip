@@ -560,3 +560,81 @@ int lr_launch_residual_postnorm(u16* x, const u16* h, const u16* w_out, const u1
   LR_CHECK_LAUNCH("residual_postnorm_kernel");
   return LR_OK;
 }
+
+// ---- Qwen3: per-head RMSNorm of q and k + the rotary embedding, in place on a plain-stored QKV product --------------------
+// buf [rows][ld] holds nq + nk heads of hd columns from column 0 on, in the packed pair-interleaved order LR_EPI_ROPE writes
+// (the v columns behind them are neither read nor written). Per (row, head): rstd = 1 / sqrt(mean(x^2) + eps) in fp32 from
+// the bf16 values the GEMM stored, y = rms_apply<0>(w, x, rstd) = bf16(w * bf16(x * rstd)) (HF's Qwen3RMSNorm), then the
+// rotation of bf2f(y) with the rope epilogue's (cos, sin) pairs, operation order and single rounding. q_norm serves the first
+// nq heads, k_norm the rest; both [hd], permuted like a head's rows of wq / wk.
+// A thread owns 8 consecutive columns (one 16-byte access each way), a head is L = HD / 8 consecutive lanes: chunk ids run
+// row-major over rows x (nq + nk) L chunks, every count a multiple of L and L a divisor of 64, so a head never straddles a
+// wave and the square sum is an L-lane butterfly without LDS. Lanes past the end stay in the shuffles (their groups are whole).
+template <int HD>
+__global__ __launch_bounds__(256) void qk_norm_rope_kernel(u16* buf, size_t total, int per_row, int ld, int nq,
+                                                           const u16* q_norm, const u16* k_norm, float eps,
+                                                           const int32_t* tok_pos, const float* rope_cs) {
+  constexpr int L = HD / 8;
+  const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = id < total;
+  const size_t row = live ? id / per_row : 0;
+  const int chunk = live ? (int)(id % per_row) : 0;
+  const int head = chunk / L, part = chunk % L;
+  u16* p = buf + row * ld + (size_t)chunk * 8;
+  u16x8 x = {0, 0, 0, 0, 0, 0, 0, 0}, w = x;
+  if (live) {
+    x = *reinterpret_cast<const u16x8*>(p);
+    w = *reinterpret_cast<const u16x8*>((head < nq ? q_norm : k_norm) + part * 8);
+  }
+  float ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float f = bf2f(x[j]);
+    ss = __builtin_fmaf(f, f, ss);
+  }
+#pragma unroll
+  for (int s = L / 2; s >= 1; s >>= 1) ss += __shfl_xor(ss, s, 64);
+  if (!live) return;
+  const float rstd = 1.0f / sqrtf(ss / (float)HD + eps);
+  const float* cs = rope_cs + ((size_t)tok_pos[row] * (HD / 2) + part * 4) * 2;
+  const float4 c01 = *reinterpret_cast<const float4*>(cs), c23 = *reinterpret_cast<const float4*>(cs + 4);
+  const float co[4] = {c01.x, c01.z, c23.x, c23.z}, si[4] = {c01.y, c01.w, c23.y, c23.w};
+  u16x8 o;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float a0 = bf2f(rms_apply<0>(w[2 * q], x[2 * q], rstd)), a1 = bf2f(rms_apply<0>(w[2 * q + 1], x[2 * q + 1], rstd));
+    o[2 * q] = f2bf(a0 * co[q] - a1 * si[q]);
+    o[2 * q + 1] = f2bf(a1 * co[q] + a0 * si[q]);
+  }
+  *reinterpret_cast<u16x8*>(p) = o;
+}
+
+// head_dim a power of two in [16, 256] (a head = 2 .. 32 lanes)
+bool lr_qk_norm_head_dim_ok(int hd) { return hd >= 16 && hd <= 256 && (hd & (hd - 1)) == 0; }
+
+int lr_launch_qk_norm_rope(u16* buf, int rows, int ld, int nq, int nk, int hd, const u16* q_norm, const u16* k_norm,
+                           float eps, const int32_t* tok_pos, const float* rope_cs, hipStream_t st) {
+  if (rows <= 0 || nq + nk == 0) return LR_OK;
+  if (!lr_qk_norm_head_dim_ok(hd)) LR_FAIL(LR_EUNSUPPORTED, "q/k norm sweep: head_dim %d (a power of two from 16 to 256)", hd);
+  if (!buf || nq < 0 || nk < 0 || (nq > 0 && !q_norm) || (nk > 0 && !k_norm) || !tok_pos || !rope_cs || ld % 8 != 0 ||
+      (long long)(nq + nk) * hd > ld || (reinterpret_cast<uintptr_t>(buf) & 15) ||
+      ((reinterpret_cast<uintptr_t>(q_norm) | reinterpret_cast<uintptr_t>(k_norm)) & 15))
+    LR_FAIL(LR_EINVAL, "q/k norm sweep: bad argument (nq %d, nk %d, head_dim %d, row stride %d; 16-byte aligned pointers)", nq,
+            nk, hd, ld);
+  const int per_row = (nq + nk) * (hd / 8);
+  const size_t total = (size_t)rows * per_row;
+  const size_t blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffffu) LR_FAIL(LR_EUNSUPPORTED, "q/k norm sweep: %d rows exceed the grid limit", rows);
+  LrProfScope prof(LR_PROF_ELEMENTWISE, 2.0 * total * 16, st);   // work = bytes moved: every chunk read and written once
+#define LR_QKN_CASE(HD)                                                                                                   \
+  case HD:                                                                                                                \
+    hipLaunchKernelGGL(qk_norm_rope_kernel<HD>, dim3((unsigned)blocks), dim3(256), 0, st, buf, total, per_row, ld, nq,    \
+                       q_norm, k_norm, eps, tok_pos, rope_cs);                                                            \
+    break;
+  switch (hd) {
+    LR_QKN_CASE(16) LR_QKN_CASE(32) LR_QKN_CASE(64) LR_QKN_CASE(128) LR_QKN_CASE(256)
+  }
+#undef LR_QKN_CASE
+  LR_CHECK_LAUNCH("qk_norm_rope_kernel");
+  return LR_OK;
+}

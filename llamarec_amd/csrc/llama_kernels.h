@@ -82,6 +82,14 @@ int lr_launch_head(const unsigned short* x, const int32_t* rows /*[B]; nullptr: 
 // with w_next, xn = bf16(gemmanorm(x, w_next)). xn may alias h (a workgroup reads its row of h before it writes any of xn).
 int lr_launch_residual_postnorm(unsigned short* x, const unsigned short* h, const unsigned short* w_out,
                                 const unsigned short* w_next, unsigned short* xn, int rows, int d, float eps, hipStream_t st);
+// Qwen3's per-head RMSNorm of q and k followed by the rotary embedding, in place on a plain-stored (LR_EPI_STORE) QKV product
+// (llama_elem.hip): buf [rows][ld] holds nq + nk heads of hd columns from column 0 on in the packed pair-interleaved order;
+// columns behind them are not touched. q_norm / k_norm: bf16 [hd] in that order, 16-byte aligned; either group may be empty.
+// hd: a power of two from 16 to 256 (lr_qk_norm_head_dim_ok), anything else LR_EUNSUPPORTED before any launch.
+bool lr_qk_norm_head_dim_ok(int hd);
+int lr_launch_qk_norm_rope(unsigned short* buf, int rows, int ld, int nq, int nk, int hd, const unsigned short* q_norm,
+                           const unsigned short* k_norm, float eps, const int32_t* tok_pos, const float* rope_cs,
+                           hipStream_t st);
 
 // C[M][N] (+epilogue) = A[M][K] * B[N][K]^T. Call sites name what they pass (designated initialisers); a member left
 // out is absent. variant: 0 auto, 1 generic, 4 = 256x256x64 MFMA tile, 5 = variant 4 with split-K when the tiles alone

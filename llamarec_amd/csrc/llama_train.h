@@ -13,11 +13,24 @@ int lr_launch_prep_lora(const float* aq, const float* bq, const float* av, const
                         hipStream_t st);
 int lr_launch_skinny(const unsigned short* X, int ldx, int n, int K, const unsigned short* W, int nt, unsigned short* out,
                      int ldo, int ocol, float scale, uint32_t drop_stream, float drop_p, hipStream_t st);
+// Qwen3's q / k norms in the LoRA forward sweep: bf16 [hd] weights in a head's packed column order, and xsave
+// [n][qcols + kcols], which receives the pre-norm q | k values (delta included) for lr_launch_qk_norm_bwd. q_norm null: no norm.
+struct LrQkNormFwd {
+  const unsigned short *q_norm = nullptr, *k_norm = nullptr;
+  float eps = 0.f;
+  unsigned short* xsave = nullptr;
+};
 int lr_launch_lora_rope_fwd(unsigned short* qkv, int n, int qw, int qcols, int kcols, int hd, const unsigned short* t,
                             const unsigned short* bq_t, const unsigned short* bv_t, int r, float scaling,
                             const int32_t* tok_pos, const float* rope_cs, hipStream_t st,
                             const unsigned short* tk = nullptr, int ldtk = 0, int tkcol = 0,
-                            const unsigned short* bk_t = nullptr);  // bk_t: k_proj's adapter, t from tk [n][ldtk] column tkcol
+                            const unsigned short* bk_t = nullptr,  // bk_t: k_proj's adapter, t from tk [n][ldtk] column tkcol
+                            const LrQkNormFwd& qkn = {});  // the norm between "add the delta" and "rotate"
+// backward of the q / k norms, in place on the q and k columns of dqkv [rows][ld] (nq + nk heads from column 0 on): the
+// gradient w.r.t. the normed unrotated q / k becomes the gradient w.r.t. the pre-norm values x [rows][ldx] (the forward's
+// xsave). The norm weights are frozen: no weight gradient. One owner per element, no atomics.
+int lr_launch_qk_norm_bwd(unsigned short* dqk, int rows, int ld, const unsigned short* x, int ldx, int nq, int nk, int hd,
+                          const unsigned short* q_norm, const unsigned short* k_norm, float eps, hipStream_t st);
 int lr_launch_rope_bwd(unsigned short* dqkv, int n, int qw, int rot_cols, int hd, const int32_t* tok_pos,
                        const float* rope_cs, hipStream_t st);
 int lr_launch_lora_db(const unsigned short* dqkv, int n, int qw, int qcols, int kcols, int hd, const unsigned short* t,

@@ -204,12 +204,17 @@ int lr_launch_skinny(const u16* X, int ldx, int n, int K, const u16* W, int nt, 
 #define LT_ROWS 4
 // HASK: k_proj carries an adapter too: its t columns come from tk [n][ldtk] (column tkcol), its B^T from bk_t, and its
 // delta is added before the rotation like q's
-template <bool HASK>
+// NORM (Qwen3): between "add the delta" and "rotate" every q / k head gets its RMSNorm over head_dim, lr_launch_qk_norm_rope's
+// arithmetic (a k_proj adapter's delta is normed too, as in HF); the pre-norm values, delta included, go to xsave
+// [n][qcols + kcols] for lr_launch_qk_norm_bwd. A head is hd / 8 consecutive threads of one wave (hd a power of two from 16 to
+// 256, the widths multiples of hd), so its square sum is a butterfly over those lanes.
+template <bool HASK, bool NORM>
 __global__ __launch_bounds__(256) void lt_lora_rope_fwd_kernel(u16* qkv, int n, int qw, int qcols, int kcols, int hd,
                                                                const u16* t /*[n][2*LT_RP]*/, const u16* bq_t,
                                                                const u16* bv_t, int r, float scaling,
                                                                const int32_t* tok_pos, const float* rope_cs,
-                                                               const u16* tk, int ldtk, int tkcol, const u16* bk_t) {
+                                                               const u16* tk, int ldtk, int tkcol, const u16* bk_t,
+                                                               const u16* q_norm, const u16* k_norm, float eps, u16* xsave) {
   __shared__ float ts[LT_ROWS][(HASK ? 3 : 2) * LT_RP];
   __shared__ int pos[LT_ROWS];
   const int row0 = blockIdx.x * LT_ROWS;
@@ -256,6 +261,24 @@ __global__ __launch_bounds__(256) void lt_lora_rope_fwd_kernel(u16* qkv, int n, 
         for (int e = 0; e < 8; ++e) v[rr][e] = bf2f(f2bf(v[rr][e] + bf2f(f2bf(bf2f(f2bf(l[rr][e])) * scaling))));
     }
     const int i0 = (c % hd) >> 1;
+    if (NORM && !isv) {
+      const u16x8 wn = *reinterpret_cast<const u16x8*>((isq ? q_norm : k_norm) + c % hd);
+#pragma unroll
+      for (int rr = 0; rr < LT_ROWS; ++rr) {   // every row, so that all lanes of a head take part in the shuffles
+        u16x8 xb;
+        float ss = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          xb[e] = f2bf(v[rr][e]);   // exact: the values are bf16 already
+          ss = __builtin_fmaf(v[rr][e], v[rr][e], ss);
+        }
+        if (rr < nrows) *reinterpret_cast<u16x8*>(xsave + (size_t)(row0 + rr) * (qcols + kcols) + c) = xb;
+        for (int sft = hd >> 4; sft >= 1; sft >>= 1) ss += __shfl_xor(ss, sft, 64);
+        const float rstd = 1.0f / sqrtf(ss / (float)hd + eps);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[rr][e] = bf2f(rms_apply<0>(wn[e], xb[e], rstd));
+      }
+    }
 #pragma unroll
     for (int rr = 0; rr < LT_ROWS; ++rr) {
       if (rr >= nrows) continue;
@@ -279,17 +302,100 @@ __global__ __launch_bounds__(256) void lt_lora_rope_fwd_kernel(u16* qkv, int n, 
 }
 int lr_launch_lora_rope_fwd(u16* qkv, int n, int qw, int qcols, int kcols, int hd, const u16* t, const u16* bq_t,
                             const u16* bv_t, int r, float scaling, const int32_t* tok_pos, const float* rope_cs,
-                            hipStream_t st, const u16* tk, int ldtk, int tkcol, const u16* bk_t) {
+                            hipStream_t st, const u16* tk, int ldtk, int tkcol, const u16* bk_t, const LrQkNormFwd& qkn) {
   if (n < 1) return LR_OK;
   if (hd % 8 != 0 || qcols % 8 != 0 || kcols % 8 != 0 || qw % 8 != 0)
     LR_FAIL(LR_EUNSUPPORTED, "lora + rotary sweep: head_dim and projection widths must be multiples of 8");
-  if (bk_t)
-    hipLaunchKernelGGL(lt_lora_rope_fwd_kernel<true>, dim3((n + LT_ROWS - 1) / LT_ROWS), dim3(256), 0, st, qkv, n, qw, qcols,
-                       kcols, hd, t, bq_t, bv_t, r, scaling, tok_pos, rope_cs, tk, ldtk, tkcol, bk_t);
-  else
-    hipLaunchKernelGGL(lt_lora_rope_fwd_kernel<false>, dim3((n + LT_ROWS - 1) / LT_ROWS), dim3(256), 0, st, qkv, n, qw, qcols,
-                       kcols, hd, t, bq_t, bv_t, r, scaling, tok_pos, rope_cs, tk, ldtk, tkcol, bk_t);
+  const bool norm = qkn.q_norm != nullptr;
+  if (norm) {
+    if (!lr_qk_norm_head_dim_ok(hd) || qcols % hd != 0 || kcols % hd != 0)
+      LR_FAIL(LR_EUNSUPPORTED, "lora + q/k norm + rotary sweep: head_dim %d (a power of two from 16 to 256)", hd);
+    if (!qkn.k_norm || !qkn.xsave) LR_FAIL(LR_EINVAL, "lora + q/k norm + rotary sweep: null k norm or save buffer");
+  }
+  const dim3 grid((n + LT_ROWS - 1) / LT_ROWS);
+#define LT_ROPE_FWD(HASK, NORM)                                                                                            \
+  hipLaunchKernelGGL((lt_lora_rope_fwd_kernel<HASK, NORM>), grid, dim3(256), 0, st, qkv, n, qw, qcols, kcols, hd, t, bq_t, \
+                     bv_t, r, scaling, tok_pos, rope_cs, tk, ldtk, tkcol, bk_t, qkn.q_norm, qkn.k_norm, qkn.eps, qkn.xsave)
+  if (bk_t && norm) LT_ROPE_FWD(true, true);
+  else if (bk_t) LT_ROPE_FWD(true, false);
+  else if (norm) LT_ROPE_FWD(false, true);
+  else LT_ROPE_FWD(false, false);
+#undef LT_ROPE_FWD
   LR_CHECK_LAUNCH("lt_lora_rope_fwd_kernel");
+  return LR_OK;
+}
+
+// =============================================================================================
+// backward of Qwen3's per-head q / k RMSNorm (frozen weights: no weight gradient)
+// =============================================================================================
+// In place on the q and k columns of dqkv [n][ld] (nq + nk heads of hd columns from column 0 on), which hold the gradient
+// w.r.t. the normed, unrotated q / k (lr_launch_attention_bwd's output); x [n][ldx] = the pre-norm values the forward saved.
+// Per (row, head), with g = w .* dy and xh = x * rstd:  dx = rstd * (g - xh * mean(xh .* g)), formed in fp32 as
+// rstd * (g - x * (rstd^2 * sum(x .* g) / hd)) and rounded once. lr_launch_qk_norm_rope's thread layout: a thread owns 8 columns, a head is
+// hd / 8 lanes, both sums are butterflies over them. Every element has one owner and nothing is added atomically: two runs
+// give the same bits.
+template <int HD>
+__global__ __launch_bounds__(256) void lt_qk_norm_bwd_kernel(u16* dqk, size_t total, int per_row, int ld, const u16* x, int ldx,
+                                                             int nq, const u16* q_norm, const u16* k_norm, float eps) {
+  constexpr int L = HD / 8;
+  const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = id < total;
+  const size_t row = live ? id / per_row : 0;
+  const int chunk = live ? (int)(id % per_row) : 0;
+  const int head = chunk / L, part = chunk % L;
+  u16* p = dqk + row * ld + (size_t)chunk * 8;
+  u16x8 xv = {0, 0, 0, 0, 0, 0, 0, 0}, dy = xv, w = xv;
+  if (live) {
+    xv = *reinterpret_cast<const u16x8*>(x + row * ldx + (size_t)chunk * 8);
+    dy = *reinterpret_cast<const u16x8*>(p);
+    w = *reinterpret_cast<const u16x8*>((head < nq ? q_norm : k_norm) + part * 8);
+  }
+  float xf[8], g[8], ss = 0.f, sg = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    xf[j] = bf2f(xv[j]);
+    g[j] = bf2f(w[j]) * bf2f(dy[j]);
+    ss = __builtin_fmaf(xf[j], xf[j], ss);
+    sg = __builtin_fmaf(xf[j], g[j], sg);
+  }
+#pragma unroll
+  for (int s = L / 2; s >= 1; s >>= 1) {
+    ss += __shfl_xor(ss, s, 64);
+    sg += __shfl_xor(sg, s, 64);
+  }
+  if (!live) return;
+  const float rstd = 1.0f / sqrtf(ss / (float)HD + eps);
+  const float m = rstd * rstd * (sg / (float)HD);
+  u16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = f2bf(rstd * (g[j] - xf[j] * m));
+  *reinterpret_cast<u16x8*>(p) = o;
+}
+
+int lr_launch_qk_norm_bwd(u16* dqk, int rows, int ld, const u16* x, int ldx, int nq, int nk, int hd, const u16* q_norm,
+                          const u16* k_norm, float eps, hipStream_t st) {
+  if (rows <= 0 || nq + nk == 0) return LR_OK;
+  if (!lr_qk_norm_head_dim_ok(hd)) LR_FAIL(LR_EUNSUPPORTED, "q/k norm backward: head_dim %d (a power of two from 16 to 256)", hd);
+  if (!dqk || !x || nq < 0 || nk < 0 || (nq > 0 && !q_norm) || (nk > 0 && !k_norm) || ld % 8 != 0 || ldx % 8 != 0 ||
+      (long long)(nq + nk) * hd > ld || (long long)(nq + nk) * hd > ldx ||
+      ((reinterpret_cast<uintptr_t>(dqk) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(q_norm) |
+        reinterpret_cast<uintptr_t>(k_norm)) & 15))
+    LR_FAIL(LR_EINVAL, "q/k norm backward: bad argument (nq %d, nk %d, head_dim %d, row strides %d / %d; 16-byte aligned pointers)",
+            nq, nk, hd, ld, ldx);
+  const int per_row = (nq + nk) * (hd / 8);
+  const size_t total = (size_t)rows * per_row;
+  const size_t blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffffu) LR_FAIL(LR_EUNSUPPORTED, "q/k norm backward: %d rows exceed the grid limit", rows);
+#define LT_QKN_CASE(HD)                                                                                                    \
+  case HD:                                                                                                                 \
+    hipLaunchKernelGGL(lt_qk_norm_bwd_kernel<HD>, dim3((unsigned)blocks), dim3(256), 0, st, dqk, total, per_row, ld, x, ldx, \
+                       nq, q_norm, k_norm, eps);                                                                           \
+    break;
+  switch (hd) {
+    LT_QKN_CASE(16) LT_QKN_CASE(32) LT_QKN_CASE(64) LT_QKN_CASE(128) LT_QKN_CASE(256)
+  }
+#undef LT_QKN_CASE
+  LR_CHECK_LAUNCH("lt_qk_norm_bwd_kernel");
   return LR_OK;
 }
 

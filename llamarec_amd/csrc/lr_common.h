@@ -168,6 +168,11 @@ struct lr_llama {
   // Qwen2 (lr_llama_set_qkv_bias): [num_layers] owned copy of the caller's array of bf16 [(nh + 2 nkv) head_dim] biases in
   // wqkv's row order, or null (calloc): no bias (refuses folded norms and LoRA engines)
   const uint16_t** bqkv;
+  // Qwen3 (lr_llama_set_qk_norm): [num_layers] owned copies of the caller's arrays of bf16 [head_dim] RMSNorm weights for
+  // every q head and every k head, in a head's packed column order, or both null (calloc): no q/k norm. With them the QKV
+  // products store plainly and lr_launch_qk_norm_rope follows (refuses folded norms, a Gemma-2 extension and q/k/v biases)
+  const uint16_t** q_norm;
+  const uint16_t** k_norm;
 };
 
 #endif  // LR_COMMON_H

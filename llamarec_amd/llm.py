@@ -66,6 +66,17 @@ QWEN2_1_5B = dict(QWEN2_0_5B, hidden_size=1536, intermediate_size=8960, num_hidd
                   max_window_layers=28)
 QWEN2_7B = dict(QWEN2_1_5B, vocab_size=152064, hidden_size=3584, intermediate_size=18944, num_attention_heads=28,
                 num_key_value_heads=4, tie_word_embeddings=False)
+# Qwen/Qwen3-0.6B, Qwen3-1.7B, Qwen3-4B and Qwen3-8B (config.json of the checkpoints). Llama's arithmetic plus an RMSNorm over
+# head_dim on every q and k head between the projection and the rotation; head_dim 128 comes from the config (0.6B: 16 heads
+# of 128 on a hidden size of 1024), no biases.
+QWEN3_0_6B = dict(model_type="qwen3", vocab_size=151936, hidden_size=1024, intermediate_size=3072, num_hidden_layers=28,
+                  num_attention_heads=16, num_key_value_heads=8, head_dim=128, max_position_embeddings=40960, rms_norm_eps=1e-6,
+                  rope_theta=1000000.0, rope_scaling=None, hidden_act="silu", attention_bias=False, use_sliding_window=False,
+                  sliding_window=None, max_window_layers=28, tie_word_embeddings=True)
+QWEN3_1_7B = dict(QWEN3_0_6B, hidden_size=2048, intermediate_size=6144)
+QWEN3_4B = dict(QWEN3_0_6B, hidden_size=2560, intermediate_size=9728, num_hidden_layers=36, num_attention_heads=32,
+                max_window_layers=36)
+QWEN3_8B = dict(QWEN3_4B, hidden_size=4096, intermediate_size=12288, tie_word_embeddings=False)
 
 # model_type -> backbone family of the kernels (LrLlamaArch). Llama-2 / Llama-3 and Mistral share Llama's arithmetic.
 LLAMA_FAMILY = ("llama", "mistral")
@@ -73,13 +84,16 @@ GEMMA_FAMILY = ("gemma",)
 GEMMA2_FAMILY = ("gemma2",)
 PHI3_FAMILY = ("phi3",)
 QWEN2_FAMILY = ("qwen2",)
-SUPPORTED_MODEL_TYPES = LLAMA_FAMILY + PHI3_FAMILY + QWEN2_FAMILY + GEMMA_FAMILY + GEMMA2_FAMILY
+QWEN3_FAMILY = ("qwen3",)
+SUPPORTED_MODEL_TYPES = LLAMA_FAMILY + PHI3_FAMILY + QWEN2_FAMILY + QWEN3_FAMILY + GEMMA_FAMILY + GEMMA2_FAMILY
 # what a gemma2 config must spell out (the two caps may be null): none of them has a default the kernels could assume
 GEMMA2_REQUIRED_KEYS = ("query_pre_attn_scalar", "attn_logit_softcapping", "final_logit_softcapping", "sliding_window", "head_dim")
 # what a phi3 config must spell out (sliding_window may be null = none); every published Phi-3 config.json has all three
 PHI3_REQUIRED_KEYS = ("hidden_act", "original_max_position_embeddings", "sliding_window")
 # what a qwen2 config must spell out (sliding_window may be null); every published Qwen2 config.json has all four
 QWEN2_REQUIRED_KEYS = ("hidden_act", "use_sliding_window", "sliding_window", "max_window_layers")
+# what a qwen3 config must spell out; every published dense Qwen3 config.json has all three (head_dim is not hidden / heads)
+QWEN3_REQUIRED_KEYS = ("head_dim", "hidden_act", "attention_bias")
 
 
 _LLAMA3_NUMBERS = ("factor", "low_freq_factor", "high_freq_factor", "original_max_position_embeddings")
@@ -110,11 +124,12 @@ def rope_parameters(config: dict):
 
 
 def model_family(config: dict) -> str:
-    """'llama', 'gemma', 'gemma2', 'phi3' or 'qwen2' for a HF config dict (a missing model_type means llama); anything else raises:
+    """'llama', 'gemma', 'gemma2', 'phi3', 'qwen2' or 'qwen3' for a HF config dict (a missing model_type means llama); anything else raises:
     the kernels implement those families' arithmetic only, and a checkpoint of another family would load (same tensor names)
     and then score silently wrong. A gemma2, phi3 or qwen2 config is accepted only when it is complete (GEMMA2_REQUIRED_KEYS,
     PHI3_REQUIRED_KEYS, QWEN2_REQUIRED_KEYS). phi3 is Llama's arithmetic behind fused qkv_proj / gate_up_proj Linears
-    (from_state_dict splits them); qwen2 is Llama's arithmetic with q/k/v biases (lr_llama_set_qkv_bias)."""
+    (from_state_dict splits them); qwen2 is Llama's arithmetic with q/k/v biases (lr_llama_set_qkv_bias); qwen3 (complete by
+    QWEN3_REQUIRED_KEYS; the dense models only) is Llama's arithmetic with per-head q/k RMSNorms (lr_llama_set_qk_norm)."""
     mt = config.get("model_type") or "llama"
     if mt in LLAMA_FAMILY:
         rope_parameters(config)   # plain RoPE or a complete llama3 rule; raises otherwise
@@ -205,6 +220,40 @@ def model_family(config: dict) -> str:
             raise NotImplementedError(f"model_type {mt!r} with use_sliding_window and sliding_window={sw!r}: a positive "
                                       f"integer; {supported}")
         return "qwen2"
+    if mt in QWEN3_FAMILY:
+        missing = [k for k in QWEN3_REQUIRED_KEYS if config.get(k) is None]
+        if missing:
+            raise NotImplementedError(f"model_type {mt!r} config lacks {', '.join(missing)}: a Qwen3 config.json spells them "
+                                      f"out, and the kernels assume no defaults for them; {supported}")
+        hd = config["head_dim"]
+        if not (isinstance(hd, int) and not isinstance(hd, bool) and 16 <= hd <= 256 and hd & (hd - 1) == 0):
+            raise NotImplementedError(f"model_type {mt!r} with head_dim={hd!r}: the q/k norm kernels take a power of two from "
+                                      f"16 to 256; {supported}")
+        if config["hidden_act"] != "silu":
+            raise NotImplementedError(f"model_type {mt!r} with hidden_act={config['hidden_act']!r}: the kernels implement "
+                                      f"silu (SwiGLU); {supported}")
+        if config["attention_bias"] is not False:
+            raise NotImplementedError(f"model_type {mt!r} with attention_bias={config['attention_bias']!r}: q/k norms and "
+                                      f"q/k/v/o biases together are not implemented; {supported}")
+        if config.get("use_sliding_window"):
+            raise NotImplementedError(f"model_type {mt!r} with use_sliding_window={config['use_sliding_window']!r}: the "
+                                      f"kernels attend to the whole causal range; {supported}")
+        lt = config.get("layer_types")
+        if lt is not None and any(t != "full_attention" for t in lt):
+            raise NotImplementedError(f"model_type {mt!r} with layer_types={sorted(set(lt))!r}: every layer must be "
+                                      f"full_attention; {supported}")
+        try:
+            scaled = rope_parameters(config)[1] is not None   # yarn, dynamic, ... raise here
+        except NotImplementedError as e:
+            raise NotImplementedError(f"model_type {mt!r} with {e}; {supported}") from None
+        if scaled:
+            raise NotImplementedError(f"model_type {mt!r} with rope_scaling="
+                                      f"{config.get('rope_scaling') or config.get('rope_parameters')!r}: Qwen3 is served "
+                                      f"with plain RoPE only; {supported}")
+        return "qwen3"
+    if mt == "qwen3_moe":
+        raise NotImplementedError(f"model_type 'qwen3_moe': the mixture-of-experts Qwen3 models have no kernels here (the "
+                                  f"dense ones are model_type 'qwen3'); {supported}")
     raise NotImplementedError(f"model_type {mt!r} is not supported by the ranker's kernels; supported families: "
                               f"{', '.join(SUPPORTED_MODEL_TYPES)}")
 
@@ -459,6 +508,12 @@ class LlamaRanker:
                     if f"model.layers.{i}.self_attn.{n}_proj.bias" not in state_dict:
                         raise KeyError(f"model_type 'qwen2': model.layers.{i}.self_attn.{n}_proj.bias is missing (Qwen2's "
                                        "q/k/v Linears have biases)")
+        if self.family == "qwen3":
+            for i in range(L):
+                for n in "qk":
+                    if f"model.layers.{i}.self_attn.{n}_norm.weight" not in state_dict:
+                        raise KeyError(f"model_type 'qwen3': model.layers.{i}.self_attn.{n}_norm.weight is missing (Qwen3 "
+                                       "norms every q and k head)")
         T["embed"] = t("model.embed_tokens.weight").to(torch.bfloat16).contiguous()
         T["final_norm"] = t("model.norm.weight").to(torch.bfloat16).contiguous()
         T["lm_head"] = (t("lm_head.weight") if "lm_head.weight" in state_dict else T["embed"]).to(torch.bfloat16).contiguous()
@@ -479,6 +534,14 @@ class LlamaRanker:
                 bq, bk, bv = (t(p + f"self_attn.{n}_proj.bias").float().reshape(-1, 1) for n in "qkv")
                 T[f"{i}.bqkv"] = torch.cat([self._interleave_rope_rows(bq), self._interleave_rope_rows(bk), bv],
                                            0).reshape(-1).to(torch.bfloat16).contiguous()
+            if self.family == "qwen3":
+                # the [head_dim] norm weights in a head's packed column order: the permutation of a head's rows of wq / wk,
+                # once at load. They stay out of the NF4 round trip (Linears only) and no adapter touches them.
+                for n in "qk":
+                    wn = t(p + f"self_attn.{n}_norm.weight").float().reshape(-1, 1)
+                    if wn.shape[0] != self.hd:
+                        raise ValueError(f"{p}self_attn.{n}_norm.weight: {wn.shape[0]} elements, expected head_dim = {self.hd}")
+                    T[f"{i}.{n}_norm"] = self._interleave_rope_rows(wn).reshape(-1).to(torch.bfloat16).contiguous()
             T[f"{i}.wo"] = merged(p + "self_attn.o_proj.weight").to(torch.bfloat16).contiguous()
             T[f"{i}.wgu"] = self._interleave_gate_up(gate, up)
             T[f"{i}.wdown"] = merged(p + "mlp.down_proj.weight").to(torch.bfloat16).contiguous()
@@ -519,6 +582,9 @@ class LlamaRanker:
             T[f"{i}.wqkv"] = rnd((nh + 2 * nkv) * hd, d)
             if self.family == "qwen2":
                 T[f"{i}.bqkv"] = rnd((nh + 2 * nkv) * hd)
+            if self.family == "qwen3":
+                T[f"{i}.q_norm"] = norm(hd, dtype=torch.bfloat16, device=dev)
+                T[f"{i}.k_norm"] = norm(hd, dtype=torch.bfloat16, device=dev)
             T[f"{i}.wo"] = rnd(d, nh * hd)
             T[f"{i}.wgu"] = rnd(2 * f, d)  # already in the interleaved gate/up layout (random anyway)
             T[f"{i}.wdown"] = rnd(d, f)
@@ -605,6 +671,10 @@ class LlamaRanker:
         if "0.bqkv" in T:
             self._bqkv_arr = (C.c_void_p * L)(*[T[f"{i}.bqkv"].data_ptr() for i in range(L)])
             check(lib().lr_llama_set_qkv_bias(self._h, self._bqkv_arr), "lr_llama_set_qkv_bias")
+        if "0.q_norm" in T:
+            self._qk_norm_arrs = ((C.c_void_p * L)(*[T[f"{i}.q_norm"].data_ptr() for i in range(L)]),
+                                  (C.c_void_p * L)(*[T[f"{i}.k_norm"].data_ptr() for i in range(L)]))
+            check(lib().lr_llama_set_qk_norm(self._h, *self._qk_norm_arrs), "lr_llama_set_qk_norm")
         if self.default_gemm_variant:
             self.set_variants(gemm=self.default_gemm_variant)
         if self.fold_norms:
@@ -634,6 +704,8 @@ class LlamaRanker:
             raise NotImplementedError("folded norms: Gemma's (1 + w) RMSNorm cannot be folded into bf16 weights at HF's rounding")
         if enable and self.family == "qwen2":
             raise NotImplementedError("folded norms: not with Qwen2's q/k/v biases (lr_llama_set_qkv_bias)")
+        if enable and self.family == "qwen3":
+            raise NotImplementedError("folded norms: not with Qwen3's q/k norms (lr_llama_set_qk_norm)")
         if not enable:
             check(lib().lr_llama_set_folded_norms(self._h, None, None), "lr_llama_set_folded_norms")
             for i in range(L):

@@ -211,6 +211,46 @@ def synth_qwen2_state(cfg: dict, seed: int, std: float = 0.02, bias_std: float =
     return sd
 
 
+def qwen3_param_shapes(cfg: dict) -> list[tuple[str, tuple]]:
+    """HF Qwen3ForCausalLM parameter names and shapes: Llama's at the config's head_dim (q_proj [nh hd][hidden], o_proj
+    [hidden][nh hd]) with q_norm.weight and k_norm.weight [head_dim] behind o_proj (HF's module order), and no lm_head.weight
+    when the embeddings are tied."""
+    hd = cfg["head_dim"]
+    out = []
+    for name, shape in gemma_param_shapes(cfg):   # Llama's names with head_dim from the config, no lm_head
+        out.append((name, shape))
+        if name.endswith("o_proj.weight"):
+            p = name[: -len("o_proj.weight")]
+            out += [(p + "q_norm.weight", (hd,)), (p + "k_norm.weight", (hd,))]
+    if not cfg.get("tie_word_embeddings"):
+        out.append(("lm_head.weight", (cfg["vocab_size"], cfg["hidden_size"])))
+    return out
+
+
+# a tiny Qwen3 (train_ranker.py --synthetic --llm qwen3; tests/gen_goldens_qwen3.py's hd128_gqa with another vocab): 4 query
+# heads of head_dim 128 on 2 KV heads over a hidden size of 256 (nh * hd != hidden), tied head
+QWEN3_TINY = dict(model_type="qwen3", vocab_size=1000, hidden_size=256, intermediate_size=512, num_hidden_layers=2,
+                  num_attention_heads=4, num_key_value_heads=2, head_dim=128, max_position_embeddings=4096, rms_norm_eps=1e-6,
+                  rope_theta=1000000.0, rope_scaling=None, hidden_act="silu", attention_bias=False, use_sliding_window=False,
+                  sliding_window=None, max_window_layers=2, tie_word_embeddings=True)
+
+
+def synth_qwen3_state(cfg: dict, seed: int, std: float = 0.02, norm_jitter: float = 0.1, qk_norm_spread: float = 0.75) -> dict:
+    """As synth_llama_state under Qwen3's names: matrices ~ U(std), the hidden-size norm weights 1 + U(norm_jitter), the q / k
+    norm weights 1 + U(qk_norm_spread) -- mean 1 and wide enough (uniform of standard deviation 0.75) that a model with ones in their place
+    is clearly another model (tests/gen_goldens_qwen3.py checks by how much). bf16 values."""
+    sd = {}
+    for i, (name, shape) in enumerate(qwen3_param_shapes(cfg)):
+        if name.endswith(("q_norm.weight", "k_norm.weight")):
+            w = np.float32(1.0) + hash_uniform(seed * 1000 + i, shape, qk_norm_spread)
+        elif len(shape) == 1:
+            w = np.float32(1.0) + hash_uniform(seed * 1000 + i, shape, norm_jitter)
+        else:
+            w = hash_uniform(seed * 1000 + i, shape, std)
+        sd[name] = bf16_round(w)
+    return sd
+
+
 def synth_gemma_state(cfg: dict, seed: int, std: float = 0.02, norm_std: float = 0.3) -> dict:
     """name -> float32 array for a Gemma config. Matrices ~ U(std); norm weights ~ U(norm_std) around 0 -- Gemma scales by
     (1 + w), so non-zero w exercises that form (w = 0 would make it indistinguishable from Llama's w = 1). bf16 values."""

@@ -2,7 +2,7 @@
 """Entry point compatible with the reference's
 `python train_ranker.py --llm_retrieved_path experiments/lru/<dataset>`: `trainer.train()` -- LoRA
 fine-tuning of q_proj / v_proj on the HIP training step (train_ranker.py:110 of the reference,
-SURVEY.md 8(f) #4) -- then `trainer.test(test_retrieval)` (:111). Pass a local base model directory
+SURVEY.md 8(f) #4; Llama-family and Qwen3 bases) -- then `trainer.test(test_retrieval)` (:111). Pass a local base model directory
 (--llm_base_model); with --eval_only (and optionally a local PEFT adapter, --llm_adapter_path, merged
 into the bf16 weights at load) only the scoring half runs. Nothing is downloaded. --synthetic
 fabricates a tiny model + tokenizer. The tuned adapter is written in PEFT's format to
@@ -61,8 +61,8 @@ def main(argv=None, export_root=None):
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
     if args.synthetic:
-        from llamarec_amd.synth import (PHI3_TINY, QWEN2_TINY, FakeTokenizer, synth_gemma2_state, synth_gemma_state,
-                                        synth_llama_state, synth_phi3_state, synth_qwen2_state)
+        from llamarec_amd.synth import (PHI3_TINY, QWEN2_TINY, QWEN3_TINY, FakeTokenizer, synth_gemma2_state, synth_gemma_state,
+                                        synth_llama_state, synth_phi3_state, synth_qwen2_state, synth_qwen3_state)
 
         dataset = D.synthetic_dataset(num_users=300, num_items=1000, seed=args.seed)
         tokenizer = FakeTokenizer()
@@ -90,6 +90,10 @@ def main(argv=None, export_root=None):
             c = dict(QWEN2_TINY, vocab_size=c["vocab_size"])
             model = LlamaRanker.from_state_dict(synth_qwen2_state(c, args.seed), c, device=device, lora=lora,
                                                 nf4=args.llm_load_in_4bit)
+        elif args.llm == "qwen3":   # a tiny Qwen3: per-head q/k norms, 4 heads of head_dim 128 on 2 KV heads, hidden 256; trains
+            c = dict(QWEN3_TINY, vocab_size=c["vocab_size"])
+            model = LlamaRanker.from_state_dict(synth_qwen3_state(c, args.seed), c, device=device, lora=lora,
+                                                nf4=args.llm_load_in_4bit)
         else:
             model = LlamaRanker.from_state_dict(synth_llama_state(c, args.seed), c, device=device, lora=lora,
                                                 nf4=args.llm_load_in_4bit)
@@ -106,7 +110,7 @@ def main(argv=None, export_root=None):
         tokenizer.clean_up_tokenization_spaces = True
         model = LlamaRanker.from_pretrained(args.llm_base_model, device=device, adapter_path=args.llm_adapter_path,
                                             load_in_4bit=args.llm_load_in_4bit)
-    if model.family != "llama" and not args.eval_only:
+    if model.family not in ("llama", "qwen3") and not args.eval_only:   # qwen3: the LoRA step norms q / k and has the backward
         raise SystemExit(TRAIN_LLAMA_ONLY)
     ncls = args.llm_negative_sample_size + 1
     args.num_items = len(dataset["smap"])
