@@ -793,6 +793,94 @@ int lr_attention_varlen_bwd_ex(const uint16_t* qkv, const uint16_t* out, const u
                                void* scratch, size_t scratch_bytes, const int32_t* tok_pos, const float* rope_cs,
                                int32_t rope_positions, int32_t deterministic, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The LoRA step's small kernels alone (exposed for parity tests): the row sweeps, rank-r products, token reductions, loss
+ * head and optimizer that lr_llama_lora_loss_grad / lr_llama_lora_apply run between their GEMMs and attention passes, each
+ * behind one call with flat arguments. All pointers DEVICE, bf16 as uint16_t, r = the adapter's rank (1..16; the bf16
+ * working copies are zero-padded to 16 rows / columns). Every call checks on the host, before it launches anything, what
+ * its kernel assumes about the arguments: LR_EINVAL (null pointer, negative count, a tile past the row stride, r, layout,
+ * dropout outside [0, 1)) or LR_EUNSUPPORTED (a width the kernel has no path for, a pointer that is not 16-byte aligned
+ * where the kernel moves 16 bytes at a time), with a message in lr_last_error and nothing written. What only the device can
+ * see is the caller's promise: out_rows names distinct rows inside the output, targets may be anything (a value outside
+ * [0, vocab) is "no token id"). A count of zero rows is LR_OK and launches nothing. drop_stream / drop_p: the counter-based
+ * dropout mask keep(stream, row, col) of the step (kept elements are scaled by 1 / (1 - p) and rounded to bf16); p = 0: none.
+ * The arithmetic, rounding points and element-wise error bounds of every call: tests/lora_kernels_ref.py.
+ * ------------------------------------------------------------------------------------------ */
+/* out[row][ocol + 16 t + j] = bf16(scale * sum_k drop(x)[row][k] * w[16 t + j][k]), t < nt (1 or 2): x [n][ldx], w [16 nt][K],
+ * K a multiple of 64, out [n][ldo]. */
+int lr_lora_skinny_bf16(const uint16_t* x, int32_t ldx, int32_t n, int32_t k, const uint16_t* w, int32_t nt, uint16_t* out,
+                        int32_t ldo, int32_t ocol, float scale, uint32_t drop_stream, float drop_p, void* hip_stream);
+/* Token reduction, ADDED to fp32 outputs: out_a[..] += scale * sum_tok t[tok][tcol + 16 a + j] * drop(x)[tok][c], a < nj (1 or
+ * 2), j < r, c < cols (a multiple of 64). layout 0: out_a[j * cols + c]; 1: out0[c * r + j]; 2: out0[orig(c) * r + j] with the
+ * rotary pair interleave of head_dim-wide heads undone; 3 (nj = 2): x = the interleaved gate / up gradient (16 gate columns,
+ * 16 up columns, ...), tile 0 keeps the gate columns in out0[f_col * r + j], tile 1 the up columns in out1, either may be
+ * null. det_part null: one fp32 atomic per element and token chunk. det_part given (16-byte aligned like the outputs then,
+ * det_part_floats >= lr_lora_tn_det_floats(...), else LR_EWORKSPACE): per-chunk partial tiles stored there and folded in
+ * chunk order, the same bits on every run. Rows of x and t that are 16-byte aligned take the LDS-staged kernel, any other
+ * alignment the 2-byte gather kernel; the two give the same bits. */
+size_t lr_lora_tn_det_floats(int32_t nj, int32_t n, int32_t cols, int32_t r, int32_t layout);
+int lr_lora_tn_f32(int32_t nj, const uint16_t* t, int32_t ldt, int32_t tcol, const uint16_t* x, int32_t ldx, int32_t n,
+                   int32_t cols, float scale, float* out0, float* out1, int32_t r, int32_t layout, int32_t head_dim,
+                   uint32_t drop_stream, float drop_p, float* det_part, size_t det_part_floats, void* hip_stream);
+/* y[row][c] = bf16(y + bf16(bf16(sum_j t[row][tcol + j] * w[j][c]) * s)) where keep(row, c), else unchanged: y [n][ldy] in
+ * place, cols a multiple of 8, t [n][ldt] (16 columns from tcol), w [16][cols]. */
+int lr_lora_expand_bf16(uint16_t* y, int32_t ldy, int32_t n, int32_t cols, const uint16_t* t, int32_t ldt, int32_t tcol,
+                        const uint16_t* w, int32_t r, float s, uint32_t drop_stream, float drop_p, void* hip_stream);
+/* SwiGLU on the interleaved gate / up layout gu [n][2f] (16 gate columns, 16 up columns, ...), f a multiple of 16:
+ * h [n][f] = bf16(silu(gate) * up); the backward rewrites gu in place into (d gate, d up) given dh [n][f]. */
+int lr_swiglu_fwd_bf16(const uint16_t* gu, uint16_t* h, int32_t n, int32_t f, void* hip_stream);
+int lr_swiglu_bwd_bf16(uint16_t* gu, const uint16_t* dh, int32_t n, int32_t f, void* hip_stream);
+/* RMSNorm backward over dense [rows][d] rows (d a multiple of 8, <= 8192): out[out_rows ? out_rows[i] : i] = (res ? res[i] :
+ * 0) + dx[i], dx = rstd g - x rstd^3 mean(x g), g = w dy. dt non-null: dy first gets the adapters' term,
+ * dy = bf16(dy + bf16(ds * sum_j dt[i][j] a_cat[j][c] + dt[i][16 + j] a_cat[16 + j][c])) where keep(i, c): dt [rows][ldt]
+ * (32 columns used), a_cat [32][d]. */
+int lr_rmsnorm_bwd_bf16(const uint16_t* dy, const uint16_t* x, const uint16_t* w, const uint16_t* res, uint16_t* out,
+                        int32_t rows, int32_t d, float eps, const int32_t* out_rows, const uint16_t* dt, int32_t ldt,
+                        const uint16_t* a_cat, int32_t r, uint32_t drop_stream, float drop_p, void* hip_stream);
+/* Softmax cross-entropy over logits [m][vocab], rewritten in place into (softmax - onehot) * gscale; a row whose target is
+ * outside [0, vocab) becomes zeros. out[0] = sum of the rows' -log p(target) / m, out[1] = m, out[2] = rows without a token
+ * id. scal: scratch of 2 floats, or 2 + m with deterministic != 0 (the losses summed in row order). m = 0 still writes
+ * out = {0, 0, 0}. */
+int lr_ce_bf16(uint16_t* logits, int32_t m, int32_t vocab, const int32_t* targets, float gscale, float* scal, float* out,
+               int32_t deterministic, void* hip_stream);
+/* out[row * num_heads + h] = sum_d o[row][h][d] * d_o[row][h][d], fp32; head_dim a multiple of 8. */
+int lr_rowdot_bf16(const uint16_t* o, const uint16_t* d_o, int32_t n, int32_t num_heads, int32_t head_dim, float* out,
+                   void* hip_stream);
+/* The forward sweep behind the q|k|v projection, in place on qkv [n][qw] (q columns [0, qcols), k [qcols, qcols + kcols), v the
+ * rest; packed, pair-interleaved heads): q and v get their adapters' delta bf16(bf16(sum_j t[row][j (+16)] b[j][c]) * scaling)
+ * (t [n][32]: 16 q ranks, 16 v ranks; bq_t [16][qcols], bv_t [16][vcols]), k too when bk_t is given (its ranks from tk [n][ldtk],
+ * column tkcol; bk_t [16][kcols]); then, when q_norm is given, every q / k head its RMSNorm over head_dim (a power of two from
+ * 16 to 256; weights [head_dim] in packed order; the pre-norm q | k values go to xsave [n][qcols + kcols]); then the rotation
+ * of q and k at rope_cs[tok_pos[row]] (lr_rope_table's fp32 part). tk / bk_t null: no k adapter. q_norm, k_norm and xsave all
+ * null: no norm. */
+int lr_lora_rope_fwd_bf16(uint16_t* qkv, int32_t n, int32_t qw, int32_t qcols, int32_t kcols, int32_t head_dim, const uint16_t* t,
+                          const uint16_t* bq_t, const uint16_t* bv_t, int32_t r, float scaling, const int32_t* tok_pos,
+                          const float* rope_cs, const uint16_t* tk, int32_t ldtk, int32_t tkcol, const uint16_t* bk_t,
+                          const uint16_t* q_norm, const uint16_t* k_norm, float eps, uint16_t* xsave, void* hip_stream);
+/* The transpose of that rotation, in place on the first rot_cols columns of dqkv [n][qw] (head_dim a multiple of 8 dividing
+ * rot_cols). */
+int lr_rope_bwd_bf16(uint16_t* dqkv, int32_t n, int32_t qw, int32_t rot_cols, int32_t head_dim, const int32_t* tok_pos,
+                     const float* rope_cs, void* hip_stream);
+/* lr_swiglu_fwd_bf16 with the gate / up adapters' delta: gu += bf16(bf16(t w) * s) (t [n][ldt] from column tcol: 16 gate ranks,
+ * 16 up ranks; w [32][2f]: their B^T in gu's interleaved column order), the sum written back to gu, h = swiglu of the sum. */
+int lr_swiglu_lora_fwd_bf16(uint16_t* gu, uint16_t* h, int32_t n, int32_t f, const uint16_t* t, int32_t ldt, int32_t tcol,
+                            const uint16_t* w, int32_t r, float s, void* hip_stream);
+/* The bf16 working copies of fp32 masters (peft's lora_A [r][in], lora_B [out][r]), zero-padded to 16 rows. q|v pair: a_cat
+ * [32][d] (rows 0.. = A_q, 16.. = A_v), bq_t [16][qcols] = B_q^T in the packed (pair-interleaved) column order, bv_t [16][vcols]
+ * = B_v^T. One module: a_w [16][in], b_t [16][ldb] = B^T with perm 0 plain, 1 the pair interleave within heads of head_dim, 2 / 3
+ * the gate / up columns of the interleaved gate-up layout (ldb >= 2 out; the other half's columns are not written). */
+int lr_lora_prep_bf16(const float* aq, const float* bq, const float* av, const float* bv, int32_t r, int32_t d, int32_t qcols,
+                      int32_t vcols, int32_t head_dim, uint16_t* a_cat, uint16_t* bq_t, uint16_t* bv_t, void* hip_stream);
+int lr_lora_prep_module_bf16(const float* a, const float* b, int32_t r, int32_t in, int32_t out, int32_t perm, int32_t head_dim,
+                             uint16_t* a_w, uint16_t* b_t, int32_t ldb, void* hip_stream);
+/* clip_grad_norm_(max_grad_norm; <= 0: none) and one AdamW step over n fp32 elements at step ctr[0] + 1; ctr[0] is then
+ * incremented. scratch: 4 floats. g is read only. out_norm (optional) = the norm before clipping. deterministic != 0: the
+ * norm summed in an order fixed by n (g 16-byte aligned). n = 0 is LR_OK, launches nothing and is no step: ctr[0], scratch
+ * and out_norm keep what they held. */
+int lr_lora_adamw_f32(float* p, float* g, float* m, float* v, size_t n, float* scratch, int32_t* ctr, float lr,
+                      float max_grad_norm, float beta1, float beta2, float eps, float weight_decay, float* out_norm,
+                      int32_t deterministic, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

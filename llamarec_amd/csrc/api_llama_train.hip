@@ -847,3 +847,194 @@ extern "C" int lr_attention_varlen_bwd(const uint16_t* qkv, const uint16_t* out,
   return lr_attention_varlen_bwd_ex(qkv, out, d_out, lse, dqkv, cu_seqlens, cu_seqlens_host, B, num_heads, num_kv_heads,
                                     head_dim, variant, scratch, scratch_bytes, nullptr, nullptr, 0, 0, hip_stream);
 }
+
+// ---- the LoRA step's small kernels alone (exposed for parity tests) ----------------------------------------------------------
+// Thin wrappers of llama_train.h's launchers: every assumption a kernel makes about its arguments that the host can see is checked
+// here before anything is launched; no arithmetic is added. The training step calls the launchers, never these.
+static inline bool lt_al16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr,
+                           const void* e = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+           reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(e)) & 15) == 0;
+}
+static inline bool lt_drop_ok(float p) { return p >= 0.f && p < 1.f; }
+
+extern "C" int lr_lora_skinny_bf16(const uint16_t* x, int32_t ldx, int32_t n, int32_t k, const uint16_t* w, int32_t nt,
+                                   uint16_t* out, int32_t ldo, int32_t ocol, float scale, uint32_t drop_stream, float drop_p,
+                                   void* hip_stream) {
+  if (!x || !w || !out) LR_FAIL(LR_EINVAL, "lr_lora_skinny_bf16: null pointer");
+  if (n < 0 || k < 1 || ldx < k || (nt != 1 && nt != 2) || ocol < 0 || (long long)ocol + 16 * nt > ldo || !lt_drop_ok(drop_p))
+    LR_FAIL(LR_EINVAL, "lr_lora_skinny_bf16: bad argument (n %d, K %d <= ldx %d, %d tiles from column %d of %d, dropout %g)", n, k,
+            ldx, nt, ocol, ldo, (double)drop_p);
+  if (k % 64 != 0 || ldx % 8 != 0 || !lt_al16(x, w))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_lora_skinny_bf16: K %d must be a multiple of 64, ldx %d of 8, x and w 16-byte aligned", k, ldx);
+  return lr_launch_skinny(x, ldx, n, k, w, nt, out, ldo, ocol, scale, drop_stream, drop_p, (hipStream_t)hip_stream);
+}
+
+// the C name of llama_train.h's lr_lora_tn_partial_floats (one quantity: the floats of det_part), with the arguments checked
+extern "C" size_t lr_lora_tn_det_floats(int32_t nj, int32_t n, int32_t cols, int32_t r, int32_t layout) {
+  if ((nj != 1 && nj != 2) || n < 1 || cols < 1 || r < 1 || r > LT_RP || layout < 0 || layout > 3) return 0;
+  return lr_lora_tn_partial_floats(nj, n, cols, r, layout);
+}
+
+extern "C" int lr_lora_tn_f32(int32_t nj, const uint16_t* t, int32_t ldt, int32_t tcol, const uint16_t* x, int32_t ldx, int32_t n,
+                              int32_t cols, float scale, float* out0, float* out1, int32_t r, int32_t layout, int32_t head_dim,
+                              uint32_t drop_stream, float drop_p, float* det_part, size_t det_part_floats, void* hip_stream) {
+  if (!t || !x) LR_FAIL(LR_EINVAL, "lr_lora_tn_f32: null pointer");
+  if ((nj != 1 && nj != 2) || n < 0 || r < 1 || r > LT_RP || layout < 0 || layout > 3 || tcol < 0 ||
+      (long long)tcol + 16 * nj > ldt || cols < 1 || cols > ldx || !lt_drop_ok(drop_p))
+    LR_FAIL(LR_EINVAL, "lr_lora_tn_f32: bad argument (%d tiles from column %d of %d, n %d, cols %d <= ldx %d, r %d, layout %d, "
+            "dropout %g)", nj, tcol, ldt, n, cols, ldx, r, layout, (double)drop_p);
+  // which outputs a layout writes: layout 3 splits the two tiles over out0 (gate) and out1 (up), either may be null;
+  // the others write tile a to out_a
+  if (layout == 3 ? (nj != 2 || (!out0 && !out1)) : (!out0 || (nj == 2 && !out1)))
+    LR_FAIL(LR_EINVAL, "lr_lora_tn_f32: layout %d with %d tiles: null output", layout, nj);
+  if (cols % 64 != 0) LR_FAIL(LR_EUNSUPPORTED, "lr_lora_tn_f32: %d columns (must be a multiple of 64)", cols);
+  if (layout == 2 && (head_dim < 2 || head_dim % 2 != 0 || cols % head_dim != 0))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_lora_tn_f32: layout 2 needs an even head_dim %d dividing %d columns", head_dim, cols);
+  if (((uintptr_t)out0 | (uintptr_t)out1 | (uintptr_t)det_part) & 3) LR_FAIL(LR_EINVAL, "lr_lora_tn_f32: misaligned fp32 pointer");
+  if (det_part && det_part_floats < lr_lora_tn_partial_floats(nj, n, cols, r, layout))
+    LR_FAIL(LR_EWORKSPACE, "lr_lora_tn_f32: %zu floats of partial tiles, %zu needed", det_part_floats,
+            lr_lora_tn_partial_floats(nj, n, cols, r, layout));
+  return lr_launch_lora_tn(nj, t, ldt, tcol, x, ldx, n, cols, scale, out0, out1, r, layout, head_dim, drop_stream, drop_p,
+                           (hipStream_t)hip_stream, det_part);
+}
+
+extern "C" int lr_lora_expand_bf16(uint16_t* y, int32_t ldy, int32_t n, int32_t cols, const uint16_t* t, int32_t ldt, int32_t tcol,
+                                   const uint16_t* w, int32_t r, float s, uint32_t drop_stream, float drop_p, void* hip_stream) {
+  if (!y || !t || !w) LR_FAIL(LR_EINVAL, "lr_lora_expand_bf16: null pointer");
+  if (n < 0 || cols < 1 || cols > ldy || r < 1 || r > LT_RP || tcol < 0 || (long long)tcol + LT_RP > ldt || !lt_drop_ok(drop_p))
+    LR_FAIL(LR_EINVAL, "lr_lora_expand_bf16: bad argument (n %d, cols %d <= ldy %d, r %d, column %d of %d, dropout %g)", n, cols,
+            ldy, r, tcol, ldt, (double)drop_p);
+  if (cols % 8 != 0 || ldy % 8 != 0 || !lt_al16(y, w))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_lora_expand_bf16: cols %d and ldy %d must be multiples of 8, y and w 16-byte aligned", cols, ldy);
+  return lr_launch_lora_expand(y, ldy, n, cols, t, ldt, tcol, w, r, s, drop_stream, drop_p, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_swiglu_fwd_bf16(const uint16_t* gu, uint16_t* h, int32_t n, int32_t f, void* hip_stream) {
+  if (!gu || !h || n < 0 || f < 1) LR_FAIL(LR_EINVAL, "lr_swiglu_fwd_bf16: bad argument (n %d, f %d)", n, f);
+  if (f % 16 != 0 || !lt_al16(gu, h)) LR_FAIL(LR_EUNSUPPORTED, "lr_swiglu_fwd_bf16: intermediate size %d (a multiple of 16)", f);
+  return lr_launch_swiglu_fwd(gu, h, n, f, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_swiglu_bwd_bf16(uint16_t* gu, const uint16_t* dh, int32_t n, int32_t f, void* hip_stream) {
+  if (!gu || !dh || n < 0 || f < 1) LR_FAIL(LR_EINVAL, "lr_swiglu_bwd_bf16: bad argument (n %d, f %d)", n, f);
+  if (f % 16 != 0 || !lt_al16(gu, dh)) LR_FAIL(LR_EUNSUPPORTED, "lr_swiglu_bwd_bf16: intermediate size %d (a multiple of 16)", f);
+  return lr_launch_swiglu_bwd(gu, dh, n, f, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_rmsnorm_bwd_bf16(const uint16_t* dy, const uint16_t* x, const uint16_t* w, const uint16_t* res, uint16_t* out,
+                                   int32_t rows, int32_t d, float eps, const int32_t* out_rows, const uint16_t* dt, int32_t ldt,
+                                   const uint16_t* a_cat, int32_t r, uint32_t drop_stream, float drop_p, void* hip_stream) {
+  if (!dy || !x || !w || !out) LR_FAIL(LR_EINVAL, "lr_rmsnorm_bwd_bf16: null pointer");
+  if (rows < 0 || d < 1 || !(eps >= 0.f) || !(eps < __builtin_inff()) || !lt_drop_ok(drop_p))
+    LR_FAIL(LR_EINVAL, "lr_rmsnorm_bwd_bf16: bad argument (rows %d, d %d, eps %g, dropout %g)", rows, d, (double)eps,
+            (double)drop_p);
+  if (dt && (!a_cat || r < 1 || r > LT_RP || ldt < 2 * LT_RP))
+    LR_FAIL(LR_EINVAL, "lr_rmsnorm_bwd_bf16: the LoRA arm needs a_cat, 1 <= r %d <= 16 and ldt %d >= 32", r, ldt);
+  if (d % 8 != 0 || d > 256 * 8 * 4)
+    LR_FAIL(LR_EUNSUPPORTED, "lr_rmsnorm_bwd_bf16: hidden_size %d (multiple of 8, <= 8192)", d);
+  if (!lt_al16(dy, x, w, res, out) || !lt_al16(a_cat))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_rmsnorm_bwd_bf16: pointers must be 16-byte aligned");
+  return lr_launch_rmsnorm_bwd(dy, x, w, res, out, rows, d, eps, out_rows, dt, a_cat, r, drop_stream, drop_p,
+                               (hipStream_t)hip_stream, ldt);
+}
+
+extern "C" int lr_ce_bf16(uint16_t* logits, int32_t m, int32_t vocab, const int32_t* targets, float gscale, float* scal,
+                          float* out, int32_t deterministic, void* hip_stream) {
+  if (!logits || !targets || !scal || !out || m < 0 || vocab < 1)
+    LR_FAIL(LR_EINVAL, "lr_ce_bf16: bad argument (m %d, vocab %d)", m, vocab);
+  hipStream_t st = (hipStream_t)hip_stream;
+  LR_CHECK_HIP(hipMemsetAsync(scal, 0, 2 * sizeof(float), st));
+  LR_RUN(lr_launch_ce_bf16(logits, m, vocab, targets, gscale, scal, st, deterministic != 0));
+  return lr_launch_finish_loss(scal, m, out, st, deterministic != 0);
+}
+
+extern "C" int lr_rowdot_bf16(const uint16_t* o, const uint16_t* d_o, int32_t n, int32_t num_heads, int32_t head_dim, float* out,
+                              void* hip_stream) {
+  if (!o || !d_o || !out || n < 0 || num_heads < 1 || head_dim < 1 || (long long)n * num_heads > 0x7fffffff - 16)
+    LR_FAIL(LR_EINVAL, "lr_rowdot_bf16: bad argument (n %d, %d heads of %d)", n, num_heads, head_dim);
+  if (head_dim % 8 != 0 || !lt_al16(o, d_o)) LR_FAIL(LR_EUNSUPPORTED, "lr_rowdot_bf16: head_dim %d (a multiple of 8)", head_dim);
+  return lr_launch_rowdot(o, d_o, n, num_heads, head_dim, out, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_lora_adamw_f32(float* p, float* g, float* m, float* v, size_t n, float* scratch, int32_t* ctr, float lr,
+                                 float max_grad_norm, float beta1, float beta2, float eps, float weight_decay, float* out_norm,
+                                 int32_t deterministic, void* hip_stream) {
+  if (!p || !g || !m || !v || !scratch || !ctr) LR_FAIL(LR_EINVAL, "lr_lora_adamw_f32: null pointer");
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f))
+    LR_FAIL(LR_EINVAL, "lr_lora_adamw_f32: bad argument (betas %g %g, eps %g)", (double)beta1, (double)beta2, (double)eps);
+  if (n == 0) return LR_OK;   // no parameters, no step: ctr stays (the header says so)
+  if (deterministic && !lt_al16(g)) LR_FAIL(LR_EUNSUPPORTED, "lr_lora_adamw_f32: deterministic norm needs a 16-byte aligned g");
+  return lr_launch_lora_adamw(p, g, m, v, n, scratch, ctr, lr, max_grad_norm, beta1, beta2, eps, weight_decay, out_norm,
+                              (hipStream_t)hip_stream, deterministic != 0);
+}
+
+extern "C" int lr_lora_rope_fwd_bf16(uint16_t* qkv, int32_t n, int32_t qw, int32_t qcols, int32_t kcols, int32_t head_dim,
+                                     const uint16_t* t, const uint16_t* bq_t, const uint16_t* bv_t, int32_t r, float scaling,
+                                     const int32_t* tok_pos, const float* rope_cs, const uint16_t* tk, int32_t ldtk, int32_t tkcol,
+                                     const uint16_t* bk_t, const uint16_t* q_norm, const uint16_t* k_norm, float eps,
+                                     uint16_t* xsave, void* hip_stream) {
+  if (!qkv || !t || !bq_t || !bv_t || !tok_pos || !rope_cs) LR_FAIL(LR_EINVAL, "lr_lora_rope_fwd_bf16: null pointer");
+  if (n < 0 || r < 1 || r > LT_RP || head_dim < 2 || qcols < 0 || kcols < 0 || (long long)qcols + kcols > qw)
+    LR_FAIL(LR_EINVAL, "lr_lora_rope_fwd_bf16: bad argument (n %d, r %d, head_dim %d, q %d + k %d columns of %d)", n, r, head_dim,
+            qcols, kcols, qw);
+  if (bk_t && (!tk || tkcol < 0 || (long long)tkcol + LT_RP > ldtk))
+    LR_FAIL(LR_EINVAL, "lr_lora_rope_fwd_bf16: the k adapter needs tk and column %d + 16 <= ldtk %d", tkcol, ldtk);
+  if (!q_norm && (k_norm || xsave)) LR_FAIL(LR_EINVAL, "lr_lora_rope_fwd_bf16: k norm or save buffer without a q norm");
+  if (q_norm && (!(eps >= 0.f) || !(eps < __builtin_inff()))) LR_FAIL(LR_EINVAL, "lr_lora_rope_fwd_bf16: eps %g", (double)eps);
+  if (head_dim % 8 != 0 || qw % 8 != 0 || qcols % head_dim != 0 || kcols % head_dim != 0)
+    LR_FAIL(LR_EUNSUPPORTED, "lr_lora_rope_fwd_bf16: head_dim %d must be a multiple of 8 and divide the q %d and k %d columns, "
+            "row stride %d a multiple of 8", head_dim, qcols, kcols, qw);
+  if (!lt_al16(qkv, bq_t, bv_t, bk_t, rope_cs) || !lt_al16(q_norm, k_norm, xsave))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_lora_rope_fwd_bf16: pointers must be 16-byte aligned");
+  LrQkNormFwd qkn;
+  qkn.q_norm = q_norm;
+  qkn.k_norm = k_norm;
+  qkn.eps = eps;
+  qkn.xsave = xsave;
+  return lr_launch_lora_rope_fwd(qkv, n, qw, qcols, kcols, head_dim, t, bq_t, bv_t, r, scaling, tok_pos, rope_cs,
+                                 (hipStream_t)hip_stream, tk, ldtk, tkcol, bk_t, qkn);
+}
+
+extern "C" int lr_rope_bwd_bf16(uint16_t* dqkv, int32_t n, int32_t qw, int32_t rot_cols, int32_t head_dim, const int32_t* tok_pos,
+                                const float* rope_cs, void* hip_stream) {
+  if (!dqkv || !tok_pos || !rope_cs) LR_FAIL(LR_EINVAL, "lr_rope_bwd_bf16: null pointer");
+  if (n < 0 || rot_cols < 0 || rot_cols > qw || head_dim < 2)
+    LR_FAIL(LR_EINVAL, "lr_rope_bwd_bf16: bad argument (n %d, %d rotated columns of %d, head_dim %d)", n, rot_cols, qw, head_dim);
+  if (!lt_al16(dqkv)) LR_FAIL(LR_EUNSUPPORTED, "lr_rope_bwd_bf16: dqkv must be 16-byte aligned");
+  return lr_launch_rope_bwd(dqkv, n, qw, rot_cols, head_dim, tok_pos, rope_cs, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_swiglu_lora_fwd_bf16(uint16_t* gu, uint16_t* h, int32_t n, int32_t f, const uint16_t* t, int32_t ldt, int32_t tcol,
+                                       const uint16_t* w, int32_t r, float s, void* hip_stream) {
+  if (!gu || !h || !t || !w) LR_FAIL(LR_EINVAL, "lr_swiglu_lora_fwd_bf16: null pointer");
+  if (n < 0 || f < 1 || r < 1 || r > LT_RP || tcol < 0 || (long long)tcol + 2 * LT_RP > ldt)
+    LR_FAIL(LR_EINVAL, "lr_swiglu_lora_fwd_bf16: bad argument (n %d, f %d, r %d, column %d + 32 <= ldt %d)", n, f, r, tcol, ldt);
+  if (f % 16 != 0 || !lt_al16(gu, h, w))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_swiglu_lora_fwd_bf16: intermediate size %d (a multiple of 16), 16-byte aligned pointers", f);
+  return lr_launch_swiglu_lora_fwd(gu, h, n, f, t, ldt, tcol, w, r, s, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_lora_prep_bf16(const float* aq, const float* bq, const float* av, const float* bv, int32_t r, int32_t d,
+                                 int32_t qcols, int32_t vcols, int32_t head_dim, uint16_t* a_cat, uint16_t* bq_t, uint16_t* bv_t,
+                                 void* hip_stream) {
+  if (!aq || !bq || !av || !bv || !a_cat || !bq_t || !bv_t) LR_FAIL(LR_EINVAL, "lr_lora_prep_bf16: null pointer");
+  if (r < 1 || r > LT_RP || d < 1 || qcols < 1 || vcols < 1 || head_dim < 2 || head_dim % 2 != 0 || qcols % head_dim != 0 ||
+      2LL * LT_RP * d + (long long)LT_RP * ((long long)qcols + vcols) > 0x7fffffff)
+    LR_FAIL(LR_EINVAL, "lr_lora_prep_bf16: bad argument (r %d, hidden %d, q %d and v %d columns, head_dim %d)", r, d, qcols, vcols,
+            head_dim);
+  return lr_launch_prep_lora(aq, bq, av, bv, r, d, qcols, vcols, head_dim, a_cat, bq_t, bv_t, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_lora_prep_module_bf16(const float* a, const float* b, int32_t r, int32_t in, int32_t out, int32_t perm,
+                                        int32_t head_dim, uint16_t* a_w, uint16_t* b_t, int32_t ldb, void* hip_stream) {
+  if (!a || !b || !a_w || !b_t) LR_FAIL(LR_EINVAL, "lr_lora_prep_module_bf16: null pointer");
+  if (r < 1 || r > LT_RP || in < 1 || out < 1 || perm < 0 || perm > 3 || (long long)LT_RP * ((long long)in + out) > 0x7fffffff ||
+      ldb < (perm >= 2 ? 2LL * out : (long long)out))
+    LR_FAIL(LR_EINVAL, "lr_lora_prep_module_bf16: bad argument (r %d, in %d, out %d, perm %d, ldb %d)", r, in, out, perm, ldb);
+  if (perm == 1 && (head_dim < 2 || head_dim % 2 != 0 || out % head_dim != 0))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_lora_prep_module_bf16: perm 1 needs an even head_dim %d dividing %d rows", head_dim, out);
+  if (perm >= 2 && out % 16 != 0)
+    LR_FAIL(LR_EUNSUPPORTED, "lr_lora_prep_module_bf16: perm %d needs out %d a multiple of 16", perm, out);
+  return lr_launch_prep_module(a, b, r, in, out, perm, head_dim, a_w, b_t, ldb, (hipStream_t)hip_stream);
+}

@@ -423,7 +423,11 @@ __global__ __launch_bounds__(256) void lt_rope_bwd_kernel(u16* dqkv, int n, int 
 }
 int lr_launch_rope_bwd(u16* dqkv, int n, int qw, int rot_cols, int hd, const int32_t* tok_pos, const float* rope_cs,
                        hipStream_t st) {
-  if (n < 1) return LR_OK;
+  if (n < 1 || rot_cols < 1) return LR_OK;
+  // a thread rotates 4 pairs of one head with one 16-byte access, and reads their 8 table entries in a row
+  if (hd % 8 != 0 || rot_cols % hd != 0 || qw % 8 != 0 || rot_cols > qw)
+    LR_FAIL(LR_EUNSUPPORTED, "rotary backward: head_dim %d must be a multiple of 8 and divide the %d rotated columns of %d (a multiple of 8)",
+            hd, rot_cols, qw);
   const size_t total = (size_t)n * (rot_cols / 8);
   hipLaunchKernelGGL(lt_rope_bwd_kernel, dim3((unsigned)min((size_t)8192, (total + 255) / 256)), dim3(256), 0, st, dqkv,
                      n, qw, rot_cols, hd, tok_pos, rope_cs);
