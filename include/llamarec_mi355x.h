@@ -639,6 +639,23 @@ int lr_lru_train_buffers(lr_lru_train_t* h, float** params, float** grads, size_
  * e.g. "model.lru_blocks.1.lru_layer.in_proj.weight" (complex: 2 floats per element). */
 int lr_lru_train_param_range(const lr_lru_train_t* h, const char* name, size_t* offset, size_t* count);
 
+/* The step's item GEMM + softmax cross-entropy alone, in each of its three forms (exposed for parity tests):
+ *   form 0  stored logits, row-panel kernels (what a step with ce_mode 1 and lr_lru_train_set_fused(h, 1) launches)
+ *   form 1  fused, logits never stored       (ce_mode 2)
+ *   form 2  stored logits, one generic GEMM launch per product (ce_mode 1 with lr_lru_train_set_fused(h, 0))
+ * x [R][64], E [C][64], bias [C] fp32 and labels int64 [R] are DEVICE arrays; label 0 = ignored, labels outside [0, C - 1]
+ * are ignored and counted. The call starts as a step does: it counts the labels and zeroes dX [R][64]; dE [C][64] and
+ * dbias [C] are ADDED into. out_scal, DEVICE float[4]: the loss SUM over the labelled rows, their count, unused, the number
+ * of out-of-range labels. Gradients are those of the MEAN loss. Runs with the deterministic mode off. R >= 1, C >= 2. */
+size_t lr_lru_train_ce_parity_workspace_bytes(int32_t form, int32_t R, int32_t C);
+int lr_lru_train_ce_parity(int32_t form, const float* x, const float* E, const float* bias, const int64_t* labels,
+                           int32_t R, int32_t C, void* workspace, size_t workspace_bytes, float* out_scal, float* dX,
+                           float* dE, float* dbias, void* hip_stream);
+/* The splits the launcher of a form uses at a shape (host arithmetic only). form 0: out[0..4] = item splits of the score
+ * pass, item splits of the d x pass, row parts of the d E pass, 64-item super-blocks, rows padded to 16. form 1:
+ * out[0..3] = item chunks, 32-item tiles per chunk, row chunks of the d E pass, 32-row tiles per chunk. form 2: zeros. */
+int lr_lru_train_ce_plan(int32_t form, int32_t R, int32_t C, int32_t out[8]);
+
 /* ------------------------------------------------------------------------------------------
  * Ranker LoRA fine-tuning step.
  * Replaces the HF Trainer loop of trainer/llm.py:103-136 over the patched LlamaForCausalLM

@@ -34,11 +34,6 @@ LR_DET_DEFINE(train)
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-// fused item GEMM + cross-entropy (lru_train_ce.hip)
-size_t lr_train_ce_part_floats(int R, int C);
-int lr_launch_train_ce(const float* X, const float* E, const float* bias, const long long* labels, int R, int C,
-                       float* ws_part, float* scal, float* dX, float* dE, float* dbias, hipStream_t st);
-
 // =============================================================================================
 // flat parameter layout (floats)
 // =============================================================================================
@@ -855,6 +850,8 @@ struct TrWs {
 // instead of 3) but never stores logits; while the logits fit the Infinity Cache (Beauty: 155 MB) storing them is
 // ~10 % faster per step, at V = 10^6 the fused path is 3.7 x faster (290 -> 79 ms) and needs no 1 GiB buffer.
 #define TR_MATERIALISE_ELEMS ((size_t)64 << 20)
+// row pitch of the generic form's stored logits: a multiple of 4 floats, so that the score product's 16-byte stores are aligned
+#define TR_GENERIC_LDL(C) (((long long)(C) + 3) & ~3LL)
 
 static bool tr_use_materialised(const LrLruTrainConfig& cfg, int R, int C) {
   if (cfg.ce_mode == 1) return true;
@@ -926,7 +923,7 @@ static TrWs tr_carve(const TrLayout& lay, const LrLruTrainConfig& cfg, int R, ch
   w.materialise = tr_use_materialised(cfg, R, lay.V + 1);
   // stored logits: rows padded to a multiple of 4 floats, so that the score product's 16-byte stores are aligned
   {
-    const size_t generic = (size_t)R * (((size_t)lay.V + 1 + 3) & ~(size_t)3), panels = lr_train_scores_ws_floats(R, lay.V + 1);
+    const size_t generic = (size_t)R * (size_t)TR_GENERIC_LDL(lay.V + 1), panels = lr_train_scores_ws_floats(R, lay.V + 1);
     w.ce = take(w.materialise ? (generic > panels ? generic : panels) : lr_train_ce_part_floats(R, lay.V + 1));
   }
   const size_t shadow_len[4] = {lay.total, doff, (size_t)R * 64, 8};
@@ -1148,6 +1145,20 @@ extern "C" int lr_lru_train_param_range(const lr_lru_train_t* h, const char* nam
     LR_CHECK_LAUNCH(#kernel);                                                                         \
   } while (0)
 
+// The cross-entropy in its first form: the [R][C] logits stored (pitch TR_GENERIC_LDL), one generic GEMM launch per product
+// and the row softmax in between. scal[1] must be there, dX zero; dE / dbias receive added contributions.
+static int tr_launch_train_generic_ce(const float* x, const float* E, const float* bias, const long long* lab, int R, int C,
+                                      float* logits, float* scal, float* dx, float* dE, float* dbias, hipStream_t st) {
+  const long long ldl = TR_GENERIC_LDL(C);
+  TR_RUN(tr_gemm(x, 64, 1, E, 1, 64, logits, ldl, bias, R, C, 64, 0, st));  // scores (model/lru.py:85)
+  hipLaunchKernelGGL(tr_ce_kernel, dim3(R), dim3(256), 0, st, logits, ldl, C, lab, scal);
+  LR_CHECK_LAUNCH("tr_ce_kernel");
+  TR_RUN(tr_gemm(logits, ldl, 1, E, 64, 1, dx, 64, nullptr, R, 64, C, 1, st, true));  // d x
+  // d table += d logits^T x, and d bias += column sums of d logits (the row sums of the A operand)
+  TR_RUN(tr_gemm(logits, 1, ldl, x, 64, 1, dE, 64, nullptr, C, 64, R, 1, st, true, dbias));
+  return LR_OK;
+}
+
 static int tr_enqueue_loss_grad(lr_lru_train_t* h, const int64_t* tokens, const int64_t* labels, int32_t B, int32_t L,
                                 float* out_loss, void* workspace, size_t workspace_bytes, hipStream_t st) {
   const TrLayout& lay = h->lay;
@@ -1254,14 +1265,7 @@ static int tr_enqueue_loss_grad(lr_lru_train_t* h, const int64_t* tokens, const 
   if (ws.materialise && h->fused) {
     TR_RUN(lr_launch_train_scores(x, P + lay.emb, P + lay.bias, lab, R, C, ws.ce, h->scal, dx, G + lay.emb, G + lay.bias, st));
   } else if (ws.materialise) {
-    float* logits = ws.ce;
-    const long long ldl = ((long long)C + 3) & ~3LL;   // padded row pitch (see the workspace carve)
-    TR_RUN(tr_gemm(x, 64, 1, P + lay.emb, 1, 64, logits, ldl, P + lay.bias, R, C, 64, 0, st));  // scores (model/lru.py:85)
-    hipLaunchKernelGGL(tr_ce_kernel, dim3(R), dim3(256), 0, st, logits, ldl, C, lab, h->scal);
-    LR_CHECK_LAUNCH("tr_ce_kernel");
-    TR_RUN(tr_gemm(logits, ldl, 1, P + lay.emb, 64, 1, dx, 64, nullptr, R, 64, C, 1, st, true));  // d x
-    // d table += d logits^T x, and d bias += column sums of d logits (the row sums of the A operand)
-    TR_RUN(tr_gemm(logits, 1, ldl, x, 64, 1, G + lay.emb, 64, nullptr, C, 64, R, 1, st, true, G + lay.bias));
+    TR_RUN(tr_launch_train_generic_ce(x, P + lay.emb, P + lay.bias, lab, R, C, ws.ce, h->scal, dx, G + lay.emb, G + lay.bias, st));
   } else {
     TR_RUN(lr_launch_train_ce(x, P + lay.emb, P + lay.bias, lab, R, C, ws.ce, h->scal, dx, G + lay.emb, G + lay.bias, st));
   }
@@ -1449,4 +1453,66 @@ extern "C" int lr_lru_train_apply(lr_lru_train_t* h, float lr, float max_grad_no
   });
   if (rc == LR_OK) h->k_norm = out_grad_norm;
   return rc;
+}
+
+// ---- the step's three cross-entropy forms alone (exposed for parity tests) ---------------------------------------------------
+// workspace: [8 scalars | 4 counters] in 256 bytes, then the form's own scratch
+#define TR_CE_PARITY_HEAD 256
+static size_t tr_ce_parity_form_floats(int form, int R, int C) {
+  return form == 0 ? lr_train_scores_ws_floats(R, C) : form == 1 ? lr_train_ce_part_floats(R, C) : (size_t)R * (size_t)TR_GENERIC_LDL(C);
+}
+extern "C" size_t lr_lru_train_ce_parity_workspace_bytes(int32_t form, int32_t R, int32_t C) {
+  if (form < 0 || form > 2 || R < 1 || C < 2) return 0;
+  return TR_CE_PARITY_HEAD + lr_align_up(tr_ce_parity_form_floats(form, R, C) * sizeof(float), 256);
+}
+
+extern "C" int lr_lru_train_ce_plan(int32_t form, int32_t R, int32_t C, int32_t out[8]) {
+  if (!out) LR_FAIL(LR_EINVAL, "lr_lru_train_ce_plan: null argument");
+  if (form < 0 || form > 2 || R < 1 || C < 2) LR_FAIL(LR_EINVAL, "lr_lru_train_ce_plan: form=%d R=%d C=%d", form, R, C);
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (form == 0) {
+    LrTrainScoresPlan p;
+    lr_train_scores_plan(R, C, &p);
+    out[0] = p.ns; out[1] = p.ns2; out[2] = p.nq; out[3] = p.nsb; out[4] = p.Rpad;
+  } else if (form == 1) {
+    LrTrainCePlan p;
+    lr_train_ce_plan(R, C, &p);
+    out[0] = p.item_chunks; out[1] = p.item_tiles_per_chunk; out[2] = p.row_chunks; out[3] = p.row_tiles_per_chunk;
+  }
+  return LR_OK;
+}
+
+extern "C" int lr_lru_train_ce_parity(int32_t form, const float* x, const float* E, const float* bias, const int64_t* labels,
+                                      int32_t R, int32_t C, void* workspace, size_t workspace_bytes, float* out_scal, float* dX,
+                                      float* dE, float* dbias, void* hip_stream) {
+  if (!x || !E || !bias || !labels || !workspace || !out_scal || !dX || !dE || !dbias)
+    LR_FAIL(LR_EINVAL, "lr_lru_train_ce_parity: null argument");
+  if (form < 0 || form > 2 || R < 1 || C < 2) LR_FAIL(LR_EINVAL, "lr_lru_train_ce_parity: form=%d R=%d C=%d", form, R, C);
+  if (form != 1 && (size_t)R * C > TR_MATERIALISE_ELEMS * 4)   // the stored forms index their logits with 32-bit offsets
+    LR_FAIL(LR_EINVAL, "lr_lru_train_ce_parity: R=%d x C=%d logits are more than this entry point takes", R, C);
+  const size_t need = lr_lru_train_ce_parity_workspace_bytes(form, R, C);
+  if (need > workspace_bytes) LR_FAIL(LR_EWORKSPACE, "lr_lru_train_ce_parity: workspace needs %zu bytes, have %zu", need, workspace_bytes);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (g_det_current.on) {   // an engine of this process left its map behind: this call adds in place
+    LrDetMap off = {};
+    LR_CHECK_HIP(hipDeviceSynchronize());
+    if (int rc = tr_det_publish(off, st)) return rc;
+  }
+  float* scal = (float*)workspace;
+  unsigned long long* ctr = (unsigned long long*)((char*)workspace + 64);
+  float* ws = (float*)((char*)workspace + TR_CE_PARITY_HEAD);
+  const long long* lab = (const long long*)labels;
+  LR_CHECK_HIP(hipMemsetAsync(workspace, 0, TR_CE_PARITY_HEAD, st));
+  // what the step's first launch does for these buffers: d x zeroed, the labelled rows in scal[1], the out-of-range labels in scal[3]
+  hipLaunchKernelGGL(tr_pass_init_kernel, dim3(512), dim3(256), 0, st, (float*)nullptr, (size_t)0, (float*)nullptr, (size_t)0, dX,
+                     (size_t)R * 64, scal, ctr, 0ull, lab, R, C - 1);
+  LR_CHECK_LAUNCH("tr_pass_init_kernel");
+  if (form == 0)
+    TR_RUN(lr_launch_train_scores(x, E, bias, lab, R, C, ws, scal, dX, dE, dbias, st));
+  else if (form == 1)
+    TR_RUN(lr_launch_train_ce(x, E, bias, lab, R, C, ws, scal, dX, dE, dbias, st));
+  else
+    TR_RUN(tr_launch_train_generic_ce(x, E, bias, lab, R, C, ws, scal, dX, dE, dbias, st));
+  TR_EW(tr_copy_kernel, (size_t)4, out_scal, scal, (size_t)4);
+  return LR_OK;
 }

@@ -12,6 +12,7 @@
 
 #include "lr_common.h"
 #include "lr_det.h"
+#include "lru_train_scores.h"
 LR_DET_DEFINE(ce)
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
@@ -353,6 +354,19 @@ size_t lr_train_ce_part_floats(int R, int C) {
   return (size_t)ce_chunks(rg, n_tiles) * R * 2 + (size_t)R;
 }
 
+// The launch's chunks, from the shape alone (lr_launch_train_ce and lr_lru_train_ce_plan both ask here): item tiles per
+// workgroup along grid.x in passes A and B, row tiles in pass C
+void lr_train_ce_plan(int R, int C, LrTrainCePlan* p) {
+  const int item_tiles = (C + 31) / 32, row_groups = (R + 127) / 128;
+  const int chunks = ce_chunks(row_groups, item_tiles);
+  p->item_tiles_per_chunk = (item_tiles + chunks - 1) / chunks;
+  p->item_chunks = (item_tiles + p->item_tiles_per_chunk - 1) / p->item_tiles_per_chunk;
+  const int row_tiles = (R + 31) / 32, item_groups = (C + 127) / 128;
+  const int rchunks = ce_chunks(item_groups, row_tiles);
+  p->row_tiles_per_chunk = (row_tiles + rchunks - 1) / rchunks;
+  p->row_chunks = (row_tiles + p->row_tiles_per_chunk - 1) / p->row_tiles_per_chunk;
+}
+
 // scal[1] (labelled rows) must already be there. dX must be zero; dE / dbias receive added contributions.
 int lr_launch_train_ce(const float* X, const float* E, const float* bias, const long long* labels, int R, int C,
                        float* ws_part /* lr_train_ce_part_floats */, float* scal, float* dX, float* dE, float* dbias,
@@ -368,12 +382,13 @@ int lr_launch_train_ce(const float* X, const float* E, const float* bias, const 
   a.dX = dX;
   a.dE = dE;
   a.dbias = dbias;
-  const int item_tiles = (C + 31) / 32, row_groups = (R + 127) / 128;
-  const int chunks = ce_chunks(row_groups, item_tiles);
-  a.tiles_per_chunk = (item_tiles + chunks - 1) / chunks;
-  a.n_chunks = (item_tiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk;
+  const int row_groups = (R + 127) / 128, item_groups = (C + 127) / 128;
+  LrTrainCePlan plan;
+  lr_train_ce_plan(R, C, &plan);
+  a.tiles_per_chunk = plan.item_tiles_per_chunk;
+  a.n_chunks = plan.item_chunks;
   a.part = ws_part;
-  a.lse = ws_part + (size_t)chunks * R * 2;
+  a.lse = ws_part + (size_t)ce_chunks(row_groups, (C + 31) / 32) * R * 2;
   hipLaunchKernelGGL(ce_stats_kernel, dim3(a.n_chunks, row_groups), dim3(256), 0, st, a);
   LR_CHECK_LAUNCH("ce_stats_kernel");
   hipLaunchKernelGGL(ce_finish_kernel, dim3((R + 3) / 4), dim3(256), 0, st, a);
@@ -382,10 +397,8 @@ int lr_launch_train_ce(const float* X, const float* E, const float* bias, const 
   LR_CHECK_LAUNCH("ce_dx_kernel");
   // pass C: items stationary, row tiles chunked
   CeArgs c = a;
-  const int row_tiles = (R + 31) / 32, item_groups = (C + 127) / 128;
-  const int rchunks = ce_chunks(item_groups, row_tiles);
-  c.tiles_per_chunk = (row_tiles + rchunks - 1) / rchunks;
-  c.n_chunks = (row_tiles + c.tiles_per_chunk - 1) / c.tiles_per_chunk;
+  c.tiles_per_chunk = plan.row_tiles_per_chunk;
+  c.n_chunks = plan.row_chunks;
   hipLaunchKernelGGL(ce_de_kernel, dim3(c.n_chunks, item_groups), dim3(256), 0, st, c);
   LR_CHECK_LAUNCH("ce_de_kernel");
   return LR_OK;

@@ -56,8 +56,10 @@ __device__ __forceinline__ float ts_e(const float4& v, int e) { return e == 0 ? 
 //   Ef [sb][nb][j][lane] = E[64 sb + 16 nb + li][16 j + 4 g ..]             (0 for items >= C)
 //   ETf[sb][j][nb][lane] = E[64 sb + 16 j + 4 g + e][16 nb + li], e = 0..3   (0 for items >= C)
 //   xTf[it][nb][lane]    = x[16 it + 4 g + e][16 nb + li], e = 0..3          (0 for rows >= R)
-//   biasf[v]             = bias[v] log2 e                                   (0 for items >= C): the logits are kept in the
-//                          log2 domain (x and the bias scaled by log2 e), so every exponential downstream is one v_exp_f32
+//   biasf[v]             = bias[v] log2 e                                   (TS_NEG for items >= C): the logits are kept in the
+//                          log2 domain (x and the bias scaled by log2 e), so every exponential downstream is one v_exp_f32.
+//                          A padded column's stored logit is TS_NEG + x . 0: its 2^(logit - lse2) is 0 whatever lse2 is (with 0
+//                          there and every real logit below -89, 2^(0 - lse2) was inf, and inf x E^T's 0 a NaN in d x)
 __global__ __launch_bounds__(256) void ts_fragments_kernel(TsArgs a) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   const int nsb = (a.ldl + 63) >> 6, nit = a.Rpad >> 4;
@@ -79,8 +81,8 @@ __global__ __launch_bounds__(256) void ts_fragments_kernel(TsArgs a) {
     v.w = item + 3 < a.C ? a.E[(size_t)(item + 3) * 64 + d] : 0.f;
     *reinterpret_cast<float4*>(a.ETf + u * 4) = v;
   } else if (t >= 2 * nE + nX) {
-    const long long u = t - 2 * nE - nX;   // bias x log2 e, 0 on the padding columns
-    if (u < a.ldl) a.biasf[u] = u < a.C ? a.bias[u] * TS_LOG2E : 0.f;
+    const long long u = t - 2 * nE - nX;   // bias x log2 e, TS_NEG on the padding columns
+    if (u < a.ldl) a.biasf[u] = u < a.C ? a.bias[u] * TS_LOG2E : TS_NEG;
   } else {
     const long long u = t - 2 * nE;
     const int it = (int)(u >> 8), nb = (int)(u >> 6) & 3;
@@ -271,7 +273,7 @@ __device__ __forceinline__ float4 ts_p4(float4 l, float lse2) {
 // ---- d x += dl E -------------------------------------------------------------------------------------------------------------
 // grid (row tiles of 64, a.ns2 item splits): a wave owns a 16-row panel, the four waves walk the same super-blocks; the splits
 // add into d x (a.ns2 adders per element; ts_combine_kernel left the one-hot term there). Columns past C: the logits there
-// are finite, E^T's fragments are 0.
+// are TS_NEG (softmax term 0), E^T's fragments are 0.
 __global__ __launch_bounds__(256) void ts_dx_kernel(TsArgs a) {
   __shared__ __attribute__((aligned(16))) float lt[4][16 * TS_LP];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
@@ -443,6 +445,29 @@ size_t lr_train_scores_ws_floats(int R, int C) {
   return ts_up64(rp * ldl) + 2 * nsb * 4096 + (rp / 16) * 1024 + ldl + ts_up64(rp) + ts_up64(rp) + ts_up64((size_t)R * TS_NS_MAX * 2);
 }
 
+// The launch's splits, from the shape alone (lr_launch_train_scores and lr_lru_train_ce_plan both ask here).
+// A workgroup is 64 TS_P rows (score pass; 64 rows in d x) x (items / splits): one full round of the chip's 256
+// workgroup slots per launch (both kernels hold > 128 registers per lane: one workgroup per CU)
+void lr_train_scores_plan(int R, int C, LrTrainScoresPlan* p) {
+  p->Rpad = ts_rpad(R);
+  p->nsb = (ts_ldl(C) + 63) / 64;
+  const int nrt = (R + 64 * TS_P - 1) / (64 * TS_P), n64 = (R + 63) / 64;
+  p->ns = 256 / nrt < 1 ? 1 : 256 / nrt > TS_NS_MAX ? TS_NS_MAX : 256 / nrt;
+  p->ns2 = 256 / n64 < 1 ? 1 : 256 / n64 > 8 ? 8 : 256 / n64;
+  if (p->ns > p->nsb) p->ns = p->nsb;
+  if (p->ns2 > p->nsb) p->ns2 = p->nsb;
+  {  // d E: P item panels x nq row parts, nq chosen for the shortest makespan on 256 CUs (a CU's workgroups run one after
+     // the other: f32 MFMA and vector work do not overlap across waves), parts of at least 8 row groups
+    const int P = (C + 63) / 64, nit = p->Rpad / 16;
+    p->nq = 1;
+    double best = 1e30;
+    for (int q = 1; q <= 8 && nit / q >= 8; ++q) {
+      const double span = (double)((P * q + 255) / 256) / q;   // rounds of workgroups x work per workgroup
+      if (span < best - 1e-9) { best = span; p->nq = q; }
+    }
+  }
+}
+
 int lr_launch_train_scores(const float* x, const float* E, const float* bias, const long long* labels, int R, int C, float* ws,
                            float* scal, float* dX, float* dE, float* dbias, hipStream_t st) {
   static bool lds_done[LR_MAX_DEVICES];
@@ -461,23 +486,10 @@ int lr_launch_train_scores(const float* x, const float* E, const float* bias, co
   a.lab32 = reinterpret_cast<int*>(p); p += ts_up64(a.Rpad);
   a.part = p;
   a.scal = scal; a.dX = dX; a.dE = dE; a.dbias = dbias;
-  // Splits: a workgroup is 64 TS_P rows (score pass; 64 rows in d x) x (items / splits): one full round of the chip's 256
-  // workgroup slots per launch (both kernels hold > 128 registers per lane: one workgroup per CU)
+  LrTrainScoresPlan plan;
+  lr_train_scores_plan(R, C, &plan);
+  a.ns = plan.ns; a.ns2 = plan.ns2; a.nq = plan.nq;
   const int nrt = (R + 64 * TS_P - 1) / (64 * TS_P), n64 = (R + 63) / 64;
-  a.ns = 256 / nrt < 1 ? 1 : 256 / nrt > TS_NS_MAX ? TS_NS_MAX : 256 / nrt;
-  a.ns2 = 256 / n64 < 1 ? 1 : 256 / n64 > 8 ? 8 : 256 / n64;
-  if (a.ns > nsb) a.ns = nsb;
-  if (a.ns2 > nsb) a.ns2 = nsb;
-  {  // d E: P item panels x nq row parts, nq chosen for the shortest makespan on 256 CUs (a CU's workgroups run one after
-     // the other: f32 MFMA and vector work do not overlap across waves), parts of at least 8 row groups
-    const int P = (C + 63) / 64, nit = a.Rpad / 16;
-    a.nq = 1;
-    double best = 1e30;
-    for (int q = 1; q <= 8 && nit / q >= 8; ++q) {
-      const double span = (double)((P * q + 255) / 256) / q;   // rounds of workgroups x work per workgroup
-      if (span < best - 1e-9) { best = span; a.nq = q; }
-    }
-  }
   const long long nt = 2LL * nsb * 1024 + (long long)(a.Rpad / 16) * 256 + a.ldl;
   hipLaunchKernelGGL(ts_fragments_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, a);
   LR_CHECK_LAUNCH("ts_fragments_kernel");

@@ -1,5 +1,7 @@
 """Retriever training step on the GPU (csrc/lru_train.hip through the C ABI) against the float64 oracle and the
 reference's own autograd / AdamW run (tests/golden/lru_train_v120.npz)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -300,3 +302,120 @@ def test_deterministic_mode_does_not_hide_a_non_finite_gradient(golden_dir):
         tok[0, -1] = 5                                   # the poisoned item is in the batch
         loss = float(eng.loss_and_grads(tok, z["labels"]))
         assert not np.isfinite(loss), (det, loss)
+
+
+# ---- the whole step against the float64 oracle past one scan chunk ---------------------------------------------------------------
+# tr_scan_fwd / tr_scan_bwd load 32 steps at a time: L = 1, 32, 33, 65, 97 are one step, one full chunk, a chunk and one step, two
+# chunks and one, three and one (the backward scan walks them downwards, d lambda crossing every seam). These tests look for errors
+# of a tensor's own size at the scan seams, the reset and the ragged 16-row panels (3, 64, 66, 195, 194 rows); the fine-grained
+# cross-entropy errors belong to tests/test_gpu_lru_train_ce_bounds.py.
+def seam_batch(B, L, V):
+    """Random left padding; from L = 65 on, row 0 is padding only (tokens and labels all 0) and row 1 carries a zero token at
+    the interior position L // 2 (label 0 there): the scan's live[t - 1] reset inside a sequence."""
+    rng = np.random.default_rng(1000 * B + L)
+    tok = rng.integers(1, V + 1, size=(B, L)).astype(np.int64)
+    lab = rng.integers(1, V + 1, size=(B, L)).astype(np.int64)
+    for b in range(B):
+        n_pad = int(rng.integers(0, L))
+        tok[b, :n_pad] = 0
+        lab[b, :n_pad] = 0
+    if L >= 65:
+        tok[0] = 0
+        lab[0] = 0
+        tok[1, :3] = 0
+        tok[1, 3:] = rng.integers(1, V + 1, size=L - 3)
+        lab[1] = np.where(tok[1] > 0, rng.integers(1, V + 1, size=L), 0)
+        tok[1, L // 2] = 0
+        lab[1, L // 2] = 0
+    return tok, lab
+
+
+@functools.lru_cache(maxsize=None)
+def seam_oracle(golden_dir, B, L, dropout=None):
+    """(tokens, labels, [(loss, grads) per pass]) -- the oracle runs once per shape, both engines are compared with it."""
+    from oracle import lru_train_oracle as TO
+
+    z, names = load(golden_dir)
+    init = {n: z["init/" + n] for n in names}
+    tok, lab = seam_batch(B, L, init["embedding.token.weight"].shape[0] - 1)
+    if dropout is None:
+        return tok, lab, [TO.loss_and_grads(init, tok, lab)]
+    seed, pd, pa = dropout
+    return tok, lab, [TO.loss_and_grads(init, tok, lab, dropout=(TO.pass_seed(seed, p), pd, pa)) for p in range(2)]
+
+
+@pytest.mark.parametrize("fused", [1, 0])
+@pytest.mark.parametrize("B,L", [(3, 1), (2, 32), (2, 33), (3, 65), (2, 97)])
+def test_step_matches_the_oracle_across_scan_chunks(golden_dir, B, L, fused):
+    z, names = load(golden_dir)
+    tok, lab, [(o_loss, o_grads)] = seam_oracle(golden_dir, B, L)
+    if L >= 65:
+        assert not tok[0].any() and tok[1, L // 2] == 0 and tok[1, L // 2 - 1] > 0 and tok[1, L // 2 + 1] > 0
+    eng = make_engine(z, names, ce_mode=0)
+    eng.set_fused(fused)
+    loss = float(eng.loss_and_grads(tok, lab))
+    assert abs(loss - o_loss) < 2e-5 * max(1.0, abs(o_loss)), (loss, o_loss)
+    got = eng.grad_dict()
+    for n in names:
+        assert np.abs(o_grads[n]).max() > 0, n
+        assert rel_err(as_pairs(got[n]), o_grads[n]) < 3e-4, (n, rel_err(as_pairs(got[n]), o_grads[n]))
+
+
+@pytest.mark.parametrize("fused", [1, 0])
+def test_step_with_dropout_matches_the_oracle_across_scan_chunks(golden_dir, fused):
+    """(3, 65) with the padding-only row and the interior zero token, dropout 0.2 / 0.3 under the oracle's restatement of the
+    kernels' masks, two consecutive passes."""
+    from llamarec_amd.train import LRUTrainEngine
+
+    z, names = load(golden_dir)
+    pd, pa, seed = 0.2, 0.3, 17
+    tok, lab, passes = seam_oracle(golden_dir, 3, 65, (seed, pd, pa))
+    eng = LRUTrainEngine({n: z["init/" + n] for n in names}, dropout=pd, attn_dropout=pa, seed=seed, ce_mode=0)
+    eng.set_fused(fused)
+    for pass_no, (o_loss, o_grads) in enumerate(passes):
+        loss = float(eng.loss_and_grads(tok, lab))
+        assert abs(loss - o_loss) < 2e-5 * max(1.0, abs(o_loss)), (pass_no, loss, o_loss)
+        got = eng.grad_dict()
+        for n in names:
+            assert rel_err(as_pairs(got[n]), o_grads[n]) < 5e-4, (pass_no, n, rel_err(as_pairs(got[n]), o_grads[n]))
+    assert abs(passes[0][0] - passes[1][0]) > 1e-3            # the two passes drew other masks
+
+
+# catalogue size: init_lru_state_dict(2080, seed=1) with embedding.token.weight scaled by CATALOGUE_FACTOR = 4, chosen on the CPU:
+# with every label equal to its own token the oracle's loss on this batch is 3.3914, 4.25 below ln 2081 = 7.6406 (factor 1 gives
+# 6.5414, 2 gives 5.4629, 3 gives 4.4097), so the softmax is far from flat. 33 x 65 = 2145 rows (1131 labelled): the stored form
+# runs ns = 21 item splits, 7 row parts, the fused form two item chunks and two row chunks.
+CATALOGUE_FACTOR = 4.0
+
+
+@functools.lru_cache(maxsize=None)
+def catalogue_oracle():
+    from oracle import lru_train_oracle as TO
+    from llamarec_amd.lru import init_lru_state_dict
+
+    sd = {k: as_pairs(np.asarray(v)).copy() for k, v in init_lru_state_dict(2080, seed=1).items()}
+    sd["embedding.token.weight"] = (sd["embedding.token.weight"] * np.float32(CATALOGUE_FACTOR)).astype(np.float32)
+    B, L, V = 33, 65, 2080
+    rng = np.random.default_rng(3365)
+    tok = rng.integers(1, V + 1, size=(B, L)).astype(np.int64)
+    for b in range(B):
+        tok[b, :int(rng.integers(0, L - 1))] = 0
+    lab = tok.copy()
+    o_loss, o_grads = TO.loss_and_grads(sd, tok, lab)
+    assert o_loss < np.log(2081.0) - 1.0 and abs(o_loss - 3.3914) < 1e-3, o_loss
+    return sd, tok, lab, o_loss, o_grads
+
+
+@pytest.mark.parametrize("ce_mode,fused", [(1, 1), (2, 1), (1, 0)])   # row-panel stored logits / fused / generic stored logits
+def test_step_matches_the_oracle_at_catalogue_size(ce_mode, fused):
+    from llamarec_amd.train import LRUTrainEngine
+
+    sd, tok, lab, o_loss, o_grads = catalogue_oracle()
+    eng = LRUTrainEngine(sd, dropout=0.0, attn_dropout=0.0, ce_mode=ce_mode)
+    eng.set_fused(fused)
+    loss = float(eng.loss_and_grads(tok, lab))
+    assert eng.bad_labels == 0
+    assert abs(loss - o_loss) < 2e-5 * max(1.0, abs(o_loss)), (loss, o_loss)
+    got = eng.grad_dict()
+    for n in sd:
+        assert rel_err(as_pairs(got[n]), o_grads[n]) < 3e-4, (n, rel_err(as_pairs(got[n]), o_grads[n]))
