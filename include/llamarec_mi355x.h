@@ -281,7 +281,9 @@ int lr_llama_set_variants(lr_llama_t* h, int32_t gemm_variant, int32_t attention
  * original_max_positions. LR_EINVAL for an unknown kind, a non-zero reserved word, factor < 1, original_max_positions < 1
  * or anything but 0 < low_freq_factor < high_freq_factor. */
 typedef struct LrRopeScaling {
-  int32_t kind;                    /* 0 = none (plain RoPE), 1 = llama3 */
+  int32_t kind;                    /* 0 = none (plain RoPE), 1 = llama3, 2 = linear: inv / factor at every frequency (reads
+                                    * factor only, finite and > 0; the three llama3 words must be zero, LR_EINVAL otherwise;
+                                    * Gemma-3's global layers) */
   float factor, low_freq_factor, high_freq_factor;
   int32_t original_max_positions;
   int32_t reserved[3];             /* must be zero */
@@ -345,6 +347,49 @@ int lr_llama_set_qkv_bias(lr_llama_t* h, const uint16_t* const* bqkv);
  * lr_llama_set_gemma2 (non-NULL) and lr_llama_set_qkv_bias (non-NULL) refuse a handle with q/k norms likewise), or a head_dim
  * that is not a power of two from 16 to 256. */
 int lr_llama_set_qk_norm(lr_llama_t* h, const uint16_t* const* q_norm, const uint16_t* const* k_norm);
+
+/* Gemma-3 (model_type "gemma3_text") on a handle created with the Gemma arch (norm_style 1, mlp_act 1, embed_scale
+ * bf16(sqrt(hidden))). What it adds to Gemma v1's layer, per HF Gemma3TextModel:
+ *   sandwich    as Gemma-2 (LrGemma2Ext above, same NAMES: post_norm stays the norm in front of the MLP)
+ *   q/k norm    a Gemma norm over head_dim on every q head and every k head between the projection and the rotation:
+ *               bf16(x * rsqrt(mean(x^2) + rms_eps) * (1 + w)) in fp32, one rounding (lr_qk_norm_rope_ex_bf16, norm_style 1)
+ *   layer kinds layer l is sliding when layer_is_sliding[l] == 1, global when 0
+ *   window      a sliding layer's query at position i sees keys j with i - sliding_window < j <= i (sliding_window keys, itself
+ *               included); a global layer the plain causal range
+ *   rotation    sliding layers: base rope_theta_local, unscaled. Global layers: LrLlamaConfig.rope_theta, every inverse
+ *               frequency divided by global_linear_factor (LrRopeScaling kind 2). The handle builds both tables per call and
+ *               every product that rotates -- the whole-prompt QKV sweep, the pruned last layer's K/V and Q sweeps, latency
+ *               mode -- reads the one of its layer. lr_llama_set_rope_scaling's words are not read by such a handle.
+ *   scores      q.k * head_dim^-0.5, no soft cap anywhere. attn_scale = 0 means that; any other value than head_dim^-0.5 is
+ *               LR_EUNSUPPORTED (the uncapped MFMA kernels have their scale compiled in, as for Gemma-2 without a cap).
+ * Routing: when every prompt of a call is within sliding_window tokens the window is the plain causal mask and the call runs
+ * exactly the kernels a Gemma handle with these norms would run, shared prefix and last-row mode included. When a prompt is
+ * longer, the sliding layers run the windowed head_dim-256 MFMA kernels (attention variants 0, 4 and 9 at head_dim 256; whole
+ * prompts and the pruned last layer's one-row mode: same bits) or, for any other head_dim or variant, the generic kernel with
+ * the window; the global layers run what they ran; and prefix_len is treated as 0 -- every prompt runs whole (same scores): no
+ * windowed kernel reads a shared prefix.
+ * q_norm / k_norm: bf16 [head_dim] permuted like a head's rows of wq / wk (entry 2i = HF's weight i, 2i + 1 = HF's weight
+ * i + head_dim / 2). All four weight arrays: HOST arrays [num_layers] of DEVICE pointers, 16-byte aligned; the caller keeps the
+ * device arrays alive (the host arrays are copied).
+ * LR_EINVAL, handle unchanged: sliding_window < 1, a layer kind other than 0 / 1, a non-finite or non-positive rope_theta_local, a
+ * non-finite or negative global_linear_factor or attn_scale, a null array, a null or misaligned entry, a non-zero reserved word.
+ * LR_EUNSUPPORTED, handle unchanged: a handle whose norm_style is not Gemma's, or one with folded norms, a Gemma-2 extension,
+ * q/k/v biases or Qwen3 norms; a head_dim that is not a power of two from 16 to 256. With the extension set,
+ * lr_llama_set_gemma2 (non-NULL), lr_llama_set_qkv_bias (non-NULL), lr_llama_set_qk_norm, lr_llama_set_folded_norms (non-NULL)
+ * and lr_llama_lora_create[_ex] return LR_EUNSUPPORTED. NULL: back to the plain Gemma layer. */
+typedef struct LrGemma3Ext {
+  int32_t sliding_window;           /* >= 1 */
+  float rope_theta_local;           /* the sliding layers' rotary base (rope_local_base_freq) */
+  float global_linear_factor;       /* 0 or 1 = none */
+  float attn_scale;                 /* 0 = head_dim^-0.5 */
+  int32_t reserved[4];              /* must be zero */
+  const uint8_t* layer_is_sliding;  /* HOST [num_layers]: 1 = sliding, 0 = global */
+  const uint16_t* const* q_norm;         /* HOST array [num_layers] of DEVICE bf16 [head_dim], packed order */
+  const uint16_t* const* k_norm;
+  const uint16_t* const* attn_out_norm;  /* HOST array [num_layers] of DEVICE bf16 [hidden]: HF's post_attention_layernorm */
+  const uint16_t* const* mlp_out_norm;   /* HF's post_feedforward_layernorm */
+} LrGemma3Ext;
+int lr_llama_set_gemma3(lr_llama_t* h, const LrGemma3Ext* ext);
 
 /* Folded RMSNorm (optional, scoring path only). HF's layer computes  proj(norm_w * bf16(x * rstd))  with its own
  * read-and-write pass over the residual stream in front of q/k/v_proj and of gate/up_proj (LlamaRMSNorm, reached from
@@ -532,6 +577,19 @@ int lr_attention_last_rows_softcap(const uint16_t* kv, const uint16_t* q_last, u
                                    const int32_t* seg_starts_host, int32_t S, int32_t prefix_len, int32_t num_heads,
                                    int32_t num_kv_heads, int32_t head_dim, float scale, float cap, int32_t variant,
                                    void* hip_stream);
+/* The same two with a sliding window (Gemma-3's sliding layers; exposed for parity tests): query i sees keys j with
+ * i - window < j <= i. window <= 0, or window >= the longest sequence (prefix included), masks nothing and routes to
+ * lr_attention_varlen_prefix / lr_attention_last_rows: same checks, same kernels, bit-identical results. Otherwise prefix_len
+ * must be 0 (LR_EUNSUPPORTED: no windowed kernel reads a shared prefix) and, after the segment checks of those two, variants 0
+ * and 4 at head_dim 256 run the windowed MFMA kernels, variant 1 -- and 0 / 4 at any other head_dim -- the generic kernel with
+ * the window, and every other variant returns LR_EUNSUPPORTED; lr_attention_last_rows_window needs head_dim 256 and variant
+ * 0 / 4, and writes for every prompt the bits lr_attention_varlen_window writes for that prompt's last row. */
+int lr_attention_varlen_window(const uint16_t* qkv, uint16_t* out, const int32_t* seg_starts, const int32_t* seg_starts_host,
+                               int32_t S, int32_t prefix_len, int32_t num_heads, int32_t num_kv_heads, int32_t head_dim,
+                               int32_t window, int32_t variant, void* hip_stream);
+int lr_attention_last_rows_window(const uint16_t* kv, const uint16_t* q_last, uint16_t* out_last, const int32_t* seg_starts,
+                                  const int32_t* seg_starts_host, int32_t S, int32_t prefix_len, int32_t num_heads,
+                                  int32_t num_kv_heads, int32_t head_dim, int32_t window, int32_t variant, void* hip_stream);
 /* Gemma-2's sandwich norm on [rows][d] bf16 DEVICE rows (exposed for parity tests), Gemma norms with fp32 statistics:
  *   x  <- bf16( float(x) + float(bf16(h * rsqrt(mean(h^2) + eps) * (1 + w_out))) )       in place
  *   xn  = bf16( x * rsqrt(mean(x^2) + eps) * (1 + w_next) )                               when w_next != NULL
@@ -554,6 +612,13 @@ int lr_rmsnorm_bf16(const uint16_t* x, const uint16_t* w, uint16_t* out, int32_t
 int lr_qk_norm_rope_bf16(uint16_t* buf, int32_t rows, int32_t ld, int32_t col0, int32_t nq, int32_t nk, int32_t head_dim,
                          const uint16_t* q_norm, const uint16_t* k_norm, float eps, const int32_t* tok_pos, const float* rope_cs,
                          void* hip_stream);
+
+/* The same sweep with the norm's rounding as a trailing argument: norm_style 0 = the call above (same kernel, same bits),
+ * 1 = Gemma-3's y = bf16(x * rsqrt(mean(x^2) + eps) * (1 + w)) in fp32 with one rounding; the rotation is unchanged. Any other
+ * norm_style is LR_EINVAL. */
+int lr_qk_norm_rope_ex_bf16(uint16_t* buf, int32_t rows, int32_t ld, int32_t col0, int32_t nq, int32_t nk, int32_t head_dim,
+                            const uint16_t* q_norm, const uint16_t* k_norm, float eps, const int32_t* tok_pos,
+                            const float* rope_cs, void* hip_stream, int32_t norm_style);
 
 /* ------------------------------------------------------------------------------------------
  * Optional in-library kernel timing (HIP events on the caller's stream). Not part of the

@@ -69,7 +69,7 @@ class LrLlamaArch(C.Structure):
 
 class LrRopeScaling(C.Structure):
     _fields_ = [
-        ("kind", C.c_int32),                  # 0 = none, 1 = llama3
+        ("kind", C.c_int32),                  # 0 = none, 1 = llama3, 2 = linear (factor only)
         ("factor", C.c_float),
         ("low_freq_factor", C.c_float),
         ("high_freq_factor", C.c_float),
@@ -86,6 +86,22 @@ class LrGemma2Ext(C.Structure):
         ("attn_scale", C.c_float),             # 0 = head_dim ** -0.5
         ("reserved", C.c_int32 * 5),
         ("attn_out_norm", C.POINTER(C.c_void_p)),   # host array [num_layers] of device pointers, or NULL with mlp_out_norm
+        ("mlp_out_norm", C.POINTER(C.c_void_p)),
+    ]
+
+
+class LrGemma3Ext(C.Structure):
+    """include/llamarec_mi355x.h: LrGemma3Ext (lr_llama_set_gemma3)."""
+    _fields_ = [
+        ("sliding_window", C.c_int32),
+        ("rope_theta_local", C.c_float),
+        ("global_linear_factor", C.c_float),   # 0 or 1 = none
+        ("attn_scale", C.c_float),             # 0 = head_dim ** -0.5
+        ("reserved", C.c_int32 * 4),
+        ("layer_is_sliding", C.POINTER(C.c_uint8)),   # host [num_layers]
+        ("q_norm", C.POINTER(C.c_void_p)),            # host arrays [num_layers] of device pointers
+        ("k_norm", C.POINTER(C.c_void_p)),
+        ("attn_out_norm", C.POINTER(C.c_void_p)),
         ("mlp_out_norm", C.POINTER(C.c_void_p)),
     ]
 

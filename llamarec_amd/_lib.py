@@ -86,10 +86,13 @@ PROTOTYPES = {
     "lr_llama_set_last_layer_pruning": (C.c_int, [C.c_void_p, C.c_int32]),
     "lr_llama_set_rope_scaling": (C.c_int, [C.c_void_p, C.POINTER(A.LrRopeScaling)]),
     "lr_llama_set_gemma2": (C.c_int, [C.c_void_p, C.POINTER(A.LrGemma2Ext)]),
+    "lr_llama_set_gemma3": (C.c_int, [C.c_void_p, C.POINTER(A.LrGemma3Ext)]),
     "lr_llama_set_qkv_bias": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lr_llama_set_qk_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lr_qk_norm_rope_bf16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lr_qk_norm_rope_ex_bf16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "lr_qk_norm_bwd_bf16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "lr_fold_norm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -125,6 +128,10 @@ PROTOTYPES = {
     "lr_attention_last_rows_softcap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32,
                                                  C.c_void_p]),
+    "lr_attention_varlen_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "lr_attention_last_rows_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "lr_residual_postnorm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_float, C.c_void_p]),
     "lr_rmsnorm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),

@@ -15,8 +15,9 @@ STATE_DICT_KEY = "model_state_dict"
 RAW_DATASET_ROOT_FOLDER = "data"
 # --llm -> base model / tokenizer of the reference's set_template (config.py:29-55). The ranker's kernels serve the llama
 # (llama2, llama3, mistral), gemma, gemma2, phi3, qwen2 and qwen3 families (llm.model_family; phi3 and qwen2 for scoring only,
-# plain RoPE; qwen3 -- not a choice of the reference's -- scores and trains, with Llama-2's batch sizes).
-LLM_CHOICES = ["llama2", "llama3", "phi3", "gemma", "mistral", "gemma2", "qwen2", "qwen3"]
+# plain RoPE; qwen3 -- not a choice of the reference's -- scores and trains, with Llama-2's batch sizes; gemma3 -- not a choice
+# of the reference's either -- scores only, with Gemma's batch sizes).
+LLM_CHOICES = ["llama2", "llama3", "phi3", "gemma", "mistral", "gemma2", "qwen2", "gemma3", "qwen3"]
 LLM_BASE_MODELS = {
     "phi3": "microsoft/Phi-3-mini-4k-instruct",
     "llama2": "meta-llama/Llama-2-7b-hf",
@@ -26,6 +27,7 @@ LLM_BASE_MODELS = {
     "gemma2": "google/gemma-2-9b",
     "qwen2": "Qwen/Qwen2-0.5B",
     "qwen3": "Qwen/Qwen3-0.6B",
+    "gemma3": "google/gemma-3-1b-pt",
 }
 DEFAULT_LLM_BASE = "meta-llama/Llama-2-7b-hf"
 
@@ -137,7 +139,8 @@ def set_template(args):
             args.llm_base_model = LLM_BASE_MODELS[llm]
         if args.llm_base_tokenizer == DEFAULT_LLM_BASE:
             args.llm_base_tokenizer = LLM_BASE_MODELS[llm]
-    llm_div = {"llama3": 2, "gemma": 4}.get(llm, 1)       # config.py:90-102: llama3 halves the batches, gemma quarters them
+    # config.py:90-102: llama3 halves the batches, gemma quarters them (gemma3 takes Gemma's)
+    llm_div = {"llama3": 2, "gemma": 4, "gemma3": 4}.get(llm, 1)
     if args.train_batch_size is None:                      # config.py:90-107
         args.train_batch_size = (32 if ml else 16) // llm_div if args.model_code == "llm" else (16 if ml else 64)
     if args.lr is None:                                    # config.py:121-124

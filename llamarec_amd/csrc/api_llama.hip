@@ -101,6 +101,7 @@ extern "C" int lr_llama_set_gemma2(lr_llama_t* h, const LrGemma2Ext* e) {
       LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_gemma2: attn_scale %g without a soft cap (the uncapped kernels scale by "
               "head_dim^-0.5 = %g)", (double)scale, (double)own);
     if (h->wqkv_folded) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_gemma2: the handle has folded norms");
+    if (h->gemma3) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_gemma2: the handle has a Gemma-3 extension (lr_llama_set_gemma3)");
     if (h->q_norm) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_gemma2: the handle has q/k norms (lr_llama_set_qk_norm)");
     if (e->attn_out_norm) {
       an = (const uint16_t**)malloc(sizeof(void*) * L);
@@ -114,6 +115,7 @@ extern "C" int lr_llama_set_gemma2(lr_llama_t* h, const LrGemma2Ext* e) {
       memcpy(mn, e->mlp_out_norm, sizeof(void*) * L);
     }
   }
+  if (!e && h->gemma3) return LR_OK;   // nothing of Gemma-2 is set: the out-norms are the Gemma-3 extension's
   free(h->attn_out_norm);
   free(h->mlp_out_norm);
   h->attn_out_norm = an;
@@ -136,6 +138,7 @@ extern "C" int lr_llama_set_qkv_bias(lr_llama_t* h, const uint16_t* const* bqkv)
       if ((reinterpret_cast<uintptr_t>(bqkv[l]) & 7) || (h->cfg.num_heads * h->cfg.head_dim) % 4 != 0)
         LR_FAIL(LR_EINVAL, "lr_llama_set_qkv_bias: layer %d's bias is not 8-byte aligned", l);
     if (h->wqkv_folded) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_qkv_bias: the handle has folded norms");
+    if (h->gemma3) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_qkv_bias: the handle has a Gemma-3 extension (lr_llama_set_gemma3)");
     if (h->q_norm) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_qkv_bias: the handle has q/k norms (lr_llama_set_qk_norm)");
     own = (const uint16_t**)malloc(sizeof(void*) * L);
     if (!own) LR_FAIL(LR_EINVAL, "lr_llama_set_qkv_bias: out of host memory");
@@ -151,6 +154,8 @@ extern "C" int lr_llama_set_qk_norm(lr_llama_t* h, const uint16_t* const* q_norm
   const int L = h->cfg.num_layers;
   const uint16_t **qn = nullptr, **kn = nullptr;
   if ((q_norm == nullptr) != (k_norm == nullptr)) LR_FAIL(LR_EINVAL, "lr_llama_set_qk_norm: give both arrays or neither");
+  // (NULL, NULL too: the norms of such a handle are the extension's, and lr_llama_set_gemma3(h, NULL) takes them off)
+  if (h->gemma3) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_qk_norm: the handle has a Gemma-3 extension (lr_llama_set_gemma3)");
   if (q_norm) {   // every check before the handle changes
     for (int l = 0; l < L; ++l)
       if (!q_norm[l] || !k_norm[l]) LR_FAIL(LR_EINVAL, "lr_llama_set_qk_norm: layer %d has a null norm weight", l);
@@ -179,6 +184,88 @@ extern "C" int lr_llama_set_qk_norm(lr_llama_t* h, const uint16_t* const* q_norm
   return LR_OK;
 }
 
+// Gemma-3: see include/llamarec_mi355x.h. The extension fills the handle's out-norm and q/k-norm arrays (run_body reads them as it
+// does for Gemma-2 and Qwen3) and adds what is Gemma-3's own: the window, the layer kinds and the second rotary table.
+extern "C" int lr_llama_set_gemma3(lr_llama_t* h, const LrGemma3Ext* e) {
+  const char* who = "lr_llama_set_gemma3";
+  if (!h) LR_FAIL(LR_EINVAL, "%s: null handle", who);
+  const int L = h->cfg.num_layers;
+  if (!e) {
+    if (!h->gemma3) return LR_OK;
+    free(h->attn_out_norm);
+    free(h->mlp_out_norm);
+    free(h->q_norm);
+    free(h->k_norm);
+    free(h->layer_sliding);
+    h->attn_out_norm = h->mlp_out_norm = h->q_norm = h->k_norm = nullptr;
+    h->layer_sliding = nullptr;
+    h->gemma3 = h->window = 0;
+    h->rope_theta_local = h->global_linear_factor = 0.f;
+    return LR_OK;
+  }
+  // every check before the handle changes
+  if (e->sliding_window < 1) LR_FAIL(LR_EINVAL, "%s: sliding_window %d (>= 1)", who, e->sliding_window);
+  if (!(e->rope_theta_local > 0.f) || !(e->rope_theta_local < __builtin_inff()) || !finite_nonneg(e->global_linear_factor) ||
+      !finite_nonneg(e->attn_scale))
+    LR_FAIL(LR_EINVAL, "%s: rope_theta_local=%g (finite and > 0) global_linear_factor=%g attn_scale=%g (finite and >= 0)", who,
+            (double)e->rope_theta_local, (double)e->global_linear_factor, (double)e->attn_scale);
+  for (int i = 0; i < 4; ++i)
+    if (e->reserved[i]) LR_FAIL(LR_EINVAL, "%s: reserved word %d is not zero", who, i);
+  if (!e->layer_is_sliding || !e->q_norm || !e->k_norm || !e->attn_out_norm || !e->mlp_out_norm)
+    LR_FAIL(LR_EINVAL, "%s: a null array (layer kinds, q_norm, k_norm, attn_out_norm, mlp_out_norm)", who);
+  for (int l = 0; l < L; ++l) {
+    if (e->layer_is_sliding[l] > 1) LR_FAIL(LR_EINVAL, "%s: layer %d's kind is %d (0 global, 1 sliding)", who, l, e->layer_is_sliding[l]);
+    if (!e->q_norm[l] || !e->k_norm[l] || !e->attn_out_norm[l] || !e->mlp_out_norm[l])
+      LR_FAIL(LR_EINVAL, "%s: layer %d has a null norm weight", who, l);
+    // the sweep and the sandwich-norm kernel load their weights 16 bytes at a time
+    if ((reinterpret_cast<uintptr_t>(e->q_norm[l]) | reinterpret_cast<uintptr_t>(e->k_norm[l]) |
+         reinterpret_cast<uintptr_t>(e->attn_out_norm[l]) | reinterpret_cast<uintptr_t>(e->mlp_out_norm[l])) & 15)
+      LR_FAIL(LR_EINVAL, "%s: layer %d's norm weights are not 16-byte aligned", who, l);
+  }
+  if (h->arch.norm_style != 1)
+    LR_FAIL(LR_EUNSUPPORTED, "%s: needs a handle with the Gemma norm (norm_style %d)", who, h->arch.norm_style);
+  if (h->wqkv_folded) LR_FAIL(LR_EUNSUPPORTED, "%s: the handle has folded norms", who);
+  if (h->gemma2) LR_FAIL(LR_EUNSUPPORTED, "%s: the handle has a Gemma-2 extension (lr_llama_set_gemma2)", who);
+  if (h->bqkv) LR_FAIL(LR_EUNSUPPORTED, "%s: the handle has q/k/v biases (lr_llama_set_qkv_bias)", who);
+  if (h->q_norm && !h->gemma3) LR_FAIL(LR_EUNSUPPORTED, "%s: the handle has Qwen3 q/k norms (lr_llama_set_qk_norm)", who);
+  if (!lr_qk_norm_head_dim_ok(h->cfg.head_dim))
+    LR_FAIL(LR_EUNSUPPORTED, "%s: head_dim %d (the q/k norm sweep takes a power of two from 16 to 256)", who, h->cfg.head_dim);
+  const float own = 1.0f / sqrtf((float)h->cfg.head_dim);
+  if (e->attn_scale > 0.f && e->attn_scale != own)
+    LR_FAIL(LR_EUNSUPPORTED, "%s: attn_scale %g (the uncapped kernels scale by head_dim^-0.5 = %g)", who, (double)e->attn_scale,
+            (double)own);
+  const uint16_t** arr[4] = {nullptr, nullptr, nullptr, nullptr};
+  const uint16_t* const* src[4] = {e->attn_out_norm, e->mlp_out_norm, e->q_norm, e->k_norm};
+  uint8_t* kinds = (uint8_t*)malloc((size_t)L);
+  bool ok = kinds != nullptr;
+  for (int i = 0; i < 4; ++i) {
+    arr[i] = (const uint16_t**)malloc(sizeof(void*) * L);
+    ok = ok && arr[i];
+  }
+  if (!ok) {
+    free(kinds);
+    for (int i = 0; i < 4; ++i) free(arr[i]);
+    LR_FAIL(LR_EINVAL, "%s: out of host memory", who);
+  }
+  for (int i = 0; i < 4; ++i) memcpy(arr[i], src[i], sizeof(void*) * L);
+  memcpy(kinds, e->layer_is_sliding, (size_t)L);
+  free(h->attn_out_norm);
+  free(h->mlp_out_norm);
+  free(h->q_norm);
+  free(h->k_norm);
+  free(h->layer_sliding);
+  h->attn_out_norm = arr[0];
+  h->mlp_out_norm = arr[1];
+  h->q_norm = arr[2];
+  h->k_norm = arr[3];
+  h->layer_sliding = kinds;
+  h->gemma3 = 1;
+  h->window = e->sliding_window;
+  h->rope_theta_local = e->rope_theta_local;
+  h->global_linear_factor = (e->global_linear_factor > 0.f && e->global_linear_factor != 1.0f) ? e->global_linear_factor : 0.f;
+  return LR_OK;
+}
+
 extern "C" int lr_llama_set_last_layer_pruning(lr_llama_t* h, int32_t enable) {
   if (!h) LR_FAIL(LR_EINVAL, "lr_llama_set_last_layer_pruning: null handle");
   h->prune_last = enable ? 1 : 0;
@@ -195,6 +282,7 @@ extern "C" void lr_llama_destroy(lr_llama_t* h) {
   free(h->bqkv);
   free(h->q_norm);
   free(h->k_norm);
+  free(h->layer_sliding);
   free(h);
 }
 
@@ -214,6 +302,8 @@ extern "C" int lr_llama_set_folded_norms(lr_llama_t* h, const uint16_t* const* w
     LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: not with a Gemma-2 extension (lr_llama_set_gemma2)");
   if (h->bqkv && (wqkv_folded || wgu_folded))
     LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: not with q/k/v biases (lr_llama_set_qkv_bias)");
+  if (h->gemma3 && (wqkv_folded || wgu_folded))
+    LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: not with a Gemma-3 extension (lr_llama_set_gemma3)");
   if (h->q_norm && (wqkv_folded || wgu_folded))
     LR_FAIL(LR_EUNSUPPORTED, "lr_llama_set_folded_norms: not with q/k norms (lr_llama_set_qk_norm)");
   free(h->wqkv_folded);
@@ -234,6 +324,7 @@ extern "C" int lr_llama_set_folded_norms(lr_llama_t* h, const uint16_t* const* w
 struct LlamaWs {
   int32_t *tok_pos, *tok_src, *last_rows, *last_pos, *seg_start;
   float *rope, *rstd;
+  float* rope_local;                          // Gemma-3: the sliding layers' fp32 table (null without the extension)
   u16 *x, *xn, *qkv, *att, *hmid;
   u16 *x_last, *xn_last, *att_last, *h_last, *q_last;  // compact [B][.] buffers of the pruned last layer
   LrGemmSplitK splitk;                        // fp32 partial planes of the split-K GEMMs (gemm variant 5)
@@ -245,7 +336,7 @@ struct LlamaWs {
   size_t total;
 };
 
-static LlamaWs carve(const LrLlamaConfig& c, int max_tokens, int max_seqs, char* base) {
+static LlamaWs carve(const LrLlamaConfig& c, int max_tokens, int max_seqs, char* base, bool two_rope_tables) {
   LlamaWs w;
   w.compact = false;
   size_t o = 0;
@@ -263,6 +354,8 @@ static LlamaWs carve(const LrLlamaConfig& c, int max_tokens, int max_seqs, char*
   const size_t rope_rows = (size_t)(c.max_positions < max_tokens ? c.max_positions : max_tokens);
   w.rope = (float*)take(rope_rows * (c.head_dim / 2) * 2 * sizeof(float));
   w.rope16 = (unsigned*)take(rope_rows * (c.head_dim / 2) * sizeof(unsigned));
+  // (the q/k sweep, the only reader of a Gemma-3 handle's tables, reads the fp32 form)
+  w.rope_local = two_rope_tables ? (float*)take(rope_rows * (c.head_dim / 2) * 2 * sizeof(float)) : nullptr;
   w.rstd = (float*)take(n * sizeof(float));
   w.x = (u16*)take(n * c.hidden_size * 2);
   w.xn = (u16*)take(n * c.hidden_size * 2);
@@ -290,7 +383,7 @@ extern "C" size_t lr_llama_workspace_bytes(const lr_llama_t* h, int32_t max_toke
   if (!h || max_tokens < 1) return 0;
   if (max_seqs < 1) max_seqs = 1;
   if (max_seqs > max_tokens) max_seqs = max_tokens;
-  return carve(h->cfg, max_tokens, max_seqs, nullptr).total;
+  return carve(h->cfg, max_tokens, max_seqs, nullptr, h->gemma3 != 0).total;
 }
 
 // What run_body derives from a prompt batch before any launch: the internal layout, the carved workspace and seg_host, the
@@ -300,6 +393,7 @@ extern "C" size_t lr_llama_workspace_bytes(const lr_llama_t* h, int32_t max_toke
 // exactly the operands of the unshared run, so the scores are bit-identical to prefix_len = 0.
 struct PrefillPlan {
   int P, n, S, maxT;              // shared prefix in effect, internal rows, segments, longest prompt
+  bool windowed;                  // Gemma-3 with a prompt longer than the window: the sliding layers run windowed kernels
   std::vector<int32_t> seg_host;  // [S + 1]
   LlamaWs ws;
 };
@@ -314,8 +408,12 @@ static int plan_batch(const lr_llama_t* h, const int32_t* cu_host, int B, int P,
     LR_FAIL(LR_EINVAL, "llama prefill: shared prefix of %d tokens, shortest prompt has %d (every prompt keeps >= 1 own token)",
             P, minT);
   if (B == 1 || !lr_attention_reads_prefix(h->attn_variant, c.head_dim, h->attn_softcap)) P = 0;
+  // Gemma-3: a prompt longer than the window makes the sliding layers windowed, and the windowed kernels read no shared prefix:
+  // the call runs every prompt whole (same scores). Within the window the window is the causal mask and nothing changes.
+  out->windowed = h->gemma3 && out->maxT > h->window;
+  if (out->windowed) P = 0;
   const int n_in = cu_host[B];
-  out->ws = carve(c, n_in, B, (char*)workspace);
+  out->ws = carve(c, n_in, B, (char*)workspace, h->gemma3 != 0);
   if (out->ws.total > workspace_bytes)
     LR_FAIL(LR_EWORKSPACE, "llama prefill: workspace needs %zu bytes for %d tokens, have %zu", out->ws.total, n_in,
             workspace_bytes);
@@ -370,7 +468,13 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
   };
   LR_RUN(lr_launch_token_meta(cu, B, P, ws.seg_start, ws.tok_pos, ws.tok_src, ws.last_rows, st, ws.last_pos, ids,
                               ws.prefix_bad));
-  LR_RUN(lr_launch_rope_table(ws.rope, plan.maxT, hd, c.rope_theta, st, ws.rope16, &h->rope_scaling));
+  if (h->gemma3) {   // global layers: rope_theta with the linear factor; sliding layers: rope_theta_local, unscaled
+    const LrRopeScaling lin = {2, h->global_linear_factor, 0.f, 0.f, 0, {0, 0, 0}};
+    LR_RUN(lr_launch_rope_table(ws.rope, plan.maxT, hd, c.rope_theta, st, ws.rope16, h->global_linear_factor > 0.f ? &lin : nullptr));
+    LR_RUN(lr_launch_rope_table(ws.rope_local, plan.maxT, hd, h->rope_theta_local, st));
+  } else {
+    LR_RUN(lr_launch_rope_table(ws.rope, plan.maxT, hd, c.rope_theta, st, ws.rope16, &h->rope_scaling));
+  }
   if (attn_kernel == LR_ATTN_ROWS256)
     LR_RUN(lr_launch_attn256_items(ws.seg_start, S, n, nh, P, ws.attn_items, ws.attn_items_bytes, st));
   LR_RUN(lr_launch_embed(ids, ws.tok_src, h->embed, c.vocab_size, d, ws.x, n, st, h->arch.embed_scale));
@@ -391,7 +495,18 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
     // needed for B rows only -- K and V for all of them. The projection runs on the K | V rows of wqkv (2/3 of the
     // product) for every row and on its Q rows for the B last rows; the attention kernel then evaluates ONE query row
     // per (prompt, head) over the prompt's keys instead of every tile.
-    const bool last_q_only = last_pruned && !folded && lr_attention_has_last_row_mode(attn_kernel, hd) && gv != 1;
+    // Gemma-3: a sliding layer reads the local rotary table and, when the call has a prompt longer than the window
+    // (plan.windowed), attends through the window: HD256's windowed kernels where HD256 was resolved, the generic kernel with
+    // the window everywhere else (no other MFMA kernel has a windowed form)
+    const bool sliding = h->gemma3 && h->layer_sliding[l];
+    const float* const rope_l = sliding ? ws.rope_local : ws.rope;
+    const int qk_ns = h->gemma3 ? 1 : 0;   // the sweep's norm: Gemma's (1 + w) in fp32, or Qwen3's
+    const int win = (plan.windowed && sliding) ? h->window : 0;
+    const LrAttnKernel kernel_l = (win && attn_kernel != LR_ATTN_HD256) ? LR_ATTN_GENERIC : attn_kernel;
+    const bool mfma_l = win ? kernel_l == LR_ATTN_HD256 : attn_mfma;
+    LrAttnArgs attn_l = attn;
+    attn_l.window = win;
+    const bool last_q_only = last_pruned && !folded && lr_attention_has_last_row_mode(kernel_l, hd) && gv != 1;
     if (folded && !EXP_SKIP_SWEEP) LR_RUN(lr_launch_rms_rstd(ws.x, ws.rstd, n, d, c.rms_eps, st));
     if (!folded && !input_normed) LR_RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st, ns));
     const int q_w = nh * hd, kv_w = 2 * nkv * hd;
@@ -404,32 +519,32 @@ static int run_body(lr_llama_t* h, const int32_t* ids, const int32_t* cu, const 
       LR_RUN(lr_launch_gemm({.A = ws.xn, .B = w.wqkv + (size_t)q_w * d, .C = ws.qkv, .M = n, .N = kv_w, .K = d,
                              .epi = epi_qkv, .variant = gv, .rope = qn ? LrGemmRope{} : rope(ws.tok_pos, kv_w / 2),
                              .bias = bias ? bias + q_w : nullptr, .splitk = ws.splitk}, st));
-      if (qn) LR_RUN(lr_launch_qk_norm_rope(ws.qkv, n, kv_w, 0, nkv, hd, nullptr, kn, c.rms_eps, ws.tok_pos, ws.rope, st));
+      if (qn) LR_RUN(lr_launch_qk_norm_rope(ws.qkv, n, kv_w, 0, nkv, hd, nullptr, kn, c.rms_eps, ws.tok_pos, rope_l, st, qk_ns));
       LR_RUN(lr_launch_gather_rows(ws.xn, ws.last_rows, B, d, ws.xn_last, st));
       LR_RUN(lr_launch_gemm({.A = ws.xn_last, .B = w.wqkv, .C = ws.q_last, .M = B, .N = q_w, .K = d, .epi = epi_qkv,
                              .variant = pv, .rope = qn ? LrGemmRope{} : rope(ws.last_pos, q_w), .bias = bias,
                              .splitk = ws.splitk}, st));
-      if (qn) LR_RUN(lr_launch_qk_norm_rope(ws.q_last, B, q_w, nh, 0, hd, qn, nullptr, c.rms_eps, ws.last_pos, ws.rope, st));
+      if (qn) LR_RUN(lr_launch_qk_norm_rope(ws.q_last, B, q_w, nh, 0, hd, qn, nullptr, c.rms_eps, ws.last_pos, rope_l, st, qk_ns));
       LR_RUN(lr_launch_attention_last(ws.qkv, ws.q_last, ws.att_last, attn.cu, attn.cu_host, S, n, nh, nkv, hd, st, P, a_scale,
-                                      a_cap));
+                                      a_cap, win));
     } else {
       LR_RUN(lr_launch_gemm({.A = folded ? ws.x : ws.xn, .B = folded ? h->wqkv_folded[l] : w.wqkv, .C = ws.qkv, .M = n,
                              .N = q_w + kv_w, .K = d, .epi = epi_qkv, .variant = gv,
                              .rope = qn ? LrGemmRope{} : rope(ws.tok_pos, q_w + kv_w / 2),
                              .row_scale = folded ? ws.rstd : nullptr, .bias = bias, .splitk = ws.splitk}, st));
-      if (qn) LR_RUN(lr_launch_qk_norm_rope(ws.qkv, n, q_w + kv_w, nh, nkv, hd, qn, kn, c.rms_eps, ws.tok_pos, ws.rope, st));
+      if (qn) LR_RUN(lr_launch_qk_norm_rope(ws.qkv, n, q_w + kv_w, nh, nkv, hd, qn, kn, c.rms_eps, ws.tok_pos, rope_l, st, qk_ns));
     }
     if (!last_pruned) {
-      LR_RUN(lr_launch_attention(attn, attn_kernel, st));
+      LR_RUN(lr_launch_attention(attn_l, kernel_l, st));
     } else {
       // Only each prompt's LAST token is consumed after the final layer (model/llm.py:131), so the
       // last layer needs K/V for every token but attention output, o_proj, and the MLP for B rows only.
       // last_q_only: ws.att_last already holds the attention rows of the last tokens
-      if (!last_q_only && attn_mfma) {
-        LR_RUN(lr_launch_attention(attn, attn_kernel, st));
+      if (!last_q_only && mfma_l) {
+        LR_RUN(lr_launch_attention(attn_l, kernel_l, st));
         LR_RUN(lr_launch_gather_rows(ws.att, ws.last_rows, B, nh * hd, ws.att_last, st));
       } else if (!last_q_only) {
-        LR_RUN(lr_launch_attention_rows(ws.qkv, ws.att_last, cu, B, ws.last_rows, B, nh, nkv, hd, st, a_scale, a_cap));
+        LR_RUN(lr_launch_attention_rows(ws.qkv, ws.att_last, cu, B, ws.last_rows, B, nh, nkv, hd, st, a_scale, a_cap, win));
       }
       LR_RUN(lr_launch_gather_rows(ws.x, ws.last_rows, B, d, ws.x_last, st));
       ws.compact = true;   // and this was the last layer
@@ -764,6 +879,62 @@ extern "C" int lr_attention_last_rows_softcap(const uint16_t* kv, const uint16_t
                                   scale > 0.f ? scale : 1.0f / sqrtf((float)head_dim), cap);
 }
 
+// The windowed pair (Gemma-3's sliding layers). A window that masks nothing -- <= 0, or >= the longest segment -- is the plain
+// causal call: the uncapped entry point's own path (and bits).
+static int check_window_request(const char* who, const int32_t* cu_host, int S, int prefix_len, int nh, int nkv, int hd,
+                                int window, bool* real) {
+  *real = false;
+  if (window <= 0) return LR_OK;
+  int longest = 0;
+  if (!cu_host || S < 1 || prefix_len < 0 || nh < 1 || nkv < 1 || hd < 1 || hd > 256) LR_FAIL(LR_EINVAL, "%s: bad argument", who);
+  LR_RUN(lr_check_segments(cu_host, S, who, nullptr, &longest));
+  if (window >= longest + (prefix_len > 0 ? prefix_len : 0)) return LR_OK;
+  if (nh % nkv != 0) LR_FAIL(LR_EINVAL, "%s: num_heads %d not a multiple of num_kv_heads %d", who, nh, nkv);
+  if (prefix_len > 0) LR_FAIL(LR_EUNSUPPORTED, "%s: a window of %d with a shared prefix of %d (the windowed kernels read none)", who,
+                              window, prefix_len);
+  *real = true;
+  return LR_OK;
+}
+
+extern "C" int lr_attention_varlen_window(const uint16_t* qkv, uint16_t* out, const int32_t* seg_starts,
+                                          const int32_t* seg_starts_host, int32_t S, int32_t prefix_len, int32_t num_heads,
+                                          int32_t num_kv_heads, int32_t head_dim, int32_t window, int32_t variant,
+                                          void* hip_stream) {
+  const char* who = "lr_attention_varlen_window";
+  bool real;
+  LR_RUN(check_window_request(who, seg_starts_host, S, prefix_len, num_heads, num_kv_heads, head_dim, window, &real));
+  if (!real)
+    return lr_attention_varlen_prefix(qkv, out, seg_starts, seg_starts_host, S, prefix_len, num_heads, num_kv_heads, head_dim,
+                                      variant, hip_stream);
+  if (!qkv || !out || !seg_starts) LR_FAIL(LR_EINVAL, "%s: null pointer", who);
+  LrAttnKernel kernel;
+  if (variant == 1 || ((variant == 0 || variant == 4) && head_dim != 256)) kernel = LR_ATTN_GENERIC;
+  else if (variant == 0 || variant == 4) kernel = LR_ATTN_HD256;
+  else LR_FAIL(LR_EUNSUPPORTED, "%s: variant %d has no windowed form (0 / 4: the head_dim-256 MFMA kernel, generic off head_dim "
+               "256; 1 generic)", who, variant);
+  return lr_launch_attention({.qkv = qkv, .out = out, .cu = seg_starts, .cu_host = seg_starts_host, .S = S,
+                              .n_tok = seg_starts_host[S], .nh = num_heads, .nkv = num_kv_heads, .hd = head_dim,
+                              .window = window}, kernel, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_attention_last_rows_window(const uint16_t* kv, const uint16_t* q_last, uint16_t* out_last,
+                                             const int32_t* seg_starts, const int32_t* seg_starts_host, int32_t S,
+                                             int32_t prefix_len, int32_t num_heads, int32_t num_kv_heads, int32_t head_dim,
+                                             int32_t window, int32_t variant, void* hip_stream) {
+  const char* who = "lr_attention_last_rows_window";
+  bool real;
+  LR_RUN(check_window_request(who, seg_starts_host, S, prefix_len, num_heads, num_kv_heads, head_dim, window, &real));
+  if (!real)
+    return lr_attention_last_rows(kv, q_last, out_last, seg_starts, seg_starts_host, S, prefix_len, num_heads, num_kv_heads,
+                                  head_dim, variant, hip_stream);
+  if (!kv || !q_last || !out_last || !seg_starts) LR_FAIL(LR_EINVAL, "%s: null pointer", who);
+  if (head_dim != 256 || (variant != 0 && variant != 4))
+    LR_FAIL(LR_EUNSUPPORTED, "%s: variant %d at head_dim %d has no one-row mode with a window (0 / 4 at 256)", who, variant,
+            head_dim);
+  return lr_launch_attention_last(kv, q_last, out_last, seg_starts, seg_starts_host, S, seg_starts_host[S], num_heads,
+                                  num_kv_heads, head_dim, (hipStream_t)hip_stream, 0, 0.f, 0.f, window);
+}
+
 extern "C" int lr_residual_postnorm_bf16(uint16_t* x, const uint16_t* hrows, const uint16_t* w_out, const uint16_t* w_next,
                                          uint16_t* xn, int32_t rows, int32_t d, float eps, void* hip_stream) {
   if (!x || !hrows || !w_out || rows < 1 || (w_next == nullptr) != (xn == nullptr) || !(eps >= 0.f) || !(eps < __builtin_inff()))
@@ -779,9 +950,10 @@ extern "C" int lr_rmsnorm_bf16(const uint16_t* x, const uint16_t* w, uint16_t* o
   return lr_launch_rmsnorm(x, w, out, rows, d, eps, nullptr, (hipStream_t)hip_stream, norm_style);
 }
 
-extern "C" int lr_qk_norm_rope_bf16(uint16_t* buf, int32_t rows, int32_t ld, int32_t col0, int32_t nq, int32_t nk,
-                                    int32_t head_dim, const uint16_t* q_norm, const uint16_t* k_norm, float eps,
-                                    const int32_t* tok_pos, const float* rope_cs, void* hip_stream) {
+extern "C" int lr_qk_norm_rope_ex_bf16(uint16_t* buf, int32_t rows, int32_t ld, int32_t col0, int32_t nq, int32_t nk,
+                                       int32_t head_dim, const uint16_t* q_norm, const uint16_t* k_norm, float eps,
+                                       const int32_t* tok_pos, const float* rope_cs, void* hip_stream, int32_t norm_style) {
+  if (norm_style != 0 && norm_style != 1) LR_FAIL(LR_EINVAL, "lr_qk_norm_rope_bf16: norm_style %d (0 Qwen3, 1 Gemma-3)", norm_style);
   if (!lr_qk_norm_head_dim_ok(head_dim))
     LR_FAIL(LR_EUNSUPPORTED, "lr_qk_norm_rope_bf16: head_dim %d (a power of two from 16 to 256)", head_dim);
   if (!buf || rows < 1 || ld < 8 || col0 < 0 || col0 % 8 != 0 || nq < 0 || nk < 0 || nq + nk < 1 ||
@@ -789,7 +961,13 @@ extern "C" int lr_qk_norm_rope_bf16(uint16_t* buf, int32_t rows, int32_t ld, int
     LR_FAIL(LR_EINVAL, "lr_qk_norm_rope_bf16: bad argument (rows %d, ld %d, col0 %d a multiple of 8, %d + %d heads of %d)", rows,
             ld, col0, nq, nk, head_dim);
   return lr_launch_qk_norm_rope(buf + col0, rows, ld, nq, nk, head_dim, q_norm, k_norm, eps, tok_pos, rope_cs,
-                                (hipStream_t)hip_stream);
+                                (hipStream_t)hip_stream, norm_style);
+}
+
+extern "C" int lr_qk_norm_rope_bf16(uint16_t* buf, int32_t rows, int32_t ld, int32_t col0, int32_t nq, int32_t nk,
+                                    int32_t head_dim, const uint16_t* q_norm, const uint16_t* k_norm, float eps,
+                                    const int32_t* tok_pos, const float* rope_cs, void* hip_stream) {
+  return lr_qk_norm_rope_ex_bf16(buf, rows, ld, col0, nq, nk, head_dim, q_norm, k_norm, eps, tok_pos, rope_cs, hip_stream, 0);
 }
 
 extern "C" size_t lr_attention_workspace_bytes(int32_t total_tokens, int32_t B, int32_t num_heads) {

@@ -185,6 +185,8 @@ extern "C" int lr_llama_lora_create_ex(lr_llama_t* base, const LrLlamaWeightsTDe
     LR_FAIL(LR_EUNSUPPORTED, "lr_llama_lora_create: fine-tuning needs a Llama base (no GeGLU / Gemma-norm backward)");
   if (base->gemma2)
     LR_FAIL(LR_EUNSUPPORTED, "lr_llama_lora_create: fine-tuning needs a Llama base (no soft-cap / sandwich-norm backward)");
+  if (base->gemma3)
+    LR_FAIL(LR_EUNSUPPORTED, "lr_llama_lora_create: fine-tuning needs a Llama base (no sliding-window / sandwich-norm backward)");
   if (base->bqkv)   // the live-adapter forward adds its delta and rotates in lr_launch_lora_rope_fwd, which knows no bias
     LR_FAIL(LR_EUNSUPPORTED, "lr_llama_lora_create: fine-tuning needs a base without q/k/v biases (lr_llama_set_qkv_bias)");
   if (!wt || !wt->layers || !wt->lm_head_t || !state || !out) LR_FAIL(LR_EINVAL, "lr_llama_lora_create: null argument");

@@ -42,7 +42,8 @@ typedef u16 u16x8 __attribute__((ext_vector_type(8)));
 // =============================================================================================
 __global__ __launch_bounds__(256) void attn_generic_kernel(const u16* qkv, u16* out, const int32_t* cu, int B,
                                                            int n_tok, int nh, int nkv, int hd,
-                                                           const int32_t* q_rows, float* lse, float scale_arg, float cap) {
+                                                           const int32_t* q_rows, float* lse, float scale_arg, float cap,
+                                                           int window) {
   __shared__ float qs[4][256];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int item = blockIdx.x * 4 + wave;  // (token, head)
@@ -65,7 +66,10 @@ __global__ __launch_bounds__(256) void attn_generic_kernel(const u16* qkv, u16* 
   const float scale = scale_arg > 0.f ? scale_arg : 1.0f / sqrtf((float)hd);   // 0: the head_dim's own
   float m = -__builtin_inff(), l = 0.f;
   float o[4] = {0.f, 0.f, 0.f, 0.f};  // dims lane, lane+64, lane+128, lane+192
-  for (int k0 = 0; k0 <= pos; k0 += 64) {
+  // window = W > 0: the row sees keys pos - W < key <= pos, and the walk starts at its first visible key (every 64-key step
+  // then holds a visible key, as in the causal walk). 0: from key 0, the arithmetic the kernel had without the argument.
+  const int key_lo = window > 0 ? max(0, pos - window + 1) : 0;
+  for (int k0 = key_lo; k0 <= pos; k0 += 64) {
     const int key = k0 + lane;
     float s = -__builtin_inff();
     if (key <= pos) {
@@ -527,12 +531,13 @@ extern "C" int lr_debug_attn_stamps(unsigned long long* out, int n) {
 
 // attention for a list of query tokens only (the last layer needs just each prompt's last token)
 int lr_launch_attention_rows(const u16* qkv, u16* out, const int32_t* cu, int B, const int32_t* q_rows,
-                             int n_rows, int nh, int nkv, int hd, hipStream_t st, float scale, float cap) {
+                             int n_rows, int nh, int nkv, int hd, hipStream_t st, float scale, float cap, int window) {
   if (n_rows <= 0) return LR_OK;
+  if (window < 0) LR_FAIL(LR_EINVAL, "attention: window %d", window);
   if (hd > 256) LR_FAIL(LR_EUNSUPPORTED, "attention: head_dim %d > 256", hd);
   const int items = n_rows * nh;
   hipLaunchKernelGGL(attn_generic_kernel, dim3((items + 3) / 4), dim3(256), 0, st, qkv, out, cu, B, n_rows,
-                     nh, nkv, hd, q_rows, (float*)nullptr, scale, cap);
+                     nh, nkv, hd, q_rows, (float*)nullptr, scale, cap, window);
   LR_CHECK_LAUNCH("attn_generic_kernel(rows)");
   return LR_OK;
 }
@@ -624,6 +629,10 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
     LR_FAIL(LR_EINVAL, "attention: scale %g cap %g", (double)a.scale, (double)a.cap);
   if (a.cap > 0.f && kernel != LR_ATTN_HD256 && kernel != LR_ATTN_GENERIC)
     LR_FAIL(LR_EUNSUPPORTED, "attention: kernel %d has no soft-capped form", (int)kernel);
+  if (a.window < 0) LR_FAIL(LR_EINVAL, "attention: window %d", a.window);
+  if (a.window > 0 && ((kernel != LR_ATTN_HD256 && kernel != LR_ATTN_GENERIC) || prefix_len != 0 || a.lse || a.cap > 0.f))
+    LR_FAIL(LR_EUNSUPPORTED, "attention: a sliding window runs on the head_dim-256 MFMA kernel or the generic one, without a "
+            "shared prefix, lse or a soft cap (kernel %d, prefix %d)", (int)kernel, prefix_len);
   if (kernel == LR_ATTN_ROWS256) return lr_launch_attention256(a, st);
   if (nh % nkv != 0) LR_FAIL(LR_EINVAL, "attention: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
   if (kernel == LR_ATTN_HD256) {
@@ -631,6 +640,7 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
       LR_FAIL(LR_EINVAL, "attention: the head_dim-256 MFMA kernel writes no lse with a shared prefix or a soft cap (prefix %d)",
               prefix_len);
     if (a.cap > 0.f) return lr_launch_attention_hd256_softcap(a, st);
+    if (a.window > 0) return lr_launch_attention_hd256_window(a, st);
     return prefix_len > 0 ? lr_launch_attention_hd256_prefix(a, st) : lr_launch_attention_hd256(a, st);
   }
   if (kernel == LR_ATTN_HD64) {
@@ -679,7 +689,7 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
     if (hd > 256) LR_FAIL(LR_EUNSUPPORTED, "attention: head_dim %d > 256", hd);
     const int items = n_tok * nh;
     hipLaunchKernelGGL(attn_generic_kernel, dim3((items + 3) / 4), dim3(256), 0, st, a.qkv, a.out, a.cu, B,
-                       n_tok, nh, nkv, hd, (const int32_t*)nullptr, a.lse, a.scale, a.cap);
+                       n_tok, nh, nkv, hd, (const int32_t*)nullptr, a.lse, a.scale, a.cap, a.window);
     LR_CHECK_LAUNCH("attn_generic_kernel");
   }
   return LR_OK;
@@ -688,8 +698,15 @@ int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st
 // The pruned last layer (head_dim 128 here, 64, 96 and 256 in the _prefix files of their kernels): kv = [n_tok][2 * nkv * hd] (K | V of every row), q_last = [prompts][nh * hd] rotated query rows
 // of each prompt's last token, out_last = [prompts][nh * hd]. cu / cu_host / prefix_len as lr_launch_attention.
 int lr_launch_attention_last(const u16* kv, const u16* q_last, u16* out_last, const int32_t* cu, const int32_t* cu_host,
-                             int S, int n_tok, int nh, int nkv, int hd, hipStream_t st, int prefix_len, float scale, float cap) {
+                             int S, int n_tok, int nh, int nkv, int hd, hipStream_t st, int prefix_len, float scale, float cap,
+                             int window) {
   if (n_tok <= 0 || S <= 0) return LR_OK;
+  if (window < 0) LR_FAIL(LR_EINVAL, "attention (last rows): window %d", window);
+  if (window > 0) {
+    if (hd != 256 || nkv < 1 || nh % nkv != 0 || prefix_len != 0 || cap > 0.f)
+      LR_FAIL(LR_EUNSUPPORTED, "attention (last rows, window): head_dim 256 and nh %% nkv == 0 only, no shared prefix, no cap");
+    return lr_launch_attention_hd256_window_last(kv, q_last, out_last, cu, cu_host, S, n_tok, nh, nkv, window, st);
+  }
   if (cap > 0.f) {
     if (hd != 256 || nkv < 1 || nh % nkv != 0)
       LR_FAIL(LR_EUNSUPPORTED, "attention (last rows, soft cap): head_dim 256 and nh %% nkv == 0 only");

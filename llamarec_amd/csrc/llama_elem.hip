@@ -328,6 +328,22 @@ __global__ void rope_table_llama3_kernel(float* cs, unsigned* cs16, int T, int h
   if (cs16) cs16[i] = (unsigned)c | ((unsigned)sn << 16);
 }
 
+// Linear scaling (LrRopeScaling kind 2; Gemma-3's global layers): every inverse frequency divided by factor, in fp32 like HF's
+// inv_freq / factor. A kernel of its own for the same reason.
+__global__ void rope_table_linear_kernel(float* cs, unsigned* cs16, int T, int hd, float theta, float factor) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  int half = hd / 2;
+  if (i >= T * half) return;
+  int pos = i / half, j = i % half;
+  float inv = 1.0f / powf(theta, (float)(2 * j) / (float)hd);
+  inv = inv / factor;
+  float ang = (float)pos * inv;
+  const u16 c = f2bf(cosf(ang)), sn = f2bf(sinf(ang));
+  cs[2 * i + 0] = bf2f(c);
+  cs[2 * i + 1] = bf2f(sn);
+  if (cs16) cs16[i] = (unsigned)c | ((unsigned)sn << 16);
+}
+
 // ---- final RMSNorm on each prompt's last token + dot with selected lm_head rows -------------
 // grid (B, ceil(C/32)); out[b][c] = float(bf16(sum_k xn[k] * W[row_c][k])), row_c = ids ? ids[c] : c
 // CAP (Gemma-2's final_logit_softcapping): HF runs logits / cap, tanh, * cap on the bf16 logits and then .float(), so each of
@@ -439,7 +455,16 @@ int lr_check_rope_scaling(const LrRopeScaling* s, const char* who) {
   for (int i = 0; i < 3; ++i)
     if (s->reserved[i]) LR_FAIL(LR_EINVAL, "%s: rope scaling reserved word %d is not zero", who, i);
   if (s->kind == 0) return LR_OK;
-  if (s->kind != 1) LR_FAIL(LR_EINVAL, "%s: unknown rope scaling kind %d (0 none, 1 llama3)", who, s->kind);
+  if (s->kind == 2) {   // linear: factor alone; the llama3 words it does not read must be zero (a llama3 block with the kind
+                        // mistyped is refused, as every kind but 0 and 1 was before this one existed)
+    if (!(s->factor > 0.f) || !(s->factor < __builtin_inff()) || s->low_freq_factor != 0.f || s->high_freq_factor != 0.f ||
+        s->original_max_positions != 0)
+      LR_FAIL(LR_EINVAL, "%s: linear rope scaling factor=%g (finite and > 0) low_freq_factor=%g high_freq_factor=%g "
+              "original_max_positions=%d (must be zero: not read)", who, (double)s->factor, (double)s->low_freq_factor,
+              (double)s->high_freq_factor, s->original_max_positions);
+    return LR_OK;
+  }
+  if (s->kind != 1) LR_FAIL(LR_EINVAL, "%s: unknown rope scaling kind %d (0 none, 1 llama3, 2 linear)", who, s->kind);
   if (!(s->factor >= 1.0f) || !(s->low_freq_factor > 0.f) || !(s->low_freq_factor < s->high_freq_factor) ||
       !(s->high_freq_factor < __builtin_inff()) || !(s->factor < __builtin_inff()) || s->original_max_positions < 1)
     LR_FAIL(LR_EINVAL, "%s: llama3 rope scaling factor=%g low_freq_factor=%g high_freq_factor=%g original_max_positions=%d",
@@ -455,6 +480,11 @@ int lr_launch_rope_table(float* cs, int T, int hd, float theta, hipStream_t st, 
                        scaling->factor, scaling->low_freq_factor, scaling->high_freq_factor,
                        (float)scaling->original_max_positions);
     LR_CHECK_LAUNCH("rope_table_llama3_kernel");
+    return LR_OK;
+  }
+  if (scaling && scaling->kind == 2) {
+    hipLaunchKernelGGL(rope_table_linear_kernel, dim3((n + 255) / 256), dim3(256), 0, st, cs, cs16, T, hd, theta, scaling->factor);
+    LR_CHECK_LAUNCH("rope_table_linear_kernel");
     return LR_OK;
   }
   hipLaunchKernelGGL(rope_table_kernel, dim3((n + 255) / 256), dim3(256), 0, st, cs, cs16, T, hd, theta);
@@ -570,7 +600,8 @@ int lr_launch_residual_postnorm(u16* x, const u16* h, const u16* w_out, const u1
 // A thread owns 8 consecutive columns (one 16-byte access each way), a head is L = HD / 8 consecutive lanes: chunk ids run
 // row-major over rows x (nq + nk) L chunks, every count a multiple of L and L a divisor of 64, so a head never straddles a
 // wave and the square sum is an L-lane butterfly without LDS. Lanes past the end stay in the shuffles (their groups are whole).
-template <int HD>
+// NS = the norm's rounding (rms_apply): 0 Qwen3's bf16(w * bf16(x * rstd)), 1 Gemma-3's bf16(x * rstd * (1 + w)) in fp32.
+template <int HD, int NS = 0>
 __global__ __launch_bounds__(256) void qk_norm_rope_kernel(u16* buf, size_t total, int per_row, int ld, int nq,
                                                            const u16* q_norm, const u16* k_norm, float eps,
                                                            const int32_t* tok_pos, const float* rope_cs) {
@@ -602,7 +633,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_kernel(u16* buf, size_t tota
   u16x8 o;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const float a0 = bf2f(rms_apply<0>(w[2 * q], x[2 * q], rstd)), a1 = bf2f(rms_apply<0>(w[2 * q + 1], x[2 * q + 1], rstd));
+    const float a0 = bf2f(rms_apply<NS>(w[2 * q], x[2 * q], rstd)), a1 = bf2f(rms_apply<NS>(w[2 * q + 1], x[2 * q + 1], rstd));
     o[2 * q] = f2bf(a0 * co[q] - a1 * si[q]);
     o[2 * q + 1] = f2bf(a1 * co[q] + a0 * si[q]);
   }
@@ -613,8 +644,9 @@ __global__ __launch_bounds__(256) void qk_norm_rope_kernel(u16* buf, size_t tota
 bool lr_qk_norm_head_dim_ok(int hd) { return hd >= 16 && hd <= 256 && (hd & (hd - 1)) == 0; }
 
 int lr_launch_qk_norm_rope(u16* buf, int rows, int ld, int nq, int nk, int hd, const u16* q_norm, const u16* k_norm,
-                           float eps, const int32_t* tok_pos, const float* rope_cs, hipStream_t st) {
+                           float eps, const int32_t* tok_pos, const float* rope_cs, hipStream_t st, int norm_style) {
   if (rows <= 0 || nq + nk == 0) return LR_OK;
+  if (norm_style != 0 && norm_style != 1) LR_FAIL(LR_EINVAL, "q/k norm sweep: norm_style %d (0 Qwen3, 1 Gemma-3)", norm_style);
   if (!lr_qk_norm_head_dim_ok(hd)) LR_FAIL(LR_EUNSUPPORTED, "q/k norm sweep: head_dim %d (a power of two from 16 to 256)", hd);
   if (!buf || nq < 0 || nk < 0 || (nq > 0 && !q_norm) || (nk > 0 && !k_norm) || !tok_pos || !rope_cs || ld % 8 != 0 ||
       (long long)(nq + nk) * hd > ld || (reinterpret_cast<uintptr_t>(buf) & 15) ||
@@ -628,8 +660,12 @@ int lr_launch_qk_norm_rope(u16* buf, int rows, int ld, int nq, int nk, int hd, c
   LrProfScope prof(LR_PROF_ELEMENTWISE, 2.0 * total * 16, st);   // work = bytes moved: every chunk read and written once
 #define LR_QKN_CASE(HD)                                                                                                   \
   case HD:                                                                                                                \
-    hipLaunchKernelGGL(qk_norm_rope_kernel<HD>, dim3((unsigned)blocks), dim3(256), 0, st, buf, total, per_row, ld, nq,    \
-                       q_norm, k_norm, eps, tok_pos, rope_cs);                                                            \
+    if (norm_style == 1)                                                                                                  \
+      hipLaunchKernelGGL((qk_norm_rope_kernel<HD, 1>), dim3((unsigned)blocks), dim3(256), 0, st, buf, total, per_row, ld, \
+                         nq, q_norm, k_norm, eps, tok_pos, rope_cs);                                                      \
+    else                                                                                                                  \
+      hipLaunchKernelGGL((qk_norm_rope_kernel<HD, 0>), dim3((unsigned)blocks), dim3(256), 0, st, buf, total, per_row, ld, \
+                         nq, q_norm, k_norm, eps, tok_pos, rope_cs);                                                      \
     break;
   switch (hd) {
     LR_QKN_CASE(16) LR_QKN_CASE(32) LR_QKN_CASE(64) LR_QKN_CASE(128) LR_QKN_CASE(256)

@@ -57,9 +57,10 @@ int lr_launch_token_meta(const int32_t* cu, int B, int prefix_len, int32_t* seg_
 int lr_launch_gather_rows(const unsigned short* x, const int32_t* rows, int n_rows, int d, unsigned short* out,
                           hipStream_t st);
 // scale / cap: as LrAttnArgs below (0 / 0 = head_dim^-0.5 and no soft cap: the kernel's path is then what it was)
+// window: as LrAttnArgs below (0 = the plain causal range)
 int lr_launch_attention_rows(const unsigned short* qkv, unsigned short* out, const int32_t* cu, int B,
                              const int32_t* q_rows, int n_rows, int nh, int nkv, int hd, hipStream_t st, float scale = 0.f,
-                             float cap = 0.f);
+                             float cap = 0.f, int window = 0);
 int lr_launch_embed(const int32_t* ids, const int32_t* tok_src /*nullptr: identity*/, const unsigned short* table,
                     int vocab, int d, unsigned short* out, int n, hipStream_t st,
                     float scale = 1.0f /* != 1: rows bf16(e * scale) (Gemma's embedding scale) */);
@@ -87,9 +88,10 @@ int lr_launch_residual_postnorm(unsigned short* x, const unsigned short* h, cons
 // columns behind them are not touched. q_norm / k_norm: bf16 [hd] in that order, 16-byte aligned; either group may be empty.
 // hd: a power of two from 16 to 256 (lr_qk_norm_head_dim_ok), anything else LR_EUNSUPPORTED before any launch.
 bool lr_qk_norm_head_dim_ok(int hd);
+// norm_style 1 (Gemma-3): the norm is rms_apply<1>, bf16(x * rstd * (1 + w)) in fp32 with one rounding; the rotation is the same.
 int lr_launch_qk_norm_rope(unsigned short* buf, int rows, int ld, int nq, int nk, int hd, const unsigned short* q_norm,
                            const unsigned short* k_norm, float eps, const int32_t* tok_pos, const float* rope_cs,
-                           hipStream_t st);
+                           hipStream_t st, int norm_style = 0);
 
 // C[M][N] (+epilogue) = A[M][K] * B[N][K]^T. Call sites name what they pass (designated initialisers); a member left
 // out is absent. variant: 0 auto, 1 generic, 4 = 256x256x64 MFMA tile, 5 = variant 4 with split-K when the tiles alone
@@ -216,7 +218,8 @@ static inline int lr_attn_check_grid(const LrAttnPlan& p) {
 //   ROWS256  head_dim 128, 256-row query tiles over a device-built item list, shared prefix <= 64 (llama_attn256.hip)
 //   HD256    head_dim 256; one body (llama_attn_hd256_body.h) instantiated without a shared prefix in llama_attn_hd256.hip,
 //            with lse (variant 9, no prefix) in llama_attn_hd256_lse.hip, with a shared prefix in llama_attn_hd256_prefix.hip
-//            and with soft-capped scores in llama_attn_hd256_softcap.hip
+//            and with soft-capped scores in llama_attn_hd256_softcap.hip; the sliding-window form (LrAttnArgs.window) is a body
+//            of its own in llama_attn_hd256_window.hip
 //   HD64     head_dim 64; one body (llama_attn_hd64_body.h) instantiated without a shared prefix in llama_attn_hd64.hip, with
 //            lse (variant 6, no prefix) in llama_attn_hd64_lse.hip and with a shared prefix in llama_attn_hd64_prefix.hip
 //   HD96     head_dim 96; one body (llama_attn_hd96_body.h) instantiated without a shared prefix in llama_attn_hd96.hip, with
@@ -311,6 +314,11 @@ enum LrAttnKernel {
 //                                                                     so does a cap above LR_SOFTCAP_MFMA_MAX at head_dim 256)
 //   other                                                    LR_EINVAL
 //
+// With a sliding window (LrAttnArgs.window > 0: Gemma-3, lr_attention_varlen_window) the kernel is resolved WITHOUT the window
+// and lr_launch_attention / lr_launch_attention_last then take HD256's windowed kernels or GENERIC with the window; a resolved
+// MFMA128, ROWS256, HD64 or HD96, a shared prefix, lse or a cap with a window is LR_EUNSUPPORTED there (the prefill sends a
+// windowed layer of such a handle to GENERIC itself, api_llama.hip).
+//
 // LR_SOFTCAP_MFMA_MAX: the MFMA kernels evaluate the capped score as c2 - 2 c2 rcp(1 + exp2(a s)) with c2 = cap log2(e), whose
 // absolute error is about two ulps of 1 times c2 (1.7e-7 cap in the exp2 domain, at small a s as well: there 1 + exp2(a s)
 // rounds a s to an ulp of 2). At cap 256 that is 4e-5, a hundredth of a bf16 step of P; the generic kernel's tanhf keeps a
@@ -355,12 +363,16 @@ struct LrAttnArgs {
   // cap > 0: scores cap * tanh(q.k * scale / cap) (HD256's SOFTCAP instantiations and GENERIC only), scale > 0 then required
   // by HD256; GENERIC takes scale = 0 as head_dim^-0.5. Both 0: the kernels' own head_dim^-0.5 and no cap.
   float scale = 0.f, cap = 0.f;
+  // window = W > 0 (Gemma-3's sliding layers): query i sees keys i - W < j <= i. HD256 (its windowed kernels,
+  // llama_attn_hd256_window.hip) and GENERIC only, without a shared prefix, lse or cap. 0: the plain causal range.
+  int window = 0;
 };
 int lr_launch_attention(const LrAttnArgs& a, LrAttnKernel kernel, hipStream_t st);
 // The pruned last layer (MFMA128's, HD64's, HD96's or HD256's last-row kernel by head_dim): one query row per (prompt, head) over the prompt's keys
 int lr_launch_attention_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
                              const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int hd,
-                             hipStream_t st, int prefix_len, float scale = 0.f, float cap = 0.f /* > 0: head_dim 256 only */);
+                             hipStream_t st, int prefix_len, float scale = 0.f, float cap = 0.f /* > 0: head_dim 256 only */,
+                             int window = 0 /* > 0: head_dim 256 only, no prefix, no cap */);
 // ROWS256's item list for (cu, S, nh, prefix_len) into items_ws (lr_attn256_ws_bytes), built once per call; any number of
 // lr_launch_attention calls over the same segments may follow (one per layer)
 size_t lr_attn256_ws_bytes(int n_tok, int S, int nh);
@@ -394,6 +406,11 @@ int lr_launch_attention_hd256_softcap(const LrAttnArgs& a, hipStream_t st);
 int lr_launch_attention_hd256_softcap_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
                                            const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv,
                                            int prefix_len, float scale, float cap, hipStream_t st);
+// HD256 with a sliding window (llama_attn_hd256_window.hip): whole prompts (a.window >= 1, no shared prefix) and the last-row mode
+int lr_launch_attention_hd256_window(const LrAttnArgs& a, hipStream_t st);
+int lr_launch_attention_hd256_window_last(const unsigned short* kv, const unsigned short* q_last, unsigned short* out_last,
+                                          const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int window,
+                                          hipStream_t st);
 
 // ---- the launch sequence of the HD64 / HD96 / HD256 kernels, once ------------------------------------------------------------
 // Every lr_launch_attention_hd* above is one call of lr_attn_launch_tiles or lr_attn_launch_last with its kernel (a template

@@ -173,6 +173,14 @@ struct lr_llama {
   // products store plainly and lr_launch_qk_norm_rope follows (refuses folded norms, a Gemma-2 extension and q/k/v biases)
   const uint16_t** q_norm;
   const uint16_t** k_norm;
+  // Gemma-3 (lr_llama_set_gemma3); all zero / null (calloc): none. The extension owns attn_out_norm / mlp_out_norm (the
+  // sandwich of Gemma-2) and q_norm / k_norm (the sweep of Qwen3, run with norm_style 1) while it is set, so the prefill reads
+  // them where it read them; gemma2 stays 0.
+  int gemma3;                        // the extension is set (refuses folded norms, the other extensions and LoRA engines)
+  int window;                        // sliding layers: query i sees keys i - window < j <= i
+  uint8_t* layer_sliding;            // [num_layers] owned copy: 1 = sliding (window, local rotary table), 0 = global
+  float rope_theta_local;            // sliding layers' rotary base, unscaled; global layers: cfg.rope_theta / global_linear_factor
+  float global_linear_factor;        // > 0 and != 1: linear scaling of the global layers' table; 0: none
 };
 
 #endif  // LR_COMMON_H

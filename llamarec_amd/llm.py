@@ -48,6 +48,14 @@ GEMMA2_2B = dict(model_type="gemma2", vocab_size=256000, hidden_size=2304, inter
                  attn_logit_softcapping=50.0, final_logit_softcapping=30.0, sliding_window=4096)
 GEMMA2_9B = dict(GEMMA2_2B, hidden_size=3584, intermediate_size=14336, num_hidden_layers=42, num_attention_heads=16,
                  num_key_value_heads=8)
+# google/gemma-3-1b-pt (config.json of the checkpoint; model_type "gemma3_text"): five of every six layers attend to a window of
+# 512 tokens and rotate with base 10 000, every sixth is global with base 1 000 000; q/k norms, sandwich norms, no caps. The
+# larger text models (4b and up, window 1 024) add rope_scaling linear with factor 8 on the global layers.
+GEMMA3_1B = dict(model_type="gemma3_text", vocab_size=262144, hidden_size=1152, intermediate_size=6912, num_hidden_layers=26,
+                 num_attention_heads=4, num_key_value_heads=1, head_dim=256, max_position_embeddings=32768, rms_norm_eps=1e-6,
+                 rope_theta=1000000.0, rope_local_base_freq=10000.0, rope_scaling=None, sliding_window=512,
+                 sliding_window_pattern=6, query_pre_attn_scalar=256, hidden_activation="gelu_pytorch_tanh",
+                 attn_logit_softcapping=None, final_logit_softcapping=None, attention_bias=False)
 # microsoft/Phi-3-mini-4k-instruct and Phi-3-medium-4k-instruct (config.json of the checkpoints; the reference's --llm phi3).
 # Llama's arithmetic with fused qkv_proj / gate_up_proj Linears; mini's head_dim is 3072 / 32 = 96.
 PHI3_MINI = dict(model_type="phi3", vocab_size=32064, hidden_size=3072, intermediate_size=8192, num_hidden_layers=32,
@@ -81,13 +89,18 @@ QWEN3_8B = dict(QWEN3_4B, hidden_size=4096, intermediate_size=12288, tie_word_em
 # model_type -> backbone family of the kernels (LrLlamaArch). Llama-2 / Llama-3 and Mistral share Llama's arithmetic.
 LLAMA_FAMILY = ("llama", "mistral")
 GEMMA_FAMILY = ("gemma",)
+GEMMA3_FAMILY = ("gemma3_text",)
 GEMMA2_FAMILY = ("gemma2",)
 PHI3_FAMILY = ("phi3",)
 QWEN2_FAMILY = ("qwen2",)
 QWEN3_FAMILY = ("qwen3",)
-SUPPORTED_MODEL_TYPES = LLAMA_FAMILY + PHI3_FAMILY + QWEN2_FAMILY + QWEN3_FAMILY + GEMMA_FAMILY + GEMMA2_FAMILY
+SUPPORTED_MODEL_TYPES = (LLAMA_FAMILY + PHI3_FAMILY + QWEN2_FAMILY + QWEN3_FAMILY + GEMMA_FAMILY + GEMMA3_FAMILY
+                         + GEMMA2_FAMILY)
 # what a gemma2 config must spell out (the two caps may be null): none of them has a default the kernels could assume
 GEMMA2_REQUIRED_KEYS = ("query_pre_attn_scalar", "attn_logit_softcapping", "final_logit_softcapping", "sliding_window", "head_dim")
+# what a gemma3_text config must spell out, besides one of layer_types / sliding_window_pattern (rope_local_base_freq may instead
+# come as transformers 5's rope_parameters["sliding_attention"]["rope_theta"])
+GEMMA3_REQUIRED_KEYS = ("head_dim", "query_pre_attn_scalar", "sliding_window", "rope_local_base_freq")
 # what a phi3 config must spell out (sliding_window may be null = none); every published Phi-3 config.json has all three
 PHI3_REQUIRED_KEYS = ("hidden_act", "original_max_position_embeddings", "sliding_window")
 # what a qwen2 config must spell out (sliding_window may be null); every published Qwen2 config.json has all four
@@ -123,13 +136,88 @@ def rope_parameters(config: dict):
     return float(theta if theta is not None else 10000.0), {k: src[k] for k in _LLAMA3_NUMBERS}
 
 
+def _is_pos_number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and 0 < v < float("inf")
+
+
+def gemma3_parameters(config: dict) -> dict:
+    """What a gemma3_text config says about its layers: dict(window, sliding = [bool per layer], theta_global, theta_local,
+    factor = the global layers' linear scaling factor or None). Both spellings of the four rotary numbers are read: rope_theta /
+    rope_local_base_freq / rope_scaling (transformers 4) and rope_parameters = {"full_attention": {...}, "sliding_attention":
+    {...}} (transformers 5). Raises NotImplementedError (with the "supported families" text) for anything the kernels do not
+    compute: a missing key, caps, biases, another activation, a rope scaling other than linear on the global layers."""
+    mt = config.get("model_type")
+    supported = f"supported families: {', '.join(SUPPORTED_MODEL_TYPES)}"
+
+    def refuse(why):
+        raise NotImplementedError(f"model_type {mt!r} {why}; {supported}")
+
+    rp = config.get("rope_parameters")
+    v5 = isinstance(rp, dict) and isinstance(rp.get("full_attention"), dict) and isinstance(rp.get("sliding_attention"), dict)
+    missing = [k for k in GEMMA3_REQUIRED_KEYS if config.get(k) is None and not (k == "rope_local_base_freq" and v5)]
+    if config.get("layer_types") is None and config.get("sliding_window_pattern") is None:
+        missing.append("layer_types / sliding_window_pattern")
+    if missing:
+        refuse(f"config lacks {', '.join(missing)}: window, layer kinds, local rotary base, score scale and head_dim have no "
+               "defaults the kernels could assume")
+    act = config.get("hidden_activation") or config.get("hidden_act")
+    if act != "gelu_pytorch_tanh":
+        refuse(f"with hidden_activation={act!r}: the kernels implement gelu_pytorch_tanh")
+    for k in ("attn_logit_softcapping", "final_logit_softcapping"):
+        if config.get(k) is not None:
+            refuse(f"with {k}={config[k]!r}: Gemma-3 has no soft caps and the windowed kernels have no capped form")
+    if config.get("attention_bias"):
+        refuse(f"with attention_bias={config['attention_bias']!r}: q/k norms and q/k/v/o biases together are not implemented")
+    hd, W, L = config["head_dim"], config["sliding_window"], config["num_hidden_layers"]
+    if not (isinstance(hd, int) and not isinstance(hd, bool) and 16 <= hd <= 256 and hd & (hd - 1) == 0):
+        refuse(f"with head_dim={hd!r}: the q/k norm kernels take a power of two from 16 to 256")
+    if not (isinstance(W, int) and not isinstance(W, bool) and W >= 1):
+        refuse(f"with sliding_window={W!r}: a positive integer")
+    if not _is_pos_number(config["query_pre_attn_scalar"]) or config["query_pre_attn_scalar"] != hd:
+        refuse(f"with query_pre_attn_scalar={config['query_pre_attn_scalar']!r} != head_dim: the uncapped attention kernels scale "
+               "by head_dim ** -0.5")
+    lt = config.get("layer_types")
+    if lt is not None:
+        if len(lt) != L or any(t not in ("sliding_attention", "full_attention") for t in lt):
+            refuse(f"with layer_types={lt!r}: {L} entries of 'sliding_attention' / 'full_attention'")
+        sliding = [t == "sliding_attention" for t in lt]
+    else:
+        pat = config["sliding_window_pattern"]
+        if not (isinstance(pat, int) and not isinstance(pat, bool) and pat >= 1):
+            refuse(f"with sliding_window_pattern={pat!r}: a positive integer")
+        sliding = [(i + 1) % pat != 0 for i in range(L)]
+    if v5:
+        g, loc = rp["full_attention"], rp["sliding_attention"]
+        theta_g, theta_l = g.get("rope_theta"), loc.get("rope_theta")
+        if (loc.get("rope_type") or loc.get("type") or "default") != "default":
+            refuse(f"with rope_parameters['sliding_attention']={loc!r}: the sliding layers rotate unscaled")
+        scaling = g
+    else:
+        theta_g, theta_l, scaling = config.get("rope_theta", 1000000.0), config["rope_local_base_freq"], config.get("rope_scaling")
+    if not _is_pos_number(theta_g) or not _is_pos_number(theta_l):
+        refuse(f"with rotary bases {theta_g!r} (global) and {theta_l!r} (sliding): positive finite numbers")
+    factor = None
+    if scaling is not None:
+        kind = (scaling.get("rope_type") or scaling.get("type") or "default") if isinstance(scaling, dict) else scaling
+        if kind == "linear":
+            factor = scaling.get("factor")
+            if not _is_pos_number(factor):
+                refuse(f"with rope scaling {scaling!r}: rope_type 'linear' needs a positive finite factor")
+        elif kind != "default":
+            refuse(f"with rope scaling {scaling!r}: the global layers' table implements plain RoPE and rope_type 'linear' only")
+    return dict(window=W, sliding=sliding, theta_global=float(theta_g), theta_local=float(theta_l),
+                factor=float(factor) if factor is not None else None)
+
+
 def model_family(config: dict) -> str:
-    """'llama', 'gemma', 'gemma2', 'phi3', 'qwen2' or 'qwen3' for a HF config dict (a missing model_type means llama); anything else raises:
+    """'llama', 'gemma', 'gemma2', 'gemma3', 'phi3', 'qwen2' or 'qwen3' for a HF config dict (a missing model_type means llama); anything else raises:
     the kernels implement those families' arithmetic only, and a checkpoint of another family would load (same tensor names)
     and then score silently wrong. A gemma2, phi3 or qwen2 config is accepted only when it is complete (GEMMA2_REQUIRED_KEYS,
     PHI3_REQUIRED_KEYS, QWEN2_REQUIRED_KEYS). phi3 is Llama's arithmetic behind fused qkv_proj / gate_up_proj Linears
     (from_state_dict splits them); qwen2 is Llama's arithmetic with q/k/v biases (lr_llama_set_qkv_bias); qwen3 (complete by
-    QWEN3_REQUIRED_KEYS; the dense models only) is Llama's arithmetic with per-head q/k RMSNorms (lr_llama_set_qk_norm)."""
+    QWEN3_REQUIRED_KEYS; the dense models only) is Llama's arithmetic with per-head q/k RMSNorms (lr_llama_set_qk_norm); gemma3
+    (model_type "gemma3_text", complete by gemma3_parameters) is Gemma's with sandwich norms, (1 + w) q/k norms, sliding-window
+    layers and a rotary table per layer kind (lr_llama_set_gemma3)."""
     mt = config.get("model_type") or "llama"
     if mt in LLAMA_FAMILY:
         rope_parameters(config)   # plain RoPE or a complete llama3 rule; raises otherwise
@@ -143,6 +231,12 @@ def model_family(config: dict) -> str:
             raise NotImplementedError(f"gemma with hidden_activation={act!r}: the kernels implement gelu_pytorch_tanh")
         return "gemma"
     supported = f"supported families: {', '.join(SUPPORTED_MODEL_TYPES)}"
+    if mt in GEMMA3_FAMILY:
+        gemma3_parameters(config)   # complete and computable, or NotImplementedError
+        return "gemma3"
+    if mt == "gemma3":
+        raise NotImplementedError(f"model_type 'gemma3' is the multimodal wrapper (vision tower + text model): the ranker serves "
+                                  f"the text-only checkpoints, model_type 'gemma3_text' (google/gemma-3-1b-pt, -1b-it); {supported}")
     if mt in GEMMA2_FAMILY:
         missing = [k for k in GEMMA2_REQUIRED_KEYS if k not in config or (config[k] is None and "softcapping" not in k)]
         if missing:
@@ -410,12 +504,17 @@ class LlamaRanker:
         self.device = torch.device(device)
         c = self.config
         self.family = model_family(c)
-        self.rope_theta, self.rope_scaling = rope_parameters(c)   # scaling: None (plain RoPE) or the llama3 numbers
+        if self.family == "gemma3":   # two tables per call (lr_llama_set_gemma3); the handle's rope_theta is the global layers'
+            self.gemma3 = gemma3_parameters(c)
+            self.rope_theta, self.rope_scaling = self.gemma3["theta_global"], None
+        else:
+            self.rope_theta, self.rope_scaling = rope_parameters(c)   # scaling: None (plain RoPE) or the llama3 numbers
         self.hd = c.get("head_dim") or c["hidden_size"] // c["num_attention_heads"]
         # Mistral's sliding window: the kernels attend to the whole causal range, so a longer prompt is refused
         # (Gemma-2: its even layers' window; within it the window is the plain causal mask)
         # (Phi-3: every layer's window, 2047 for mini-4k; null means none)
         # (Qwen2: only with use_sliding_window, then on the layers from max_window_layers on; false: the window is ignored)
+        # (Gemma-3: its sliding layers ARE windowed -- lr_llama_set_gemma3 -- so nothing is refused for length)
         windowed = (c.get("model_type") == "mistral" or self.family in ("gemma2", "phi3")
                     or (self.family == "qwen2" and c["use_sliding_window"]))
         self.max_prompt_len = c.get("sliding_window") if windowed else None
@@ -434,7 +533,8 @@ class LlamaRanker:
         self.training = False
         # Qwen2's widths may miss the 256-column GEMM tile (0.5B: 896 and 1152): its default GEMM variant is 6, auto with a
         # ragged last column tile (set_variants overrides it; no other family's default changes)
-        self.default_gemm_variant = 6 if self.family == "qwen2" else 0
+        # (Gemma-3 too: gemma-3-1b's hidden width 1152 misses it)
+        self.default_gemm_variant = 6 if self.family in ("qwen2", "gemma3") else 0
 
     # -- construction ------------------------------------------------------------------------
     @classmethod
@@ -508,12 +608,13 @@ class LlamaRanker:
                     if f"model.layers.{i}.self_attn.{n}_proj.bias" not in state_dict:
                         raise KeyError(f"model_type 'qwen2': model.layers.{i}.self_attn.{n}_proj.bias is missing (Qwen2's "
                                        "q/k/v Linears have biases)")
-        if self.family == "qwen3":
+        if self.family in ("qwen3", "gemma3"):
+            owner = "Qwen3" if self.family == "qwen3" else "Gemma-3"
             for i in range(L):
                 for n in "qk":
                     if f"model.layers.{i}.self_attn.{n}_norm.weight" not in state_dict:
-                        raise KeyError(f"model_type 'qwen3': model.layers.{i}.self_attn.{n}_norm.weight is missing (Qwen3 "
-                                       "norms every q and k head)")
+                        raise KeyError(f"model_type {config.get('model_type')!r}: model.layers.{i}.self_attn.{n}_norm.weight is "
+                                       f"missing ({owner} norms every q and k head)")
         T["embed"] = t("model.embed_tokens.weight").to(torch.bfloat16).contiguous()
         T["final_norm"] = t("model.norm.weight").to(torch.bfloat16).contiguous()
         T["lm_head"] = (t("lm_head.weight") if "lm_head.weight" in state_dict else T["embed"]).to(torch.bfloat16).contiguous()
@@ -534,7 +635,7 @@ class LlamaRanker:
                 bq, bk, bv = (t(p + f"self_attn.{n}_proj.bias").float().reshape(-1, 1) for n in "qkv")
                 T[f"{i}.bqkv"] = torch.cat([self._interleave_rope_rows(bq), self._interleave_rope_rows(bk), bv],
                                            0).reshape(-1).to(torch.bfloat16).contiguous()
-            if self.family == "qwen3":
+            if self.family in ("qwen3", "gemma3"):
                 # the [head_dim] norm weights in a head's packed column order: the permutation of a head's rows of wq / wk,
                 # once at load. They stay out of the NF4 round trip (Linears only) and no adapter touches them.
                 for n in "qk":
@@ -546,7 +647,7 @@ class LlamaRanker:
             T[f"{i}.wgu"] = self._interleave_gate_up(gate, up)
             T[f"{i}.wdown"] = merged(p + "mlp.down_proj.weight").to(torch.bfloat16).contiguous()
             T[f"{i}.input_norm"] = t(p + "input_layernorm.weight").to(torch.bfloat16).contiguous()
-            if self.family == "gemma2":
+            if self.family in ("gemma2", "gemma3"):
                 # LrLlamaLayerWeights.post_norm is the norm in FRONT of the MLP: Gemma-2's pre_feedforward_layernorm. HF's
                 # post_attention_layernorm acts on the attention output there (LrGemma2Ext.attn_out_norm).
                 T[f"{i}.post_norm"] = t(p + "pre_feedforward_layernorm.weight").to(torch.bfloat16).contiguous()
@@ -573,7 +674,7 @@ class LlamaRanker:
 
         T = self._tensors
         # unit norm scale: w = 1 for Llama, w = 0 for Gemma's (1 + w); Gemma's lm_head is the (tied) embedding
-        gemma = self.family in ("gemma", "gemma2")
+        gemma = self.family in ("gemma", "gemma2", "gemma3")
         norm = torch.zeros if gemma else torch.ones
         T["embed"] = rnd(v, d)
         T["final_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
@@ -582,7 +683,7 @@ class LlamaRanker:
             T[f"{i}.wqkv"] = rnd((nh + 2 * nkv) * hd, d)
             if self.family == "qwen2":
                 T[f"{i}.bqkv"] = rnd((nh + 2 * nkv) * hd)
-            if self.family == "qwen3":
+            if self.family in ("qwen3", "gemma3"):
                 T[f"{i}.q_norm"] = norm(hd, dtype=torch.bfloat16, device=dev)
                 T[f"{i}.k_norm"] = norm(hd, dtype=torch.bfloat16, device=dev)
             T[f"{i}.wo"] = rnd(d, nh * hd)
@@ -590,7 +691,7 @@ class LlamaRanker:
             T[f"{i}.wdown"] = rnd(d, f)
             T[f"{i}.input_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
             T[f"{i}.post_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
-            if self.family == "gemma2":
+            if self.family in ("gemma2", "gemma3"):
                 T[f"{i}.attn_out_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
                 T[f"{i}.mlp_out_norm"] = norm(d, dtype=torch.bfloat16, device=dev)
         self._create()
@@ -633,8 +734,8 @@ class LlamaRanker:
 
     def arch(self):
         """The LrLlamaArch of this ranker's family (include/llamarec_mi355x.h)."""
-        if self.family in ("gemma", "gemma2"):
-            # HF GemmaModel / Gemma2Model: hidden * torch.tensor(hidden_size ** 0.5, dtype=bf16)
+        if self.family in ("gemma", "gemma2", "gemma3"):
+            # HF GemmaModel / Gemma2Model / Gemma3TextModel: hidden * torch.tensor(hidden_size ** 0.5, dtype=bf16)
             scale = float(torch.tensor(self.config["hidden_size"] ** 0.5, dtype=torch.bfloat16))
             return A.LrLlamaArch(norm_style=1, mlp_act=1, embed_scale=scale)
         return A.LrLlamaArch(norm_style=0, mlp_act=0, embed_scale=1.0)
@@ -671,7 +772,10 @@ class LlamaRanker:
         if "0.bqkv" in T:
             self._bqkv_arr = (C.c_void_p * L)(*[T[f"{i}.bqkv"].data_ptr() for i in range(L)])
             check(lib().lr_llama_set_qkv_bias(self._h, self._bqkv_arr), "lr_llama_set_qkv_bias")
-        if "0.q_norm" in T:
+        if self.family == "gemma3":
+            ext, self._gemma3_arrs = self.gemma3_ext()
+            check(lib().lr_llama_set_gemma3(self._h, C.byref(ext)), "lr_llama_set_gemma3")
+        elif "0.q_norm" in T:
             self._qk_norm_arrs = ((C.c_void_p * L)(*[T[f"{i}.q_norm"].data_ptr() for i in range(L)]),
                                   (C.c_void_p * L)(*[T[f"{i}.k_norm"].data_ptr() for i in range(L)]))
             check(lib().lr_llama_set_qk_norm(self._h, *self._qk_norm_arrs), "lr_llama_set_qk_norm")
@@ -694,13 +798,25 @@ class LlamaRanker:
             ext.attn_out_norm, ext.mlp_out_norm = arrs
         return ext, arrs
 
+    def gemma3_ext(self):
+        """(LrGemma3Ext, the arrays it names) of a gemma3 ranker: window, layer kinds, the local rotary base, the global
+        layers' linear factor and the four per-layer norm arrays."""
+        g, T, L = self.gemma3, self._tensors, self.config["num_hidden_layers"]
+        kinds = (C.c_uint8 * L)(*[1 if s else 0 for s in g["sliding"]])
+        arrs = tuple((C.c_void_p * L)(*[T[f"{i}.{n}"].data_ptr() for i in range(L)])
+                     for n in ("q_norm", "k_norm", "attn_out_norm", "mlp_out_norm"))
+        ext = A.LrGemma3Ext(sliding_window=int(g["window"]), rope_theta_local=g["theta_local"],
+                            global_linear_factor=float(g["factor"] or 0.0), attn_scale=0.0, layer_is_sliding=kinds)
+        ext.q_norm, ext.k_norm, ext.attn_out_norm, ext.mlp_out_norm = arrs
+        return ext, (kinds,) + arrs
+
     def set_fold_norms(self, enable=True):
         """Fold the two RMSNorms of every layer into the following projection (include/llamarec_mi355x.h,
         lr_llama_set_folded_norms): wqkv * diag(input_norm) and wgu * diag(post_norm) are built once on the GPU and
         kept beside the originals (+66 % of the q/k/v/gate/up bytes; the originals serve LoRA fine-tuning and the
         pruned last layer). Opt-in: see the note at LlamaRanker.fold_norms."""
         T, L = self._tensors, self.config["num_hidden_layers"]
-        if enable and self.family in ("gemma", "gemma2"):
+        if enable and self.family in ("gemma", "gemma2", "gemma3"):
             raise NotImplementedError("folded norms: Gemma's (1 + w) RMSNorm cannot be folded into bf16 weights at HF's rounding")
         if enable and self.family == "qwen2":
             raise NotImplementedError("folded norms: not with Qwen2's q/k/v biases (lr_llama_set_qkv_bias)")

@@ -132,6 +132,50 @@ def synth_gemma2_state(cfg: dict, seed: int, std: float = 0.02, norm_std: float 
     return sd
 
 
+def gemma3_param_shapes(cfg: dict) -> list[tuple[str, tuple]]:
+    """HF Gemma3ForCausalLM (text) parameter names and shapes: Gemma-2's, with q_norm.weight and k_norm.weight [head_dim] behind
+    o_proj (HF's module order). No lm_head (tied)."""
+    hd = cfg["head_dim"]
+    out = []
+    for name, shape in gemma2_param_shapes(cfg):
+        out.append((name, shape))
+        if name.endswith("o_proj.weight"):
+            p = name[: -len("o_proj.weight")]
+            out += [(p + "q_norm.weight", (hd,)), (p + "k_norm.weight", (hd,))]
+    return out
+
+
+# a tiny Gemma-3 (train_ranker.py --synthetic --llm gemma3): 7 layers, so both layer kinds occur and the last one is sliding;
+# MQA at head_dim 256 on a hidden size that misses the 256-column GEMM tile; a window far below the synthetic prompts' length
+GEMMA3_TINY = dict(model_type="gemma3_text", vocab_size=1000, hidden_size=320, intermediate_size=512, num_hidden_layers=7,
+                   num_attention_heads=2, num_key_value_heads=1, head_dim=256, max_position_embeddings=4096, rms_norm_eps=1e-6,
+                   rope_theta=1000000.0, rope_local_base_freq=10000.0, rope_scaling=None, sliding_window=64,
+                   sliding_window_pattern=6, query_pre_attn_scalar=256, hidden_activation="gelu_pytorch_tanh",
+                   attn_logit_softcapping=None, final_logit_softcapping=None, attention_bias=False)
+
+
+def synth_gemma3_state(cfg: dict, seed: int, std: float = 0.02, norm_std: float = 0.3, qk_norm_spread: float = 0.75,
+                       qk_norm_mean=0.0, attn_out_mean: float = 0.0, mlp_out_mean: float = 0.0) -> dict:
+    """As synth_gemma2_state for a Gemma-3 config: matrices ~ U(std), the hidden-size norm weights ~ U(norm_std) around 0 (Gemma
+    scales by 1 + w), the q / k norm weights qk_norm_mean + U(qk_norm_spread) -- wide enough that a model normed with w in place
+    of 1 + w is clearly another model; the q / k norm fixes the scale of the scores whatever q_proj / k_proj hold, so
+    qk_norm_mean (one number, or one per layer) is what makes the attention peaked (scores ~ (1 + w)^2). attn_out_mean / mlp_out_mean: the means of the two
+    out-norms of the sandwich, which weigh the attention branch against the MLP branch in the residual stream. bf16 values."""
+    sd = {}
+    for i, (name, shape) in enumerate(gemma3_param_shapes(cfg)):
+        if name.endswith(("q_norm.weight", "k_norm.weight")):
+            layer = int(name.split(".")[2])
+            mean = qk_norm_mean[layer] if isinstance(qk_norm_mean, (list, tuple)) else qk_norm_mean
+            w = np.float32(mean) + hash_uniform(seed * 1000 + i, shape, qk_norm_spread)
+        elif name.endswith(("post_attention_layernorm.weight", "post_feedforward_layernorm.weight")):
+            mean = attn_out_mean if "post_attention" in name else mlp_out_mean
+            w = np.float32(mean) + hash_uniform(seed * 1000 + i, shape, norm_std)
+        else:
+            w = hash_uniform(seed * 1000 + i, shape, norm_std if len(shape) == 1 else std)
+        sd[name] = bf16_round(w)
+    return sd
+
+
 def phi3_param_shapes(cfg: dict) -> list[tuple[str, tuple]]:
     """HF Phi3ForCausalLM parameter names and shapes: Llama's with the q | k | v Linears fused into self_attn.qkv_proj and
     gate | up into mlp.gate_up_proj (no biases, untied lm_head)."""

@@ -44,6 +44,8 @@ def main(argv=None, export_root=None):
         raise SystemExit("--llm_retrieved_path experiments/lru/<dataset> is required")
     if args.llm in ("gemma", "gemma2", "phi3", "qwen2") and not args.eval_only:
         raise SystemExit(TRAIN_LLAMA_ONLY)
+    if args.llm == "gemma3" and not args.eval_only:   # Gemma-3: as Gemma-2, plus no backward through the window
+        raise SystemExit(TRAIN_LLAMA_ONLY)
     if args.resume_from_checkpoint and (args.eval_only or args.llm_adapter_path):
         raise SystemExit("--resume_from_checkpoint continues a training run: it goes with neither --eval_only nor "
                          "--llm_adapter_path (to score a checkpoint, pass it as --eval_only --llm_adapter_path <checkpoint-N>)")
@@ -61,8 +63,9 @@ def main(argv=None, export_root=None):
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
     if args.synthetic:
-        from llamarec_amd.synth import (PHI3_TINY, QWEN2_TINY, QWEN3_TINY, FakeTokenizer, synth_gemma2_state, synth_gemma_state,
-                                        synth_llama_state, synth_phi3_state, synth_qwen2_state, synth_qwen3_state)
+        from llamarec_amd.synth import (GEMMA3_TINY, PHI3_TINY, QWEN2_TINY, QWEN3_TINY, FakeTokenizer, synth_gemma2_state,
+                                        synth_gemma3_state, synth_gemma_state, synth_llama_state, synth_phi3_state,
+                                        synth_qwen2_state, synth_qwen3_state)
 
         dataset = D.synthetic_dataset(num_users=300, num_items=1000, seed=args.seed)
         tokenizer = FakeTokenizer()
@@ -81,6 +84,10 @@ def main(argv=None, export_root=None):
                      attn_logit_softcapping=2.0, final_logit_softcapping=1.0, sliding_window=4096,
                      hidden_activation="gelu_pytorch_tanh")
             model = LlamaRanker.from_state_dict(synth_gemma2_state(c, args.seed), c, device=device, lora=lora,
+                                                nf4=args.llm_load_in_4bit)
+        elif args.llm == "gemma3":   # a tiny Gemma-3: sliding and global layers, two rotary bases, (1 + w) q/k norms, a 64-token window
+            c = dict(GEMMA3_TINY, vocab_size=c["vocab_size"])
+            model = LlamaRanker.from_state_dict(synth_gemma3_state(c, args.seed), c, device=device, lora=lora,
                                                 nf4=args.llm_load_in_4bit)
         elif args.llm == "phi3":   # a tiny Phi-3: fused qkv_proj / gate_up_proj, 8 heads of head_dim 96
             c = dict(PHI3_TINY, vocab_size=c["vocab_size"])
