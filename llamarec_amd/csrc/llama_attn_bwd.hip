@@ -547,6 +547,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const u16* __restr
 }
 
 // =============================================================================================
+// The variants that are the two passes of lr_attn_bwd_body.h at one head size, each with a launcher in a unit of its own
+struct AbHeadSize {
+  int variant, hd;
+  int (*launch)(const u16*, const u16*, const float*, const float*, u16*, const int32_t*, const int32_t*, int, int, int, int,
+                int, hipStream_t, const float*);
+};
+static const AbHeadSize AB_HEAD_SIZES[] = {
+    {6, 64, lr_launch_attention_bwd_hd64}, {8, 96, lr_launch_attention_bwd_hd96}, {9, 256, lr_launch_attention_bwd_hd256}};
+
 int lr_launch_attention_bwd(const u16* qkv, const u16* out, const u16* d_out, const float* lse, u16* dqkv, float* dsum,
                             float* dkv32, const int32_t* cu, const int32_t* cu_host, int B, int n_tok, int nh, int nkv,
                             int hd, int variant, hipStream_t st, const int32_t* tok_pos, const float* rope_cs,
@@ -555,9 +564,11 @@ int lr_launch_attention_bwd(const u16* qkv, const u16* out, const u16* d_out, co
   if (nh % nkv != 0) LR_FAIL(LR_EINVAL, "attention backward: num_heads %d not a multiple of num_kv_heads %d", nh, nkv);
   if (hd > 256) LR_FAIL(LR_EUNSUPPORTED, "attention backward: head_dim %d > 256", hd);
   if (variant == 0 || variant == 3) variant = (hd == 128) ? 2 : 1;
-  if (variant == 6 && hd != 64) LR_FAIL(LR_EUNSUPPORTED, "attention backward variant 6 needs head_dim 64 (got %d)", hd);
-  if (variant == 8 && hd != 96) LR_FAIL(LR_EUNSUPPORTED, "attention backward variant 8 needs head_dim 96 (got %d)", hd);
-  if (variant == 9 && hd != 256) LR_FAIL(LR_EUNSUPPORTED, "attention backward variant 9 needs head_dim 256 (got %d)", hd);
+  const AbHeadSize* hs = nullptr;   // the variant's row of AB_HEAD_SIZES, if it is one of them
+  for (const AbHeadSize& e : AB_HEAD_SIZES)
+    if (e.variant == variant) hs = &e;
+  if (hs && hd != hs->hd)
+    LR_FAIL(LR_EUNSUPPORTED, "attention backward variant %d needs head_dim %d (got %d)", variant, hs->hd, hd);
   int rc = lr_launch_rowdot(out, d_out, n_tok, nh, hd, dsum, st);
   if (rc) return rc;
   double work = 0;  // 5 causal tile products of 2*T^2/2*hd flops each
@@ -608,15 +619,9 @@ int lr_launch_attention_bwd(const u16* qkv, const u16* out, const u16* d_out, co
       rc = lr_launch_rope_bwd(dqkv, n_tok, (nh + 2 * nkv) * hd, (nh + nkv) * hd, hd, tok_pos, rope_cs, st);
       if (rc) return rc;
     }
-  } else if (variant == 6) {   // one owner per element either way: `deterministic` changes nothing
+  } else if (hs) {   // variants 6, 8, 9. One owner per element either way: `deterministic` changes nothing
     if (rope_cs && !tok_pos) LR_FAIL(LR_EINVAL, "attention backward: rotary table without token positions");
-    return lr_launch_attention_bwd_hd64(qkv, d_out, lse, dsum, dqkv, cu, cu_host, B, n_tok, nh, nkv, hd, st, rope_cs);
-  } else if (variant == 8) {   // as variant 6
-    if (rope_cs && !tok_pos) LR_FAIL(LR_EINVAL, "attention backward: rotary table without token positions");
-    return lr_launch_attention_bwd_hd96(qkv, d_out, lse, dsum, dqkv, cu, cu_host, B, n_tok, nh, nkv, hd, st, rope_cs);
-  } else if (variant == 9) {   // as variant 6
-    if (rope_cs && !tok_pos) LR_FAIL(LR_EINVAL, "attention backward: rotary table without token positions");
-    return lr_launch_attention_bwd_hd256(qkv, d_out, lse, dsum, dqkv, cu, cu_host, B, n_tok, nh, nkv, hd, st, rope_cs);
+    return hs->launch(qkv, d_out, lse, dsum, dqkv, cu, cu_host, B, n_tok, nh, nkv, hd, st, rope_cs);
   } else {
     LR_FAIL(LR_EINVAL, "attention backward: unknown variant %d (0 auto, 1 generic, 2 = head_dim-128 MFMA, 3 as 0, "
             "6 = head_dim-64 MFMA, 8 = head_dim-96 MFMA, 9 = head_dim-256 MFMA; 4, 5 and 7 have no backward)", variant);

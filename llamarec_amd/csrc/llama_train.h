@@ -83,6 +83,8 @@ int lr_launch_attention_bwd(const unsigned short* qkv, const unsigned short* out
                             const int32_t* cu_host, int B, int n_tok, int nh, int nkv, int hd, int variant,
                             hipStream_t st, const int32_t* tok_pos = nullptr, const float* rope_cs = nullptr,
                             bool deterministic = false);
+// Variants 6, 8 and 9 are one text of the two passes (lr_attn_bwd_body.h, lr_attn_bwd_dq_body.h, lr_attn_bwd_dkv_body.h) and
+// one launcher (lr_attn_bwd_launch); a unit holds its head size's geometry, the two kernels and the launcher's one call.
 // variant 6's two passes (llama_attn_bwd_hd64.hip): head_dim 64 only, dsum = rowsum(dO .* O) already computed; one owner per
 // element of dqkv, no atomics, no dkv32
 int lr_launch_attention_bwd_hd64(const unsigned short* qkv, const unsigned short* d_out, const float* lse, const float* dsum,
