@@ -621,6 +621,48 @@ int lr_qk_norm_rope_ex_bf16(uint16_t* buf, int32_t rows, int32_t ld, int32_t col
                             const float* rope_cs, void* hip_stream, int32_t norm_style);
 
 /* ------------------------------------------------------------------------------------------
+ * The prefill's norm, head, embedding and metadata kernels alone (exposed for parity tests): what every scored prompt passes
+ * through between the GEMMs and the attention passes, each behind one call with flat arguments. All pointers DEVICE, bf16 as
+ * uint16_t. Every call checks on the host, before it launches anything, what its kernel assumes: LR_EINVAL (null pointer,
+ * negative count, d not a multiple of 8, eps not finite or negative, a norm_style other than 0 / 1) or LR_EUNSUPPORTED (a
+ * width the kernel has no path for, a pointer that is not 16-byte aligned where the kernel moves 16 bytes at a time), with a
+ * message in lr_last_error and nothing written. Zero rows is LR_OK and launches nothing. What only the device can see is the
+ * caller's promise: rows / tok_src name rows inside their arrays, cu_seqlens is increasing and every prompt longer than
+ * prefix_len. The arithmetic, rounding points and element-wise error bounds of every call: tests/prefill_kernels_ref.py.
+ * (lr_rmsnorm_bf16, lr_residual_postnorm_bf16, lr_gemm_bf16_nt_residual_rmsnorm_ex and lr_fold_norm_bf16 above belong here too.)
+ * ------------------------------------------------------------------------------------------ */
+/* Final norm of one row per prompt + the verbalizer's dot products: out[b][c] = float(bf16(sum_k xn[k] * lm_head[id_c][k])),
+ * xn = norm(x[rows ? rows[b] : b]) with norm_w in norm_style (0 Llama, 1 Gemma), id_c = class_ids ? class_ids[c] : c; an id
+ * outside [0, vocab) gives NaN in that column; *poison != 0 (optional device word) gives NaN everywhere. final_softcap > 0
+ * (norm_style 1 only, else LR_EUNSUPPORTED): bf16(bf16(tanh(bf16(logit / cap))) * cap) on the bf16 logit. x [..][d], out fp32
+ * [B][C]; lm_head 16-byte aligned; a d whose d * 2 bytes of LDS the kernel cannot have is LR_EUNSUPPORTED. */
+int lr_llama_head_bf16(const uint16_t* x, const int32_t* rows, const uint16_t* norm_w, const uint16_t* lm_head,
+                       const int32_t* class_ids, int32_t B, int32_t C, int32_t d, float eps, float* out, int32_t vocab,
+                       const int32_t* poison, int32_t norm_style, float final_softcap, void* hip_stream);
+/* out[t][:] = table[id][:] (scale == 1) or bf16(table[id][:] * scale), id = ids[tok_src ? tok_src[t] : t], an id outside
+ * [0, vocab) reads row 0. table [vocab][d] and out [n][d] 16-byte aligned. */
+int lr_llama_embed_bf16(const int32_t* ids, const int32_t* tok_src, const uint16_t* table, int32_t vocab, int32_t d,
+                        uint16_t* out, int32_t n, float scale, void* hip_stream);
+/* The packed batch's row map from cu_seqlens [B + 1]. prefix_len = 0: segment b = prompt b. prefix_len = P > 0: segment 0 =
+ * prompt 0's first P tokens, segment b + 1 = prompt b from position P on. seg_start [segments + 1], tok_pos [rows] (position
+ * inside the prompt), tok_src [rows] (index into the packed ids), last_rows / last_pos [B] (row and position of each prompt's
+ * last token), *prefix_bad = 1 when some prompt's first P ids differ from prompt 0's (needs ids), else 0. */
+int lr_llama_token_meta(const int32_t* cu_seqlens, int32_t B, int32_t prefix_len, const int32_t* ids, int32_t* seg_start,
+                        int32_t* tok_pos, int32_t* tok_src, int32_t* last_rows, int32_t* last_pos, int32_t* prefix_bad,
+                        void* hip_stream);
+/* out[i][:] = x[rows[i]][:], rows of d bf16 values; x and out 16-byte aligned. */
+int lr_gather_rows_bf16(const uint16_t* x, const int32_t* rows, int32_t n_rows, int32_t d, uint16_t* out, void* hip_stream);
+/* rstd[m] = 1 / sqrt(mean(x[m][:]^2) + eps) in fp32, the statistic of the folded RMSNorm; x [rows][d] 16-byte aligned. */
+int lr_rms_rstd_f32(const uint16_t* x, float* rstd, int32_t rows, int32_t d, float eps, void* hip_stream);
+/* lr_gemm_bf16_nt_epi with the folded RMSNorm's row scale: epilogues 2 and 3 multiply the fp32 accumulator of row m by
+ * row_scale[m] (fp32 [M]) in front of their first rounding. row_scale = NULL is lr_gemm_bf16_nt_epi bit for bit; a row scale
+ * with epilogue 0, 1 or 5 is LR_EINVAL (nothing is launched). */
+int lr_gemm_bf16_nt_rowscale_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const uint16_t* R, int32_t M, int32_t N,
+                                 int32_t K, int32_t epilogue, int32_t variant, const int32_t* tok_pos, const float* rope_cs,
+                                 int32_t rope_positions, int32_t head_dim, int32_t rot_cols, void* workspace,
+                                 size_t workspace_bytes, const float* row_scale, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optional in-library kernel timing (HIP events on the caller's stream). Not part of the
  * reference's surface: it exists so a benchmark can report the measured duration and the
  * algorithmic work of each kernel family over its timed region.

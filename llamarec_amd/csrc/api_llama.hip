@@ -950,6 +950,88 @@ extern "C" int lr_rmsnorm_bf16(const uint16_t* x, const uint16_t* w, uint16_t* o
   return lr_launch_rmsnorm(x, w, out, rows, d, eps, nullptr, (hipStream_t)hip_stream, norm_style);
 }
 
+// ---- the prefill's norm, head, embedding and metadata kernels alone (exposed for parity tests) ---------------------------------
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+extern "C" int lr_llama_head_bf16(const uint16_t* x, const int32_t* rows, const uint16_t* norm_w, const uint16_t* lm_head,
+                                  const int32_t* class_ids, int32_t B, int32_t C, int32_t d, float eps, float* out,
+                                  int32_t vocab, const int32_t* poison, int32_t norm_style, float final_softcap,
+                                  void* hip_stream) {
+  if (!x || !norm_w || !lm_head || !out) LR_FAIL(LR_EINVAL, "lr_llama_head_bf16: null pointer");
+  if (B < 0 || C < 0 || vocab < 1) LR_FAIL(LR_EINVAL, "lr_llama_head_bf16: B %d, C %d, vocab %d", B, C, vocab);
+  if (d < 8 || d % 8 != 0) LR_FAIL(LR_EINVAL, "lr_llama_head_bf16: d %d (a multiple of 8)", d);
+  if (!finite_nonneg(eps)) LR_FAIL(LR_EINVAL, "lr_llama_head_bf16: eps %g (finite and >= 0)", (double)eps);
+  if (norm_style != 0 && norm_style != 1) LR_FAIL(LR_EINVAL, "lr_llama_head_bf16: norm_style %d", norm_style);
+  if (!finite_nonneg(final_softcap))
+    LR_FAIL(LR_EINVAL, "lr_llama_head_bf16: final_softcap %g (finite and >= 0; 0 = none)", (double)final_softcap);
+  if (final_softcap > 0.f && norm_style != 1)
+    LR_FAIL(LR_EUNSUPPORTED, "lr_llama_head_bf16: a final soft cap goes with the Gemma norm (norm_style 1)");
+  // the normalised row lives in d * 2 bytes of dynamic LDS beside 16 static bytes; 64 KB without a raised attribute
+  if ((size_t)d * sizeof(uint16_t) > (size_t)65536 - 64)
+    LR_FAIL(LR_EUNSUPPORTED, "lr_llama_head_bf16: d %d needs %zu bytes of LDS for the normalised row", d, (size_t)d * 2);
+  if ((C + 31) / 32 > 65535) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_head_bf16: %d classes exceed the grid limit", C);
+  if (!aligned16(lm_head)) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_head_bf16: lm_head must be 16-byte aligned");
+  if (B == 0 || C == 0) return LR_OK;
+  return lr_launch_head(x, rows, norm_w, lm_head, class_ids, B, C, d, eps, out, vocab, (hipStream_t)hip_stream, poison,
+                        norm_style, final_softcap);
+}
+
+extern "C" int lr_llama_embed_bf16(const int32_t* ids, const int32_t* tok_src, const uint16_t* table, int32_t vocab, int32_t d,
+                                   uint16_t* out, int32_t n, float scale, void* hip_stream) {
+  if (!ids || !table || !out) LR_FAIL(LR_EINVAL, "lr_llama_embed_bf16: null pointer");
+  if (n < 0 || vocab < 1) LR_FAIL(LR_EINVAL, "lr_llama_embed_bf16: n %d, vocab %d", n, vocab);
+  if (d < 8 || d % 8 != 0) LR_FAIL(LR_EINVAL, "lr_llama_embed_bf16: d %d (a multiple of 8)", d);
+  if (!(scale > -__builtin_inff()) || !(scale < __builtin_inff()))
+    LR_FAIL(LR_EINVAL, "lr_llama_embed_bf16: scale %g is not finite", (double)scale);
+  if (!aligned16(table) || !aligned16(out)) LR_FAIL(LR_EUNSUPPORTED, "lr_llama_embed_bf16: table and out must be 16-byte aligned");
+  if (n == 0) return LR_OK;
+  return lr_launch_embed(ids, tok_src, table, vocab, d, out, n, (hipStream_t)hip_stream, scale);
+}
+
+extern "C" int lr_llama_token_meta(const int32_t* cu, int32_t B, int32_t prefix_len, const int32_t* ids, int32_t* seg_start,
+                                   int32_t* tok_pos, int32_t* tok_src, int32_t* last_rows, int32_t* last_pos,
+                                   int32_t* prefix_bad, void* hip_stream) {
+  if (!cu || !seg_start || !tok_pos) LR_FAIL(LR_EINVAL, "lr_llama_token_meta: null pointer");
+  if (B < 0 || prefix_len < 0) LR_FAIL(LR_EINVAL, "lr_llama_token_meta: B %d, prefix_len %d", B, prefix_len);
+  if (prefix_bad && !ids) LR_FAIL(LR_EINVAL, "lr_llama_token_meta: prefix_bad without ids (nothing would be verified)");
+  if (B == 0) return LR_OK;
+  return lr_launch_token_meta(cu, B, prefix_len, seg_start, tok_pos, tok_src, last_rows, (hipStream_t)hip_stream, last_pos, ids,
+                              prefix_bad);
+}
+
+extern "C" int lr_gather_rows_bf16(const uint16_t* x, const int32_t* rows, int32_t n_rows, int32_t d, uint16_t* out,
+                                   void* hip_stream) {
+  if (!x || !rows || !out) LR_FAIL(LR_EINVAL, "lr_gather_rows_bf16: null pointer");
+  if (n_rows < 0) LR_FAIL(LR_EINVAL, "lr_gather_rows_bf16: n_rows %d", n_rows);
+  if (d < 8 || d % 8 != 0) LR_FAIL(LR_EINVAL, "lr_gather_rows_bf16: d %d (a multiple of 8)", d);
+  if (!aligned16(x) || !aligned16(out)) LR_FAIL(LR_EUNSUPPORTED, "lr_gather_rows_bf16: x and out must be 16-byte aligned");
+  return lr_launch_gather_rows(x, rows, n_rows, d, out, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_rms_rstd_f32(const uint16_t* x, float* rstd, int32_t rows, int32_t d, float eps, void* hip_stream) {
+  if (!x || !rstd) LR_FAIL(LR_EINVAL, "lr_rms_rstd_f32: null pointer");
+  if (rows < 0) LR_FAIL(LR_EINVAL, "lr_rms_rstd_f32: rows %d", rows);
+  if (d < 8 || d % 8 != 0) LR_FAIL(LR_EINVAL, "lr_rms_rstd_f32: d %d (a multiple of 8)", d);
+  if (!finite_nonneg(eps)) LR_FAIL(LR_EINVAL, "lr_rms_rstd_f32: eps %g (finite and >= 0)", (double)eps);
+  if (!aligned16(x)) LR_FAIL(LR_EUNSUPPORTED, "lr_rms_rstd_f32: x must be 16-byte aligned");
+  return lr_launch_rms_rstd(x, rstd, rows, d, eps, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_gemm_bf16_nt_rowscale_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const uint16_t* R, int32_t M,
+                                            int32_t N, int32_t K, int32_t epilogue, int32_t variant, const int32_t* tok_pos,
+                                            const float* rope_cs, int32_t rope_positions, int32_t head_dim, int32_t rot_cols,
+                                            void* workspace, size_t workspace_bytes, const float* row_scale, void* hip_stream) {
+  if (!A || !B || !C) LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt_rowscale_epi: null pointer");
+  if (epilogue < LR_EPI_STORE || epilogue > LR_EPI_GEGLU || epilogue == LR_EPI_PARTIAL)
+    LR_FAIL(LR_EINVAL, "lr_gemm_bf16_nt_rowscale_epi: epilogue %d", epilogue);
+  const unsigned* cs16 = (rope_cs && rope_positions > 0 && head_dim >= 2)
+                             ? reinterpret_cast<const unsigned*>(rope_cs + (size_t)rope_positions * head_dim) : nullptr;
+  return lr_launch_gemm({.A = A, .B = B, .C = C, .R = R, .M = M, .N = N, .K = K, .epi = epilogue, .variant = variant,
+                         .rope = {.tok_pos = tok_pos, .cs = rope_cs, .cs16 = cs16, .head_dim = head_dim, .rot_cols = rot_cols},
+                         .row_scale = row_scale, .splitk = {.ws = (float*)workspace, .bytes = workspace_bytes}},
+                        (hipStream_t)hip_stream);
+}
+
 extern "C" int lr_qk_norm_rope_ex_bf16(uint16_t* buf, int32_t rows, int32_t ld, int32_t col0, int32_t nq, int32_t nk,
                                        int32_t head_dim, const uint16_t* q_norm, const uint16_t* k_norm, float eps,
                                        const int32_t* tok_pos, const float* rope_cs, void* hip_stream, int32_t norm_style) {
