@@ -139,6 +139,61 @@ int lr_lru_scores_last(lr_lru_t* h, const int64_t* ids, int32_t B, int32_t L,
                        size_t workspace_bytes, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LRURec user states: append ids to a stored recurrence state instead of re-encoding the history.
+ * No counterpart in the reference (it re-runs LRURec.forward on the whole sequence, demo/inference.py:46-53).
+ * ------------------------------------------------------------------------------------------
+ * The encoder's recurrence h_t = lambda * h_{t-1} + bu_t is a sequential scan and everything around it is per position,
+ * so (h_re, h_im) of every block after t tokens summarises the history. A caller-owned DEVICE table keeps one row per
+ * user ("slot"); a row of a model with nb blocks is
+ *     float   h[nb][2][128]   re | im per block, channel order of the packed image's lam_re / lam_im
+ *     float   q[64]           the last hidden state written (what lr_lru_encode_last returns for the history so far)
+ *     int32_t live            tokens since reset, saturating at INT32_MAX; only `== 0` is read
+ *     padding to a multiple of 256 bytes      (lr_lru_user_state_row_bytes(nb) = nb * 1024 + 512)
+ * at byte offset slot * row_bytes; the table pointer must be 4-byte aligned. An all-zero row IS the reset state, so
+ * hipMemset resets. A table copied to the host and back (or into another table of the same model) continues with the same
+ * bits: that is the persistence story, there is no file format.
+ *
+ * CONTRACT. For a row that was reset and then advanced by ANY chunking of a history of ids >= 1, in any batch, through
+ * any slot, q has the bits lr_lru_encode_last returns for that history (left padded to any length), and the top-K from
+ * the state with exclude_ids = that history has the indices and scores of lr_lru_retrieve_topk.
+ * The state sees EVERYTHING since reset. A caller that truncates a history to its last L ids, as the reference's datasets
+ * do (dataloader/lru.py:142-151), gets a different, longer-memory answer from the state once the history exceeds L.
+ *
+ *   slots   : DEVICE int32 [B], row u of the call -> table row; NULL: 0..B-1 (reset: every slot, B ignored). Distinct
+ *             values are the caller's duty. A value outside [0, num_slots) makes the kernel skip that row: nothing is read
+ *             or written for it and its out_q row is zero.
+ *   new_ids : DEVICE int64 [B][Ln], consumed left to right per user. Ids <= 0 are SKIPPED, they do not cut the history
+ *             (they are the left padding that lets one call append different counts per user; only a reset cuts). Ids
+ *             above num_items are embedded as row 0, as the encoder embeds them. A reset row's first live id starts the
+ *             history as the encoder starts it (h = bu). NULL with Ln = 0: nothing is consumed.
+ *   out_q   : DEVICE fp32 [B][64] (may be NULL): the last block's output at the user's last consumed token, also stored
+ *             in the row. A user with no live id in the call keeps its state and returns its stored q; a never-advanced
+ *             row returns zeros.
+ * Argument checks run before any device work (LR_EINVAL / LR_EWORKSPACE with an lr_last_error text); B = 0 is LR_OK and
+ * launches nothing. */
+
+/* Pure CPU. 0 for num_blocks outside 1..LR_MAX_LRU_BLOCKS. */
+size_t lr_lru_user_state_row_bytes(int32_t num_blocks);
+
+/* Zero the listed rows (slots NULL: the whole table). Ordered on hip_stream. */
+int lr_lru_user_state_reset(lr_lru_t* h, void* states, int32_t num_slots, const int32_t* slots, int32_t B,
+                            void* hip_stream);
+
+/* Append new_ids to the users' states. Needs no workspace. */
+int lr_lru_user_state_advance(lr_lru_t* h, void* states, int32_t num_slots, const int32_t* slots,
+                              const int64_t* new_ids, int32_t B, int32_t Ln, float* out_q, void* hip_stream);
+
+/* lr_lru_user_state_advance, then the item GEMM and ordered top-K of lr_lru_retrieve_topk on the resulting q.
+ *   new_ids NULL with Ln = 0: query only.
+ *   exclude_ids: DEVICE int64 [B][Lx], the caller's history for the -1e9 mask (ids and the pad id 0, as
+ *             lr_lru_retrieve_topk masks with exclude_history = 1), Lx <= 8192; NULL with Lx = 0: nothing is masked.
+ *   workspace: lr_lru_workspace_bytes(h, B, K, max(Lx, 1)) bytes. */
+int lr_lru_retrieve_topk_user_state(lr_lru_t* h, void* states, int32_t num_slots, const int32_t* slots,
+                                    const int64_t* new_ids, int32_t B, int32_t Ln, const int64_t* exclude_ids,
+                                    int32_t Lx, int32_t K, int32_t* out_idx, float* out_score, void* workspace,
+                                    size_t workspace_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
  * Ranking metrics  (trainer/utils.py:43-90 with preprocessed ranks)
  * ------------------------------------------------------------------------------------------ */
 

@@ -231,3 +231,64 @@ extern "C" int lr_lru_scores_last(lr_lru_t* h, const int64_t* ids, int32_t B, in
   LR_RUN(encode(h, ids, B, L, w.q, w.rest, w.rest_bytes, st));
   return lr_launch_item_scores(h, w.q, ids, B, L, exclude_history, out_scores, st);
 }
+
+// ---- user states (lru_state.hip) -------------------------------------------------------------------------------------
+extern "C" size_t lr_lru_user_state_row_bytes(int32_t num_blocks) {
+  if (num_blocks < 1 || num_blocks > LR_MAX_LRU_BLOCKS) return 0;
+  return lr_lru_state_row_bytes(num_blocks);
+}
+
+// What the three entry points share; every check here runs before any device work.
+static int check_states(const char* fn, const lr_lru_t* h, const void* states, int num_slots, int B) {
+  if (!h || !states) LR_FAIL(LR_EINVAL, "%s: null handle or state table", fn);
+  if (num_slots < 1) LR_FAIL(LR_EINVAL, "%s: num_slots=%d, a table has at least one row", fn, num_slots);
+  if (B < 0) LR_FAIL(LR_EINVAL, "%s: B=%d", fn, B);
+  if ((uintptr_t)states % sizeof(float)) LR_FAIL(LR_EINVAL, "%s: the state table must be 4-byte aligned", fn);
+  return LR_OK;
+}
+
+static int check_new_ids(const char* fn, const void* new_ids, int Ln) {
+  if (Ln < 0) LR_FAIL(LR_EINVAL, "%s: Ln=%d", fn, Ln);
+  if (Ln > 0 && !new_ids) LR_FAIL(LR_EINVAL, "%s: new_ids is null with Ln=%d", fn, Ln);
+  return LR_OK;
+}
+
+extern "C" int lr_lru_user_state_reset(lr_lru_t* h, void* states, int32_t num_slots, const int32_t* slots, int32_t B,
+                                       void* hip_stream) {
+  LR_RUN(check_states("lr_lru_user_state_reset", h, states, num_slots, slots ? B : 0));
+  return lr_launch_lru_state_reset(h, states, num_slots, slots, B, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_lru_user_state_advance(lr_lru_t* h, void* states, int32_t num_slots, const int32_t* slots,
+                                         const int64_t* new_ids, int32_t B, int32_t Ln, float* out_q, void* hip_stream) {
+  LR_RUN(check_states("lr_lru_user_state_advance", h, states, num_slots, B));
+  LR_RUN(check_new_ids("lr_lru_user_state_advance", new_ids, Ln));
+  return lr_launch_lru_state_advance(h, states, num_slots, slots, new_ids, B, Ln, out_q, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_lru_retrieve_topk_user_state(lr_lru_t* h, void* states, int32_t num_slots, const int32_t* slots,
+                                               const int64_t* new_ids, int32_t B, int32_t Ln, const int64_t* exclude_ids,
+                                               int32_t Lx, int32_t K, int32_t* out_idx, float* out_score, void* workspace,
+                                               size_t workspace_bytes, void* hip_stream) {
+  const char* fn = "lr_lru_retrieve_topk_user_state";
+  LR_RUN(check_states(fn, h, states, num_slots, B));
+  LR_RUN(check_new_ids(fn, new_ids, Ln));
+  if (Lx < 0) LR_FAIL(LR_EINVAL, "%s: Lx=%d", fn, Lx);
+  if (Lx > 0 && !exclude_ids) LR_FAIL(LR_EINVAL, "%s: exclude_ids is null with Lx=%d", fn, Lx);
+  if (Lx > 8192) LR_FAIL(LR_EUNSUPPORTED, "%s: Lx=%d > 8192 is not supported by the mask pre-pass", fn, Lx);
+  if (K < 1 || K > LR_MAX_TOPK) LR_FAIL(LR_EINVAL, "%s: K=%d outside 1..%d", fn, K, LR_MAX_TOPK);
+  if (!out_idx || !workspace) LR_FAIL(LR_EINVAL, "%s: null output/workspace", fn);
+  if (B == 0) return LR_OK;
+  QSplit w;
+  LR_RUN(split_q(fn, workspace, workspace_bytes, B, &w));
+  const int exclude = Lx > 0 ? 1 : 0, L = exclude ? Lx : 1;
+  // lr_launch_item_topk makes this check too, but behind the advance launch: a workspace error must leave the states as
+  // they were, so it is made here first
+  const size_t need = tk_plan(h->lay.rows_padded / LR_ITEM_TILE, B, K, L, exclude).total;
+  if (need > w.rest_bytes) LR_FAIL(LR_EWORKSPACE, "%s: top-K workspace: need %zu bytes, have %zu", fn, need, w.rest_bytes);
+  hipStream_t st = (hipStream_t)hip_stream;
+  LR_RUN(lr_launch_lru_state_advance(h, states, num_slots, slots, new_ids, B, Ln, w.q, st));
+  // without exclusion no kernel reads the ids, but bound_select_kernel is handed the pointer: give it the q rows
+  const int64_t* ids = exclude ? exclude_ids : reinterpret_cast<const int64_t*>(w.q);
+  return lr_launch_item_topk(h, w.q, ids, B, L, K, exclude, out_idx, out_score, w.rest, w.rest_bytes, st);
+}

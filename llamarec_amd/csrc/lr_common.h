@@ -143,6 +143,15 @@ int lr_launch_item_topk(const lr_lru* h, const float* q, const int64_t* ids, int
 int lr_launch_item_scores(const lr_lru* h, const float* q, const int64_t* ids, int B, int L,
                           int exclude_history, float* out_scores, hipStream_t st);
 
+// user states (lru_state.hip): a table row is [h[nb][2][128] f32 | q[64] f32 | live i32 | padding to 256 bytes]
+static inline size_t lr_lru_state_row_bytes(int num_blocks) {
+  return lr_align_up((size_t)num_blocks * 2 * LR_H * sizeof(float) + 64 * sizeof(float) + sizeof(int32_t), 256);
+}
+int lr_launch_lru_state_reset(const lr_lru* h, void* states, int num_slots, const int32_t* slots, int B, hipStream_t st);
+// new_ids null or Ln 0: no token is consumed, out_q gets the stored q rows
+int lr_launch_lru_state_advance(const lr_lru* h, void* states, int num_slots, const int32_t* slots, const int64_t* new_ids,
+                                int B, int Ln, float* out_q, hipStream_t st);
+
 // ---- stage-2 handle -------------------------------------------------------------------------
 struct lr_llama {
   LrLlamaConfig cfg;

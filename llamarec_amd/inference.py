@@ -20,6 +20,29 @@ def retrieve_candidates(model, query, top_k: int = 20):
     return idx[0].tolist()
 
 
+class RetrieverSession:
+    """One user's retriever state carried across interactions: `append` the items as they arrive, `candidates` whenever
+    a list is wanted. Returns what `retrieve_candidates(model, whole_query, top_k)` returns for everything appended so
+    far, without re-encoding it (LRURec.advance: one recurrence step per new item)."""
+
+    def __init__(self, model):
+        self.model = model
+        self.states = model.new_user_states(1)
+        self.query = []
+
+    def append(self, item_ids):
+        """Add one item id or a sequence of them to the end of the user's history."""
+        items = np.asarray(item_ids, dtype=np.int64).reshape(-1)
+        if items.size:
+            self.model.advance(self.states, items.reshape(1, -1))
+            self.query.extend(items.tolist())
+        return self
+
+    def candidates(self, top_k: int = 20):
+        idx, _ = self.model.retrieve_topk_from_states(self.states, top_k)
+        return idx[0].tolist()
+
+
 def generate_prompt(query, candidates, dataset_map, instruction=P.DEFAULT_SYSTEM_TEMPLATE,
                     input_template=P.DEFAULT_INPUT_TEMPLATE, prompter=None):
     """demo/inference.py:79-109 (titles verbatim, alpaca_short layout)."""

@@ -85,6 +85,22 @@ def pack_state_dict(state_dict) -> tuple[np.ndarray, int, int]:
     return img, int(desc.num_items), int(desc.num_blocks)
 
 
+class UserStates:
+    """A device table of LRURec user states, one row per slot (layout: include/llamarec_mi355x.h, "LRURec user
+    states"). An all-zero row is a user with no history. Made by `LRURec.new_user_states` / `load_user_states`."""
+
+    def __init__(self, table):
+        self.table = table  # uint8 [num_slots, row_bytes]
+
+    @property
+    def num_slots(self):
+        return int(self.table.shape[0])
+
+    def numpy(self):
+        """Host copy; `LRURec.load_user_states` of a model with the same weights continues from it with the same bits."""
+        return self.table.cpu().numpy()
+
+
 class LRURec:
     """Scoring-only LRURec on one MI355X.
 
@@ -218,6 +234,87 @@ class LRURec:
             check(lib().lr_lru_retrieve_topk(self._h, ids.data_ptr(), B, L, k, int(bool(exclude_history)),
                                              idx.data_ptr(), sc.data_ptr(), ws.data_ptr(), ws.numel(),
                                              stream_ptr()), "lr_lru_retrieve_topk")
+        return idx, sc
+
+    # -- user states: append ids to a stored recurrence state (lr_lru_user_state_*) ---------------
+    def new_user_states(self, num_slots):
+        """A table of `num_slots` reset user states on the model's device."""
+        if num_slots < 1:
+            raise ValueError("num_slots must be at least 1")
+        rb = lib().lr_lru_user_state_row_bytes(self.num_blocks)
+        return UserStates(torch.zeros((int(num_slots), rb), dtype=torch.uint8, device=self.device))
+
+    def load_user_states(self, array):
+        """A table from `UserStates.numpy()` of a model with the same weights: continues with the same bits."""
+        a = np.ascontiguousarray(array, dtype=np.uint8)
+        rb = lib().lr_lru_user_state_row_bytes(self.num_blocks)
+        if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != rb:
+            raise ValueError(f"expected a uint8 table [num_slots, {rb}], got {a.shape}")
+        return UserStates(torch.from_numpy(a).to(self.device))
+
+    def _slots(self, slots, B=None):
+        if slots is None:
+            return None
+        if not isinstance(slots, torch.Tensor):
+            slots = torch.as_tensor(np.asarray(slots))
+        if slots.dim() != 1 or (B is not None and slots.numel() != B):
+            raise ValueError(f"expected slots of shape [{'B' if B is None else B}], got {tuple(slots.shape)}")
+        return slots.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def _states(self, st, slots, B):
+        if slots is None and B > st.num_slots:
+            raise ValueError(f"{B} users but the table has {st.num_slots} slots")
+        return st.table.data_ptr(), st.num_slots, (slots.data_ptr() if slots is not None else None)
+
+    def reset_user_states(self, st, slots=None):
+        """Back to the empty history: the listed slots, or every slot."""
+        slots = self._slots(slots)
+        with torch.cuda.device(self.device):
+            check(lib().lr_lru_user_state_reset(self._h, st.table.data_ptr(), st.num_slots,
+                                                slots.data_ptr() if slots is not None else None,
+                                                slots.numel() if slots is not None else 0, stream_ptr()),
+                  "lr_lru_user_state_reset")
+
+    def advance(self, st, new_ids, slots=None):
+        """Append new_ids [B, Ln] (ids <= 0 are skipped) to the users in `slots` (default 0..B-1); returns q [B, 64],
+        the bits `encode_last` returns for each user's whole history since reset."""
+        ids = self._ids(new_ids)
+        B, Ln = ids.shape
+        slots = self._slots(slots, B)
+        q = torch.empty((B, 64), dtype=torch.float32, device=self.device)
+        if B == 0:
+            return q
+        table, n, sp = self._states(st, slots, B)
+        with torch.cuda.device(self.device):
+            check(lib().lr_lru_user_state_advance(self._h, table, n, sp, ids.data_ptr() if Ln else None, B, Ln,
+                                                  q.data_ptr(), stream_ptr()), "lr_lru_user_state_advance")
+        return q
+
+    def retrieve_topk_from_states(self, st, k, new_ids=None, exclude=None, slots=None):
+        """`advance` (new_ids None: query only) and the ordered top-k of `retrieve_topk` on the result. exclude [B, Lx]:
+        ids masked to -1e9 together with the pad id 0 (pass the users' histories); None: nothing is masked."""
+        if not 1 <= k <= MAX_TOPK:
+            raise ValueError(f"k must be in 1..{MAX_TOPK}")
+        ids = self._ids(new_ids) if new_ids is not None else None
+        excl = self._ids(exclude) if exclude is not None else None
+        slots = self._slots(slots)
+        sizes = {t.shape[0] for t in (ids, excl, slots) if t is not None}
+        if len(sizes) > 1:
+            raise ValueError("new_ids, exclude and slots must have the same number of rows")
+        B = sizes.pop() if sizes else st.num_slots
+        Ln = ids.shape[1] if ids is not None else 0
+        Lx = excl.shape[1] if excl is not None else 0
+        idx = torch.empty((B, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        if B == 0:
+            return idx, sc
+        table, n, sp = self._states(st, slots, B)
+        ws = self._workspace(B, k, max(Lx, 1))
+        with torch.cuda.device(self.device):
+            check(lib().lr_lru_retrieve_topk_user_state(self._h, table, n, sp, ids.data_ptr() if Ln else None, B, Ln,
+                                                        excl.data_ptr() if Lx else None, Lx, k, idx.data_ptr(),
+                                                        sc.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()),
+                  "lr_lru_retrieve_topk_user_state")
         return idx, sc
 
     def set_encoder_pipeline(self, enable):
