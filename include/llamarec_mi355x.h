@@ -193,6 +193,45 @@ int lr_lru_retrieve_topk_user_state(lr_lru_t* h, void* states, int32_t num_slots
                                     int32_t Lx, int32_t K, int32_t* out_idx, float* out_score, void* workspace,
                                     size_t workspace_bytes, void* hip_stream);
 
+/* States seeded from WHOLE histories by the batched encoder's own pass: one call encodes ids[B][L] (q as
+ * lr_lru_encode_last, same bits) and leaves every listed row ready for lr_lru_user_state_advance -- the encoder's
+ * recurrence already holds each block's state at each user's last row; these calls write it to the table instead of
+ * dropping it. Day-one users of a deployed system, or users whose state was lost, need no bootstrap through advance.
+ *
+ * CONTRACT ADDED. For a history ending in an id >= 1 the row has the bytes (h, q, the `live == 0` test) that reset plus
+ * lr_lru_user_state_advance of the same LIVE ids leaves, so every later advance / retrieve_topk_user_state on it returns
+ * the bits of lr_lru_encode_last / lr_lru_retrieve_topk on the concatenated history.
+ *   - The state written is that of the live tokens the encoder processed: the ids behind the last id <= 0 among the first
+ *     L-1 positions. A pad in the middle CUTS (the state equals reset + advance of what follows the cut); ids above
+ *     num_items are embedded as row 0, as everywhere.
+ *   - A history whose LAST id is <= 0 (the all-pad row included) is outside the states' contract: the encoder embeds that
+ *     pad as a token, a state skips it. Its table row is written as the reset state (zeros in h, q, live); its out_q row
+ *     stays the encoder's.
+ *   - The call OVERWRITES h, q and live of each listed row (padding bytes are left alone); no reset is needed first.
+ *   - A slot outside [0, num_slots): nothing of the table is read or written for that user. Its out_q row is still the
+ *     encoder's (the history is in the call) -- unlike advance, which answers zeros. Distinct slots are the caller's duty.
+ *   - These calls need the batched MFMA encoder: a workspace that is NULL or smaller than
+ *     lr_lru_user_state_encode_workspace_bytes(h, B, K, L) is LR_EWORKSPACE (there is no scratch-free form).
+ * Argument checks run before any device work, with lr_last_error texts; B = 0 is LR_OK and launches nothing. */
+
+/* lr_lru_workspace_bytes(h, max_users, max_k, max_len) plus the export buffers of blocks 0 .. nb-2:
+ * (nb - 1) * min(max_users, users per encoder chunk at max_len) * 1 KB, 256-byte aligned; nothing more for nb = 1.
+ * NULL h returns 0 and sets lr_last_error. Monotone like lr_lru_workspace_bytes. For lr_lru_user_state_encode pass
+ * max_k = 1. */
+size_t lr_lru_user_state_encode_workspace_bytes(const lr_lru_t* h, int32_t max_users, int32_t max_k, int32_t max_len);
+
+/* lr_lru_encode_last on ids[B][L] that also writes the users' table rows. out_q: DEVICE fp32 [B][64], may be NULL. */
+int lr_lru_user_state_encode(lr_lru_t* h, void* states, int32_t num_slots, const int32_t* slots, const int64_t* ids,
+                             int32_t B, int32_t L, float* out_q, void* workspace, size_t workspace_bytes,
+                             void* hip_stream);
+
+/* lr_lru_retrieve_topk (same top-K plan, same bits in out_idx / out_score) whose encoder pass also writes the users'
+ * table rows. */
+int lr_lru_retrieve_topk_seed_user_state(lr_lru_t* h, void* states, int32_t num_slots, const int32_t* slots,
+                                         const int64_t* ids, int32_t B, int32_t L, int32_t K, int32_t exclude_history,
+                                         int32_t* out_idx, float* out_score, void* workspace, size_t workspace_bytes,
+                                         void* hip_stream);
+
 /* ------------------------------------------------------------------------------------------
  * Ranking metrics  (trainer/utils.py:43-90 with preprocessed ranks)
  * ------------------------------------------------------------------------------------------ */

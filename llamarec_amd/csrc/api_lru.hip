@@ -292,3 +292,63 @@ extern "C" int lr_lru_retrieve_topk_user_state(lr_lru_t* h, void* states, int32_
   const int64_t* ids = exclude ? exclude_ids : reinterpret_cast<const int64_t*>(w.q);
   return lr_launch_item_topk(h, w.q, ids, B, L, K, exclude, out_idx, out_score, w.rest, w.rest_bytes, st);
 }
+
+// ---- user states seeded from whole histories by the encoder pass ---------------------------------------------------
+// Workspace of the two seeding calls: [what lr_lru_workspace_bytes(h, B, K, L) lays out, unchanged | export buffers of
+// blocks 0 .. nb-2]. The export buffers start at the size of the CALL's (B, K, L), so a workspace sized for larger
+// arguments serves it.
+extern "C" size_t lr_lru_user_state_encode_workspace_bytes(const lr_lru_t* h, int32_t max_users, int32_t max_k,
+                                                           int32_t max_len) {
+  if (!h) {
+    lr_set_error("lr_lru_user_state_encode_workspace_bytes: the model handle is null");
+    return 0;
+  }
+  if (max_users < 1) max_users = 1;
+  if (max_len < 1) max_len = 1;
+  return lr_lru_workspace_bytes(h, max_users, max_k, max_len) + lr_encoder_mfma_export_bytes(h->lay.num_blocks, max_users, max_len);
+}
+
+// The workspace check both seeding calls share (the last one before any device work), then the split. B >= 1.
+static int seed_split(const char* fn, lr_lru_t* h, void* states, int num_slots, const int32_t* slots, int B, int L, int K,
+                      void* workspace, size_t workspace_bytes, QSplit* w, LrLruSeed* seed) {
+  const size_t base = lr_lru_workspace_bytes(h, B, K, L), need = base + lr_encoder_mfma_export_bytes(h->lay.num_blocks, B, L);
+  if (!workspace || workspace_bytes < need)
+    LR_FAIL(LR_EWORKSPACE, "%s: the batched encoder needs a workspace of %zu bytes (lr_lru_user_state_encode_workspace_bytes), have %zu",
+            fn, need, workspace ? workspace_bytes : (size_t)0);
+  *w = {(float*)workspace, (char*)workspace + q_bytes(B), base - q_bytes(B)};
+  *seed = {states, num_slots, slots, (float*)((char*)workspace + base)};
+  return LR_OK;
+}
+
+extern "C" int lr_lru_user_state_encode(lr_lru_t* h, void* states, int32_t num_slots, const int32_t* slots,
+                                        const int64_t* ids, int32_t B, int32_t L, float* out_q, void* workspace,
+                                        size_t workspace_bytes, void* hip_stream) {
+  const char* fn = "lr_lru_user_state_encode";
+  LR_RUN(check_states(fn, h, states, num_slots, B));
+  if (L < 1) LR_FAIL(LR_EINVAL, "%s: L=%d", fn, L);
+  if (B > 0 && !ids) LR_FAIL(LR_EINVAL, "%s: ids is null with B=%d", fn, B);
+  if (B == 0) return LR_OK;
+  QSplit w;
+  LrLruSeed seed;
+  LR_RUN(seed_split(fn, h, states, num_slots, slots, B, L, 1, workspace, workspace_bytes, &w, &seed));
+  return lr_launch_lru_encode_mfma_seed(h, ids, B, L, out_q ? out_q : w.q, w.rest, w.rest_bytes, &seed, (hipStream_t)hip_stream);
+}
+
+extern "C" int lr_lru_retrieve_topk_seed_user_state(lr_lru_t* h, void* states, int32_t num_slots, const int32_t* slots,
+                                                    const int64_t* ids, int32_t B, int32_t L, int32_t K,
+                                                    int32_t exclude_history, int32_t* out_idx, float* out_score,
+                                                    void* workspace, size_t workspace_bytes, void* hip_stream) {
+  const char* fn = "lr_lru_retrieve_topk_seed_user_state";
+  LR_RUN(check_states(fn, h, states, num_slots, B));
+  if (L < 1) LR_FAIL(LR_EINVAL, "%s: L=%d", fn, L);
+  if (B > 0 && !ids) LR_FAIL(LR_EINVAL, "%s: ids is null with B=%d", fn, B);
+  if (K < 1 || K > LR_MAX_TOPK) LR_FAIL(LR_EINVAL, "%s: K=%d outside 1..%d", fn, K, LR_MAX_TOPK);
+  if (!out_idx) LR_FAIL(LR_EINVAL, "%s: out_idx is null", fn);
+  if (B == 0) return LR_OK;
+  QSplit w;
+  LrLruSeed seed;
+  LR_RUN(seed_split(fn, h, states, num_slots, slots, B, L, K, workspace, workspace_bytes, &w, &seed));
+  hipStream_t st = (hipStream_t)hip_stream;
+  LR_RUN(lr_launch_lru_encode_mfma_seed(h, ids, B, L, w.q, w.rest, w.rest_bytes, &seed, st));
+  return lr_launch_item_topk(h, w.q, ids, B, L, K, exclude_history, out_idx, out_score, w.rest, w.rest_bytes, st);
+}

@@ -151,6 +151,22 @@ int lr_launch_lru_state_reset(const lr_lru* h, void* states, int num_slots, cons
 // new_ids null or Ln 0: no token is consumed, out_q gets the stored q rows
 int lr_launch_lru_state_advance(const lr_lru* h, void* states, int num_slots, const int32_t* slots, const int64_t* new_ids,
                                 int B, int Ln, float* out_q, hipStream_t st);
+// States seeded by the batched encoder's pass over whole histories (lr_lru_user_state_encode): the LRU layers of blocks
+// 0 .. nb-2 store each user's last-row recurrence state to exp [nb-1][users of a chunk][256] (lr_encoder_mfma_export_bytes),
+// and lr_launch_lru_state_seed, launched behind every chunk, gathers them, the last block's Ul, the chunk's q rows and
+// live counts into the table rows slots[u] (null: slot0 + u).
+struct LrLruSeed {
+  void* states;
+  int num_slots;
+  const int32_t* slots;  // [B] of the call, or null
+  float* exp;
+};
+size_t lr_encoder_mfma_export_bytes(int num_blocks, int B, int L);
+int lr_launch_lru_encode_mfma_seed(const lr_lru* h, const int64_t* ids, int B, int L, float* out_q, void* ws,
+                                   size_t ws_bytes, const LrLruSeed* seed, hipStream_t st);
+int lr_launch_lru_state_seed(const lr_lru* h, void* states, int num_slots, const int32_t* slots, int slot0, const int64_t* ids,
+                             int users, int L, const int* n, const float* exp, size_t exp_block_floats, const float* Ul,
+                             const float* q, hipStream_t st);
 
 // ---- stage-2 handle -------------------------------------------------------------------------
 struct lr_llama {

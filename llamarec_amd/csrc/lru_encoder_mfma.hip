@@ -228,6 +228,9 @@ __device__ __forceinline__ void em_gelu_tab12(const float (&x)[N], float (&y)[N]
 //   MODE 1  feed-forward   : w_1 + GELU -> w_2 + residual + LayerNorm                                  Y -> X
 //   MODE 2  LRU, last block: in_proj -> recurrence, the state of each user's LAST row only             X -> Ul[user][256]
 //   MODE 3  out_proj + residual + LayerNorm of rows given as [row][256] (the last rows)                Ul -> Yl
+//   EXPORT (MODE 0 only, the user-state seeding calls): the recurrence also stores the state of each user's LAST row,
+//     which MODE 0 otherwise only writes back over the LDS tile, to EXP[user][256] -- one float4 per lane, in the scan's
+//     lane order (lane l: re of channels sc_k, sc_k + 2, then their im); lru_state.hip undoes the permutation.
 // The 256-wide intermediate of a super tile (in_proj output / FFN hidden) lives only in LDS: the layer reads 256 B and
 // writes 256 B per row instead of 1 KiB + 1 KiB (+ 2 KiB for the recurrence) per row through HBM.
 //   phase A (K = 64, weights in registers): wave w owns output blocks 2w, 2w+1 for both 32-row tiles of the super
@@ -283,6 +286,15 @@ struct EmLayer {
   int n_rows_fixed;
   int stamp;
 };
+// The EXPORT instantiations' argument: the others keep EmLayer, so their kernel argument layout -- and with it their code --
+// is what it was before the export existed.
+struct EmLayerExp : EmLayer {
+  float* EXP;             // [users][256] recurrence state at each user's last row, lane order
+};
+template <bool EXPORT> struct EmArgs { typedef EmLayer type; };
+template <> struct EmArgs<true> { typedef EmLayerExp type; };
+__device__ __forceinline__ float* em_exp(const EmLayer&) { return nullptr; }
+__device__ __forceinline__ float* em_exp(const EmLayerExp& p) { return p.EXP; }
 
 __device__ __forceinline__ int em_pos(int out) { return (out >> 6) * 64 + (out & 1) * 32 + ((out & 63) >> 1); }
 
@@ -297,8 +309,9 @@ __device__ __forceinline__ void em_load_rows8(float4 (&v)[2], const float* M, in
   }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void em_layer_kernel(EmLayer p) {
+template <int MODE, bool EXPORT = false>
+__global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void em_layer_kernel(typename EmArgs<EXPORT>::type p) {
+  static_assert(!EXPORT || MODE == 0, "em_layer_kernel: only the LRU layer of blocks 0 .. nb-2 exports its state");
   constexpr bool HAS_A = MODE != 3, HAS_B = MODE != 2, SCAN = MODE == 0 || MODE == 2;
   extern __shared__ __attribute__((aligned(16))) float smem_f[];
   float* ws = smem_f;                    // [64][EM_WS]   phase B weights, de-interleaved per 64-k chunk
@@ -487,8 +500,10 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         }
         float* base = ul + sc_pos;
         // one recurrence step on the lane's two complex channels (the oracle's fmaf order), then the row's hand-over:
-        // MODE 0 writes the state back over the row, MODE 2 emits it where a user ends
-#define EM_SCAN_STEP(t_, bre_, bim_, is_first_)                                                        \
+        // MODE 0 writes the state back over the row (EXPORT: and emits it where a user ends), MODE 2 emits it where a user ends
+#define EM_EXPORT_ROW(t_)                                                                              \
+  *reinterpret_cast<float4*>(em_exp(p) + (size_t)(tags[(t_)] >> 2) * 256 + 4 * lane) = make_float4(h_r0, h_r1, h_i0, h_i1);
+#define EM_SCAN_STEP(t_, bre_, bim_, is_first_, exp_)                                                  \
   {                                                                                                    \
     if (is_first_) {                                                                                   \
       h_r0 = (bre_).x; h_r1 = (bre_).y; h_i0 = (bim_).x; h_i1 = (bim_).y;                             \
@@ -502,6 +517,7 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     if (MODE == 0) {                                                                                   \
       *reinterpret_cast<float2*>(base + (t_) * EM_US) = make_float2(h_r0, h_r1);                       \
       *reinterpret_cast<float2*>(base + (t_) * EM_US + 128) = make_float2(h_i0, h_i1);                 \
+      if (EXPORT && (exp_) && ((lasts >> (t_)) & 1)) EM_EXPORT_ROW(t_)                                 \
     } else if ((lasts >> (t_)) & 1) {                                                                  \
       float* o = p.OUT + (size_t)(tags[(t_)] >> 2) * 256;                                              \
       o[sc_k] = h_r0;                                                                                  \
@@ -523,7 +539,7 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             const float2 b_re = *reinterpret_cast<const float2*>(base + t * EM_US);
             const float2 b_im = *reinterpret_cast<const float2*>(base + t * EM_US + 128);
             const bool first = (firsts >> t) & 1;   // wave-uniform
-            EM_SCAN_STEP(t, b_re, b_im, first)
+            EM_SCAN_STEP(t, b_re, b_im, first, false)
             ++t;
           }
           float2 cr[4], ci[4], nr[4], ni[4];
@@ -541,7 +557,7 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
               ni[i] = *reinterpret_cast<const float2*>(base + tt * EM_US + 128);
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) EM_SCAN_STEP(t + i, cr[i], ci[i], false)
+            for (int i = 0; i < 4; ++i) EM_SCAN_STEP(t + i, cr[i], ci[i], false, false)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               cr[i] = nr[i];
@@ -550,7 +566,10 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
           }
 #pragma unroll
           for (int i = 0; i < 3; ++i)
-            if (t + i < sb) EM_SCAN_STEP(t + i, cr[i], ci[i], false)   // wave-uniform
+            if (t + i < sb) EM_SCAN_STEP(t + i, cr[i], ci[i], false, false)   // wave-uniform
+          // EXPORT: one user from sa to sb, so the only row that can be a user's last is sb - 1 (a last row is followed by a
+          // first row or by the tile's end): no test per row on this path, the state after the walk is that row's
+          if (EXPORT && MODE == 0 && ((lasts >> (sb - 1)) & 1)) EM_EXPORT_ROW(sb - 1)
         } else {
         for (int t0 = sa; t0 < sb; t0 += 4) {
           float2 br[4], bi[4];
@@ -565,12 +584,13 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             const int t = t0 + i;
             if (t < sb) {  // wave-uniform
               const bool first = (firsts >> t) & 1;
-              EM_SCAN_STEP(t, br[i], bi[i], first)
+              EM_SCAN_STEP(t, br[i], bi[i], first, true)
             }
           }
         }
         }
 #undef EM_SCAN_STEP
+#undef EM_EXPORT_ROW
         // (the other buffer: wave 0 may not have read this tile's carry-in yet)
         if (sb == EM_ST) *reinterpret_cast<float4*>(carry + (par ^ 1) * 256 + 4 * lane) = make_float4(h_r0, h_r1, h_i0, h_i1);
       }
@@ -713,9 +733,10 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 // oracle. MODE 0 (LRU layer) and MODE 1 (feed-forward); the last block's two kernels (MODE 2, 3) stay on em_layer_kernel.
 #define EP_B1 4
 
-template <int MODE>
-__global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void em_pipe_kernel(EmLayer p) {
+template <int MODE, bool EXPORT = false>
+__global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void em_pipe_kernel(typename EmArgs<EXPORT>::type p) {
   static_assert(MODE == 0 || MODE == 1, "em_pipe_kernel: LRU layer or feed-forward");
+  static_assert(!EXPORT || MODE == 0, "em_pipe_kernel: only the LRU layer exports its state");
   constexpr bool SCAN = MODE == 0;
   extern __shared__ __attribute__((aligned(16))) float smem_f[];
   float* ul0 = smem_f;                       // [2][EM_ST][EM_US] the 256-wide intermediate of two tiles
@@ -866,6 +887,7 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
   auto scan = [&](float* ulb, const int* tg) {
     const int tg_lane = tg[lane];
     const unsigned long long firsts = __ballot(tg_lane & 1);
+    const unsigned long long lasts = EXPORT ? __ballot(tg_lane & 2) : 0ull;   // EXPORT: the rows whose state is emitted
     int sa = 0, sb = EM_ST;
     if (aw > 0) {
       const unsigned long long m = firsts & (~0ull << (16 * aw));
@@ -886,7 +908,9 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         h_r0 = h_r1 = h_i0 = h_i1 = 0.f;  // overwritten by the segment's first row
       }
       float* base = ulb + sc_pos;
-#define EP_SCAN_STEP(t_, bre_, bim_, is_first_)                                                        \
+#define EP_EXPORT_ROW(t_)                                                                              \
+  *reinterpret_cast<float4*>(em_exp(p) + (size_t)(tg[(t_)] >> 2) * 256 + 4 * lane) = make_float4(h_r0, h_r1, h_i0, h_i1);
+#define EP_SCAN_STEP(t_, bre_, bim_, is_first_, exp_)                                                  \
   {                                                                                                    \
     if (is_first_) {                                                                                   \
       h_r0 = (bre_).x; h_r1 = (bre_).y; h_i0 = (bim_).x; h_i1 = (bim_).y;                             \
@@ -899,6 +923,7 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     }                                                                                                  \
     *reinterpret_cast<float2*>(base + (t_) * EM_US) = make_float2(h_r0, h_r1);                         \
     *reinterpret_cast<float2*>(base + (t_) * EM_US + 128) = make_float2(h_i0, h_i1);                   \
+    if (EXPORT && (exp_) && ((lasts >> (t_)) & 1)) EP_EXPORT_ROW(t_)                                   \
   }
       const unsigned long long upto = sb >= 64 ? ~0ull : ((1ull << sb) - 1ull);
       const unsigned long long inner_firsts = firsts & upto & ~((2ull << sa) - 1ull);
@@ -908,7 +933,7 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
           const float2 b_re = *reinterpret_cast<const float2*>(base + t * EM_US);
           const float2 b_im = *reinterpret_cast<const float2*>(base + t * EM_US + 128);
           const bool first = (firsts >> t) & 1;   // wave-uniform
-          EP_SCAN_STEP(t, b_re, b_im, first)
+          EP_SCAN_STEP(t, b_re, b_im, first, false)
           ++t;
         }
         float2 cr[4], ci[4], nr[4], ni[4];
@@ -926,7 +951,7 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             ni[i] = *reinterpret_cast<const float2*>(base + tt * EM_US + 128);
           }
 #pragma unroll
-          for (int i = 0; i < 4; ++i) EP_SCAN_STEP(t + i, cr[i], ci[i], false)
+          for (int i = 0; i < 4; ++i) EP_SCAN_STEP(t + i, cr[i], ci[i], false, false)
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             cr[i] = nr[i];
@@ -935,7 +960,9 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         }
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-          if (t + i < sb) EP_SCAN_STEP(t + i, cr[i], ci[i], false)   // wave-uniform
+          if (t + i < sb) EP_SCAN_STEP(t + i, cr[i], ci[i], false, false)   // wave-uniform
+        // EXPORT: the only row of a one-user segment that can be a user's last is sb - 1 (em_layer_kernel): no test per row
+        if (EXPORT && ((lasts >> (sb - 1)) & 1)) EP_EXPORT_ROW(sb - 1)
       } else {
         for (int t0 = sa; t0 < sb; t0 += 4) {
           float2 br[4], bi2[4];
@@ -950,12 +977,13 @@ __global__ __launch_bounds__(EM_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             const int t = t0 + i;
             if (t < sb) {  // wave-uniform
               const bool first = (firsts >> t) & 1;
-              EP_SCAN_STEP(t, br[i], bi2[i], first)
+              EP_SCAN_STEP(t, br[i], bi2[i], first, true)
             }
           }
         }
       }
 #undef EP_SCAN_STEP
+#undef EP_EXPORT_ROW
       // (the other buffer: wave 0 may not have read this tile's carry-in yet)
       if (sb == EM_ST) *reinterpret_cast<float4*>(carry + (par ^ 1) * 256 + 4 * lane) = make_float4(h_r0, h_r1, h_i0, h_i1);
     }
@@ -1188,6 +1216,13 @@ static EmWs em_carve(int B, int L, char* base) {
 
 size_t lr_encoder_mfma_workspace_bytes(int B, int L) { return em_carve(B, L, nullptr).total; }
 
+// The seeding calls' export buffers, outside the workspace above (whose layout stays what it is): one [users_cap][256]
+// buffer per block 0 .. nb-2; the last block's state is in Ul already.
+size_t lr_encoder_mfma_export_bytes(int num_blocks, int B, int L) {
+  const size_t users_cap = (size_t)B < em_chunk_users(L) ? (size_t)B : em_chunk_users(L);
+  return lr_align_up((size_t)(num_blocks - 1) * users_cap * 256 * sizeof(float), 256);
+}
+
 // LR_EM_PIPE=0 in the environment (A/B runs) or lr_lru_set_encoder_pipeline(h, 0) (the bit-identity test of the two kernels,
 // tests/test_gpu_lru.py): the LRU layer on em_layer_kernel (one tile at a time) instead of em_pipe_kernel. Same bits.
 static bool em_env_pipe() {
@@ -1199,8 +1234,8 @@ static bool em_env_pipe() {
   return v != 0;
 }
 
-template <int MODE>
-static int em_launch_layer(int grid, size_t lds, hipStream_t st, const EmLayer& p, bool pipe = true) {
+template <int MODE, bool EXPORT = false>
+static int em_launch_layer(int grid, size_t lds, hipStream_t st, const typename EmArgs<EXPORT>::type& p, bool pipe = true) {
   // The pipelined kernel serves the LRU layer only. Measured at Synth-1M / Beauty (gpurun_out/r4s5): LRU layer 425 -> 395 us /
   // 144 -> 139 us, feed-forward 409 -> 449 us / 152 -> 171 us. The stamps say why the gain is small and the feed-forward
   // loses: v_mfma_f32_32x32x2_f32 runs on the f32 vector datapath, so a SIMD's vector work (recurrence, LayerNorm, GELU) does
@@ -1213,21 +1248,24 @@ static int em_launch_layer(int grid, size_t lds, hipStream_t st, const EmLayer& 
       // [2][64][EM_US] intermediates | xs | hand-over | LayerNorm | 2 x tags | erf table | carry
       const size_t lds_pipe = (size_t)(2 * EM_ST * EM_US + EM_ST * EM_XS + 2 * 16 * 64 + 128 + 2 * EM_ST + LR_ERF_NINT * EM_ERF_ROW + 512) * sizeof(float);
       static bool lds_set_pipe[LR_MAX_DEVICES] = {};
-      if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(em_pipe_kernel<MODE>), (int)lds_pipe, lds_set_pipe)) return rc;
-      hipLaunchKernelGGL(em_pipe_kernel<MODE>, dim3(grid), dim3(EM_THREADS), lds_pipe, st, p);
+      if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(em_pipe_kernel<MODE, EXPORT>), (int)lds_pipe, lds_set_pipe)) return rc;
+      hipLaunchKernelGGL((em_pipe_kernel<MODE, EXPORT>), dim3(grid), dim3(EM_THREADS), lds_pipe, st, p);
       LR_CHECK_LAUNCH("em_pipe_kernel");
       return LR_OK;
     }
   }
   static bool lds_set[LR_MAX_DEVICES] = {};
-  if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(em_layer_kernel<MODE>), (int)lds, lds_set)) return rc;
-  hipLaunchKernelGGL(em_layer_kernel<MODE>, dim3(grid), dim3(EM_THREADS), lds, st, p);
+  if (int rc = lr_ensure_dynamic_lds(reinterpret_cast<const void*>(em_layer_kernel<MODE, EXPORT>), (int)lds, lds_set)) return rc;
+  hipLaunchKernelGGL((em_layer_kernel<MODE, EXPORT>), dim3(grid), dim3(EM_THREADS), lds, st, p);
   LR_CHECK_LAUNCH("em_layer_kernel");
   return LR_OK;
 }
 
-int lr_launch_lru_encode_mfma(const lr_lru* h, const int64_t* ids, int B, int L, float* out_q, void* ws,
-                              size_t ws_bytes, hipStream_t st) {
+// seed (null for the plain encoder): the LRU layers of blocks 0 .. nb-2 run their EXPORT instantiation, and behind each
+// chunk's last kernel lru_state.hip's finishing kernel writes the chunk's table rows (Ul, n and the export buffers are
+// reused by the next chunk). slots and the table rows are indexed by the CALL's user index u0 + u.
+static int em_encode(const lr_lru* h, const int64_t* ids, int B, int L, float* out_q, void* ws, size_t ws_bytes,
+                     const LrLruSeed* seed, hipStream_t st) {
   if (B <= 0) return LR_OK;
   const EmWs w = em_carve(B, L, (char*)ws);
   if (ws_bytes < w.total) LR_FAIL(LR_EWORKSPACE, "encoder: workspace needs %zu bytes, have %zu", w.total, ws_bytes);
@@ -1277,7 +1315,14 @@ int lr_launch_lru_encode_mfma(const lr_lru* h, const int64_t* ids, int B, int L,
       ffn.wb = img + BL.w2t; ffn.bb = img + BL.b2; ffn.lnw = img + BL.ln2_w; ffn.lnb = img + BL.ln2_b;
       if (b < nb - 1) {
         lru.OUT = Y;
-        if (int rc = em_launch_layer<0>(c.G, lds, st, lru, h->encoder_pipeline != 0)) return rc;
+        if (seed) {
+          EmLayerExp lru_exp;
+          static_cast<EmLayer&>(lru_exp) = lru;
+          lru_exp.EXP = seed->exp + (size_t)b * w.users_cap * 256;
+          if (int rc = em_launch_layer<0, true>(c.G, lds, st, lru_exp, h->encoder_pipeline != 0)) return rc;
+        } else {
+          if (int rc = em_launch_layer<0>(c.G, lds, st, lru, h->encoder_pipeline != 0)) return rc;
+        }
         ffn.IN = Y; ffn.RES = Y; ffn.OUT = X; ffn.n_rows_ptr = c.off + c.users;  // no recurrence: super tiles strided over the rows
         if (int rc = em_launch_layer<1>(c.G, lds, st, ffn)) return rc;
       } else {  // only each user's last row is consumed after the last block
@@ -1290,6 +1335,19 @@ int lr_launch_lru_encode_mfma(const lr_lru* h, const int64_t* ids, int B, int L,
         if (int rc = em_launch_layer<1>(grid_last, lds, st, ffn)) return rc;
       }
     }
+    if (seed)
+      LR_RUN(lr_launch_lru_state_seed(h, seed->states, seed->num_slots, seed->slots ? seed->slots + u0 : nullptr, (int)u0, c.ids,
+                                      c.users, L, c.n, seed->exp, w.users_cap * 256, Ul, out_q + u0 * 64, st));
   }
   return LR_OK;
+}
+
+int lr_launch_lru_encode_mfma(const lr_lru* h, const int64_t* ids, int B, int L, float* out_q, void* ws,
+                              size_t ws_bytes, hipStream_t st) {
+  return em_encode(h, ids, B, L, out_q, ws, ws_bytes, nullptr, st);
+}
+
+int lr_launch_lru_encode_mfma_seed(const lr_lru* h, const int64_t* ids, int B, int L, float* out_q, void* ws,
+                                   size_t ws_bytes, const LrLruSeed* seed, hipStream_t st) {
+  return em_encode(h, ids, B, L, out_q, ws, ws_bytes, seed, st);
 }

@@ -19,6 +19,8 @@
 //  * the last block's out_proj / FFN tail runs once per call, on each row's last consumed token, as the encoder runs it
 //    for its last tile only.
 //  * a slot outside [0, num_slots) makes its row inert: nothing of the table is read or written for it.
+//  * a state for a history that already exists is not made here column by column: the batched encoder exports every block's
+//    state at each user's last row in its own pass and lru_state_seed_kernel (below) writes the table rows.
 #include "lr_common.h"
 #include "lr_profile.h"
 
@@ -289,6 +291,71 @@ __global__ __launch_bounds__(256) void lru_state_reset_kernel(char* states, size
   if (s < 0 || s >= num_slots) return;
   uint32_t* row = reinterpret_cast<uint32_t*>(states + (size_t)s * row_bytes);
   for (int i = threadIdx.x; i < (int)(row_bytes / 4); i += 256) row[i] = 0u;
+}
+
+// ---- states seeded by the batched encoder (lru_encoder_mfma.hip, EXPORT) ----------------------------------------------
+// The encoder's pass over whole histories has every block's recurrence state at each user's last row: blocks 0 .. nb-2 in
+// the export buffers, one float4 per lane of the scan (lane l holds re of channels sc_k, sc_k + 2, then their im, with
+// sc_k = (l >> 5) * 64 + 4 * (l & 15) + ((l >> 4) & 1)), the last block in Ul in channel order. One workgroup per user of
+// the chunk writes the table row: h in the table's channel order (the lane permutation is undone here), q from the call's
+// out_q row, live from em_live_kernel's count. A history whose LAST id is <= 0 is outside the states' contract (the
+// encoder embeds that pad as a token, a state skips it): its row is written as the reset state. The slot guard is the
+// advance kernel's.
+struct SeedParams {
+  char* states;
+  size_t row_bytes;
+  int num_slots;
+  const int32_t* slots;  // [users] of this chunk or null: user u -> slot slot0 + u
+  int slot0;
+  const int64_t* ids;    // [users][L] of this chunk
+  int users, L, nb;
+  const int* n;          // [users] live tokens
+  const float* exp;      // [nb - 1] blocks of exp_block_floats, [users][256] each, lane order
+  size_t exp_block_floats;
+  const float* Ul;       // [users][256] the last block's state, channel order
+  const float* q;        // [users][64]
+};
+
+__global__ __launch_bounds__(256) void lru_state_seed_kernel(SeedParams p) {
+  const int u = blockIdx.x, tid = threadIdx.x;
+  const int s = p.slots ? p.slots[u] : p.slot0 + u;
+  if (s < 0 || s >= p.num_slots) return;
+  float* row = reinterpret_cast<float*>(p.states + (size_t)s * p.row_bytes);
+  const bool ok = p.ids[(size_t)u * p.L + (p.L - 1)] > 0;
+  const int c = tid & 127;  // element tid of h[b] = re (tid < 128) or im of channel c
+  const int src = 4 * ((c >> 6) * 32 + (c & 1) * 16 + ((c & 63) >> 2)) + ((c >> 1) & 1) + 2 * (tid >> 7);
+  for (int b = 0; b < p.nb; ++b) {
+    float v = 0.0f;
+    if (ok) v = b < p.nb - 1 ? p.exp[(size_t)b * p.exp_block_floats + (size_t)u * 256 + src] : p.Ul[(size_t)u * 256 + tid];
+    row[b * 2 * LR_H + tid] = v;
+  }
+  const int q_off = p.nb * 2 * LR_H;
+  if (tid < 64) row[q_off + tid] = ok ? p.q[(size_t)u * 64 + tid] : 0.0f;
+  else if (tid == 64) reinterpret_cast<int*>(row)[q_off + 64] = ok ? p.n[u] : 0;
+}
+
+int lr_launch_lru_state_seed(const lr_lru* h, void* states, int num_slots, const int32_t* slots, int slot0, const int64_t* ids,
+                             int users, int L, const int* n, const float* exp, size_t exp_block_floats, const float* Ul,
+                             const float* q, hipStream_t st) {
+  if (users <= 0) return LR_OK;
+  SeedParams p;
+  p.states = (char*)states;
+  p.row_bytes = lr_lru_state_row_bytes(h->lay.num_blocks);
+  p.num_slots = num_slots;
+  p.slots = slots;
+  p.slot0 = slot0;
+  p.ids = ids;
+  p.users = users;
+  p.L = L;
+  p.nb = h->lay.num_blocks;
+  p.n = n;
+  p.exp = exp;
+  p.exp_block_floats = exp_block_floats;
+  p.Ul = Ul;
+  p.q = q;
+  hipLaunchKernelGGL(lru_state_seed_kernel, dim3(users), dim3(256), 0, st, p);
+  LR_CHECK_LAUNCH("lru_state_seed_kernel");
+  return LR_OK;
 }
 
 int lr_launch_lru_state_reset(const lr_lru* h, void* states, int num_slots, const int32_t* slots, int B, hipStream_t st) {

@@ -23,12 +23,18 @@ def retrieve_candidates(model, query, top_k: int = 20):
 class RetrieverSession:
     """One user's retriever state carried across interactions: `append` the items as they arrive, `candidates` whenever
     a list is wanted. Returns what `retrieve_candidates(model, whole_query, top_k)` returns for everything appended so
-    far, without re-encoding it (LRURec.advance: one recurrence step per new item)."""
+    far, without re-encoding it (LRURec.advance: one recurrence step per new item). A `history` the user already has is
+    encoded once, in one call that also leaves the state (LRURec.encode_states), and `query` starts as that list."""
 
-    def __init__(self, model):
+    def __init__(self, model, history=None):
         self.model = model
         self.states = model.new_user_states(1)
         self.query = []
+        if history is not None:
+            items = np.asarray(history, dtype=np.int64).reshape(-1)
+            if items.size:
+                model.encode_states(self.states, items.reshape(1, -1))
+                self.query = items.tolist()
 
     def append(self, item_ids):
         """Add one item id or a sequence of them to the end of the user's history."""

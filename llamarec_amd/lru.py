@@ -217,17 +217,31 @@ class LRURec:
                   "lr_lru_scores_last")
         return out
 
-    def retrieve_topk(self, x, k, exclude_history=True):
+    def retrieve_topk(self, x, k, exclude_history=True, states=None, slots=None):
         """Ordered top-k item ids (score desc, ties -> lower id) and their scores.
         Fuses `model(seqs)[:, -1, :]`, the -1e9 masking loop and torch.topk / argsort
-        (trainer/lru.py:33-38,82-84,113-115)."""
+        (trainer/lru.py:33-38,82-84,113-115).
+        With `states` (a UserStates table) the same call also seeds the users' rows (`slots`, default 0..B-1) from
+        these histories, as `encode_states` does: same ids and scores, and the rows are ready for `advance`."""
         if not 1 <= k <= MAX_TOPK:
             raise ValueError(f"k must be in 1..{MAX_TOPK}")
         ids = self._ids(x)
         B, L = ids.shape
+        if states is None and slots is not None:
+            raise ValueError("slots without states")
+        slots = self._slots(slots, B)
         idx = torch.empty((B, k), dtype=torch.int32, device=self.device)
         sc = torch.empty((B, k), dtype=torch.float32, device=self.device)
         if B == 0:
+            return idx, sc
+        if states is not None:
+            table, n, sp = self._states(states, slots, B)
+            ws = self._seed_workspace(B, k, L)
+            with torch.cuda.device(self.device):
+                check(lib().lr_lru_retrieve_topk_seed_user_state(self._h, table, n, sp, ids.data_ptr(), B, L, k,
+                                                                 int(bool(exclude_history)), idx.data_ptr(), sc.data_ptr(),
+                                                                 ws.data_ptr(), ws.numel(), stream_ptr()),
+                      "lr_lru_retrieve_topk_seed_user_state")
             return idx, sc
         ws = self._workspace(B, k, L)
         with torch.cuda.device(self.device):
@@ -288,6 +302,29 @@ class LRURec:
         with torch.cuda.device(self.device):
             check(lib().lr_lru_user_state_advance(self._h, table, n, sp, ids.data_ptr() if Ln else None, B, Ln,
                                                   q.data_ptr(), stream_ptr()), "lr_lru_user_state_advance")
+        return q
+
+    def _seed_workspace(self, B, K, L):
+        need = lib().lr_lru_user_state_encode_workspace_bytes(self._h, B, K, L)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def encode_states(self, st, x, slots=None):
+        """`encode_last` of the whole histories x [B, L] that also writes the users' rows of `st` (`slots`, default
+        0..B-1): one encoder pass instead of `advance` over the history. Returns q [B, 64]. A row is overwritten, no reset
+        is needed; a history ending in a pad id leaves a reset row (include/llamarec_mi355x.h, "CONTRACT ADDED")."""
+        ids = self._ids(x)
+        B, L = ids.shape
+        slots = self._slots(slots, B)
+        q = torch.empty((B, 64), dtype=torch.float32, device=self.device)
+        if B == 0:
+            return q
+        table, n, sp = self._states(st, slots, B)
+        ws = self._seed_workspace(B, 1, L)
+        with torch.cuda.device(self.device):
+            check(lib().lr_lru_user_state_encode(self._h, table, n, sp, ids.data_ptr(), B, L, q.data_ptr(), ws.data_ptr(),
+                                                 ws.numel(), stream_ptr()), "lr_lru_user_state_encode")
         return q
 
     def retrieve_topk_from_states(self, st, k, new_ids=None, exclude=None, slots=None):
