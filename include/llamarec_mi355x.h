@@ -545,6 +545,43 @@ int lr_llama_last_logits(lr_llama_t* h, const int32_t* packed_ids, const int32_t
                          const int32_t* cu_seqlens_host, int32_t B, float* out_logits,
                          void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Ranker sessions: a per-user K / V cache of the prompt prefix (the stage-2 half of the user-state work above). The demo
+ * prompt numbers the history (1) .. (n) without truncating it, so when a user adds an item, or is ranked against another
+ * candidate pool, everything up to the end of the old history is token for token the prompt that was just prefilled. A
+ * slot keeps the rotated keys and the values of those tokens for every layer; a call prefills only the new tokens,
+ * attends over cache plus new tokens and returns the verbalizer scores.
+ *
+ * The caller owns one DEVICE table [num_slots][slot_bytes], 16-byte aligned. A slot is
+ *     [num_layers][max_tokens] rows of [K rotated | V], 2 * num_kv_heads * head_dim bf16 a row (row p = prompt position p),
+ *     padded to a multiple of 256 bytes        (lr_llama_kv_cache_slot_bytes, pure CPU, 0 for a shape no handle can have)
+ * with no header and no device-side length: how many rows of a slot are valid, and for which token ids, is host state.
+ *
+ * lr_llama_extend_verbalize: prompt b of the call continues slot slots[b] behind its first cached_len[b] tokens with the
+ * packed ids new_ids[cu_new[b] .. cu_new[b+1]) at positions cached_len[b] .. . Their K / V rows are written into the slot and
+ * out_scores[b][c] (DEVICE fp32 [B][C]) is the logit of label c at the prompt's last new token. slots, cached_len and cu_new
+ * are given twice, DEVICE and HOST with the same values (the host copies are launch geometry and what is checked).
+ * keep_host[b] in 0 .. q_len[b] is the number of leading new tokens the caller will count as cached afterwards; rows behind
+ * it are scratch that the next call overwrites, so keep needs no device work: it is checked, and only defines what the
+ * caller may pass as cached_len next time (at most cached_len[b] + keep[b]; lowering it rolls the slot back for free).
+ * Scores are BIT-IDENTICAL to lr_llama_prefill_verbalize of the whole prompt (cached ids + new ids) on the same handle in
+ * the default GEMM mode, at head_dim 128 on the MFMA attention kernel (variants 0 / 2) and at any head_dim on the generic
+ * one (variant 1; auto off head_dim 128): rows are computed by row-invariant products and by attention kernels that keep
+ * 64-key blocks and 128-row query tiles aligned to positions inside the prompt. A handle in latency mode (gemm variant 5)
+ * runs the default-mode products here. cached_len[b] = 0 with an empty slot is the plain call.
+ * LR_EINVAL before anything is launched (out_scores and the table untouched): a null pointer, a table that is not 16-byte
+ * aligned, a slot outside [0, num_slots), the same slot twice in one call, q_len[b] < 1, cached_len[b] < 0,
+ * cached_len[b] + q_len[b] > max_tokens or > max_positions, keep[b] outside [0, q_len[b]], C < 1.
+ * LR_EUNSUPPORTED: a handle with Gemma norms, a soft cap, a sliding window, q/k norms, q/k/v biases or folded norms, an
+ * attention variant other than 0 / 1 / 2 (2 off head_dim 128), a slot layer of 2 GiB or more. LR_EWORKSPACE: fewer than
+ * lr_llama_extend_workspace_bytes(h, new tokens, B, max_tokens) bytes. */
+size_t lr_llama_kv_cache_slot_bytes(int32_t num_layers, int32_t num_kv_heads, int32_t head_dim, int32_t max_tokens);
+size_t lr_llama_extend_workspace_bytes(const lr_llama_t* h, int32_t max_new_tokens, int32_t max_seqs, int32_t max_tokens);
+int lr_llama_extend_verbalize(lr_llama_t* h, void* table, int32_t num_slots, int32_t max_tokens, const int32_t* slots,
+                              const int32_t* slots_host, const int32_t* cached_len, const int32_t* cached_len_host,
+                              const int32_t* new_ids, const int32_t* cu_new, const int32_t* cu_new_host,
+                              const int32_t* keep_host, int32_t B, const int32_t* label_token_ids, int32_t C,
+                              float* out_scores, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Host helper: stack HF q_proj/k_proj/v_proj ([nh*hd][hidden], [nkv*hd][hidden] x2, bf16) into the
  * wqkv layout above (pair-interleaved q/k head rows). Pure CPU. */
 int lr_llama_pack_qkv(const uint16_t* q, const uint16_t* k, const uint16_t* v, int32_t num_heads,
@@ -656,6 +693,20 @@ int lr_attention_varlen_prefix(const uint16_t* qkv, uint16_t* out, const int32_t
 int lr_attention_last_rows(const uint16_t* kv, const uint16_t* q_last, uint16_t* out_last, const int32_t* seg_starts,
                            const int32_t* seg_starts_host, int32_t S, int32_t prefix_len, int32_t num_heads,
                            int32_t num_kv_heads, int32_t head_dim, int32_t variant, void* hip_stream);
+
+/* The attention of lr_llama_extend_verbalize alone (exposed for parity tests): qkv as lr_attention_varlen, the B segments
+ * being the NEW rows of B prompts, segment b at positions cached_len[b] .. of slot slots[b] of the cache table described at
+ * lr_llama_extend_verbalize (num_layers and layer place the rows inside a slot). The call first copies the K | V columns of
+ * its rows into the slot rows cached_len[b] .. cached_len[b] + q_len[b] - 1 of that layer -- the only bytes of the table it
+ * writes -- and then query row i of segment b attends to rows 0 .. cached_len[b] + i of the slot. out [total][nh*hd].
+ * variant 0 = auto (2 at head_dim 128, else 1), 1 generic, 2 = head_dim-128 MFMA, whose rows carry the bits
+ * lr_attention_varlen's variant 2 writes for the same rows of the whole prompt; anything else LR_EUNSUPPORTED. The host checks
+ * of lr_llama_extend_verbalize apply (LR_EINVAL, nothing launched). */
+int lr_attention_varlen_cached(const uint16_t* qkv, uint16_t* out, void* table, int32_t num_slots, int32_t max_tokens,
+                               int32_t num_layers, int32_t layer, const int32_t* slots, const int32_t* slots_host,
+                               const int32_t* cached_len, const int32_t* cached_len_host, const int32_t* cu_q,
+                               const int32_t* cu_q_host, int32_t B, int32_t num_heads, int32_t num_kv_heads, int32_t head_dim,
+                               int32_t variant, void* hip_stream);
 
 /* The same two with soft-capped scores, cap * tanh(q.k * scale / cap) (Gemma-2; exposed for parity tests). scale = 0 means
  * head_dim^-0.5. cap = 0 (with scale 0 or head_dim^-0.5) routes to lr_attention_varlen_prefix / lr_attention_last_rows: same

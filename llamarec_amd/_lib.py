@@ -118,6 +118,15 @@ PROTOTYPES = {
                                                     C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                                     C.c_void_p]),
     "lr_common_prefix_len": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32]),
+    # ranker sessions: a per-user K / V cache of the prompt prefix
+    "lr_llama_kv_cache_slot_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "lr_llama_extend_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "lr_llama_extend_verbalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lr_attention_varlen_cached": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "lr_llama_last_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "lr_llama_pack_gate_up": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),

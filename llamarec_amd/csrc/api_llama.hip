@@ -1075,3 +1075,211 @@ extern "C" int lr_attention_varlen_ws(const uint16_t* qkv, uint16_t* out, float*
                               .n_tok = n, .nh = num_heads, .nkv = num_kv_heads, .hd = head_dim, .items_ws = workspace},
                              kernel, st);
 }
+
+// ---- ranker sessions: a per-user K / V cache of the prompt prefix ---------------------------------------------------
+// Slot s of the caller's table = [num_layers][max_tokens] rows of [K rotated | V] (2 nkv hd bf16), padded to 256 bytes; row p of
+// a layer is prompt position p. No header, no device-side length: what a slot holds is the caller's host state.
+static size_t kv_slot_bytes(int num_layers, int nkv, int hd, int max_tokens) {
+  return lr_align_up((size_t)num_layers * (size_t)max_tokens * 2 * nkv * hd * sizeof(u16), 256);
+}
+
+extern "C" size_t lr_llama_kv_cache_slot_bytes(int32_t num_layers, int32_t num_kv_heads, int32_t head_dim, int32_t max_tokens) {
+  if (num_layers < 1 || num_kv_heads < 1 || head_dim < 4 || head_dim % 4 != 0 || head_dim > 256 || max_tokens < 1) return 0;
+  return kv_slot_bytes(num_layers, num_kv_heads, head_dim, max_tokens);
+}
+
+// Host checks of a cached call, before any launch: the table, every prompt's slot, what it keeps and what it adds.
+static int check_cache_request(const char* who, const void* table, int num_slots, int max_tokens, int max_positions, int nkv, int hd,
+                               const int32_t* slots_host, const int32_t* cached_len_host, const int32_t* cu_host,
+                               const int32_t* keep_host, int B) {
+  if (!table || !slots_host || !cached_len_host || !cu_host) LR_FAIL(LR_EINVAL, "%s: null pointer", who);
+  if (reinterpret_cast<uintptr_t>(table) & 15) LR_FAIL(LR_EINVAL, "%s: the cache table is not 16-byte aligned", who);
+  if (B < 1 || num_slots < 1 || max_tokens < 1) LR_FAIL(LR_EINVAL, "%s: B %d, num_slots %d, max_tokens %d", who, B, num_slots, max_tokens);
+  if (cu_host[0] != 0) LR_FAIL(LR_EINVAL, "%s: cu_new[0] = %d (must be 0)", who, cu_host[0]);
+  // one layer of a slot is what a key block's buffer descriptor addresses
+  if ((long long)max_tokens * 2 * nkv * hd * 2 > 0x7fffffffLL)
+    LR_FAIL(LR_EUNSUPPORTED, "%s: max_tokens %d rows of a slot layer exceed the 2 GiB a buffer descriptor addresses here", who, max_tokens);
+  std::vector<int32_t> seen(slots_host, slots_host + B);
+  for (int b = 0; b < B; ++b) {
+    const int q_len = cu_host[b + 1] - cu_host[b], c = cached_len_host[b];
+    if (slots_host[b] < 0 || slots_host[b] >= num_slots)
+      LR_FAIL(LR_EINVAL, "%s: prompt %d names slot %d of %d", who, b, slots_host[b], num_slots);
+    if (q_len < 1) LR_FAIL(LR_EINVAL, "%s: prompt %d adds %d tokens (at least 1)", who, b, q_len);
+    if (c < 0) LR_FAIL(LR_EINVAL, "%s: prompt %d has cached_len %d", who, b, c);
+    if ((long long)c + q_len > max_tokens)
+      LR_FAIL(LR_EINVAL, "%s: prompt %d reaches %lld tokens, a slot holds %d", who, b, (long long)c + q_len, max_tokens);
+    if ((long long)c + q_len > max_positions)
+      LR_FAIL(LR_EINVAL, "%s: prompt %d reaches %lld tokens, max_positions is %d", who, b, (long long)c + q_len, max_positions);
+    if (keep_host && (keep_host[b] < 0 || keep_host[b] > q_len))
+      LR_FAIL(LR_EINVAL, "%s: prompt %d keeps %d of %d new tokens", who, b, keep_host[b], q_len);
+  }
+  for (int b = 0; b < B; ++b)   // B is a batch of users: the quadratic scan stays small
+    for (int a = 0; a < b; ++a)
+      if (seen[a] == seen[b]) LR_FAIL(LR_EINVAL, "%s: prompts %d and %d name the same slot %d", who, a, b, seen[b]);
+  return LR_OK;
+}
+
+// The session calls run the plain Llama layer only, on the head_dim-128 MFMA kernel or the generic one.
+static int check_cache_handle(const char* who, const lr_llama_t* h, bool* generic) {
+  if (h->arch.norm_style != 0 || h->arch.mlp_act != 0 || h->gemma2 || h->gemma3)
+    LR_FAIL(LR_EUNSUPPORTED, "%s: a handle with Gemma norms, soft caps or sliding windows has no cached form", who);
+  if (h->attn_softcap > 0.f || h->final_softcap > 0.f) LR_FAIL(LR_EUNSUPPORTED, "%s: a handle with a soft cap has no cached form", who);
+  if (h->q_norm) LR_FAIL(LR_EUNSUPPORTED, "%s: a handle with q/k norms has no cached form", who);
+  if (h->bqkv) LR_FAIL(LR_EUNSUPPORTED, "%s: a handle with q/k/v biases has no cached form", who);
+  if (h->wqkv_folded) LR_FAIL(LR_EUNSUPPORTED, "%s: a handle with folded norms has no cached form", who);
+  const int v = h->attn_variant, hd = h->cfg.head_dim;
+  if (v != 0 && v != 1 && v != 2)
+    LR_FAIL(LR_EUNSUPPORTED, "%s: attention variant %d has no cached form (0 auto, 1 generic, 2 = head_dim-128 MFMA)", who, v);
+  if (v == 2 && hd != 128) LR_FAIL(LR_EUNSUPPORTED, "%s: attention variant 2 needs head_dim 128 (got %d)", who, hd);
+  *generic = v == 1 || hd != 128;
+  return LR_OK;
+}
+
+// carve()'s buffers for the call's new rows, then rotary tables long enough for a whole cached prompt
+static LlamaWs carve_extend(const LrLlamaConfig& c, int max_new_tokens, int max_seqs, int max_tokens, char* base) {
+  LlamaWs w = carve(c, max_new_tokens, max_seqs, base, false);
+  size_t o = w.total;
+  auto take = [&](size_t bytes) {
+    size_t at = o;
+    o += lr_align_up(bytes, 256);
+    return base + at;
+  };
+  const size_t rope_rows = (size_t)(c.max_positions < max_tokens ? c.max_positions : max_tokens);
+  w.rope = (float*)take(rope_rows * (c.head_dim / 2) * 2 * sizeof(float));
+  w.rope16 = (unsigned*)take(rope_rows * (c.head_dim / 2) * sizeof(unsigned));
+  w.total = o;
+  return w;
+}
+
+extern "C" size_t lr_llama_extend_workspace_bytes(const lr_llama_t* h, int32_t max_new_tokens, int32_t max_seqs, int32_t max_tokens) {
+  if (!h || max_new_tokens < 1 || max_tokens < 1) return 0;
+  if (max_seqs < 1) max_seqs = 1;
+  if (max_seqs > max_new_tokens) max_seqs = max_new_tokens;
+  return carve_extend(h->cfg, max_new_tokens, max_seqs, max_tokens, nullptr).total;
+}
+
+extern "C" int lr_llama_extend_verbalize(lr_llama_t* h, void* table, int32_t num_slots, int32_t max_tokens, const int32_t* slots,
+                                         const int32_t* slots_host, const int32_t* cached_len, const int32_t* cached_len_host,
+                                         const int32_t* new_ids, const int32_t* cu_new, const int32_t* cu_new_host,
+                                         const int32_t* keep_host, int32_t B, const int32_t* label_token_ids, int32_t C,
+                                         float* out_scores, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  const char* who = "lr_llama_extend_verbalize";
+  if (!h || !slots || !cached_len || !new_ids || !cu_new || !keep_host || !label_token_ids || !out_scores || !workspace)
+    LR_FAIL(LR_EINVAL, "%s: null pointer", who);
+  if (C < 1) LR_FAIL(LR_EINVAL, "%s: %d label ids", who, C);
+  const LrLlamaConfig& c = h->cfg;
+  const int d = c.hidden_size, f = c.intermediate_size, nh = c.num_heads, nkv = c.num_kv_heads, hd = c.head_dim;
+  LR_RUN(check_cache_request(who, table, num_slots, max_tokens, c.max_positions, nkv, hd, slots_host, cached_len_host, cu_new_host,
+                             keep_host, B));
+  bool generic;
+  LR_RUN(check_cache_handle(who, h, &generic));
+  const int n = cu_new_host[B];
+  int maxT = 0;
+  for (int b = 0; b < B; ++b) {
+    const int T = cached_len_host[b] + cu_new_host[b + 1] - cu_new_host[b];
+    maxT = T > maxT ? T : maxT;
+  }
+  LlamaWs ws = carve_extend(c, n, B, max_tokens, (char*)workspace);
+  if (ws.total > workspace_bytes)
+    LR_FAIL(LR_EWORKSPACE, "%s: workspace needs %zu bytes for %d new tokens, have %zu", who, ws.total, n, workspace_bytes);
+  hipStream_t st = (hipStream_t)hip_stream;
+  // The default-mode products: their rows do not depend on how many other rows the launch has, so a row's bits are those of the
+  // whole-prompt call. The latency mode's split choice depends on the row count: it is not taken here.
+  const int gv = h->gemm_variant == 5 ? 0 : h->gemm_variant;
+  const int pv = ((gv == 0 || gv == 6) && B <= 256) ? 5 : 1;   // b_row_gemm_variant without the latency mode
+  const int q_w = nh * hd, kv_w = 2 * nkv * hd;
+  const long long slot_elems = (long long)(kv_slot_bytes(c.num_layers, nkv, hd, max_tokens) / sizeof(u16));
+  struct LayerRows { u16 *att, *x, *xn, *hmid; int M, gemm_variant; };   // what o_proj and the MLP run on
+  const LayerRows full = {ws.att, ws.x, ws.xn, ws.hmid, n, gv}, last = {ws.att_last, ws.x_last, ws.xn_last, ws.h_last, B, pv};
+  auto rope = [&](const int32_t* tok_pos, int rot_cols) {
+    return LrGemmRope{.tok_pos = tok_pos, .cs = ws.rope, .cs16 = ws.rope16, .head_dim = hd, .rot_cols = rot_cols};
+  };
+  LR_RUN(lr_launch_kv_cache_meta(cu_new, cached_len, B, n, ws.tok_pos, ws.last_rows, ws.last_pos, st));
+  LR_RUN(lr_launch_rope_table(ws.rope, maxT, hd, c.rope_theta, st, ws.rope16, &h->rope_scaling));
+  LR_RUN(lr_launch_embed(new_ids, nullptr, h->embed, c.vocab_size, d, ws.x, n, st, h->arch.embed_scale));
+  bool input_normed = false;   // ws.xn already holds RMSNorm(ws.x) with this layer's input_norm
+  for (int l = 0; l < c.num_layers; ++l) {
+    const LrLlamaLayerWeights& w = h->layers[l];
+    const bool last_pruned = l == c.num_layers - 1 && h->prune_last;
+    // as run_body: Q for the last rows only where the kernel has a one-query-row mode; K | V for every new row either way,
+    // because the next call reads them
+    const bool last_q_only = last_pruned && !generic && gv != 1;
+    u16* const kv_l = (u16*)table + (size_t)l * max_tokens * kv_w;
+    LrAttnCachedArgs attn = {.q = ws.qkv, .q_ld = q_w + kv_w, .out = ws.att, .kv = kv_l, .slot_elems = slot_elems, .slots = slots,
+                             .cached_len = cached_len, .cu = cu_new, .cached_len_host = cached_len_host, .cu_host = cu_new_host,
+                             .B = B, .nh = nh, .nkv = nkv, .hd = hd, .generic = generic};
+    if (!input_normed) LR_RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st, 0));
+    if (last_q_only) {
+      LR_RUN(lr_launch_gemm({.A = ws.xn, .B = w.wqkv + (size_t)q_w * d, .C = ws.qkv, .M = n, .N = kv_w, .K = d, .epi = LR_EPI_ROPE,
+                             .variant = gv, .rope = rope(ws.tok_pos, kv_w / 2), .splitk = ws.splitk}, st));
+      LR_RUN(lr_launch_kv_cache_write(ws.qkv, kv_w, 0, kv_w, cu_new, cached_len, slots, B, slot_elems, kv_l, n, st));
+      LR_RUN(lr_launch_gather_rows(ws.xn, ws.last_rows, B, d, ws.xn_last, st));
+      LR_RUN(lr_launch_gemm({.A = ws.xn_last, .B = w.wqkv, .C = ws.q_last, .M = B, .N = q_w, .K = d, .epi = LR_EPI_ROPE,
+                             .variant = pv, .rope = rope(ws.last_pos, q_w), .splitk = ws.splitk}, st));
+      attn.q = ws.q_last;
+      attn.q_ld = q_w;
+      attn.out = ws.att_last;
+      attn.last = true;
+      LR_RUN(lr_launch_attention_cached(attn, st));
+    } else {
+      LR_RUN(lr_launch_gemm({.A = ws.xn, .B = w.wqkv, .C = ws.qkv, .M = n, .N = q_w + kv_w, .K = d, .epi = LR_EPI_ROPE,
+                             .variant = gv, .rope = rope(ws.tok_pos, q_w + kv_w / 2), .splitk = ws.splitk}, st));
+      LR_RUN(lr_launch_kv_cache_write(ws.qkv, q_w + kv_w, q_w, kv_w, cu_new, cached_len, slots, B, slot_elems, kv_l, n, st));
+    }
+    if (!last_pruned) {
+      LR_RUN(lr_launch_attention_cached(attn, st));
+    } else {
+      if (!last_q_only && !generic) {   // every new row on the MFMA kernel, the last rows kept (run_body's order)
+        LR_RUN(lr_launch_attention_cached(attn, st));
+        LR_RUN(lr_launch_gather_rows(ws.att, ws.last_rows, B, nh * hd, ws.att_last, st));
+      } else if (!last_q_only) {
+        attn.out = ws.att_last;
+        attn.last = true;
+        attn.q_rows = ws.last_rows;
+        LR_RUN(lr_launch_attention_cached(attn, st));
+      }
+      LR_RUN(lr_launch_gather_rows(ws.x, ws.last_rows, B, d, ws.x_last, st));
+      ws.compact = true;   // and this was the last layer
+    }
+    const LayerRows& r = last_pruned ? last : full;
+    bool post_normed = false;
+    LR_RUN(lr_launch_gemm({.A = r.att, .B = w.wo, .C = r.x, .R = r.x, .M = r.M, .N = d, .K = nh * hd, .epi = LR_EPI_RESIDUAL,
+                           .variant = r.gemm_variant, .splitk = ws.splitk,
+                           .then_norm = {.w = w.post_norm, .out = r.xn, .eps = c.rms_eps, .style = 0, .done = &post_normed}}, st));
+    if (!post_normed) LR_RUN(lr_launch_rmsnorm(r.x, w.post_norm, r.xn, r.M, d, c.rms_eps, nullptr, st, 0));
+    LR_RUN(lr_launch_gemm({.A = r.xn, .B = w.wgu, .C = r.hmid, .M = r.M, .N = 2 * f, .K = d, .epi = LR_EPI_SWIGLU,
+                           .variant = r.gemm_variant, .splitk = ws.splitk}, st));
+    LR_RUN(lr_launch_gemm({.A = r.hmid, .B = w.wdown, .C = r.x, .R = r.x, .M = r.M, .N = d, .K = f, .epi = LR_EPI_RESIDUAL,
+                           .variant = r.gemm_variant, .splitk = ws.splitk,
+                           .then_norm = {.w = l + 1 < c.num_layers ? h->layers[l + 1].input_norm : nullptr, .out = r.xn,
+                                         .eps = c.rms_eps, .style = 0, .done = &input_normed}}, st));
+  }
+  return lr_launch_head(ws.compact ? ws.x_last : ws.x, ws.compact ? nullptr : ws.last_rows, h->final_norm, h->lm_head,
+                        label_token_ids, B, C, d, c.rms_eps, out_scores, c.vocab_size, st, nullptr, 0, 0.f);
+}
+
+extern "C" int lr_attention_varlen_cached(const uint16_t* qkv, uint16_t* out, void* table, int32_t num_slots, int32_t max_tokens,
+                                          int32_t num_layers, int32_t layer, const int32_t* slots, const int32_t* slots_host,
+                                          const int32_t* cached_len, const int32_t* cached_len_host, const int32_t* cu_q,
+                                          const int32_t* cu_q_host, int32_t B, int32_t num_heads, int32_t num_kv_heads,
+                                          int32_t head_dim, int32_t variant, void* hip_stream) {
+  const char* who = "lr_attention_varlen_cached";
+  if (!qkv || !out || !slots || !cached_len || !cu_q) LR_FAIL(LR_EINVAL, "%s: null pointer", who);
+  if (num_heads < 1 || num_kv_heads < 1 || num_heads % num_kv_heads != 0 || head_dim < 4 || head_dim % 4 != 0 || head_dim > 256 ||
+      num_layers < 1 || layer < 0 || layer >= num_layers)
+    LR_FAIL(LR_EINVAL, "%s: heads %d / %d, head_dim %d, layer %d of %d", who, num_heads, num_kv_heads, head_dim, layer, num_layers);
+  LR_RUN(check_cache_request(who, table, num_slots, max_tokens, 0x7fffffff, num_kv_heads, head_dim, slots_host, cached_len_host,
+                             cu_q_host, nullptr, B));
+  if (variant != 0 && variant != 1 && variant != 2)
+    LR_FAIL(LR_EUNSUPPORTED, "%s: variant %d (0 auto, 1 generic, 2 = head_dim-128 MFMA)", who, variant);
+  if (variant == 2 && head_dim != 128) LR_FAIL(LR_EUNSUPPORTED, "%s: variant 2 needs head_dim 128 (got %d)", who, head_dim);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int q_w = num_heads * head_dim, kv_w = 2 * num_kv_heads * head_dim, n = cu_q_host[B];
+  const long long slot_elems = (long long)(kv_slot_bytes(num_layers, num_kv_heads, head_dim, max_tokens) / sizeof(u16));
+  u16* const kv_l = (u16*)table + (size_t)layer * max_tokens * kv_w;
+  LR_RUN(lr_launch_kv_cache_write(qkv, q_w + kv_w, q_w, kv_w, cu_q, cached_len, slots, B, slot_elems, kv_l, n, st));
+  return lr_launch_attention_cached({.q = qkv, .q_ld = q_w + kv_w, .out = out, .kv = kv_l, .slot_elems = slot_elems, .slots = slots,
+                                     .cached_len = cached_len, .cu = cu_q, .cached_len_host = cached_len_host, .cu_host = cu_q_host,
+                                     .B = B, .nh = num_heads, .nkv = num_kv_heads, .hd = head_dim,
+                                     .generic = variant == 1 || head_dim != 128}, st);
+}

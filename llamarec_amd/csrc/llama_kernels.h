@@ -469,4 +469,34 @@ static inline int lr_attn_launch_last(const char* kernel_name, const char* layou
                                                           (int)pl.n_pairs, q_last, tail...);
 }
 
+// ---- attention over a per-user K / V cache (llama_attn_cached.hip; ranker sessions) -------------------------------
+// A slot of the caller's table is [num_layers][max_tokens] rows of [K rotated | V] (2 nkv hd bf16), a row per prompt position.
+// Prompt b of a call owns the packed rows cu[b] .. cu[b + 1] - 1, which sit at positions
+// cached_len[b] .. of slot slots[b].
+// tok_pos[r] = the position of packed row r, last_rows[b] / last_pos[b] = prompt b's last packed row and its position
+int lr_launch_kv_cache_meta(const int32_t* cu, const int32_t* cached_len, int B, int n, int32_t* tok_pos, int32_t* last_rows,
+                            int32_t* last_pos, hipStream_t st);
+// columns [col0, col0 + kv_w) of src [n][ld] -> the rows' slot rows in dst (the table at the layer's row offset)
+int lr_launch_kv_cache_write(const unsigned short* src, int ld, int col0, int kv_w, const int32_t* cu, const int32_t* cached_len,
+                             const int32_t* slots, int B, long long slot_elems, unsigned short* dst, int n, hipStream_t st);
+// Query row i of prompt b (position cached_len[b] + i) over keys 0 .. cached_len[b] + i of the slot, whose rows up to the
+// prompt's last position are written. q [rows][q_ld] with head h at column h * hd; out [rows][nh hd]. kv = the table at the
+// layer's row offset, slot_elems = elements from one slot to the next.
+//   last     : one query row per prompt, the one at its last position. The MFMA kernel then reads q as one compact row per
+//              prompt ([B][q_ld]); the generic kernel reads the packed rows q_rows[b] (= last_rows). out is [B][nh hd].
+//   generic  : the scalar kernel (any head_dim <= 256); otherwise the head_dim-128 MFMA kernel
+struct LrAttnCachedArgs {
+  const unsigned short* q;
+  int q_ld;
+  unsigned short* out;
+  const unsigned short* kv;
+  long long slot_elems;
+  const int32_t *slots, *cached_len, *cu;       // DEVICE [B], [B], [B + 1]
+  const int32_t *cached_len_host, *cu_host;     // the same values on the host (launch geometry)
+  int B, nh, nkv, hd;
+  bool last = false, generic = false;
+  const int32_t* q_rows = nullptr;
+};
+int lr_launch_attention_cached(const LrAttnCachedArgs& a, hipStream_t st);
+
 #endif

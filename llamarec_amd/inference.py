@@ -64,3 +64,46 @@ def rank_candidates(model, tokenizer, prompt, candidates, verbalizer, top_k: int
     scores = model.prefill_verbalize([np.asarray(ids, dtype=np.int32)], verbalizer.label_token_ids[: len(candidates)])
     order = M.rank_classes(scores)[0].tolist()
     return [candidates[i] for i in order[:top_k]]
+
+
+class RankerSession:
+    """One user's prompt K / V cache carried across rankings, the stage-2 counterpart of RetrieverSession: `rank` returns
+    what `rank_candidates(model, tokenizer, prompt, candidates, verbalizer, top_k)` returns, but prefills only the tokens
+    behind the longest prefix the prompt shares with the previous one (LlamaRanker.extend_verbalize). The numbered history
+    of generate_prompt is not truncated, so after one more item, or with another candidate pool, that prefix reaches to the
+    end of the old history.
+
+    Matching is on token ids, never on text: whatever the tokenizer does where history and pool meet, a mismatch only
+    shortens the reuse. Every new token is kept in the slot (keep = all of them) and the NEXT call's comparison decides how
+    much of it is reused; whatever lies behind the common prefix is dropped by lowering the host length, which costs
+    nothing. `sent_tokens` counts the tokens prefilled so far, `last_sent` those of the last call."""
+
+    def __init__(self, model, tokenizer, verbalizer, max_tokens=2048):
+        self.model, self.tokenizer, self.verbalizer = model, tokenizer, verbalizer
+        self.max_tokens = int(max_tokens)
+        self.cache = model.new_prompt_cache(1, self.max_tokens)
+        self.sent_tokens = 0
+        self.last_sent = 0
+
+    def extend(self, ids, label_token_ids):
+        """Scores (fp32 [1, C]) of the prompt `ids` at its last token, reusing what the slot shares with it."""
+        ids = [int(t) for t in ids]
+        if not ids:
+            raise ValueError("RankerSession: an empty prompt")
+        if len(ids) > self.max_tokens:
+            raise ValueError(f"RankerSession: a prompt of {len(ids)} tokens exceeds max_tokens {self.max_tokens}")
+        held = self.cache.ids[0]
+        c = 0
+        while c < len(held) and c < len(ids) - 1 and held[c] == ids[c]:   # the last token is always prefilled: its row scores
+            c += 1
+        new = ids[c:]
+        scores = self.model.extend_verbalize(self.cache, [0], [new], label_token_ids, keep=[len(new)], cached_len=[c])
+        self.last_sent = len(new)
+        self.sent_tokens += len(new)
+        return scores
+
+    def rank(self, prompt, candidates, top_k: int = 10):
+        ids = self.tokenizer(prompt, truncation=False, padding=False, return_tensors=None)["input_ids"]
+        scores = self.extend(ids, self.verbalizer.label_token_ids[: len(candidates)])
+        order = M.rank_classes(scores)[0].tolist()
+        return [candidates[i] for i in order[:top_k]]

@@ -496,6 +496,16 @@ def load_peft_adapter(adapter_path):
     return dict(r=r, alpha=alpha, weights=adapter_weights(t, r, modules), target_modules=modules)
 
 
+class PromptCache:
+    """LlamaRanker.new_prompt_cache: `table` is the device table [num_slots][slot_bytes] of rotated keys and values
+    (include/llamarec_mi355x.h, lr_llama_extend_verbalize), `ids[s]` the token ids slot s holds rows for. The table has no
+    device-side length: ids is the only record, and shortening ids[s] is the whole of a rollback."""
+
+    def __init__(self, table, num_slots, max_tokens):
+        self.table, self.num_slots, self.max_tokens = table, num_slots, max_tokens
+        self.ids = [[] for _ in range(num_slots)]
+
+
 class LlamaRanker:
     """One replica of the ranker's weights on one MI355X + the prefill/verbalizer entry points."""
 
@@ -913,6 +923,59 @@ class LlamaRanker:
         lab = torch.as_tensor(np.asarray(label_token_ids, dtype=np.int32)).to(self.device)
         return self.prefill_verbalize_packed(torch.from_numpy(ids_host).to(self.device),
                                              torch.from_numpy(cu_host).to(self.device), cu_host, lab, prefix_len=P)
+
+    # -- sessions: a per-user K / V cache of the prompt prefix (include/llamarec_mi355x.h, lr_llama_extend_verbalize) ------
+    def new_prompt_cache(self, num_slots, max_tokens):
+        """A table of `num_slots` slots of `max_tokens` prompt positions each, and the host list of the token ids every slot
+        holds K / V rows for (PromptCache). Nothing is zeroed: a row is read only after a call has written it."""
+        c = self.config
+        slot_bytes = int(lib().lr_llama_kv_cache_slot_bytes(c["num_hidden_layers"], c["num_key_value_heads"], self.hd,
+                                                            int(max_tokens)))
+        if num_slots < 1 or slot_bytes == 0:
+            raise ValueError(f"prompt cache: num_slots {num_slots}, max_tokens {max_tokens}")
+        table = torch.empty((int(num_slots), slot_bytes), dtype=torch.uint8, device=self.device)
+        return PromptCache(table, int(num_slots), int(max_tokens))
+
+    def extend_verbalize(self, cache, slots, new_ids_list, label_token_ids, keep=None, cached_len=None):
+        """scores[b, c] (fp32 [B, C]) of the prompts  cache.ids[slots[b]][:cached_len[b]] + new_ids_list[b]  at their last
+        token, prefilling only the new ids. cached_len defaults to everything the slot holds; a smaller value rolls the
+        slot back. keep[b] (default: all) leading new tokens count as cached afterwards. Bit-identical to
+        prefill_verbalize of the whole prompts in the default GEMM mode (see the header for the attention variants)."""
+        B = len(slots)
+        seqs = [np.asarray(s, dtype=np.int32).reshape(-1) for s in new_ids_list]
+        slots_h = np.asarray(slots, dtype=np.int32).reshape(-1)
+        if len(seqs) != B or B < 1:
+            raise ValueError(f"extend_verbalize: {B} slots, {len(seqs)} id lists")
+        held = [len(cache.ids[s]) if 0 <= s < cache.num_slots else 0 for s in slots_h.tolist()]
+        cl_h = np.asarray(held if cached_len is None else cached_len, dtype=np.int32).reshape(-1)
+        keep_h = np.asarray([len(s) for s in seqs] if keep is None else keep, dtype=np.int32).reshape(-1)
+        if len(cl_h) != B or len(keep_h) != B:
+            raise ValueError("extend_verbalize: cached_len and keep take one value per slot")
+        if any(int(c) > n for c, n in zip(cl_h, held)):
+            raise ValueError(f"extend_verbalize: cached_len {cl_h.tolist()} exceeds what the slots hold {held}")
+        ids_h = np.concatenate(seqs) if seqs else np.zeros(0, np.int32)
+        cu_h = np.zeros(B + 1, np.int32)
+        cu_h[1:] = np.cumsum([len(s) for s in seqs])
+        dev = self.device
+        lab = torch.as_tensor(np.asarray(label_token_ids, dtype=np.int32)).to(dev)
+        # one upload: slots | cached_len | cu | ids
+        meta = torch.from_numpy(np.concatenate([slots_h, cl_h, cu_h, ids_h]).astype(np.int32)).to(dev)
+        slots_d, cl_d, cu_d, ids_d = meta[:B], meta[B:2 * B], meta[2 * B:3 * B + 1], meta[3 * B + 1:]
+        out = torch.empty((B, lab.numel()), dtype=torch.float32, device=dev)
+        n = max(int(cu_h[-1]), 1)
+        need = lib().lr_llama_extend_workspace_bytes(self._h, n, B, cache.max_tokens)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(lib().lr_llama_extend_verbalize(
+                self._h, cache.table.data_ptr(), cache.num_slots, cache.max_tokens, slots_d.data_ptr(), slots_h.ctypes.data,
+                cl_d.data_ptr(), cl_h.ctypes.data, ids_d.data_ptr(), cu_d.data_ptr(), cu_h.ctypes.data, keep_h.ctypes.data, B,
+                lab.data_ptr(), lab.numel(), out.data_ptr(), self._ws.data_ptr(), self._ws.numel(), stream_ptr()),
+                "lr_llama_extend_verbalize")
+        for b, s in enumerate(slots_h.tolist()):
+            cache.ids[s] = cache.ids[s][:int(cl_h[b])] + seqs[b][:int(keep_h[b])].tolist()
+        return out
 
     def last_logits(self, seqs):
         ids, cu, cu_host = self._packed(seqs)
