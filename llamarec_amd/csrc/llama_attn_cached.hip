@@ -7,28 +7,19 @@
 //
 //  kv_cache_meta_kernel        : per new row its position; per prompt its last row and that row's position
 //  kv_cache_write_kernel       : K | V columns of the call's packed rows -> slot rows cached_len[b] ..
-//  attn_cached_generic_kernel  : any head_dim <= 256, GQA, one wave per (query row, head): attn_generic_kernel's arithmetic
-//                                 (llama_attn.hip) on the slot's rows
-//  attn_cached128_kernel       : head_dim 128: attn_mfma128_kernel's arithmetic (llama_attn.hip: S^T = K Q^T and
-//                                 O^T = V^T P^T on v_mfma_f32_16x16x32_bf16, K / V by LDS-DMA, 128 query rows per workgroup,
-//                                 16-row tiles against 64-key blocks, deferred maximum) with the K / V source and the row
-//                                 ownership changed and nothing else: query tiles and 64-key blocks stay aligned to positions
-//                                 inside the prompt, a key block's LDS image (swizzles, zero rows past the prompt's end) is the
-//                                 one that kernel builds, and a row runs the same operations in the same order on it. That is
-//                                 why a row's bits equal the whole-prompt kernel's. LASTQ = its one-query-row mode: one row per
-//                                 prompt, the query at position kv_len - 1 (the pruned last layer).
-// The whole-prompt kernels are held to their instruction streams, so this is a translation unit of its own and no mode of
-// theirs.
-#include "llama_kernels.h"
-#include "lr_attn_util.h"
+//  attn_cached_generic_kernel  : any head_dim <= 256, GQA, one wave per (query row, head): the text attn_generic_kernel
+//                                 (llama_attn.hip) runs, attn_generic_row of llama_attn_generic_body.h, on the slot's rows
+//  attn_cached128_kernel       : head_dim 128: the body attn_mfma128_kernel (llama_attn.hip) runs, attn_hd128_body of
+//                                 llama_attn_hd128_body.h, with the K / V source and the row ownership its own: query tiles
+//                                 and 64-key blocks stay aligned to positions inside the prompt, a key block's LDS image
+//                                 (swizzles, zero rows past the prompt's end) is the one that kernel builds, and the body runs
+//                                 the same lines on it. That is why a row's bits equal the whole-prompt kernel's. LASTQ = its
+//                                 one-query-row mode: one row per prompt, the query at position kv_len - 1 (the pruned last
+//                                 layer).
+// The two bodies are instantiated here, in a translation unit of their own: the whole-prompt code object holds no cached kernel.
+#include "llama_attn_generic_body.h"
+#include "llama_attn_hd128_body.h"
 
-#include <type_traits>
-
-typedef unsigned short u16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 // =============================================================================================
 // metadata and the cache write
@@ -78,81 +69,21 @@ __global__ __launch_bounds__(256) void attn_cached_generic_kernel(const u16* q, 
                                                                   long long slot_elems, const int32_t* slots,
                                                                   const int32_t* cached_len, const int32_t* cu, int B, int n_rows,
                                                                   int nh, int nkv, int hd, const int32_t* q_rows) {
-  __shared__ float qs[4][256];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int item = blockIdx.x * 4 + wave;  // (query row, head)
+  const int item = blockIdx.x * 4 + (threadIdx.x >> 6);  // (query row, head)
   if (item >= n_rows * nh) return;
   // q_rows (optional): only these packed rows are evaluated and the output is compact [n_rows][nh * hd]
   const int orow = item / nh, h = item % nh;
   const int tok = q_rows ? q_rows[orow] : orow;
   const int kvh = h / (nh / nkv);
-  const int stride = 2 * nkv * hd;
   const int b = kc_segment_of(cu, B, tok);
-  const int pos = cached_len[b] + tok - cu[b];
-  const u16* kbase = kv + (size_t)slots[b] * slot_elems + kvh * hd;
-  const u16* vbase = kbase + nkv * hd;
-  const u16* qp = q + (size_t)tok * q_ld + h * hd;
-  for (int d = lane; d < hd; d += 64) qs[wave][d] = bf2f(qp[d]);
-  __builtin_amdgcn_wave_barrier();
-  const float scale = 1.0f / sqrtf((float)hd);
-  float m = -__builtin_inff(), l = 0.f;
-  float o[4] = {0.f, 0.f, 0.f, 0.f};  // dims lane, lane+64, lane+128, lane+192
-  for (int k0 = 0; k0 <= pos; k0 += 64) {
-    const int key = k0 + lane;
-    float s = -__builtin_inff();
-    if (key <= pos) {
-      const u16* kp = kbase + (size_t)key * stride;
-      float acc = 0.f;
-      for (int d = 0; d < hd; ++d) acc = __builtin_fmaf(qs[wave][d], bf2f(kp[d]), acc);
-      s = acc * scale;
-    }
-    float mx = s;
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sft, 64));
-    const float m_new = fmaxf(m, mx);
-    const float alpha = __expf(m - m_new);
-    const float p = (key <= pos) ? __expf(s - m_new) : 0.f;
-    float ps = p;
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1) ps += __shfl_xor(ps, sft, 64);
-    l = l * alpha + ps;
-    m = m_new;
-    const float pb = bf2f(f2bf(p));  // P enters the PV product in bf16, like the MFMA path
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] *= alpha;
-    const int nk = min(64, pos - k0 + 1);
-    for (int j = 0; j < nk; ++j) {
-      const float pj = __shfl(pb, j, 64);
-      const u16* vp = vbase + (size_t)(k0 + j) * stride;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int d = lane + 64 * i;
-        if (d < hd) o[i] = __builtin_fmaf(pj, bf2f(vp[d]), o[i]);
-      }
-    }
-  }
-  u16* op = out + (size_t)orow * nh * hd + h * hd;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int d = lane + 64 * i;
-    if (d < hd) op[d] = f2bf(o[i] / l);
-  }
+  const u16* kbase = kv + (size_t)slots[b] * slot_elems + kvh * hd;   // the row of position p is row p of the slot
+  attn_generic_row(q + (size_t)tok * q_ld + h * hd, kbase, kbase + nkv * hd, 2 * nkv * hd, cached_len[b] + tok - cu[b], hd,
+                   1.0f / sqrtf((float)hd), 0.f, 0, out + (size_t)orow * nh * hd + h * hd, nullptr);
 }
 
 // =============================================================================================
-// MFMA, head_dim 128
+// MFMA, head_dim 128 (the body: llama_attn_hd128_body.h)
 // =============================================================================================
-#define FC_QROWS 128  // query rows per workgroup
-#define FC_KB 64      // keys per block
-#define FC_DEFER 8.0f  // a row's softmax reference moves only when a score exceeds it by more than this (exp2 domain)
-
-__device__ __forceinline__ int fc_v_off(int row, int ch) {  // dual-use swizzle, 256-byte rows
-  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-
-#define FC_TILE_BYTES (FC_KB * 256)        // one K or V tile: 64 keys x 128 dims bf16
-#define FC_STAGE_BYTES (2 * FC_TILE_BYTES)  // K tile + V tile
-
 // grid (query tiles of the call's longest new part, nh, B). A workgroup's tile is tile cached_len / 128 + (its x from the
 // end: heavy tiles first) of the prompt's positions; rows of the tile at positions < cached_len (they are cached, not this
 // call's) or >= kv_len are computed on a clamped row and not stored. LASTQ: grid (1, nh, B), q / out hold one row per prompt.
@@ -161,245 +92,38 @@ __global__ __launch_bounds__(256, 2) void attn_cached128_kernel(const u16* __res
                                                                 const u16* __restrict__ kv, long long slot_elems,
                                                                 const int32_t* slots, const int32_t* cached_len,
                                                                 const int32_t* cu, int nh, int nkv) {
-  // [2 stages][K 16 KiB | V 16 KiB]; filled by LDS-DMA (lane-linear 1 KiB pieces = 4 rows x 256 B),
-  // the XOR swizzles are applied to the SOURCE chunk: position p of row r holds chunk p ^ s(r).
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int hd = 128;
   const int seg = blockIdx.z, h = blockIdx.y;
   const int q0 = cu[seg];
   const int c = cached_len[seg];          // keys [0, c) were cached by earlier calls
   const int T = c + cu[seg + 1] - q0;     // sequence length, cached part included
   int qb;
   if (LASTQ) {
-    qb = (T - 1) / FC_QROWS;
+    qb = (T - 1) / FA_QROWS;
   } else {
-    qb = c / FC_QROWS + ((int)gridDim.x - 1 - (int)blockIdx.x);
-    if (qb * FC_QROWS >= T) return;  // no query row of this prompt in the tile
+    qb = c / FA_QROWS + ((int)gridDim.x - 1 - (int)blockIdx.x);
+    if (qb * FA_QROWS >= T) return;  // no query row of this prompt in the tile
   }
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int quad = lane >> 4, li = lane & 15;
   const int kvh = __builtin_amdgcn_readfirstlane(h / (nh / nkv));
-  const int stride = 2 * nkv * hd;
-  const u16* kbase = kv + (size_t)slots[seg] * (size_t)slot_elems + kvh * hd;   // the row of position p is row p of the slot
-  const u16* vbase = kbase + nkv * hd;
-
-  // ---- Q fragments (B operand of S^T = K Q^T): row q, d = 32*ks + 8*quad + 0..7
-  bf16x8 qf[2][4];
-  int qabs[2];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    qabs[qt] = LASTQ ? T - 1 : qb * FC_QROWS + wave * 32 + qt * 16 + li;
-    const int qr = min(max(qabs[qt], c), T - 1);
-    const u16* qp = LASTQ ? q + (size_t)seg * q_ld + h * hd + quad * 8
-                          : q + (size_t)(q0 + qr - c) * q_ld + h * hd + quad * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[qt][ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 32);
-  }
-
-  floatx4 ot[2][8];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt) ot[qt][dt] = floatx4{0.f, 0.f, 0.f, 0.f};
-  float m_run[2] = {-__builtin_inff(), -__builtin_inff()};
-  float mthr[2] = {-__builtin_inff(), -__builtin_inff()};   // (m + FC_DEFER) / scale of the lane's row, in raw-score units
-  // row sums of P through the matrix pipe: one more A row of ones beside V^T
-  floatx4 l_acc[2] = {floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}};
-  bf16x8 ones_f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) ones_f[i] = (__bf16)1.0f;
-
-  const int q_last = min(qb * FC_QROWS + FC_QROWS - 1, T - 1);   // (LASTQ: qb is the tile of row T - 1, so this is T - 1)
-  const int kb_last = q_last / FC_KB;
-  const int wave_q_last = LASTQ ? T - 1 : qb * FC_QROWS + wave * 32 + 31;  // last query row this wave owns
-  const float sl2 = 0.08838834764831845f * 1.4426950408889634f;  // 1/sqrt(128) * log2(e)
-  const float inv_sl2 = 1.0f / sl2;
-
-  // ---- DMA staging: 16 pieces per tile (4 rows each); wave w moves pieces 4w..4w+3 of K and of V
-  const int prow = lane >> 4, ppos = lane & 15;
-  unsigned koff[4], voff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = (wave * 4 + i) * 4 + prow;
-    koff[i] = (unsigned)(row * stride + (ppos ^ (row & 15)) * 8) * 2u;
-    voff[i] = (unsigned)(row * stride + (ppos ^ (((row & 3) << 2) | ((row >> 2) & 3))) * 8) * 2u;
-  }
+  const FaSeg sg{q0, c, T, q0 - c};   // the call's packed row of position p >= c is q0 - c + p
+  const u16* kbase = kv + (size_t)slots[seg] * (size_t)slot_elems + kvh * FA_HD;   // the row of position p is row p of the slot
+  const FaKV rows{kbase, kbase + nkv * FA_HD, nullptr, nullptr, 2 * nkv * FA_HD};
   // Every block is fetched through a per-block buffer descriptor: base = the block's first K (V) row in the slot,
   // num_records = the bytes up to the end of row T - 1, so rows past the sequence end -- slot rows an earlier, longer prompt
   // may have left behind -- are range-checked to ZERO by the hardware, as the whole-prompt kernel's are (those keys are
   // causally masked for every stored query row: P = 0 exactly).
-  auto stage = [&](int kb, int buf) {
-    char* base = smem + buf * FC_STAGE_BYTES + wave * 4096;
-    const size_t blk_off = (size_t)kb * FC_KB * stride * 2;
-    const int records = ((T - 1 - kb * FC_KB) * stride + hd) * 2;  // bytes from the block's first K (V) element
-    const fa_int4 rk = fa_make_rsrc(reinterpret_cast<const char*>(kbase) + blk_off, records);
-    const fa_int4 rv = fa_make_rsrc(reinterpret_cast<const char*>(vbase) + blk_off, records);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      fa_dma16(rk, base + i * 1024, koff[i]);
-      fa_dma16(rv, base + FC_TILE_BYTES + i * 1024, voff[i]);
-    }
+  auto stage = [&](int kb, char* base, const unsigned (&koff)[4], const unsigned (&voff)[4]) {
+    fa_stage_block<false, FA_HD, FA_KB, 4, FA_TILE_BYTES>(base, rows, sg, kb, koff, voff, nullptr);   // (no row's home to ask for)
   };
 
-  // LDS read addresses: everything lane-dependent is computed ONCE (4 K bases, 8 V bases)
-  typedef __attribute__((address_space(3))) char lds_char;
-  lds_char* const lds = (lds_char*)smem;
-  lds_char *kb_off[4], *vb_off[8];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) kb_off[ks] = lds + (li * 256 + (((ks * 4 + quad) ^ li) << 4));   // row nt*16 + li: (row & 15) = li
-  {
-    const int qp = li >> 2, p4 = li & 3;
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt) vb_off[dt] = lds + (fc_v_off(quad * 4 + qp, dt * 2 + (p4 >> 1)) + 8 * (p4 & 1));   // + 8192 ks2 + 4096 half
-  }
-
-  stage(0, 0);
-  // Q must be resident before the loop (llama_attn.hip)
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) asm volatile("" ::"v"(qf[qt][ks]));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the asm DMAs of block 0 (hipcc does not count them)
-  __syncthreads();
-
-  auto block = [&](const int kb, auto buf_c) {
-    constexpr int BUF = decltype(buf_c)::value;
-    constexpr int KS = BUF * FC_STAGE_BYTES, VS = KS + FC_TILE_BYTES;   // LDS byte offsets of this block's K and V tiles
-    if (kb < kb_last) stage(kb + 1, BUF ^ 1);
-
-    if (kb * FC_KB <= wave_q_last && wave_q_last >= c && (!LASTQ || wave == 0)) {  // otherwise every key of the block is masked
-                                                          // for this wave (or all its rows are cached rows)
-      // ---- S^T = K Q^T : st[qt][nt] rows = keys nt*16 + 4*quad + r, col = query li
-      floatx4 st[2][4];
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) st[qt][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
-      typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
-      bf16x8 kf[2][4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) kf[0][nt] = *reinterpret_cast<lds_bf16x8*>(kb_off[0] + (KS + nt * 4096));
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        if (ks < 3) {
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt)
-            kf[(ks + 1) & 1][nt] = *reinterpret_cast<lds_bf16x8*>(kb_off[ks + 1] + (KS + nt * 4096));
-        }
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt)
-            st[qt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[ks & 1][nt], qf[qt][ks], st[qt][nt], 0, 0, 0);
-      }
-
-      // ---- online softmax (lane-local row), P packed as the B operand of O^T = V^T P^T
-      bf16x8 pa[2][2];
-      const bool diag = (kb * FC_KB + FC_KB - 1) > (LASTQ ? T - 1 : qb * FC_QROWS + wave * 32);  // block needs masking
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) {
-        float mx = -__builtin_inff();
-        if (diag) {  // a real (wave-uniform) branch
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int key = kb * FC_KB + nt * 16 + quad * 4 + r;
-              st[qt][nt][r] = (key <= qabs[qt]) ? st[qt][nt][r] : -__builtin_inff();
-            }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        mx = fa_max3(st[qt][0][0], st[qt][0][1], st[qt][0][2]);
-        mx = fa_max3(mx, st[qt][0][3], st[qt][1][0]);
-#pragma unroll
-        for (int nt = 1; nt < 4; ++nt) {
-          mx = fa_max3(mx, st[qt][nt][1], st[qt][nt][2]);
-          if (nt < 3) mx = fa_max3(mx, st[qt][nt][3], st[qt][nt + 1][0]);
-        }
-        mx = fa_max2(mx, st[qt][3][3]);      // this lane's 16 keys of the row
-        // deferred maximum, decided per row: a row that keeps its reference multiplies by exactly 1 (llama_attn.hip)
-        if (__any(mx > mthr[qt])) {
-          const float rmx = fa_max_xor16_32(mx);
-          const bool grew = rmx > mthr[qt];
-          const float m_new = grew ? rmx * sl2 : m_run[qt];
-          const float alpha = __builtin_amdgcn_exp2f(m_run[qt] - m_new);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) l_acc[qt][r] *= alpha;
-#pragma unroll
-          for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ot[qt][dt][r] *= alpha;
-          m_run[qt] = m_new;
-          mthr[qt] = (m_new + FC_DEFER) * inv_sl2;
-        }
-        const float m_new = m_run[qt];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[qt][nt][r], sl2, -m_new));
-            pa[qt][nt >> 1][(nt & 1) * 4 + r] = (__bf16)p;
-          }
-      }
-
-      // ---- O^T += V^T P^T : A = V^T fragment via transposed LDS reads
-#pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) l_acc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones_f, pa[qt][ks2], l_acc[qt], 0, 0, 0);
-#pragma unroll
-        for (int dt = 0; dt < 8; ++dt) {
-          const short4v t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) short4v*)(vb_off[dt] + (VS + ks2 * 8192)));
-          const short4v t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) short4v*)(vb_off[dt] + (VS + ks2 * 8192 + 4096)));
-          bf16x8 vf;
-          const bf16x4 b0 = __builtin_bit_cast(bf16x4, t0), b1 = __builtin_bit_cast(bf16x4, t1);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            vf[r] = b0[r];
-            vf[4 + r] = b1[r];
-          }
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt)
-            ot[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pa[qt][ks2], ot[qt][dt], 0, 0, 0);
-        }
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces of block kb + 1 have landed
-    __syncthreads();  // ... and every wave is done with block kb
-  };
-  for (int kb = 0; kb <= kb_last; kb += 2) {
-    block(kb, std::integral_constant<int, 0>{});
-    if (kb + 1 <= kb_last) block(kb + 1, std::integral_constant<int, 1>{});
-  }
-
-  // ---- normalise and store: lane owns query row li, d = dt*16 + 4*quad + r (v_permlane16_swap pairs -> 16-byte stores).
-  // Every lane takes part in the swaps; only rows this call owns store.
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const float l = l_acc[qt][0];
-    const float inv = 1.0f / l;
-    const bool live = LASTQ ? (wave == 0 && qt == 0 && li == 0) : (qabs[qt] < T && qabs[qt] >= c);
-    u16* op = out + (size_t)(LASTQ ? seg : q0 + (live ? qabs[qt] - c : 0)) * nh * hd + h * hd + (quad & 1) * 16 + (quad >> 1) * 8;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      unsigned a[2], b[2];
-#pragma unroll
-      for (int w = 0; w < 2; ++w) {
-        a[w] = (unsigned)f2bf(ot[qt][2 * k][2 * w] * inv) | ((unsigned)f2bf(ot[qt][2 * k][2 * w + 1] * inv) << 16);
-        b[w] = (unsigned)f2bf(ot[qt][2 * k + 1][2 * w] * inv) | ((unsigned)f2bf(ot[qt][2 * k + 1][2 * w + 1] * inv) << 16);
-        const auto sw = __builtin_amdgcn_permlane16_swap(a[w], b[w], false, false);
-        a[w] = sw[0];
-        b[w] = sw[1];
-      }
-      if (live) {
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-        *reinterpret_cast<u32x4*>(op + k * 32) = u32x4{a[0], a[1], b[0], b[1]};
-      }
-    }
-  }
+  Fa128Src src;
+  src.T = T; src.P = c; src.qb = qb; src.h = h; src.nh = nh;
+  src.kv_stride = rows.stride;
+  src.q = q;
+  src.q_ld = q_ld;
+  src.out = out;
+  src.lse = nullptr;
+  src.row0 = LASTQ ? seg : sg.vtok0;
+  attn_hd128_body<false, LASTQ>(src, stage, Fa128Stamps{});
 }
 
 // =============================================================================================
@@ -439,7 +163,7 @@ int lr_launch_attention_cached(const LrAttnCachedArgs& a, hipStream_t st) {
   for (int b = 0; b < B; ++b) {
     const double c = a.cached_len_host[b], T = c + a.cu_host[b + 1] - a.cu_host[b];
     work += 4.0 * nh * hd * (a.last ? T : T * (T + 1) / 2 - c * (c + 1) / 2);
-    const int tiles = ((int)T - 1) / FC_QROWS - (int)c / FC_QROWS + 1;
+    const int tiles = ((int)T - 1) / FA_QROWS - (int)c / FA_QROWS + 1;
     max_tiles = tiles > max_tiles ? tiles : max_tiles;
   }
   if (a.generic) {
@@ -462,13 +186,13 @@ int lr_launch_attention_cached(const LrAttnCachedArgs& a, hipStream_t st) {
   LrProfScope prof(LR_PROF_ATTN_MFMA, work, st);
   static bool lds_set[LR_MAX_DEVICES] = {}, lds_set_last[LR_MAX_DEVICES] = {};
   if (a.last) {
-    LR_RUN(lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_cached128_kernel<true>), 2 * FC_STAGE_BYTES, lds_set_last));
-    hipLaunchKernelGGL(attn_cached128_kernel<true>, dim3(1, nh, B), dim3(256), 2 * FC_STAGE_BYTES, st, a.q, a.q_ld, a.out, a.kv,
+    LR_RUN(lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_cached128_kernel<true>), FA_LDS_BYTES, lds_set_last));
+    hipLaunchKernelGGL(attn_cached128_kernel<true>, dim3(1, nh, B), dim3(256), FA_LDS_BYTES, st, a.q, a.q_ld, a.out, a.kv,
                        a.slot_elems, a.slots, a.cached_len, a.cu, nh, nkv);
     LR_CHECK_LAUNCH("attn_cached128_kernel<last>");
   } else {
-    LR_RUN(lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_cached128_kernel<false>), 2 * FC_STAGE_BYTES, lds_set));
-    hipLaunchKernelGGL(attn_cached128_kernel<false>, dim3(max_tiles, nh, B), dim3(256), 2 * FC_STAGE_BYTES, st, a.q, a.q_ld, a.out,
+    LR_RUN(lr_ensure_dynamic_lds(reinterpret_cast<const void*>(attn_cached128_kernel<false>), FA_LDS_BYTES, lds_set));
+    hipLaunchKernelGGL(attn_cached128_kernel<false>, dim3(max_tiles, nh, B), dim3(256), FA_LDS_BYTES, st, a.q, a.q_ld, a.out,
                        a.kv, a.slot_elems, a.slots, a.cached_len, a.cu, nh, nkv);
     LR_CHECK_LAUNCH("attn_cached128_kernel");
   }

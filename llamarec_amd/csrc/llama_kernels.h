@@ -213,8 +213,9 @@ static inline int lr_attn_check_grid(const LrAttnPlan& p) {
 // ---- varlen causal attention over packed qkv (RoPE applied) ----------------------------------------------------------------
 // The kernels (a requested variant 1 .. 5 asks for the kernel of the same number, 6 for HD64 with lse allowed, 7 for HD96,
 // 8 for HD96 with lse allowed, 9 for HD256 with lse allowed, 0 = auto):
-//   GENERIC  any head_dim <= 256, scalar                                  (llama_attn.hip)
-//   MFMA128  head_dim 128, 128-row query tiles, reads a shared prefix     (llama_attn.hip)
+//   GENERIC  any head_dim <= 256, scalar                                  (llama_attn.hip; its text: llama_attn_generic_body.h)
+//   MFMA128  head_dim 128, 128-row query tiles, reads a shared prefix     (llama_attn.hip; one body, llama_attn_hd128_body.h,
+//            shared with the cached kernels of llama_attn_cached.hip)
 //   ROWS256  head_dim 128, 256-row query tiles over a device-built item list, shared prefix <= 64 (llama_attn256.hip)
 //   HD256    head_dim 256; one body (llama_attn_hd256_body.h) instantiated without a shared prefix in llama_attn_hd256.hip,
 //            with lse (variant 9, no prefix) in llama_attn_hd256_lse.hip, with a shared prefix in llama_attn_hd256_prefix.hip
@@ -224,8 +225,8 @@ static inline int lr_attn_check_grid(const LrAttnPlan& p) {
 //            lse (variant 6, no prefix) in llama_attn_hd64_lse.hip and with a shared prefix in llama_attn_hd64_prefix.hip
 //   HD96     head_dim 96; one body (llama_attn_hd96_body.h) instantiated without a shared prefix in llama_attn_hd96.hip, with
 //            lse (variant 8, no prefix) in llama_attn_hd96_lse.hip and with a shared prefix in llama_attn_hd96_prefix.hip
-// MFMA128, HD256, HD64 and HD96 also have a one-query-row mode (lr_launch_attention_last, the pruned last layer); at HD256,
-// HD64 and HD96 it is one more instantiation of the body, in the _prefix file. The three bodies hold what differs per head
+// MFMA128, HD256, HD64 and HD96 also have a one-query-row mode (lr_launch_attention_last, the pruned last layer): one more
+// instantiation of the body, at HD256, HD64 and HD96 in the _prefix file. The four bodies hold what differs per head
 // size; what they share is lr_attn_body.h on the device side and lr_attn_launch_tiles / _last (below) on the host side.
 enum LrAttnKernel {
   LR_ATTN_GENERIC = 1, LR_ATTN_MFMA128 = 2, LR_ATTN_ROWS256 = 3, LR_ATTN_HD256 = 4, LR_ATTN_HD64 = 5, LR_ATTN_HD96 = 7
@@ -412,8 +413,9 @@ int lr_launch_attention_hd256_window_last(const unsigned short* kv, const unsign
                                           const int32_t* cu, const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int window,
                                           hipStream_t st);
 
-// ---- the launch sequence of the HD64 / HD96 / HD256 kernels, once ------------------------------------------------------------
-// Every lr_launch_attention_hd* above is one call of lr_attn_launch_tiles or lr_attn_launch_last with its kernel (a template
+// ---- the launch sequence of the MFMA128 / HD64 / HD96 / HD256 kernels, once --------------------------------------------------
+// Every lr_launch_attention_hd* above, and MFMA128's two launches in llama_attn.hip, is one call of lr_attn_launch_tiles or
+// lr_attn_launch_last with its kernel (a template
 // argument: the dynamic-LDS flag is per kernel), head_dim, threads and dynamic LDS bytes per workgroup. The kernels' argument
 // lists are (qkv, out, cu, [prefix_len,] nh, nkv, max_qblocks, n_pairs, tail...): `tail` is passed through.
 template <auto KERNEL, int BLOCK, int LDS_BYTES, class... Args>
@@ -426,8 +428,9 @@ static inline int lr_attn_launch_kernel(const LrAttnPlan& pl, const char* kernel
 }
 // Whole query tiles of QROWS rows, HPW heads per workgroup. needs = "<who> needs head_dim <HD>" for the head_dim refusal;
 // no_lse = the refusal of a.lse (nullptr: the kernel writes it, or the caller has dealt with it); extra = a check of the
-// caller's own behind those (the soft cap's). layout = the name lr_check_prefix_layout reports under: the kernel takes
-// a.prefix_len and reads a shared prefix; nullptr: whole prompts, which must fit one buffer descriptor. No rows, no launch.
+// caller's own behind those (the soft cap's). PREFIX_ARG: the kernel takes a.prefix_len and reads a shared prefix. layout = the
+// name lr_check_prefix_layout reports under; nullptr: that check is not made (whole prompts, or MFMA128, whose caller has made
+// its own) and the packed rows must fit one buffer descriptor. No rows, no launch.
 template <auto KERNEL, int HD, int QROWS, int BLOCK, int LDS_BYTES, bool PREFIX_ARG, int HPW = 1, class... Tail>
 static inline int lr_attn_launch_tiles(const char* kernel_name, const char* needs, const char* no_lse,
                                        int (*extra)(const LrAttnArgs&), const char* layout, const LrAttnArgs& a, hipStream_t st,
@@ -440,7 +443,7 @@ static inline int lr_attn_launch_tiles(const char* kernel_name, const char* need
   if (no_lse && a.lse) LR_FAIL(LR_EINVAL, "%s", no_lse);
   if (extra) LR_RUN(extra(a));
   if (layout) LR_RUN(lr_check_prefix_layout(layout, a.cu_host, S, n_tok, (nh + 2 * nkv) * hd, P));
-  const LrAttnPlan pl = lr_attn_plan(a.cu_host, S, layout ? P : 0, nh, hd, QROWS / HPW, nh / HPW);
+  const LrAttnPlan pl = lr_attn_plan(a.cu_host, S, PREFIX_ARG ? P : 0, nh, hd, QROWS / HPW, nh / HPW);
   LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
   if (HPW == 2 && (nh / nkv) % 2 != 0) LR_FAIL(LR_EINVAL, "attention: two heads per workgroup need an even nh / nkv");
   if (pl.mq == 0) return LR_OK;
@@ -455,14 +458,14 @@ static inline int lr_attn_launch_tiles(const char* kernel_name, const char* need
                                                             (int)pl.n_pairs, tail...);
 }
 // The pruned last layer (lr_launch_attention_last): kv = [n_tok][2 nkv hd], q_last / out_last = [prompts][nh hd], one workgroup
-// per (segment, head)
-template <auto KERNEL, int HD, int BLOCK, int LDS_BYTES, class... Tail>
+// per (segment, head), the grid rounded up to a multiple of GRID_MULTIPLE. layout as above.
+template <auto KERNEL, int HD, int BLOCK, int LDS_BYTES, int GRID_MULTIPLE = 1, class... Tail>
 static inline int lr_attn_launch_last(const char* kernel_name, const char* layout, const unsigned short* kv,
                                       const unsigned short* q_last, unsigned short* out_last, const int32_t* cu,
                                       const int32_t* cu_host, int S, int n_tok, int nh, int nkv, int prefix_len, hipStream_t st,
                                       Tail... tail) {
-  LR_RUN(lr_check_prefix_layout(layout, cu_host, S, n_tok, 2 * nkv * HD, prefix_len));
-  const LrAttnPlan pl = lr_attn_plan_last(cu_host, S, prefix_len, nh, HD, 1);
+  if (layout) LR_RUN(lr_check_prefix_layout(layout, cu_host, S, n_tok, 2 * nkv * HD, prefix_len));
+  const LrAttnPlan pl = lr_attn_plan_last(cu_host, S, prefix_len, nh, HD, GRID_MULTIPLE);
   LrProfScope prof(LR_PROF_ATTN_MFMA, pl.work, st);
   LR_RUN(lr_attn_check_grid(pl));
   return lr_attn_launch_kernel<KERNEL, BLOCK, LDS_BYTES>(pl, kernel_name, st, kv, out_last, cu, prefix_len, nh, nkv, 0,

@@ -11,6 +11,10 @@
 // instruction stream they had before these helpers existed, which is why a body keeps `pair` in a scope of its own and why
 // fa_segment_and_head returns by value.
 // A row's bits are the same in every mode of one head size because each mode runs these same lines on the same LDS image.
+// The head_dim-128 body (llama_attn_hd128_body.h; llama_attn.hip and llama_attn_cached.hip) takes the softmax, row-sum, V-read
+// and store steps and, for the cached kernels, fa_stage_block's form without a prefix; its prologues and variant 2's
+// shared-prefix staging (per-lane addresses, not the descriptor forms here) are its kernels' own. The vector typedefs and
+// FA_DEFER below are the ones every body uses.
 #ifndef LR_ATTN_BODY_H
 #define LR_ATTN_BODY_H
 

@@ -1,6 +1,7 @@
-// lr_attn_util.h -- device helpers shared by the MFMA flash-attention kernels (llama_attn.hip, and through lr_attn_body.h the
-// head_dim-64, -96 and -256 bodies): LDS-DMA issued from inline asm, the workgroup-to-tile order, gfx950's lane-swap
-// reductions, and max instructions on raw MFMA outputs. What the three bodies share beyond these is lr_attn_body.h.
+// lr_attn_util.h -- device helpers shared by the MFMA flash-attention kernels (through lr_attn_body.h the head_dim-64, -96,
+// -128 and -256 bodies, and the staging of llama_attn.hip and llama_attn_cached.hip): LDS-DMA issued from inline asm, the
+// workgroup-to-tile order, gfx950's lane-swap reductions, and max instructions on raw MFMA outputs. What the four bodies share
+// beyond these is lr_attn_body.h.
 #ifndef LR_ATTN_UTIL_H
 #define LR_ATTN_UTIL_H
 
@@ -34,7 +35,7 @@ __device__ __forceinline__ void fa_dma16(fa_int4 rsrc, const void* lds_wave_base
                : "memory");
 }
 
-// workgroup -> ((prompt, head) pair, query tile) of the head_dim-64, -96 and -256 kernels, variant 2's order: a pair per
+// workgroup -> ((prompt, head) pair, query tile) of the head_dim-64, -96, -128 and -256 kernels, variant 2's order: a pair per
 // dispatch stream (blockIdx.x & 7), heavy tiles first, the two lightest tiles of every pair at the end of the launch. The
 // launch holds 8 * ceil(n_pairs / 8) * max_qblocks workgroups; the caller returns when pair >= n_pairs. Neither result is
 // known to the compiler as wave-uniform yet.

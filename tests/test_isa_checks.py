@@ -1,6 +1,6 @@
 """Build-time checks on the gfx950 ISA of the kernels that issue LDS-DMA from inline asm.
 
-`fa_glds16` / `fa_dma16` (llama_attn.hip), `ab_glds16` (llama_attn_bwd.hip) and `tk_glds16` / `tk_glds4`
+`fa_glds16` / `fa_dma16` (lr_attn_util.h, here through llama_attn.hip and llama_attn_cached.hip), `ab_glds16` (llama_attn_bwd.hip) and `tk_glds16` / `tk_glds4`
 (lru_topk_bf16.hip) write M0 inside an asm block that does not (cannot: M0 is a reserved register for hipcc's inline
 asm) declare the clobber, and they are invisible to hipcc's vmcnt tracking. That is correct as long as
   (1) no compiler-emitted instruction of those kernels depends on M0 -- every M0 write is the asm block's own
@@ -20,7 +20,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "llamarec_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-function"]
-FILES = {"llama_attn.hip": [], "llama_attn_bwd.hip": [], "lru_topk_bf16.hip": ["-fno-honor-nans"]}
+FILES = {"llama_attn.hip": [], "llama_attn_cached.hip": [], "llama_attn_bwd.hip": [], "lru_topk_bf16.hip": ["-fno-honor-nans"]}
 
 DMA = re.compile(r"^\s*(global_load_lds_\w+|buffer_load_\w+ .*\blds\b)")
 M0_USERS = re.compile(r"^\s*(s_movrel\w*|v_movrel\w*|s_set_gpr_idx\w*|ds_gws_\w+|s_sendmsg\w*)\b")
