@@ -362,7 +362,15 @@ int lr_llama_create_ex(const LrLlamaConfig* cfg, const LrLlamaArch* arch, const 
  * store / residual / rope epilogue, no folded norm) runs variant 4's 256x256x64 body on ceil(N / 256) column tiles instead of
  * the generic kernel -- same arithmetic, rows of B and columns of C past N never addressed. Every other product goes where
  * auto sends it, with auto's bits. For models whose widths miss the tile (Qwen2-0.5B: hidden 896, qkv 1152);
- * llamarec_amd.llm makes it the default of a qwen2 ranker. */
+ * llamarec_amd.llm makes it the default of a qwen2 ranker.
+ * gemm 7 = ROW-INVARIANT LATENCY MODE, the online mode of ranker sessions: variant 5 with the number of splits fixed by the
+ * weight's shape alone -- what variant 5 chooses at one row tile (lr_gemm_splitk_plan) -- and the rows launched in chunks of
+ * as many 256-row tiles as the split-K workspace holds. A row's arithmetic then does not depend on how many rows the launch
+ * has: a prompt's scores are reproducible in any batch, lr_llama_extend_verbalize runs it and carries the bits of the
+ * whole-prompt call in this mode, and up to 256 rows it is variant 5 bit for bit. It names that one route: a product whose
+ * widths miss the 256 tile (N % 256 != 0 or K % 64 != 0) is LR_EINVAL under 7, where variant 5 falls back as auto does; a
+ * product too short to split runs as variant 4, which is row-invariant too. The price is paid at large M: a 32 k-row batch
+ * is many serial launches. Bulk scoring stays on auto. */
 int lr_llama_set_variants(lr_llama_t* h, int32_t gemm_variant, int32_t attention_variant);
 
 /* RoPE frequency scaling (Llama-3.1 / 3.2: rope_scaling.rope_type = "llama3" in config.json). Per frequency j of the rotary
@@ -566,8 +574,11 @@ int lr_llama_last_logits(lr_llama_t* h, const int32_t* packed_ids, const int32_t
  * Scores are BIT-IDENTICAL to lr_llama_prefill_verbalize of the whole prompt (cached ids + new ids) on the same handle in
  * the default GEMM mode, at head_dim 128 on the MFMA attention kernel (variants 0 / 2) and at any head_dim on the generic
  * one (variant 1; auto off head_dim 128): rows are computed by row-invariant products and by attention kernels that keep
- * 64-key blocks and 128-row query tiles aligned to positions inside the prompt. A handle in latency mode (gemm variant 5)
- * runs the default-mode products here. cached_len[b] = 0 with an empty slot is the plain call.
+ * 64-key blocks and 128-row query tiles aligned to positions inside the prompt. A handle in gemm variant 7 (the
+ * row-invariant latency mode: set it for online use) runs variant 7 here and the scores are BIT-IDENTICAL to the whole-prompt
+ * call under variant 7; where its QKV product splits, the reduce pass writes K | V straight into the slot rows. A handle in
+ * gemm variant 5, whose split depends on the row count, runs the default-mode products here, with the default mode's bits.
+ * cached_len[b] = 0 with an empty slot is the plain call.
  * LR_EINVAL before anything is launched (out_scores and the table untouched): a null pointer, a table that is not 16-byte
  * aligned, a slot outside [0, num_slots), the same slot twice in one call, q_len[b] < 1, cached_len[b] < 0,
  * cached_len[b] + q_len[b] > max_tokens or > max_positions, keep[b] outside [0, q_len[b]], C < 1.
@@ -609,13 +620,24 @@ int lr_nf4_dynamic_map(float* out256);
  * row-major, leading dimensions = K, K, N. variant: 0 = auto, 1 = generic (any shape),
  * 4 = 256x256x64 MFMA tile, ping-pong pipeline with balanced fragment reads and region-recycling DMA prefetch
  * (default for N%256==0, K%64==0, M>=128; any M: rows are bounds-checked), 5 = 4 with split-K (lr_gemm_bf16_nt_ws),
- * 6 = auto with a ragged last column tile for N%64==0, N%256!=0 (see lr_llama_set_variants). */
+ * 6 = auto with a ragged last column tile for N%64==0, N%256!=0 (see lr_llama_set_variants), 7 = 5 with the split fixed by
+ * (N, K) and the rows in chunks the workspace holds (lr_gemm_bf16_nt_ws; N%256==0 and K%64==0, anything else is LR_EINVAL). */
 int lr_gemm_bf16_nt(const uint16_t* A, const uint16_t* B, uint16_t* C, int32_t M, int32_t N,
                     int32_t K, int32_t variant, void* hip_stream);
-/* The same with a device workspace for variant 5 (split-K, see lr_llama_set_variants): fp32 partial
- * planes, at most 64 MiB (8 splits x M x N x 4 bytes, splits x tiles <= 256). */
+/* The same with a device workspace for variants 5 and 7 (split-K, see lr_llama_set_variants): fp32 partial
+ * planes. Variant 5: at most 64 MiB (8 splits x M x N x 4 bytes, splits x tiles <= 256). Variant 7: any size from one row
+ * tile's planes (splits x 256 x N x 4 bytes) up; a larger one means fewer launches, never other bits. */
 int lr_gemm_bf16_nt_ws(const uint16_t* A, const uint16_t* B, uint16_t* C, int32_t M, int32_t N,
                        int32_t K, int32_t variant, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* What the GEMM entry points do with an M x N x K product under variant 5 or 7 and a workspace of workspace_bytes. Pure CPU.
+ * *splits = the number of K splits (1 = not split: the product runs as variant 4, or, variant 5 only, on the generic kernel off
+ * the 256 tile);
+ * *rows_per_launch = the rows of one launch: M for variant 5 and for an unsplit product, for variant 7 the largest multiple
+ * of 256 with splits * rows * N * 4 <= workspace_bytes (M rows take ceil(M / rows_per_launch) launch pairs).
+ * LR_EWORKSPACE where the product would return it (variant 5: the M rows do not fit; variant 7: not even 256 do);
+ * LR_EINVAL for another variant, a size < 1, a null pointer, or variant 7 with N % 256 != 0 or K % 64 != 0. Honours LR_GEMM_SPLITK_MIN_TILES as the products do. */
+int lr_gemm_splitk_plan(int32_t variant, int32_t M, int32_t N, int32_t K, size_t workspace_bytes, int32_t* splits,
+                        int32_t* rows_per_launch);
 
 /* The projection GEMM with each of the prefill's fused epilogues (exposed for parity tests and per-shape timing):
  *   epilogue 0 store | 1 residual: C = bf16(bf16(acc) + R), R bf16 [M][N], may alias C | 2 SwiGLU over gate/up rows

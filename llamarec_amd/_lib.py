@@ -136,6 +136,8 @@ PROTOTYPES = {
                                   C.c_int32, C.c_void_p]),
     "lr_gemm_bf16_nt_ws": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lr_gemm_splitk_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_size_t, C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32)]),
     "lr_attention_varlen": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "lr_attention_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

@@ -56,9 +56,9 @@ extern "C" int lr_llama_create(const LrLlamaConfig* cfg, const LrLlamaWeightsDes
 }
 
 extern "C" int lr_llama_set_variants(lr_llama_t* h, int32_t gemm_variant, int32_t attention_variant) {
-  if (!h || (gemm_variant != 0 && gemm_variant != 1 && gemm_variant != 4 && gemm_variant != 5 && gemm_variant != 6) ||
+  if (!h || (gemm_variant != 0 && gemm_variant != 1 && gemm_variant != 4 && gemm_variant != 5 && gemm_variant != 6 && gemm_variant != 7) ||
       attention_variant < 0 || attention_variant > 9)
-    LR_FAIL(LR_EINVAL, "lr_llama_set_variants: gemm in {0, 1, 4, 5, 6}, attention in {0, 1, 2, 3, 4, 5, 6, 7, 8, 9}");
+    LR_FAIL(LR_EINVAL, "lr_llama_set_variants: gemm in {0, 1, 4, 5, 6, 7}, attention in {0, 1, 2, 3, 4, 5, 6, 7, 8, 9}");
   h->gemm_variant = gemm_variant;
   h->attn_variant = attention_variant;
   return LR_OK;
@@ -327,8 +327,9 @@ struct LlamaWs {
   float* rope_local;                          // Gemma-3: the sliding layers' fp32 table (null without the extension)
   u16 *x, *xn, *qkv, *att, *hmid;
   u16 *x_last, *xn_last, *att_last, *h_last, *q_last;  // compact [B][.] buffers of the pruned last layer
-  LrGemmSplitK splitk;                        // fp32 partial planes of the split-K GEMMs (gemm variant 5)
+  LrGemmSplitK splitk;                        // fp32 partial planes of the split-K GEMMs (gemm variants 5, 7)
   unsigned* rope16;                           // the rope table as packed bf16 (cos | sin << 16) pairs
+  long long* row_off;                         // extend call only: every new row's cache-row offset in a layer (kv_cache_meta_kernel)
   int32_t* prefix_bad;                        // device word: a prompt broke the shared-prefix promise (token_meta_kernel)
   void* attn_items;                           // work-item list of the 256-row attention kernel (llama_attn256.hip)
   size_t attn_items_bytes;
@@ -339,6 +340,7 @@ struct LlamaWs {
 static LlamaWs carve(const LrLlamaConfig& c, int max_tokens, int max_seqs, char* base, bool two_rope_tables) {
   LlamaWs w;
   w.compact = false;
+  w.row_off = nullptr;
   size_t o = 0;
   auto take = [&](size_t bytes) {
     size_t at = o;
@@ -430,7 +432,10 @@ static int plan_batch(const lr_llama_t* h, const int32_t* cu_host, int B, int P,
 // is one row tile, so the split count depends on the weight's shape only and a prompt's arithmetic stays the same whatever
 // else is in the batch; more prompts than that take the small-tile kernel as before. (Shapes the 256-tile kernel does not
 // take fall back to it inside lr_launch_gemm.)
+// The latency modes (gemm variants 5 and 7) split whatever B is; a variant-7 handle passes 7, which at B <= 256 is 5's split
+// and past that keeps a prompt's arithmetic independent of the batch.
 static int b_row_gemm_variant(const lr_llama_t* h, int B) {
+  if (h->gemm_variant == 7) return 7;
   return (h->gemm_variant == 5 || ((h->gemm_variant == 0 || h->gemm_variant == 6) && B <= 256)) ? 5 : 1;   // 6 routes as auto
 }
 
@@ -674,6 +679,11 @@ extern "C" int lr_llama_pack_qkv(const uint16_t* q, const uint16_t* k, const uin
   }
   memcpy(out + o * hidden, v, (size_t)num_kv_heads * head_dim * rb);
   return LR_OK;
+}
+
+extern "C" int lr_gemm_splitk_plan(int32_t variant, int32_t M, int32_t N, int32_t K, size_t workspace_bytes, int32_t* splits,
+                                   int32_t* rows_per_launch) {
+  return lr_gemm_splitk_plan_of(variant, M, N, K, workspace_bytes, splits, rows_per_launch);
 }
 
 extern "C" int lr_gemm_bf16_nt(const uint16_t* A, const uint16_t* B, uint16_t* C, int32_t M, int32_t N,
@@ -1135,7 +1145,7 @@ static int check_cache_handle(const char* who, const lr_llama_t* h, bool* generi
   return LR_OK;
 }
 
-// carve()'s buffers for the call's new rows, then rotary tables long enough for a whole cached prompt
+// carve()'s buffers for the call's new rows, then rotary tables long enough for a whole cached prompt and the new rows' cache-row offsets
 static LlamaWs carve_extend(const LrLlamaConfig& c, int max_new_tokens, int max_seqs, int max_tokens, char* base) {
   LlamaWs w = carve(c, max_new_tokens, max_seqs, base, false);
   size_t o = w.total;
@@ -1147,6 +1157,7 @@ static LlamaWs carve_extend(const LrLlamaConfig& c, int max_new_tokens, int max_
   const size_t rope_rows = (size_t)(c.max_positions < max_tokens ? c.max_positions : max_tokens);
   w.rope = (float*)take(rope_rows * (c.head_dim / 2) * 2 * sizeof(float));
   w.rope16 = (unsigned*)take(rope_rows * (c.head_dim / 2) * sizeof(unsigned));
+  w.row_off = (long long*)take((size_t)max_new_tokens * sizeof(long long));
   w.total = o;
   return w;
 }
@@ -1183,18 +1194,31 @@ extern "C" int lr_llama_extend_verbalize(lr_llama_t* h, void* table, int32_t num
   if (ws.total > workspace_bytes)
     LR_FAIL(LR_EWORKSPACE, "%s: workspace needs %zu bytes for %d new tokens, have %zu", who, ws.total, n, workspace_bytes);
   hipStream_t st = (hipStream_t)hip_stream;
-  // The default-mode products: their rows do not depend on how many other rows the launch has, so a row's bits are those of the
-  // whole-prompt call. The latency mode's split choice depends on the row count: it is not taken here.
+  // A row's bits must be those of the whole-prompt call in the handle's mode, so every n-row product must compute a row
+  // independently of how many other rows its launch has. The default-mode products do. Variant 7 does too: its split is fixed by
+  // the weight's shape and its row chunks couple nothing, so a variant-7 handle runs it here and gets the variant-7 whole prompt's
+  // bits. Variant 5 chooses its split from the row count -- 160 new rows and the 460 of the whole prompt are summed in different
+  // orders -- so a variant-5 handle runs the default-mode products here, with the default mode's bits.
   const int gv = h->gemm_variant == 5 ? 0 : h->gemm_variant;
-  const int pv = ((gv == 0 || gv == 6) && B <= 256) ? 5 : 1;   // b_row_gemm_variant without the latency mode
+  const int pv = gv == 7 ? 7 : ((gv == 0 || gv == 6) && B <= 256) ? 5 : 1;   // b_row_gemm_variant of that mode
   const int q_w = nh * hd, kv_w = 2 * nkv * hd;
   const long long slot_elems = (long long)(kv_slot_bytes(c.num_layers, nkv, hd, max_tokens) / sizeof(u16));
+  // Variant 7, where the QKV product splits: its reduce pass stores K | V straight into the slot rows (LrGemmKvScatter) instead
+  // of into ws.qkv for kv_cache_write_kernel to copy. LR_EXTEND_SEPARATE_CACHE_WRITE=1 keeps the two launches (tests and
+  // benches only: the bitwise yardstick and the A/B arm; read per call).
+  const char* const sep_env = getenv("LR_EXTEND_SEPARATE_CACHE_WRITE");
+  const bool separate_write = gv != 7 || (sep_env && sep_env[0] == '1');
+  auto reduce_writes_cache = [&](int N) {
+    int splits = 1, rows = 0;
+    return !separate_write && lr_gemm_splitk_plan_of(7, n, N, d, ws.splitk.bytes, &splits, &rows) == LR_OK && splits >= 2;
+  };
   struct LayerRows { u16 *att, *x, *xn, *hmid; int M, gemm_variant; };   // what o_proj and the MLP run on
   const LayerRows full = {ws.att, ws.x, ws.xn, ws.hmid, n, gv}, last = {ws.att_last, ws.x_last, ws.xn_last, ws.h_last, B, pv};
   auto rope = [&](const int32_t* tok_pos, int rot_cols) {
     return LrGemmRope{.tok_pos = tok_pos, .cs = ws.rope, .cs16 = ws.rope16, .head_dim = hd, .rot_cols = rot_cols};
   };
-  LR_RUN(lr_launch_kv_cache_meta(cu_new, cached_len, B, n, ws.tok_pos, ws.last_rows, ws.last_pos, st));
+  LR_RUN(lr_launch_kv_cache_meta(cu_new, cached_len, B, n, ws.tok_pos, ws.last_rows, ws.last_pos, st, slots, slot_elems, kv_w,
+                                 ws.row_off));
   LR_RUN(lr_launch_rope_table(ws.rope, maxT, hd, c.rope_theta, st, ws.rope16, &h->rope_scaling));
   LR_RUN(lr_launch_embed(new_ids, nullptr, h->embed, c.vocab_size, d, ws.x, n, st, h->arch.embed_scale));
   bool input_normed = false;   // ws.xn already holds RMSNorm(ws.x) with this layer's input_norm
@@ -1210,9 +1234,11 @@ extern "C" int lr_llama_extend_verbalize(lr_llama_t* h, void* table, int32_t num
                              .B = B, .nh = nh, .nkv = nkv, .hd = hd, .generic = generic};
     if (!input_normed) LR_RUN(lr_launch_rmsnorm(ws.x, w.input_norm, ws.xn, n, d, c.rms_eps, nullptr, st, 0));
     if (last_q_only) {
+      const bool fused = reduce_writes_cache(kv_w);   // every column is K | V: nothing goes to ws.qkv
       LR_RUN(lr_launch_gemm({.A = ws.xn, .B = w.wqkv + (size_t)q_w * d, .C = ws.qkv, .M = n, .N = kv_w, .K = d, .epi = LR_EPI_ROPE,
-                             .variant = gv, .rope = rope(ws.tok_pos, kv_w / 2), .splitk = ws.splitk}, st));
-      LR_RUN(lr_launch_kv_cache_write(ws.qkv, kv_w, 0, kv_w, cu_new, cached_len, slots, B, slot_elems, kv_l, n, st));
+                             .variant = gv, .rope = rope(ws.tok_pos, kv_w / 2), .splitk = ws.splitk,
+                             .kv_scatter = {.kv_layer = fused ? kv_l : nullptr, .row_off = ws.row_off, .col0 = 0}}, st));
+      if (!fused) LR_RUN(lr_launch_kv_cache_write(ws.qkv, kv_w, 0, kv_w, cu_new, cached_len, slots, B, slot_elems, kv_l, n, st));
       LR_RUN(lr_launch_gather_rows(ws.xn, ws.last_rows, B, d, ws.xn_last, st));
       LR_RUN(lr_launch_gemm({.A = ws.xn_last, .B = w.wqkv, .C = ws.q_last, .M = B, .N = q_w, .K = d, .epi = LR_EPI_ROPE,
                              .variant = pv, .rope = rope(ws.last_pos, q_w), .splitk = ws.splitk}, st));
@@ -1222,9 +1248,12 @@ extern "C" int lr_llama_extend_verbalize(lr_llama_t* h, void* table, int32_t num
       attn.last = true;
       LR_RUN(lr_launch_attention_cached(attn, st));
     } else {
+      const bool fused = reduce_writes_cache(q_w + kv_w);   // q stays in ws.qkv at its stride, the attention reads K | V from the slot
       LR_RUN(lr_launch_gemm({.A = ws.xn, .B = w.wqkv, .C = ws.qkv, .M = n, .N = q_w + kv_w, .K = d, .epi = LR_EPI_ROPE,
-                             .variant = gv, .rope = rope(ws.tok_pos, q_w + kv_w / 2), .splitk = ws.splitk}, st));
-      LR_RUN(lr_launch_kv_cache_write(ws.qkv, q_w + kv_w, q_w, kv_w, cu_new, cached_len, slots, B, slot_elems, kv_l, n, st));
+                             .variant = gv, .rope = rope(ws.tok_pos, q_w + kv_w / 2), .splitk = ws.splitk,
+                             .kv_scatter = {.kv_layer = fused ? kv_l : nullptr, .row_off = ws.row_off, .col0 = q_w}}, st));
+      if (!fused)
+        LR_RUN(lr_launch_kv_cache_write(ws.qkv, q_w + kv_w, q_w, kv_w, cu_new, cached_len, slots, B, slot_elems, kv_l, n, st));
     }
     if (!last_pruned) {
       LR_RUN(lr_launch_attention_cached(attn, st));

@@ -518,7 +518,7 @@ static int forward(lr_llama_lora* h, const int32_t* ids, const int32_t* cu, cons
   const int d = c.hidden_size, f = c.intermediate_size, nh = c.num_heads, nkv = c.num_kv_heads, hd = c.head_dim;
   const int qw = (nh + 2 * nkv) * hd;
   const float scaling = h->cfg.alpha / (float)h->cfg.r;
-  const int gv = h->base->gemm_variant == 5 ? 0 : h->base->gemm_variant;
+  const int gv = (h->base->gemm_variant == 5 || h->base->gemm_variant == 7) ? 0 : h->base->gemm_variant;
   const LoraMods md = lora_mods(c, h->cfg.r, h->mods);
   const int r = h->cfg.r, tw = md.tw, L = c.num_layers;
   LrAttnKernel attn_kernel;  // the backward needs the statistics: lse wanted
@@ -611,7 +611,7 @@ extern "C" int lr_llama_lora_loss_grad(lr_llama_lora_t* h, const int32_t* packed
   const int qw = (nh + 2 * nkv) * hd, r = h->cfg.r;
   const float scaling = h->cfg.alpha / (float)r, drop_p = h->cfg.dropout;
   const float drop_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-  const int gv = h->base->gemm_variant == 5 ? 0 : h->base->gemm_variant;
+  const int gv = (h->base->gemm_variant == 5 || h->base->gemm_variant == 7) ? 0 : h->base->gemm_variant;
   const int tw = md.tw, L = c.num_layers;
   // the backward follows the forward's kernel (lr_resolve_attention's lora route): the head_dim-64 MFMA pair is variant 6,
   // the head_dim-96 one variant 8, the head_dim-256 one variant 9

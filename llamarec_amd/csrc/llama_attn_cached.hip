@@ -5,7 +5,8 @@
 // 0 .. cached_len[b] + i. The call's own K | V rows are copied into the slot first (kv_cache_write_kernel), so the attention
 // has one K / V source.
 //
-//  kv_cache_meta_kernel        : per new row its position; per prompt its last row and that row's position
+//  kv_cache_meta_kernel        : per new row its position (and, on request, its cache row's offset); per prompt its last row
+//                                 and that row's position
 //  kv_cache_write_kernel       : K | V columns of the call's packed rows -> slot rows cached_len[b] ..
 //  attn_cached_generic_kernel  : any head_dim <= 256, GQA, one wave per (query row, head): the text attn_generic_kernel
 //                                 (llama_attn.hip) runs, attn_generic_row of llama_attn_generic_body.h, on the slot's rows
@@ -34,12 +35,19 @@ __device__ __forceinline__ int kc_segment_of(const int32_t* cu, int B, int r) {
   return lo;
 }
 
+// row_off (optional, with slots): the element offset of row r's cache row inside a layer of the table, slots[b] * slot_elems +
+// position * kv_w -- what kv_cache_write_kernel computes per layer, once per call for the reduce pass that writes the cache
+// (LrGemmKvScatter)
 __global__ __launch_bounds__(256) void kv_cache_meta_kernel(const int32_t* cu, const int32_t* cached_len, int B, int n,
-                                                            int32_t* tok_pos, int32_t* last_rows, int32_t* last_pos) {
+                                                            int32_t* tok_pos, int32_t* last_rows, int32_t* last_pos,
+                                                            const int32_t* slots, long long slot_elems, int kv_w,
+                                                            long long* row_off) {
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r < n) {
     const int b = kc_segment_of(cu, B, r);
-    tok_pos[r] = cached_len[b] + r - cu[b];
+    const int pos = cached_len[b] + r - cu[b];
+    tok_pos[r] = pos;
+    if (row_off) row_off[r] = (long long)slots[b] * slot_elems + (long long)pos * kv_w;
   }
   if (r < B) {
     last_rows[r] = cu[r + 1] - 1;
@@ -130,12 +138,15 @@ __global__ __launch_bounds__(256, 2) void attn_cached128_kernel(const u16* __res
 // launchers (declared in llama_kernels.h)
 // =============================================================================================
 int lr_launch_kv_cache_meta(const int32_t* cu, const int32_t* cached_len, int B, int n, int32_t* tok_pos, int32_t* last_rows,
-                            int32_t* last_pos, hipStream_t st) {
+                            int32_t* last_pos, hipStream_t st, const int32_t* slots, long long slot_elems, int kv_w,
+                            long long* row_off) {
   if (n <= 0 || B <= 0) return LR_OK;
+  if (row_off && (!slots || kv_w % 4 != 0 || slot_elems % 4 != 0))
+    LR_FAIL(LR_EINVAL, "kv cache meta: row offsets need the slots and rows of 8-byte pieces (kv_w %d)", kv_w);
   LrProfScope prof(LR_PROF_ELEMENTWISE, 0, st);
   const int rows = n > B ? n : B;
   hipLaunchKernelGGL(kv_cache_meta_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, cu, cached_len, B, n, tok_pos, last_rows,
-                     last_pos);
+                     last_pos, slots, slot_elems, kv_w, row_off);
   LR_CHECK_LAUNCH("kv_cache_meta_kernel");
   return LR_OK;
 }

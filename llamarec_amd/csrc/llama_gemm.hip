@@ -761,6 +761,22 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
+// The rope form whose K | V columns go to a K / V cache (LrGemmKvScatter; ranker sessions): the sum in split order and
+// epi_store4<LR_EPI_ROPE>'s value (epi_value4), stored to C for a column < col0 and to the row's cache row for the others.
+// 8-byte stores: N, col0 and every row_off are multiples of 4 elements, so a quad lies on one side of col0 and inside one row.
+__global__ __launch_bounds__(256) void splitk_reduce_rope_kv_kernel(const float* __restrict__ part, int S, u16* C, int M, int N,
+                                                                    RopeArgs rope, int col0, u16* kv_layer,
+                                                                    const long long* __restrict__ row_off) {
+  const size_t plane = (size_t)M * N;
+  const size_t off = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (off >= plane) return;
+  floatx4 v = *reinterpret_cast<const floatx4*>(part + off);
+  for (int s = 1; s < S; ++s) v += *reinterpret_cast<const floatx4*>(part + s * plane + off);
+  const int row = (int)(off / N), col = (int)(off % N);
+  u16* const dst = col < col0 ? C + off : kv_layer + row_off[row] + (col - col0);
+  *reinterpret_cast<u16x4*>(dst) = epi_value4<LR_EPI_ROPE>(v, v, u16x4{0, 0, 0, 0}, rope, row, col, nullptr, nullptr);
+}
+
 // number of K splits for an M x N x K product on 256 x 256 tiles (1 = do not split): split only when the
 // tiles alone leave at least half of the 256 CUs idle, keep >= 16 K tiles per split, <= 8 splits.
 // LR_GEMM_SPLITK_MIN_TILES lowers that 16 for tests only (tests/test_gpu_gemm_dma_spread.py: runs of one and two K tiles,
@@ -778,6 +794,54 @@ static int splitk_factor(int M, int N, int K) {
   const int by_k = (K >> 6) / min_tiles;
   if (S > by_k) S = by_k;
   return S < 2 ? 1 : S;
+}
+
+// Variant 7: the split splitk_factor gives at ONE row tile, whatever M is -- a function of the weight's shape alone, so a row
+// is summed in the same order in a launch of 1 row and in one of 460 (for M <= 256 it is variant 5's split by construction).
+static int splitk_factor_fixed(int N, int K) { return splitk_factor(1, N, K); }
+
+static bool gemm256_shape_ok(int M, int N, int K) { return (N % 256 == 0) && (K % 64 == 0) && M >= 1; }
+
+// What the split-K variants do with a product, for lr_launch_gemm and lr_gemm_splitk_plan alike. S = 1: not split (the
+// product then runs as variant 4; under variant 5 on the generic kernel off the 256 tile). Variant 5 launches all rows at once;
+// variant 7 launches rows_per_launch rows at a time, the largest multiple of 256 whose S planes the workspace holds -- neither
+// kernel couples rows, so chunk boundaries change no bit.
+// Variant 7 names ONE route, the 256-tile kernel with its fixed split (or unsplit): a width off the tile is LR_EINVAL, not
+// another kernel, so whoever asks for the row-invariant mode gets that arithmetic or an error. (lr_launch_gemm has sent
+// variant 5 off the tile to the generic kernel before it asks.)
+struct SplitKPlan { int S, rows_per_launch; };
+static int splitk_plan(int variant, int M, int N, int K, size_t ws_bytes, SplitKPlan* out) {
+  *out = {1, M};
+  if (!gemm256_shape_ok(M, N, K)) {
+    if (variant == 7)
+      LR_FAIL(LR_EINVAL, "gemm variant 7 takes products on the 256 tile only: N%%256==0 and K%%64==0 (N=%d K=%d)", N, K);
+    return LR_OK;
+  }
+  const int S = variant == 7 ? splitk_factor_fixed(N, K) : splitk_factor(M, N, K);
+  if (S < 2) return LR_OK;
+  if (variant == 7) {
+    const size_t tile_rows = ws_bytes / ((size_t)S * N * sizeof(float)) / 256;   // whole row tiles that fit
+    if (tile_rows < 1)
+      LR_FAIL(LR_EWORKSPACE, "gemm variant 7: split-K x%d of %dx%d needs %zu workspace bytes, have %zu", S, 256, N,
+              (size_t)S * 256 * N * sizeof(float), ws_bytes);
+    *out = {S, (int)(tile_rows > 0x7fffff ? 0x7fffff : tile_rows) * 256};
+    return LR_OK;
+  }
+  if ((size_t)S * M * N * sizeof(float) > ws_bytes)
+    LR_FAIL(LR_EWORKSPACE, "gemm variant 5: split-K x%d of %dx%d needs %zu workspace bytes, have %zu", S, M, N,
+            (size_t)S * M * N * sizeof(float), ws_bytes);
+  *out = {S, M};
+  return LR_OK;
+}
+
+int lr_gemm_splitk_plan_of(int variant, int M, int N, int K, size_t workspace_bytes, int* splits, int* rows_per_launch) {
+  if ((variant != 5 && variant != 7) || M < 1 || N < 1 || K < 1 || !splits || !rows_per_launch)
+    LR_FAIL(LR_EINVAL, "gemm split-K plan: variant %d (5 or 7), M=%d N=%d K=%d", variant, M, N, K);
+  SplitKPlan p;
+  LR_RUN(splitk_plan(variant, M, N, K, workspace_bytes, &p));
+  *splits = p.S;
+  *rows_per_launch = p.rows_per_launch;
+  return LR_OK;
 }
 
 // tile raster: M tiles per group (llama_gemm.hip header). An XCD's 32 concurrent workgroups form a group_m x (32 / group_m)
@@ -815,25 +879,47 @@ static int launch256_ext(const LrGemmArgs& g, const RopeArgs& rope, hipStream_t 
   return LR_OK;
 }
 
+// One product over K splits: per chunk of p.rows_per_launch rows (variant 5: all of them) the partial kernel on grid
+// (tiles, S) and the reduce pass, with every per-row pointer advanced by the chunk's first row.
 template <int EPI, typename... Bias>
-static int launch_splitk(const LrGemmArgs& g, int S, RopeArgs rope, hipStream_t st, Bias... bias) {
-  const int M = g.M, N = g.N, K = g.K;
+static int launch_splitk(const LrGemmArgs& g, SplitKPlan p, RopeArgs rope, hipStream_t st, Bias... bias) {
+  const int N = g.N, K = g.K, S = p.S;
   float* ws = g.splitk.ws;
   const LrGemmThenNorm& tn = g.then_norm;
-  LrProfScope prof(LR_PROF_GEMM256, 2.0 * M * (double)N * K, st, LR_PROF_GEMM_TAG(EPI, N, K));
+  const LrGemmKvScatter& kv = g.kv_scatter;
+  LrProfScope prof(LR_PROF_GEMM256, 2.0 * g.M * (double)N * K, st, LR_PROF_GEMM_TAG(EPI, N, K));
   if (int rc = gemm256_prepare<LR_EPI_PARTIAL>()) return rc;
-  const int nwg = ((M + 255) / 256) * (N / 256);
-  hipLaunchKernelGGL(gemm256rb_kernel<LR_EPI_PARTIAL>, dim3(nwg, S), dim3(512), 2 * G2_STAGE_BYTES, st, g.A, g.B,
-                     reinterpret_cast<u16*>(ws), nullptr, M, N, K, gemm256_group_m(K), rope);
-  LR_CHECK_LAUNCH("gemm256rb_kernel<partial>");
-  if (EPI == LR_EPI_RESIDUAL && tn.w && tn.out && tn.done && lr_reduce_residual_rmsnorm_fits(N)) {
-    *tn.done = true;   // the reduce pass also writes RMSNorm(C) for the next projection
-    return lr_launch_reduce_residual_rmsnorm(ws, S, g.C, g.R, M, N, tn.w, tn.out, tn.eps, st, tn.style);
+  const bool norm_too = EPI == LR_EPI_RESIDUAL && tn.w && tn.out && tn.done && lr_reduce_residual_rmsnorm_fits(N);
+  const size_t ldc = LR_EPI_IS_GATED(EPI) ? (size_t)(N >> 1) : (size_t)N;
+  for (int m0 = 0; m0 < g.M; m0 += p.rows_per_launch) {
+    const int M = g.M - m0 < p.rows_per_launch ? g.M - m0 : p.rows_per_launch;
+    RopeArgs r = rope;
+    if (r.tok_pos) r.tok_pos += m0;
+    if (r.row_scale) r.row_scale += m0;
+    u16* const C = g.C ? g.C + (size_t)m0 * ldc : nullptr;
+    const u16* const R = g.R ? g.R + (size_t)m0 * ldc : nullptr;
+    const int nwg = ((M + 255) / 256) * (N / 256);
+    hipLaunchKernelGGL(gemm256rb_kernel<LR_EPI_PARTIAL>, dim3(nwg, S), dim3(512), 2 * G2_STAGE_BYTES, st, g.A + (size_t)m0 * K,
+                       g.B, reinterpret_cast<u16*>(ws), nullptr, M, N, K, gemm256_group_m(K), r);
+    LR_CHECK_LAUNCH("gemm256rb_kernel<partial>");
+    if (norm_too) {   // the reduce pass also writes RMSNorm(C) for the next projection
+      LR_RUN(lr_launch_reduce_residual_rmsnorm(ws, S, C, R, M, N, tn.w, tn.out + (size_t)m0 * N, tn.eps, st, tn.style));
+      continue;
+    }
+    const size_t quads = (size_t)M * ldc / 4;
+    if constexpr (EPI == LR_EPI_ROPE && sizeof...(Bias) == 0) {
+      if (kv.kv_layer) {
+        hipLaunchKernelGGL(splitk_reduce_rope_kv_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, ws, S, C, M, N, r,
+                           kv.col0, kv.kv_layer, kv.row_off + m0);
+        LR_CHECK_LAUNCH("splitk_reduce_rope_kv_kernel");
+        continue;
+      }
+    }
+    hipLaunchKernelGGL((splitk_reduce_kernel<EPI, Bias...>), dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, ws, S, C,
+                       R, M, N, r, bias...);
+    LR_CHECK_LAUNCH("splitk_reduce_kernel");
   }
-  const size_t quads = (LR_EPI_IS_GATED(EPI) ? (size_t)M * (N >> 1) : (size_t)M * N) / 4;
-  hipLaunchKernelGGL((splitk_reduce_kernel<EPI, Bias...>), dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, ws, S, g.C,
-                     g.R, M, N, rope, bias...);
-  LR_CHECK_LAUNCH("splitk_reduce_kernel");
+  if (norm_too) *tn.done = true;
   return LR_OK;
 }
 
@@ -902,7 +988,7 @@ int lr_launch_gemm(const LrGemmArgs& g, hipStream_t st) {
   if (g.then_norm.done) *g.then_norm.done = false;
   if (M <= 0) return LR_OK;
   if (N <= 0 || K <= 0) LR_FAIL(LR_EINVAL, "gemm: N=%d K=%d", N, K);
-  const bool fast_ok = (N % 256 == 0) && (K % 64 == 0) && M >= 1;
+  const bool fast_ok = gemm256_shape_ok(M, N, K);
   // variant 6 = auto, except that a product whose N is a multiple of 64 but not of 256 (K % 64 == 0, M >= 128, store /
   // residual / rope epilogue, no folded norm) runs the 256-tile body with a ragged last column tile instead of the generic
   // kernel. Everything else -- N % 256 == 0, M < 128, gated epilogues, N % 64 != 0 -- goes where auto sends it, with auto's bits.
@@ -913,9 +999,10 @@ int lr_launch_gemm(const LrGemmArgs& g, hipStream_t st) {
   }
   if (variant == 0) variant = (fast_ok && M >= 128) ? 4 : 1;
   if (variant == 5 && !fast_ok) variant = 1;  // latency mode: any row count (B last-token rows too), shapes as auto
-  if (variant != 1 && variant != 4 && variant != 5 && variant != 6)
+                                              // (variant 7 off the tile: refused by splitk_plan below)
+  if (variant != 1 && variant != 4 && variant != 5 && variant != 6 && variant != 7)
     LR_FAIL(LR_EINVAL, "gemm: unknown variant %d (0 auto, 1 generic, 4 = 256x256x64 MFMA tile, 5 = 4 + split-K, 6 = auto + "
-            "ragged last column tile)", variant);
+            "ragged last column tile, 7 = 4 + split-K fixed by the weight's shape)", variant);
   if (variant == 4 && !fast_ok)
     LR_FAIL(LR_EUNSUPPORTED, "gemm variant 4 needs N%%256==0 and K%%64==0 (N=%d K=%d)", N, K);
   if (LR_EPI_IS_GATED(epi) && (N % 32 != 0)) LR_FAIL(LR_EINVAL, "gated-MLP epilogue needs N%%32==0 (N=%d)", N);
@@ -931,23 +1018,28 @@ int lr_launch_gemm(const LrGemmArgs& g, hipStream_t st) {
     if (!rope.tok_pos || !rope.cs || rope.head_dim < 2 || rope.head_dim % 4 != 0 || rope.rot_cols % 4 != 0 || rope.rot_cols > N)
       LR_FAIL(LR_EINVAL, "rope epilogue: bad arguments (head_dim=%d rot_cols=%d)", rope.head_dim, rope.rot_cols);
   }
-  if (variant == 5) {
-    const int S = splitk_factor(M, N, K);
-    if (S >= 2) {
-      if (!g.splitk.ws || (size_t)S * M * N * sizeof(float) > g.splitk.bytes)
-        LR_FAIL(LR_EWORKSPACE, "gemm variant 5: split-K x%d of %dx%d needs %zu workspace bytes, have %zu", S, M, N,
-                (size_t)S * M * N * sizeof(float), g.splitk.ws ? g.splitk.bytes : (size_t)0);
+  const LrGemmKvScatter& kv = g.kv_scatter;
+  if (variant == 5 || variant == 7) {
+    SplitKPlan p;
+    LR_RUN(splitk_plan(variant, M, N, K, g.splitk.ws ? g.splitk.bytes : (size_t)0, &p));   // before anything is launched
+    if (p.S >= 2) {
+      if (kv.kv_layer &&
+          (epi != LR_EPI_ROPE || g.bias || !kv.row_off || kv.col0 < 0 || kv.col0 >= N || kv.col0 % 4 != 0 || (kv.col0 > 0 && !g.C) ||
+           (reinterpret_cast<uintptr_t>(kv.kv_layer) & 7)))
+        LR_FAIL(LR_EINVAL, "gemm: a K / V scatter goes with the rope epilogue without a bias (epilogue %d, col0 %d of %d)", epi,
+                kv.col0, N);
       switch (epi) {
-        case LR_EPI_STORE: return g.bias ? launch_splitk<LR_EPI_STORE>(g, S, rope, st, g.bias) : launch_splitk<LR_EPI_STORE>(g, S, rope, st);
-        case LR_EPI_RESIDUAL: return launch_splitk<LR_EPI_RESIDUAL>(g, S, rope, st);
-        case LR_EPI_SWIGLU: return launch_splitk<LR_EPI_SWIGLU>(g, S, rope, st);
-        case LR_EPI_GEGLU: return launch_splitk<LR_EPI_GEGLU>(g, S, rope, st);
-        case LR_EPI_ROPE: return g.bias ? launch_splitk<LR_EPI_ROPE>(g, S, rope, st, g.bias) : launch_splitk<LR_EPI_ROPE>(g, S, rope, st);
+        case LR_EPI_STORE: return g.bias ? launch_splitk<LR_EPI_STORE>(g, p, rope, st, g.bias) : launch_splitk<LR_EPI_STORE>(g, p, rope, st);
+        case LR_EPI_RESIDUAL: return launch_splitk<LR_EPI_RESIDUAL>(g, p, rope, st);
+        case LR_EPI_SWIGLU: return launch_splitk<LR_EPI_SWIGLU>(g, p, rope, st);
+        case LR_EPI_GEGLU: return launch_splitk<LR_EPI_GEGLU>(g, p, rope, st);
+        case LR_EPI_ROPE: return g.bias ? launch_splitk<LR_EPI_ROPE>(g, p, rope, st, g.bias) : launch_splitk<LR_EPI_ROPE>(g, p, rope, st);
       }
       LR_FAIL(LR_EINVAL, "gemm: unknown epilogue %d", epi);
     }
     variant = 4;
   }
+  if (kv.kv_layer) LR_FAIL(LR_EINVAL, "gemm: a K / V scatter is written by the split-K reduce pass only (this product does not split)");
   switch (epi) {
     case LR_EPI_STORE: return g.bias ? launch_epi<LR_EPI_STORE>(g, variant, rope, st, g.bias) : launch_epi<LR_EPI_STORE>(g, variant, rope, st);
     case LR_EPI_RESIDUAL: return launch_epi<LR_EPI_RESIDUAL>(g, variant, rope, st);

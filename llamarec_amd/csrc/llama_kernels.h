@@ -96,7 +96,9 @@ int lr_launch_qk_norm_rope(unsigned short* buf, int rows, int ld, int nq, int nk
 // C[M][N] (+epilogue) = A[M][K] * B[N][K]^T. Call sites name what they pass (designated initialisers); a member left
 // out is absent. variant: 0 auto, 1 generic, 4 = 256x256x64 MFMA tile, 5 = variant 4 with split-K when the tiles alone
 // would leave most CUs idle (needs splitk), 6 = auto, with the 256-tile body on a ragged last column tile where N % 64 == 0
-// but N % 256 != 0 (llama_gemm.hip, lr_launch_gemm).
+// but N % 256 != 0 (llama_gemm.hip, lr_launch_gemm), 7 = variant 5 with the split fixed by the weight's shape (N, K) alone and
+// the rows launched in chunks the split-K workspace holds: a row's arithmetic does not depend on the launch's row count (the
+// online mode: ranker sessions; many serial launches at a large M). A width off the 256 tile is LR_EINVAL under 7.
 struct LrGemmRope {                 // LR_EPI_ROPE only
   const int32_t* tok_pos = nullptr; // [M] position of each row inside its prompt
   const float* cs = nullptr;        // lr_launch_rope_table's fp32 table
@@ -115,6 +117,14 @@ struct LrGemmThenNorm {
   int style = 0;
   bool* done = nullptr;
 };
+// Rope epilogue of a product that splits over K (variants 5 / 7) only, anything else is LR_EINVAL: the reduce pass stores
+// columns < col0 to C as always and columns >= col0 (K rotated | V of a QKV product) to kv_layer + row_off[row] + (col - col0),
+// the rows' places in a K / V cache (ranker sessions). col0 = 0: every column is scattered and C is not written.
+struct LrGemmKvScatter {
+  unsigned short* kv_layer = nullptr;   // the cache table at the layer's row offset (16-byte aligned); nullptr: absent
+  const long long* row_off = nullptr;   // DEVICE [M] element offsets of the rows' cache rows, multiples of 4
+  int col0 = 0;                         // a multiple of 4
+};
 struct LrGemmArgs {
   const unsigned short *A, *B;
   unsigned short* C;
@@ -127,8 +137,12 @@ struct LrGemmArgs {
   const unsigned short* bias = nullptr;
   LrGemmSplitK splitk;
   LrGemmThenNorm then_norm;
+  LrGemmKvScatter kv_scatter;
 };
 int lr_launch_gemm(const LrGemmArgs& g, hipStream_t st);
+// What lr_launch_gemm does with a variant-5 / 7 product (host only): *splits = the K splits (1 = not split), *rows_per_launch =
+// the rows of one launch (variant 5 and unsplit products: M). LR_EWORKSPACE where lr_launch_gemm would return it.
+int lr_gemm_splitk_plan_of(int variant, int M, int N, int K, size_t workspace_bytes, int* splits, int* rows_per_launch);
 // split-K reduce (S fp32 planes of M x N) + residual + RMSNorm of the result in one pass (llama_elem.hip)
 bool lr_reduce_residual_rmsnorm_fits(int N);
 int lr_launch_reduce_residual_rmsnorm(const float* part, int S, unsigned short* C, const unsigned short* R, int M, int N,
@@ -477,8 +491,10 @@ static inline int lr_attn_launch_last(const char* kernel_name, const char* layou
 // Prompt b of a call owns the packed rows cu[b] .. cu[b + 1] - 1, which sit at positions
 // cached_len[b] .. of slot slots[b].
 // tok_pos[r] = the position of packed row r, last_rows[b] / last_pos[b] = prompt b's last packed row and its position
+// row_off (optional, with slots): [n] element offsets slots[b] * slot_elems + position * kv_w of the rows' cache rows in a layer
 int lr_launch_kv_cache_meta(const int32_t* cu, const int32_t* cached_len, int B, int n, int32_t* tok_pos, int32_t* last_rows,
-                            int32_t* last_pos, hipStream_t st);
+                            int32_t* last_pos, hipStream_t st, const int32_t* slots = nullptr, long long slot_elems = 0,
+                            int kv_w = 0, long long* row_off = nullptr);
 // columns [col0, col0 + kv_w) of src [n][ld] -> the rows' slot rows in dst (the table at the layer's row offset)
 int lr_launch_kv_cache_write(const unsigned short* src, int ld, int col0, int kv_w, const int32_t* cu, const int32_t* cached_len,
                              const int32_t* slots, int B, long long slot_elems, unsigned short* dst, int n, hipStream_t st);

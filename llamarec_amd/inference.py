@@ -76,7 +76,11 @@ class RankerSession:
     Matching is on token ids, never on text: whatever the tokenizer does where history and pool meet, a mismatch only
     shortens the reuse. Every new token is kept in the slot (keep = all of them) and the NEXT call's comparison decides how
     much of it is reused; whatever lies behind the common prefix is dropped by lowering the host length, which costs
-    nothing. `sent_tokens` counts the tokens prefilled so far, `last_sent` those of the last call."""
+    nothing. `sent_tokens` counts the tokens prefilled so far, `last_sent` those of the last call.
+
+    For online use set the model to the row-invariant latency mode first, `model.set_variants(7, 0)`: the calls then split K
+    as the latency-mode whole prompt does and return `rank_candidates`' scores under that mode bit for bit. In the default
+    mode (and under gemm variant 5, which runs the default-mode products here) a short new part leaves most of the card idle."""
 
     def __init__(self, model, tokenizer, verbalizer, max_tokens=2048):
         self.model, self.tokenizer, self.verbalizer = model, tokenizer, verbalizer

@@ -859,7 +859,11 @@ class LlamaRanker:
     def set_variants(self, gemm=0, attention=0):
         """Kernel selection (include/llamarec_mi355x.h): 0 = auto; gemm=5 = latency mode for the online
         single-user path (split-K where a short prompt would leave most CUs idle); gemm=6 = auto with the MFMA tile on a ragged
-        last column tile (widths that are multiples of 64 but not of 256: a qwen2 ranker's default). attention: 1 generic, 2 / 3 head_dim 128,
+        last column tile (widths that are multiples of 64 but not of 256: a qwen2 ranker's default); gemm=7 = the row-invariant
+        latency mode, the one to set for ranker sessions: 5 with the split fixed by the weight's shape and the rows launched in
+        chunks, so a row's bits do not depend on the launch's row count -- extend_verbalize runs it and returns the bits of
+        prefill_verbalize under 7, and up to 256 prompt tokens 7 is 5 bit for bit. It needs widths on the 256 x 64 tile (an error otherwise). A large batch under 7 is many serial launches:
+        bulk scoring stays on auto. attention: 1 generic, 2 / 3 head_dim 128,
         4 head_dim 256, 5 head_dim 64 (scoring only: no lse), 7 head_dim 96 (scoring only: no lse), 6 = head_dim-64 MFMA attention for training (5's forward, writing
         lse when a LoRA engine runs on this base, and the head_dim-64 MFMA backward; the LoRA step's auto at head_dim 64),
         8 = the same pair at head_dim 96 (7's forward writing lse, the head_dim-96 MFMA backward; the LoRA step's auto at
@@ -940,7 +944,9 @@ class LlamaRanker:
         """scores[b, c] (fp32 [B, C]) of the prompts  cache.ids[slots[b]][:cached_len[b]] + new_ids_list[b]  at their last
         token, prefilling only the new ids. cached_len defaults to everything the slot holds; a smaller value rolls the
         slot back. keep[b] (default: all) leading new tokens count as cached afterwards. Bit-identical to
-        prefill_verbalize of the whole prompts in the default GEMM mode (see the header for the attention variants)."""
+        prefill_verbalize of the whole prompts in the default GEMM mode, and under set_variants(7, 0) -- the mode for online
+        use -- to prefill_verbalize under 7 (see the header for the attention variants; gemm variant 5 runs the default-mode
+        products here)."""
         B = len(slots)
         seqs = [np.asarray(s, dtype=np.int32).reshape(-1) for s in new_ids_list]
         slots_h = np.asarray(slots, dtype=np.int32).reshape(-1)
